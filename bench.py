@@ -8,19 +8,23 @@ by interleaved 16-row stripes (rank r renders stripes r, r+N, ...), the compact 
 rank 0 with RCCL over xGMI and de-interleaved there, so one step still produces the whole frame (strong scaling).  A rank's
 share of a frame is tens of microseconds of GPU work, so at N > 1 every rank keeps --lanes frames in flight on its GPU (member
 contexts of one device, rxr_render_stripes_batch) and moves --bucket frames per collective; `value` is measured on the exchange
-BASELINE.json names (gather to rank 0), and the SAME run also times the variants that lift that exchange's link bound (rotating
-root, several communicators) under `exchange_variants`, plus every rank's render-only and exchange-only time (`per_rank`).
+BASELINE.json names (gather to rank 0), and with --full the SAME run also times the variants that lift that exchange's link bound
+(rotating root, several communicators) under `exchange_variants`, plus every rank's render-only and exchange-only time (`per_rank`).
 
-Timing: W untimed warm-up steps, then batches of EXACTLY K steps, each bracketed by barrier + torch.cuda.synchronize()
-on both sides and timed on its own (max over ranks); batches are repeated until at least MIN_TIMED_S seconds have been
-timed (a 4K frame takes 0.2 ms: K = 20 steps alone would be a 4 ms measurement) and the MEDIAN batch is reported.
+Timing: W untimed warm-up steps (repeated until WARMUP_MIN_S seconds of them have run), then EXACTLY K timed steps, bracketed by
+barrier + torch.cuda.synchronize() on both sides (max over ranks); `value` and `ms_per_step` are that region's.  --dump-outputs DIR then writes the frame of the last timed step.
+
+A plain run does nothing else.  --full adds what takes runs of its own: batches of K steps repeated until at least MIN_TIMED_S
+seconds have been timed (the MEDIAN batch in `timing`, a 4K frame takes 0.1 ms) with the raster kernels timed on every
+PROFILE_STRIDE-th frame (`roofline`), the other light-loop arithmetic, two frames in flight, the end-to-end time of the drop-in
+call (`e2e_ms`: host projection + upload + kernels + download into the caller's pixels; at N > 1 through a multi-device context,
+every GPU downloading its own stripes), the CPU oracle's `cpu_baseline`, and at N > 1 the byte-identity check of the gathered
+frame, the exchange variants and the per-rank legs.
 
 Launch: `python bench.py --gpus N` starts its own N ranks (child processes, before anything touches a GPU) unless a
 launcher (torchrun: RANK / WORLD_SIZE in the environment) already did; the number of ranks observed must equal --gpus.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`, `cpu_baseline` and, beside the
-device-resident `value`, the end-to-end time of the drop-in call (`e2e_ms`: host projection + upload + kernels + download
-into the caller's pixels; at N > 1 through a multi-device context, every GPU downloading its own stripes).
+Prints ONE JSON line on rank 0 (contract in the task statement).
 """
 import argparse
 import ctypes as C
@@ -36,12 +40,19 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-# every PROFILE_STRIDE-th frame of the timed region has its kernels timed: a (start, stop) HIP event pair per DISPATCH (hipExtLaunchKernel:
+# --full: every PROFILE_STRIDE-th frame of the batched region has its kernels timed: a (start, stop) HIP event pair per DISPATCH (hipExtLaunchKernel:
 # the dispatch's own begin / end timestamps, what rocprofv3's kernel trace reports), no event record on the stream -- rounds 1-3 recorded
 # events between the launches, which idled the GPU and counted launch latency as kernel time (set-up 8.6 us against 5.3 in the trace)
 PROFILE_STRIDE = int(os.environ.get("RXR_BENCH_PROFILE_STRIDE", "4"))
 MIN_TIMED_S = float(os.environ.get("RXR_BENCH_MIN_TIMED_S", "1.0"))
+# the warm-up runs --warmup steps, repeated until this many seconds of them have run: the first tens of milliseconds of work on the GPU run
+# slower (measured: 20 timed steps behind 5 warm-up steps 10 % above the steady state, 200 behind 20 4 %)
+WARMUP_MIN_S = float(os.environ.get("RXR_BENCH_WARMUP_MIN_S", "0.25"))
 MAX_BATCHES = 5000
+# --dump-outputs: the whole frame as float32 up to this size, else a seeded sample of its pixels (2^21 pixels = 33.6 MB)
+DUMP_MAX_BYTES = 64_000_000
+DUMP_SAMPLE_PIXELS = 1 << 21
+DUMP_SEED = 2024
 # Rehearsal of the N > 1 code path on a box with ONE GPU (tests/test_gpu_bench_rehearsal.py): every rank uses GPU 0 and the exchange
 # goes through gloo with host staging, because RCCL refuses two ranks on one device.  Everything else -- rank bookkeeping, stripes,
 # pipelining indices, the byte-identity check, the multi-device end-to-end leg, the JSON line -- is the code the driver runs.  The
@@ -126,7 +137,7 @@ def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=20, help=f"untimed steps before the timed ones, repeated until {WARMUP_MIN_S} s of them have run")
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--lights", type=int, default=16)
@@ -150,7 +161,31 @@ def parse_args():
     ap.add_argument("--no-variants", action="store_true", help="N > 1: skip the exchange variants and the per-rank render-only / exchange-only legs")
     ap.add_argument("--force-gather", action="store_true",
                     help="debug: run the stripe -> gather -> assemble path even at N=1 (never used by the driver)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the batched median with kernel timing (roofline), the other light math, two frames in flight, end-to-end, "
+                         "the CPU baseline and, at N > 1, the identity check, exchange variants and per-rank legs (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/frame.npy (float32 RGBA 0..255; a fixed sample of "
+                         f"{DUMP_SAMPLE_PIXELS} pixels, in raster order, when the whole frame would exceed {DUMP_MAX_BYTES // 10 ** 6} MB)")
     return ap.parse_args()
+
+
+def dump_frame(frame, out_dir):
+    """frame: (H, W, 4) uint8 on the device -> out_dir/frame.npy as float32; above DUMP_MAX_BYTES the pixels at a fixed, seeded
+    choice of indices (the same for every run of the same size), sorted"""
+    import torch
+
+    H, W = int(frame.shape[0]), int(frame.shape[1])
+    os.makedirs(out_dir, exist_ok=True)
+    if H * W * 4 * 4 <= DUMP_MAX_BYTES:
+        arr = frame.cpu().numpy().astype(np.float32)
+        sampled = None
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(H * W, size=DUMP_SAMPLE_PIXELS, replace=False))
+        arr = frame.reshape(H * W, 4)[torch.from_numpy(idx).to(frame.device)].cpu().numpy().astype(np.float32)
+        sampled = DUMP_SAMPLE_PIXELS
+    np.save(os.path.join(out_dir, "frame.npy"), arr)
+    return {"frame": list(arr.shape), "sampled_pixels": sampled, "of_pixels": H * W, "seed": DUMP_SEED if sampled else None}
 
 
 def spawn_ranks(args):
@@ -279,7 +314,7 @@ def main():
 
     # every communicator any configuration of this run uses, created once, in the same order on every rank
     vk = min(world, 4)
-    n_groups = max(max(1, args.comms), 1 if args.no_variants else vk)
+    n_groups = max(max(1, args.comms), vk if args.full and not args.no_variants else 1)
     groups = [None] if world == 1 or n_groups == 1 else [dist.new_group(list(range(world))) for _ in range(n_groups)]
 
     class Pipeline:
@@ -368,29 +403,53 @@ def main():
             n = int(nb_.item())
         return n
 
-    run(args.warmup)
-    fence()
+    t_warm = time.perf_counter()
+    warmup_run = 0
+    while True:  # (the decision to go on is rank 0's, agreed by every rank)
+        run(max(1, args.warmup))
+        fence()
+        warmup_run += max(1, args.warmup)
+        if not agree(int(time.perf_counter() - t_warm < WARMUP_MIN_S)):
+            break
     check(rxr.rxr_synchronize(ctx))  # (every warm-up frame complete: no list overflowed, no program faulted)
-    # kernel durations are measured live with HIP events on the launch stream, on every PROFILE_STRIDE-th frame of the
-    # timed region: three event records per frame idle the GPU for 10-25 us, a tenth of this frame
-    first = timed_batch()  # sizes the run (timed like the others, not discarded)
-    n_batches = agree(int(min(MAX_BATCHES, max(1, np.ceil(1.25 * MIN_TIMED_S / max(first, 1e-6))))))
-    ring = min(65536, n_batches * args.steps // PROFILE_STRIDE + args.steps + 8)
-    check(rxr.rxr_profile_stride(ctx, PROFILE_STRIDE))
-    check(rxr.rxr_profile_begin(ctx, ring))
-    batch_s = [timed_batch() for _ in range(n_batches)]
+    # the headline: exactly --steps steps, one timed region, no kernel timing
+    dt = timed_batch()
     # the asynchronous loop above never asked whether its frames were complete: do it now (sticky status, rxr.h)
     check(rxr.rxr_synchronize(ctx))
-    dt = float(np.median(batch_s))
 
-    # per-launch kernel durations measured with HIP events on the launch stream during the timed region (lanes: member 0's launches)
-    setup_us = (C.c_float * ring)()
-    raster_us = (C.c_float * ring)()
-    n_prof = C.c_uint32(0)
-    check(rxr.rxr_profile_read(ctx, setup_us, raster_us, ring, C.byref(n_prof)))
-    check(rxr.rxr_profile_begin(ctx, 0))
-    raster_avg_us = float(np.mean(raster_us[: n_prof.value])) if n_prof.value else float("nan")
-    setup_avg_us = float(np.mean(setup_us[: n_prof.value])) if n_prof.value else float("nan")
+    def last_frame(p):
+        """the frame of the last step p.run() assembled, on the rank that holds it (None elsewhere)"""
+        i_last, k_last = p.last
+        if p.gather.frames is None or rank != p.gather.root_of(i_last):
+            return None
+        fr = p.gather.frames[i_last % (p.dp + 1)]
+        return (fr if p.bk == 1 else fr[k_last - 1])[:H]
+
+    final = last_frame(pipe) if sharded else frames[(args.steps - 1) % NBUF][:H]
+    if final is not None:
+        assert int(final[..., 3].min().item()) == 255 and int(final[..., :3].max().item()) > 0, "benchmark frame is not a rendered frame"
+    dumped = dump_frame(final, args.dump_outputs) if args.dump_outputs and final is not None else None
+    del final
+
+    if args.full:
+        # kernel durations are measured live with HIP events on the launch stream, on every PROFILE_STRIDE-th frame of the
+        # batched region: three event records per frame idle the GPU for 10-25 us, a tenth of this frame
+        n_batches = agree(int(min(MAX_BATCHES, max(1, np.ceil(1.25 * MIN_TIMED_S / max(dt, 1e-6))))))  # (sized by the headline region)
+        ring = min(65536, n_batches * args.steps // PROFILE_STRIDE + args.steps + 8)
+        check(rxr.rxr_profile_stride(ctx, PROFILE_STRIDE))
+        check(rxr.rxr_profile_begin(ctx, ring))
+        batch_s = [timed_batch() for _ in range(n_batches)]
+        check(rxr.rxr_synchronize(ctx))
+        batch_dt = float(np.median(batch_s))
+
+        # per-launch kernel durations measured with HIP events on the launch stream during the batched region (lanes: member 0's launches)
+        setup_us = (C.c_float * ring)()
+        raster_us = (C.c_float * ring)()
+        n_prof = C.c_uint32(0)
+        check(rxr.rxr_profile_read(ctx, setup_us, raster_us, ring, C.byref(n_prof)))
+        check(rxr.rxr_profile_begin(ctx, 0))
+        raster_avg_us = float(np.mean(raster_us[: n_prof.value])) if n_prof.value else float("nan")
+        setup_avg_us = float(np.mean(setup_us[: n_prof.value])) if n_prof.value else float("nan")
 
     def check_assembled(p):
         """on the rank that owns the last assembled frame: not empty, every pixel resolved, byte-identical to a single-launch frame
@@ -407,11 +466,8 @@ def main():
         torch.cuda.synchronize()
         assert torch.equal(direct, final), "gathered frame differs from the single-launch frame"
 
-    if sharded:
+    if sharded and args.full:
         check_assembled(pipe)
-    else:
-        final = frames[(args.steps - 1) % NBUF][:H]
-        assert int(final[..., 3].min().item()) == 255 and int(final[..., :3].max().item()) > 0, "benchmark frame is not a rendered frame"
 
     def measure(fn, t_min=min(0.3, MIN_TIMED_S), n_max=200):
         """median seconds per `steps` steps of fn over batches that add up to >= t_min seconds (the count agreed on by all ranks)"""
@@ -425,7 +481,7 @@ def main():
     # which of the two bounds the curve), (b) the exchange variants that lift the fixed root's link bound.  Never `value`.
     per_rank = None
     variants = None
-    if sharded and not args.no_variants:
+    if sharded and args.full and not args.no_variants:
         def local_time(fn, n_rep=5):
             fn(args.warmup)
             ts = []
@@ -511,7 +567,7 @@ def main():
     relaxed = os.environ.get("RXR_LIGHT_MATH", "exact" if host.rxh_get_light_math_exact() else "relaxed")[0] == "r"
     other_mode = None
     in_flight = None
-    if world == 1 and not sharded and "RXR_LIGHT_MATH" not in os.environ:
+    if args.full and world == 1 and not sharded and "RXR_LIGHT_MATH" not in os.environ:
         host.rxh_set_light_math_exact(1 if relaxed else 0)
         rc = host.rxh_rasterizer_upload(rast._h, cfg.scene._h, W, H, cfg.tile_size, cfg.assets._h)
         if rc == 0:
@@ -523,7 +579,7 @@ def main():
                           "mpix_s": round(W * H * args.steps / other_dt / 1e6, 2), "batches": len(other_s)}
         host.rxh_set_light_math_exact(0 if relaxed else 1)
         upload()
-    if world == 1 and not sharded and not args.no_in_flight:
+    if args.full and world == 1 and not sharded and not args.no_in_flight:
         # two frames in flight on the one GPU (two member contexts, frame i on lane i mod 2, each on its own stream): throughput
         # of the same K whole frames when the tail of one frame's launches runs under the head of the next.  Reported beside
         # `value` (the serial loop, one frame at a time, as a caller of rasterize() sees it), never as it.
@@ -560,7 +616,7 @@ def main():
 
     fence()
     e2e = None
-    if rank == 0 and not args.no_e2e:
+    if args.full and rank == 0 and not args.no_e2e:
         try:
             e2e = end_to_end(prod, host, rxr, cfg, W, H, world)
         except Exception as ex:  # the end-to-end leg must never cost the bench line
@@ -570,34 +626,18 @@ def main():
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
         value = W * H * args.steps / dt / 1e6
-        # algorithmic bytes of ONE raster launch: this rank's share of the framebuffer + the scene read once
         n_verts, n_tris, tex_bytes = scene_counts(cfg, prod)
-        rows_this_rank = min(stripe_rows, H) if sharded else H
-        alg = algorithmic_bytes(W, rows_this_rank, n_verts, n_tris, tex_bytes, args.lights)
-        achieved = alg / (raster_avg_us * 1e-6) / 1e9
-        default_workload = (W, H, args.lights, world) == (3840, 2160, 16, 1) and not sharded
-        PROFILE = PROFILES.get("relaxed" if relaxed else "exact")
-        default_workload = default_workload and PROFILE is not None
-        # the compute-side rooflines of the same kernel ("state both fractions"): instruction and flop counts from the
-        # committed PMC passes, the duration measured live
-        valu_issue_frac = fp32_frac = fp32_tflops = None
-        if default_workload and raster_avg_us == raster_avg_us:
-            t_s = raster_avg_us * 1e-6
-            valu_issue_frac = PROFILE["valu_wave_instructions"] * VALU_ISSUE_CYCLES / (N_SIMDS * CLOCK_GHZ * 1e9 * t_s)
-            f = PROFILE["fp32_wave_instructions"]
-            if PROFILE["valu_lane_utilisation"] and (f["ADD"] + f["MUL"] + f["FMA"]):
-                fp32_tflops = (f["ADD"] + f["MUL"] + 2 * f["FMA"]) * 64 * PROFILE["valu_lane_utilisation"] / t_s / 1e12
-                fp32_frac = fp32_tflops / FP32_VALU_PEAK_TFLOPS
         out = {
             "metric": "Mpixels/s (+ ms/frame) on rasterize_map @3840x2160, 1/2/4/8 MI355X vs CPU",
             "value": round(value, 2),
             "unit": "Mpixels/s",
             # inputs resident in HBM when the timed region starts, the frame left in HBM; the drop-in call into host pixels (host
-            # projection + upload + kernels + PCIe download) is `e2e_ms` below, never `value`
+            # projection + upload + kernels + PCIe download) is `e2e_ms` (--full), never `value`
             "value_semantics": "device-resident",
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "warmup_steps_run": warmup_run,
             "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True,
             "scaling": "strong",
@@ -606,11 +646,8 @@ def main():
             "dtype": "f32",
             "data": "synthetic",
             "timing": {
-                "batches": n_batches + 1,
-                "batch_steps": args.steps,
-                "timed_s": round(float(np.sum(batch_s)) + first, 3),
-                "reported": "median batch of `steps` steps, each batch between barrier + synchronize on both sides",
-                "batch_ms_min_median_max": [round(float(np.min(batch_s)) * 1e3, 4), round(dt * 1e3, 4), round(float(np.max(batch_s)) * 1e3, 4)],
+                "timed_s": round(dt, 4),
+                "reported": "one region of exactly `steps` steps between barrier + synchronize on both sides",
             },
             "config": {
                 "workload": f"map scene (minigame room), {W}x{H}, {args.lights} point lights, Nearest sampling, "
@@ -624,7 +661,39 @@ def main():
                 "sharding": "single GPU, one frame at a time" if not sharded else pipe.describe(),
                 **({"frames_in_flight_per_gpu": lanes, "frames_per_exchange": bucket} if sharded else {}),
             },
-            "roofline": {
+        }
+        if dumped is not None:
+            out["outputs"] = dumped
+        if args.full:
+            batch_ms_per_step = batch_dt / args.steps * 1e3
+            out["timing"]["batched"] = {
+                "batches": n_batches,
+                "batch_steps": args.steps,
+                "timed_s": round(float(np.sum(batch_s)), 3),
+                "reported": "median batch of `steps` steps, each batch between barrier + synchronize on both sides, raster kernels event-timed "
+                            f"on 1 frame in {PROFILE_STRIDE}",
+                "ms_per_step": round(batch_ms_per_step, 4),
+                "mpix_s": round(W * H * args.steps / batch_dt / 1e6, 2),
+                "batch_ms_min_median_max": [round(float(np.min(batch_s)) * 1e3, 4), round(batch_dt * 1e3, 4), round(float(np.max(batch_s)) * 1e3, 4)],
+            }
+            # algorithmic bytes of ONE raster launch: this rank's share of the framebuffer + the scene read once
+            rows_this_rank = min(stripe_rows, H) if sharded else H
+            alg = algorithmic_bytes(W, rows_this_rank, n_verts, n_tris, tex_bytes, args.lights)
+            achieved = alg / (raster_avg_us * 1e-6) / 1e9
+            default_workload = (W, H, args.lights, world) == (3840, 2160, 16, 1) and not sharded
+            PROFILE = PROFILES.get("relaxed" if relaxed else "exact")
+            default_workload = default_workload and PROFILE is not None
+            # the compute-side rooflines of the same kernel ("state both fractions"): instruction and flop counts from the
+            # committed PMC passes, the duration measured live
+            valu_issue_frac = fp32_frac = fp32_tflops = None
+            if default_workload and raster_avg_us == raster_avg_us:
+                t_s = raster_avg_us * 1e-6
+                valu_issue_frac = PROFILE["valu_wave_instructions"] * VALU_ISSUE_CYCLES / (N_SIMDS * CLOCK_GHZ * 1e9 * t_s)
+                f = PROFILE["fp32_wave_instructions"]
+                if PROFILE["valu_lane_utilisation"] and (f["ADD"] + f["MUL"] + f["FMA"]):
+                    fp32_tflops = (f["ADD"] + f["MUL"] + 2 * f["FMA"]) * 64 * PROFILE["valu_lane_utilisation"] / t_s / 1e12
+                    fp32_frac = fp32_tflops / FP32_VALU_PEAK_TFLOPS
+            out["roofline"] = {
                 "bound": "hbm",
                 "kernel": "k_raster_rl" if relaxed else "k_raster",
                 "achieved": round(achieved, 2),
@@ -640,15 +709,16 @@ def main():
                 # correction + WRITE_SIZE): from the committed profile, NOT measured in this run; only known for the default workload
                 "traffic": PROFILE["fetch_bytes_x2"] + PROFILE["write_bytes"] if default_workload else None,
                 "traffic_from": PROFILE["source"] if default_workload else None,
-                # measured live in this run, on every PROFILE_STRIDE-th frame of the timed region: HIP start / stop events bound to the
+                # measured live in this run, on every PROFILE_STRIDE-th frame of the batched region: HIP start / stop events bound to the
                 # dispatches themselves (hipExtLaunchKernel on the launch stream; no event record between the launches)
                 "algorithmic_bytes_per_launch": int(alg),
                 "kernel_avg_us": round(raster_avg_us, 2),
                 "kernel_samples": int(n_prof.value),
                 "kernel_timing": f"per-dispatch start/stop HIP events, 1 frame in {PROFILE_STRIDE}",
                 "setup_kernels_avg_us": round(setup_avg_us, 2),
-                # kernels of one step against the step (one frame at a time: they cannot exceed it; lanes overlap other lanes' launches)
-                "kernels_fit_step": bool(raster_avg_us + setup_avg_us <= ms_per_step * 1e3 * 1.005) if not (sharded and lanes > 1) else None,
+                # kernels of one step against the step of the same region (one frame at a time: they cannot exceed it; lanes overlap other
+                # lanes' launches)
+                "kernels_fit_step": bool(raster_avg_us + setup_avg_us <= batch_ms_per_step * 1e3 * 1.005) if not (sharded and lanes > 1) else None,
                 "note": "the kernel is fp32-VALU bound, not HBM bound: algorithmic HBM traffic is ~4.5 B/pixel (DESIGN.md section 6)"
                         + ("; with several frames in flight the event-timed launches overlap other lanes' launches" if sharded and lanes > 1 else ""),
                 "from_profiles": {
@@ -664,13 +734,12 @@ def main():
                     "kernel_sources_sha": PROFILE["kernel_sources_sha"],
                     "stale": PROFILE["kernel_sources_sha"] != kernel_sources_sha(),
                 } if default_workload else None,
-            },
-        }
+            }
         if other_mode is not None:
             out["other_light_math"] = other_mode
         if in_flight is not None:
             out["two_frames_in_flight"] = in_flight
-        if sharded:
+        if sharded and args.full:
             # What bounds `value` at this N, stated in the line itself: the exchange BASELINE.json names is a gather to rank 0, whose root
             # receives every other rank's share of EVERY frame, each over the one xGMI link from that rank.  A link is busy for
             # share_bytes / rate per frame whatever the render side does; against a whole frame on one GPU that is a ceiling on the
@@ -698,7 +767,7 @@ def main():
             out["exchange_variants"] = variants
         if e2e is not None:
             out.update(e2e)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(W, H, args.lights)
         print(json.dumps(out), flush=True)
 

@@ -149,17 +149,29 @@ def test_obj_parser_matches_oracle(oracle):
     assert np.array_equal(a[2], a[0][:, :2])  # no vt: uv = (x, y), wavefront.rs:92-95
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/examples/teapot.obj"), reason="reference checkout not present")
+def teapot_obj_text():
+    """tests/golden/teapot_mesh.npz written back as an OBJ file laid out like examples/teapot.obj: comment, `o` and `s` lines the
+    readers skip, one `v` per position (the shortest decimal that reads back as the same float32), one `f` per triangle with 1-based
+    `v//vn` corners"""
+    v, idx, _, real = scenes.teapot_mesh()
+    assert real, "tests/golden/teapot_mesh.npz is missing"
+    lines = ["# teapot mesh (tests/golden/teapot_mesh.npz)", "o teapot", "s 1"]
+    lines += ["v " + " ".join(np.format_float_positional(c, unique=True, trim="-") for c in p[:3]) for p in v]
+    lines += ["vn 0 0 1", "s 2"]
+    lines += ["f %d//1 %d//1 %d//1" % tuple(int(i) + 1 for i in t) for t in idx]
+    return "\n".join(lines) + "\n"
+
+
 def test_real_teapot_counts():
-    """examples/teapot.obj: 1202 v, 2256 f -- only where the reference is mounted."""
+    """examples/teapot.obj: 1202 v, 2256 f."""
     prod = rusterix_amd.load()
-    b = prod.Batch3D.from_obj(open("/root/reference/examples/teapot.obj").read())
+    b = prod.Batch3D.from_obj(teapot_obj_text())
     assert b.counts() == (1202, 2256)
 
 
 def test_teapot_fixture_is_the_mesh_the_scenes_use():
     """tests/golden/teapot_mesh.npz (made by tests/golden/make_teapot_fixture.py from the reference's examples/teapot.obj): C2 runs
-    on the real geometry wherever this repository goes, also where /root/reference does not exist (the GPU box)"""
+    on the real geometry wherever this repository goes"""
     v, idx, uv, real = scenes.teapot_mesh()
     assert real and v.shape == (1202, 4) and idx.shape == (2256, 3) and (v[:, 3] == 1.0).all()
     assert np.array_equal(uv, v[:, :2])  # no `vt` in the file: wavefront.rs:92-95
@@ -167,10 +179,10 @@ def test_teapot_fixture_is_the_mesh_the_scenes_use():
     assert scenes.teapot_scene(rusterix_amd.load(), width=64, height=36, logo_size=16).name == "C2-teapot"
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/examples/teapot.obj"), reason="reference checkout not present")
 def test_teapot_fixture_equals_the_reference_file(oracle):
-    """both OBJ readers (product host mirror and oracle) turn the reference's file into exactly the fixture's arrays"""
-    text = open("/root/reference/examples/teapot.obj").read()
+    """both OBJ readers (product host mirror and oracle) turn the fixture, written as the reference's file lays it out, into exactly
+    the fixture's arrays"""
+    text = teapot_obj_text()
     v, idx, uv, _ = scenes.teapot_mesh()
     for api in (rusterix_amd.load(), oracle):
         g = api.Batch3D.from_obj(text).geometry()

@@ -6,7 +6,7 @@ trap 'cp /tmp/new.so rusterix_amd/csrc/librxr_hip.so' EXIT   # the product libra
 for r in 1 2; do
 for name in new prev; do
   if [ $name = prev ]; then cp build/variants/librxr_hip_prev.so rusterix_amd/csrc/librxr_hip.so; else cp /tmp/new.so rusterix_amd/csrc/librxr_hip.so; fi
-  timeout 120 python bench.py --steps 300 --warmup 30 --no-cpu 2>/dev/null | python -c "
+  timeout 120 python bench.py --steps 300 --warmup 30 --full --no-cpu 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); print('$name bench ms', d['ms_per_step'], 'kernel', d['roofline']['kernel_avg_us'], 'setup', d['roofline']['setup_kernels_avg_us'])"
   for dp in "" "--device-projection"; do

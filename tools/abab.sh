@@ -8,7 +8,7 @@ for round in 1 2; do
   for which in base $V; do
     if [ $which = base ]; then cp /tmp/orig.so rusterix_amd/csrc/librxr_hip.so; else cp build/variants/librxr_hip_$which.so rusterix_amd/csrc/librxr_hip.so; fi
     for L in "$@"; do
-      python bench.py --steps 200 --warmup 20 --no-cpu --lights $L 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$which', 'lights', $L, 'ms', d['ms_per_step'], 'raster_us', d['roofline']['kernel_avg_us'])"
+      python bench.py --steps 200 --warmup 20 --full --no-cpu --lights $L 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$which', 'lights', $L, 'ms', d['ms_per_step'], 'raster_us', d['roofline']['kernel_avg_us'])"
     done
   done
 done

@@ -5,7 +5,7 @@ set -u
 TAG=${1:-final}
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
-python3 bench.py > "$OUT/bench_line.json" 2> "$OUT/bench_line.err"
+python3 bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench_line.err"
 echo "bench line done"
 python3 tools/run_configs.py --configs C2,C3,C4,C5s,C5s_shader,D2 --oracle C2,C3,C4,C5s,C5s_shader,D2 --frames 30 > "$OUT/configs.jsonl" 2> "$OUT/configs.err"
 python3 tools/run_configs.py --configs C5,C5shader --oracle C5,C5shader --frames 30 >> "$OUT/configs.jsonl" 2>> "$OUT/configs.err"

@@ -6,7 +6,7 @@ TAG=$1; shift
 export TMPDIR=/tmp
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
-ARGS="bench.py --steps 10 --warmup 2 --no-cpu --no-e2e $*"
+ARGS="bench.py --steps 10 --warmup 2 --full --no-cpu --no-e2e $*"
 RXR_BENCH_MIN_TIMED_S=0.01 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_CVT \
     --output-format csv -d "$OUT/pmc_a" -- python3 $ARGS > "$OUT/a.log" 2>&1
 RXR_BENCH_MIN_TIMED_S=0.01 rocprofv3 --pmc SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SMEM SQ_WAVE_CYCLES \
