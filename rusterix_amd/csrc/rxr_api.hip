@@ -1251,15 +1251,19 @@ int rxr_upload_frame(rxr_ctx *ctx, const rxr_frame *f) {
     };
     const bool with_tri_info = !use_meshes && n_t3 > 0 && n_t3 <= RXR_TRI_INFO_MAX;
     L.off_tinfo = take(with_tri_info ? n_t3 * sizeof(uint2) : 0);
-    // host-projected 3D batches whose bounding-box arithmetic the reference's per-tile test cannot be trusted with (rxr_device.h,
-    // rxr_ref_tile_span): per batch the pixels the reference draws it in
+    // host-projected 3D batches: per batch the pixels the reference draws it in (rxr_ref_tile_span), to which make_setup clips the pixel
+    // boxes of its triangles.  Needed for a batch whose bounding-box arithmetic the reference's per-tile test cannot be trusted with
+    // (rxr_device.h), and for EVERY batch of a frame whose raster grid is narrowed to row spans (spans_active, decided below from the same
+    // rectangles): a triangle counted into a bin outside its row's span leaves that bin non-zero -- no workgroup hands it back -- and an
+    // ordinary box can end short of its triangles too (`x + width` rounds below the maximum; a caller's box that does not enclose them)
     bool any_risky3d = false;
     if (!(use_meshes & 1u))
         for (uint32_t i = 0; i < n_b3 && !any_risky3d; ++i) {
             const rxr_batch3d &b = f->batches3d[i];
             any_risky3d = b.has_bounding_box && b.n_triangles > 0 && rxr_box_is_risky(b.bounding_box[0], b.bounding_box[1], b.bounding_box[2], b.bounding_box[3]);
         }
-    L.off_clip3d = take(any_risky3d ? n_b3 * sizeof(uint4) : 0);
+    const bool with_clip3d = any_risky3d || (!use_meshes && (f->flags & RXR_FLAG_D3_ACTIVE) && f->tile_size > 0);  // (a superset of spans_active)
+    L.off_clip3d = take(with_clip3d ? n_b3 * sizeof(uint4) : 0);
     L.off_lights = take(f->n_lights * sizeof(rxr_light));
     L.off_lights_fast = take(f->n_lights * sizeof(LightFast));
     L.off_occ = take(n_occ_total * sizeof(rxr_occluder));
@@ -1367,6 +1371,7 @@ int rxr_upload_frame(rxr_ctx *ctx, const rxr_frame *f) {
     const float W = (float)f->width, H = (float)f->height;
     DevBatch *b3 = (DevBatch *)(st + L.off_b3);
     uint32_t *base = (uint32_t *)(st + L.off_base);
+    uint4 *clip3d = with_clip3d ? (uint4 *)(st + L.off_clip3d) : nullptr;
     size_t vcur = 0, tcur = 0;
     for (uint32_t i = 0; i < f->n_batches3d; ++i) {
         const rxr_batch3d &b = f->batches3d[i];
@@ -1392,19 +1397,20 @@ int rxr_upload_frame(rxr_ctx *ctx, const rxr_frame *f) {
             keep = bb[0] < W && (bb[0] + bb[2]) > 0.0f && bb[1] < H && (bb[1] + bb[3]) > 0.0f;
         }
         if ((rc = classify3d(d, b.source, b.chunk, b.shader, b.list, keep, "batch3d")) != RXR_OK) return rc;
+        if (clip3d) clip3d[i] = make_uint4(0u, f->width, 0u, f->height);  // (a skipped batch's triangles get no pixel box at all)
         if (!keep) d.flags |= DB_SKIP;
         else {
             any_3d_visible = true;
             {
-                uint32_t y0 = 0, y1 = 0;
+                uint32_t x0 = 0, x1 = 0, y0 = 0, y1 = 0;
                 rxr_ref_tile_span(b.bounding_box[1], b.bounding_box[3], f->height, f->tile_size, 0.0f, y0, y1);
+                rxr_ref_tile_span(b.bounding_box[0], b.bounding_box[2], f->width, f->tile_size, 0.0f, x0, x1);
                 if (y0 < y1) {
                     content_y0 = std::min(content_y0, y0);
                     content_y1 = std::max(content_y1, y1);
-                    uint32_t x0 = 0, x1 = 0;
-                    rxr_ref_tile_span(b.bounding_box[0], b.bounding_box[2], f->width, f->tile_size, 0.0f, x0, x1);
                     add_span(x0, x1, y0, y1);
                 }
+                if (clip3d) clip3d[i] = make_uint4(x0, x1, y0, y1);  // (empty when the reference draws the batch nowhere)
             }
             if (d.program_plus1) uses_programs = any_3d_program = true;
             if ((d.flags & (DB_TERRAIN | DB_FULL_ALPHA)) || d.baked_plus1) uses_chunk_tex = true;
@@ -1426,18 +1432,6 @@ int rxr_upload_frame(rxr_ctx *ctx, const rxr_frame *f) {
         uint2 *ti = (uint2 *)(st + L.off_tinfo);
         for (uint32_t i = 0; i < f->n_batches3d; ++i)
             for (uint32_t t = 0; t < f->batches3d[i].n_triangles; ++t) ti[b3[i].tri_base + t] = make_uint2(i, b3[i].vert_base);
-    }
-    if (any_risky3d) {
-        uint4 *clip = (uint4 *)(st + L.off_clip3d);
-        for (uint32_t i = 0; i < n_b3; ++i) {
-            const rxr_batch3d &b = f->batches3d[i];
-            uint4 c = make_uint4(0u, f->width, 0u, f->height);
-            if (b.has_bounding_box && rxr_box_is_risky(b.bounding_box[0], b.bounding_box[1], b.bounding_box[2], b.bounding_box[3])) {
-                rxr_ref_tile_span(b.bounding_box[0], b.bounding_box[2], f->width, f->tile_size, 0.0f, c.x, c.y);
-                rxr_ref_tile_span(b.bounding_box[1], b.bounding_box[3], f->height, f->tile_size, 0.0f, c.z, c.w);
-            }
-            clip[i] = c;
-        }
     }
     // the arrays themselves: independent per batch (offsets are in the headers just written), through the host worker pool --
     // 124 MB for the 1 M-triangle grid, which one thread copies in about as long as the GPU takes for forty frames
@@ -2035,7 +2029,7 @@ int rxr_upload_frame(rxr_ctx *ctx, const rxr_frame *f) {
     P.batches3d = (const DevBatch *)(d + L.off_b3);
     P.batch_tri_base = (const uint32_t *)(d + L.off_base);
     P.tri_info = with_tri_info ? (const uint2 *)(d + L.off_tinfo) : nullptr;
-    P.batch_clip3d = any_risky3d ? (const uint4 *)(d + L.off_clip3d) : nullptr;
+    P.batch_clip3d = any_risky3d ? (const uint4 *)(d + L.off_clip3d) : nullptr;   // (and below, when the frame takes row spans)
     P.ref_tile = f->tile_size;
     P.tri_setup = (TriSetup *)ctx->d_tri_setup.p;
     P.tri_shade = (TriShade *)ctx->d_tri_shade.p;
@@ -2134,6 +2128,7 @@ int rxr_upload_frame(rxr_ctx *ctx, const rxr_frame *f) {
             if ((rc2 = ensure(ctx, ctx->d_row_spans, RXR_MAX_TILE_ROWS * sizeof(uint2))) != RXR_OK) return rc2;
             HIPCHK(ctx, hipMemcpyAsync(ctx->d_row_spans.p, ctx->h_row_spans, n_tile_rows * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
             ctx->spans_active = true;
+            P.batch_clip3d = (const uint4 *)(d + L.off_clip3d);  // every triangle inside its batch's tiles: the bins it counts lie in the spans
         }
     }
     // Device-projected 3D meshes: their boxes are made on the device, frame by frame -- the table goes there holding what is known here
@@ -2324,7 +2319,9 @@ static int render_impl(rxr_ctx *ctx, const RenderSpec &spec, void *dev_pixels, h
     } else if (prepass) {
         ctx->scratch_dirty = true;
         // counter set `parity` is clean (cleared by the previous launch's k_scan); this launch's k_scan
-        // clears the other set.  bin_count is clean because k_raster hands every bin back zeroed.
+        // clears the other set.  bin_count is clean because k_raster hands every bin back zeroed -- under row spans every bin that a
+        // triangle is counted into lies inside its row's span (make_setup clips the pixel boxes to the batch's reference tiles, from which
+        // the spans are made), so its workgroup runs and hands it back too.
         P.counters = (uint32_t *)ctx->d_counters.p + (size_t)ctx->parity * CNT_WORDS;
         P.counters_next = (uint32_t *)ctx->d_counters.p + (size_t)(ctx->parity ^ 1u) * CNT_WORDS;
         ctx->parity ^= 1u;
@@ -3516,6 +3513,47 @@ extern "C" int rxr_debug_content(rxr_ctx *ctx, uint32_t *out) {
     out[1] = ctx->content_row0;
     out[2] = ctx->content_row1;
     out[3] = ctx->spans_active ? 1u : (ctx->dev_spans ? 2u : 0u);  // (2: completed on the device from the meshes' boxes)
+    return 0;
+}
+// tests: the scratch words the next launch assumes clear, read back after the context's streams have drained.  Checked:
+//   buffer 0: every word of d_bin_count -- bin_count (rxr_device.h RasterParams.bin_count: "all-zero between launches", k_raster hands its
+//             bin back) and k_blockscan's per-block group counts behind it (RasterParams.blk_cnt: "all-zero between launches: k_blockscan
+//             hands it back"); the rest of the allocation is zeroed when it is made (rxr_upload_frame) and never written;
+//   buffer 1: words CNT_LARGE and CNT_TICKET of the 3D counter set `parity` (render_impl: "counter set `parity` is clean (cleared by the
+//             previous launch's k_scan)"; the next launch adds to those two with atomics, CNT_ENTRIES / CNT_OVERFLOW it writes before use);
+//   buffer 2: the same words of the 2D set 2 + parity2d (cleared likewise by the previous 2D k_scan);
+//   buffer 3: every word of d_bin2d_count (RasterParams.bin2d_count: "own zero-invariant buffer, like bin_count").
+// out[0] = number of non-zero words, out[1..3] = buffer, word index, value of the first one (all 0 when clean).  A context whose last launch
+// sequence was cut short (scratch_dirty) is reported as it is: its next launch restores the invariants anyway.  Finding dirt marks the
+// context dirty, so that its next launch clears the buffers instead of building on them (a failed check leaves nothing behind).
+extern "C" int rxr_debug_scratch(rxr_ctx *ctx, uint32_t *out) {
+    if (!ctx || ctx->group || !out) return -1;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = rxr_quiesce(ctx);
+    if (rc != RXR_OK) return rc;
+    out[0] = out[1] = out[2] = out[3] = 0u;
+    auto scan = [&](uint32_t id, const uint32_t *dev, size_t words, uint32_t index0) -> int {
+        if (!dev || !words) return RXR_OK;
+        std::vector<uint32_t> h(words);
+        HIPCHK(ctx, hipMemcpy(h.data(), dev, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < words; ++i)
+            if (h[i]) {
+                if (!out[0]) out[1] = id, out[2] = index0 + (uint32_t)i, out[3] = h[i];
+                out[0]++;
+            }
+        return RXR_OK;
+    };
+    if ((rc = scan(0, (const uint32_t *)ctx->d_bin_count.p, ctx->d_bin_count.cap / sizeof(uint32_t), 0u)) != RXR_OK) return rc;
+    if (ctx->d_counters.p) {
+        const uint32_t *set3 = (const uint32_t *)ctx->d_counters.p + (size_t)ctx->parity * CNT_WORDS;
+        const uint32_t *set2 = (const uint32_t *)ctx->d_counters.p + (size_t)(2u + ctx->parity2d) * CNT_WORDS;
+        for (uint32_t w : {(uint32_t)CNT_LARGE, (uint32_t)CNT_TICKET})
+            if ((rc = scan(1, set3 + w, 1, w)) != RXR_OK) return rc;
+        for (uint32_t w : {(uint32_t)CNT_LARGE, (uint32_t)CNT_TICKET})
+            if ((rc = scan(2, set2 + w, 1, w)) != RXR_OK) return rc;
+    }
+    if ((rc = scan(3, (const uint32_t *)ctx->d_bin2d_count.p, ctx->d_bin2d_count.cap / sizeof(uint32_t), 0u)) != RXR_OK) return rc;
+    if (out[0]) ctx->scratch_dirty = ctx->scratch2d_dirty = true;
     return 0;
 }
 // tests (host only, no device): rxr_ref_tile_span (quick == 0) / rxr_ref_tile_span_quick of n boxes [lo, lo + extent] on one axis; out: p0, p1 per box

@@ -323,8 +323,9 @@ struct RasterParams {
     uint32_t list2d_capacity;
     uint32_t list_capacity;
     uint32_t ref_tile;             // the reference's tile_size (rxr_frame.tile_size): only the batch box test of RISKY batches depends on it
-    const uint4 *batch_clip3d;     // host-projected frames with a risky 3D batch: per batch the pixels (x0, x1, y0, y1) the reference draws it in
-                                   // (rxr_ref_tile_span; ordinary batches: the whole frame); NULL otherwise.  make_setup clips the pixel boxes
+    const uint4 *batch_clip3d;     // host-projected frames with a risky 3D batch or under row spans: per batch the pixels (x0, x1, y0, y1) the
+                                   // reference draws it in (rxr_ref_tile_span; skipped batches: the whole frame); NULL otherwise.  make_setup
+                                   // clips the pixel boxes (device-projected frames: from dev_bbox, for risky boxes and under row_spans)
     uint32_t fused_small;          // small-scene mode (whole frame <= RXR_STAGE_TRIS triangles): 0 = binned pipeline,
                                    // 1 = fully fused (k_raster_fused builds the records itself, no pre-pass launch),
                                    // 2 = implicit list (k_setup3d writes the records, no scan / fill / bins; default)
@@ -352,7 +353,9 @@ struct RasterParams {
     uint2 *group_rng;                  // k_blockscan: per wave of k_setup3d (64 consecutive triangles) the union of its triangles' bin ranges,
                                        // packed like a triangle's (bx0 | bx1 << 16, l0 | l1 << 16); (0xFFFF, 0xFFFF) -- first bin 65535, last bin 0 -- when no triangle of the group has one
     uint2 *tri_box;                    // (bx, by) of every TriSetup once more, densely: k_fill reads these 8 bytes instead of a 96-byte stride
-    uint32_t *bin_count;           // tiles_x * tiles_y; all-zero between launches (k_raster clears its own bin)
+    uint32_t *bin_count;           // tiles_x * tiles_y; all-zero between launches (k_raster clears its own bin; under row_spans a triangle is
+                                   // counted only inside its batch's reference tiles, of which the spans are made: every non-zero bin's
+                                   // workgroup runs)
     uint32_t *bin_offset;          // chunk-local exclusive scan of bin_count; add chunk_base[bin / RXR_SCAN_CHUNK]
     uint32_t *bin_cursor;
     uint32_t *chunk_tot;           // per k_scan workgroup: number of list entries of its chunk

@@ -1395,19 +1395,21 @@ __device__ __forceinline__ bool make_setup(const RasterParams &P, uint32_t t, Tr
     uint32_t max_x = sat_index(fminf(ceilf(max_xf), (float)P.width), 0xFFFFu);
     uint32_t min_y = sat_index(fmaxf(floorf(min_yf), (float)P.row0), 0xFFFFu);
     uint32_t max_y = sat_index(fminf(ceilf(max_yf), (float)P.row1), 0xFFFFu);
-    // a batch whose box arithmetic the reference's per-tile test cannot be trusted with (rxr_device.h, rxr_ref_tile_span): only the
-    // pixels of the tiles that pass it
-    if (P.batch_clip3d) {   // uniform: host-projected, some batch is risky
+    // only the pixels of the tiles that pass the reference's batch box test (rxr_device.h, rxr_ref_tile_span), for a batch whose box
+    // arithmetic that test cannot be trusted with -- and for every batch of a launch narrowed to row spans: the spans are made of these
+    // rectangles, so a triangle is then counted only into bins whose workgroups run and hand them back zeroed (the box of an ordinary
+    // batch can end short of its triangles: `x + width` rounds below the maximum, or a caller's box does not enclose them)
+    if (P.batch_clip3d) {   // uniform: host-projected, some batch is risky or the frame takes row spans
         const uint4 c = P.batch_clip3d[lo];
         min_x = max(min_x, c.x); max_x = min(max_x, c.y); min_y = max(min_y, c.z); max_y = min(max_y, c.w);
     } else if (P.dev_bbox) {   // device-projected: the box is here
         const DevBBox bb = P.dev_bbox[lo];
         auto dec = [](uint32_t e) { return __uint_as_float((e & 0x80000000u) ? (e ^ 0x80000000u) : ~e); };
         const float bx = dec(bb.min_x), by = dec(bb.min_y), bw = dec(bb.max_x) - bx, bh = dec(bb.max_y) - by;
-        if (rxr_box_is_risky(bx, by, bw, bh)) {
+        if (P.row_spans || rxr_box_is_risky(bx, by, bw, bh)) {   // (row_spans: k_spans_from_meshes made them from these boxes, the same way)
             uint32_t x0, x1, y0, y1;
-            rxr_ref_tile_span(bx, bw, P.width, P.ref_tile, 0.0f, x0, x1);
-            rxr_ref_tile_span(by, bh, P.height, P.ref_tile, 0.0f, y0, y1);
+            rxr_ref_tile_span_quick(bx, bw, P.width, P.ref_tile, 0.0f, x0, x1);
+            rxr_ref_tile_span_quick(by, bh, P.height, P.ref_tile, 0.0f, y0, y1);
             min_x = max(min_x, x0); max_x = min(max_x, x1); min_y = max(min_y, y0); max_y = min(max_y, y1);
         }
     }

@@ -57,7 +57,10 @@ def test_stripes_and_bands_of_a_mid_sized_scene(product):
     import rusterix_amd
 
     cfg = scenes.teapot_scene(product, width=640, height=250, logo_size=64, rect_size=20.0)   # 250 rows: ragged last stripe
+    from tests.test_gpu_sparse_frames import assert_scratch_clean
+
     full = scenes.render(cfg).copy()
+    assert_scratch_clean(product, "whole frame")
     rxr = rusterix_amd.rxr_abi()
     host = product.lib
     r = cfg.setup()
@@ -66,6 +69,7 @@ def test_stripes_and_bands_of_a_mid_sized_scene(product):
     out = np.zeros((cfg.height, cfg.width, 4), np.uint8)
     for row0, row1 in ((0, 64), (64, 176), (176, 250)):
         assert rxr.rxr_render_rows(ctx, row0, row1) == 0
+        assert_scratch_clean(product, f"band [{row0}, {row1})")
         assert rxr.rxr_download_rows(ctx, out.ctypes.data_as(C.c_void_p), row0, row1) == 0
     assert_exact(out, full, "three bands")
 

@@ -309,14 +309,18 @@ def test_sparse_frames_take_their_row_spans_from_the_device_boxes(oracle, produc
     oracle's, the host-projected one, the one with the spans switched off, and the one assembled from row bands."""
     import ctypes as C
 
+    from tests.test_gpu_sparse_frames import assert_scratch_clean
+
     monkeypatch.setenv("RXR_CONTENT_MIN_TILES", "0")   # (the table only pays on large frames: these are small)
     devproj.off()
     want = scenes.render(_sparse_mesh_scene(product, kind)).copy()
+    assert_scratch_clean(product, f"{kind}, host-projected")
     ref = scenes.render(_sparse_mesh_scene(oracle, kind))
     assert np.array_equal(want, ref), kind
     devproj.on()
     cfg = _sparse_mesh_scene(product, kind)
     got = scenes.render(cfg).copy()
+    assert_scratch_clean(product, kind)
     assert np.array_equal(got, ref), f"{kind}: {(got != ref).any(axis=2).sum()} pixels differ"
     lib = product.lib
     rxr = C.CDLL(__import__("rusterix_amd").lib_paths()["rxr"])   # (a handle of its own: the argtypes set below stay here)
@@ -328,9 +332,11 @@ def test_sparse_frames_take_their_row_spans_from_the_device_boxes(oracle, produc
         hit_cols = np.nonzero((got[..., :3].max(axis=2) > 0).any(axis=0))[0]
         assert hit_cols.min() > 32 or hit_cols.max() < cfg.width - 32, "the scene leaves no tile columns empty: it tests nothing"
     again = scenes.render(cfg).copy()                     # (the second frame re-uploads the host part and completes it again)
+    assert_scratch_clean(product, f"{kind}, second frame")
     assert np.array_equal(again, ref)
     monkeypatch.setenv("RXR_ROW_SPANS", "0")
     off = scenes.render(cfg).copy()
+    assert_scratch_clean(product, f"{kind} without row spans")
     assert rxr.rxr_debug_content(C.c_void_p(lib.rxh_context()), info) == 0 and info[3] == 0
     monkeypatch.delenv("RXR_ROW_SPANS")
     assert np.array_equal(off, ref)
@@ -345,11 +351,13 @@ def test_sparse_frames_take_their_row_spans_from_the_device_boxes(oracle, produc
     H = cfg.height
     for a, b in [(0, 37), (37, H // 2 + 5), (H // 2 + 5, H)]:
         assert rxr.rxr_render_rows(ctx, a, b) == 0
+        assert_scratch_clean(product, f"{kind}: band [{a}, {b})")
         assert rxr.rxr_download_rows(ctx, bands.ctypes.data_as(C.POINTER(C.c_uint8)), a, b) == 0   # (full-frame layout: row r at r * width * 4)
     assert np.array_equal(bands, ref), kind
     rxr.rxr_render_download.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
     piped = np.full_like(got, 7)
     assert rxr.rxr_render_download(ctx, piped.ctypes.data_as(C.POINTER(C.c_uint8))) == 0
+    assert_scratch_clean(product, f"{kind}: pipelined download")
     assert np.array_equal(piped, ref), kind
 
 

@@ -390,9 +390,12 @@ def test_rows_without_content_are_filled_not_rastered(oracle, product, kind, mon
     clamp switched off (RXR_CONTENT_ROWS=0), and the frame assembled from row bands that cut through content and emptiness alike."""
     import ctypes as C
 
+    from tests.test_gpu_sparse_frames import assert_scratch_clean
+
     monkeypatch.setenv("RXR_CONTENT_MIN_TILES", "0")   # (the clamps only pay from 8192 empty tiles on: these frames are small)
     cfg = _sparse_scene(product, kind)
     got = scenes.render(cfg).copy()
+    assert_scratch_clean(product, f"sparse frame ({kind})")
     ref = scenes.render(_sparse_scene(oracle, kind))
     assert_exact(got, ref, f"sparse frame ({kind}) vs oracle")
     hit_rows = np.nonzero((got[..., :3].max(axis=2) > 0).any(axis=1))[0]
@@ -412,11 +415,13 @@ def test_rows_without_content_are_filled_not_rastered(oracle, product, kind, mon
         assert info[1] >= info[2], list(info)
     monkeypatch.setenv("RXR_ROW_SPANS", "0")
     no_spans = scenes.render(cfg).copy()
+    assert_scratch_clean(product, f"sparse frame ({kind}) without row spans")
     assert rxr.rxr_debug_content(C.c_void_p(lib.rxh_context()), info) == 0 and info[3] == 0
     monkeypatch.delenv("RXR_ROW_SPANS")
     assert_exact(got, no_spans, f"sparse frame ({kind}): row spans on vs off")
     monkeypatch.setenv("RXR_CONTENT_ROWS", "0")
     unclamped = scenes.render(cfg).copy()
+    assert_scratch_clean(product, f"sparse frame ({kind}) without the clamp")
     assert rxr.rxr_debug_content(C.c_void_p(lib.rxh_context()), info) == 0 and info[0] == 0 and info[3] == 0
     monkeypatch.delenv("RXR_CONTENT_ROWS")
     assert_exact(got, unclamped, f"sparse frame ({kind}): clamp on vs off")
@@ -431,6 +436,7 @@ def test_rows_without_content_are_filled_not_rastered(oracle, product, kind, mon
     cuts = sorted({0, 5, H // 7, H // 3 + 1, H // 2, (2 * H) // 3 + 3, H - 9, H})
     for a, b in zip(cuts[:-1], cuts[1:]):
         assert rxr.rxr_render_rows(ctx, a, b) == 0
+        assert_scratch_clean(product, f"sparse frame ({kind}): band [{a}, {b})")
         assert rxr.rxr_download_rows(ctx, out.ctypes.data_as(C.POINTER(C.c_uint8)), a, b) == 0
     assert_exact(out, got, f"sparse frame ({kind}): row bands vs whole frame")
 
