@@ -634,6 +634,32 @@ void *rxr_device_framebuffer(rxr_ctx *ctx);
 #define RXR_MATH_KINDS 13
 int rxr_selftest_math(rxr_ctx *ctx, uint64_t n_tuples, uint64_t seed, uint64_t mismatches[RXR_MATH_KINDS]);
 
+/* ---- ray picking over the meshes of the last rxr_set_meshes (rusterix_amd/csrc/rxr_intersect.hip) ---------------------------
+ * Scene::intersect (src/scene.rs:216-276) with Batch3D::intersect per mesh (src/batch/batch3d.rs:844-948), exact to the bit:
+ * Moeller-Trumbore on the OBJECT-SPACE vertices (transform_3d is ignored, as in the reference) against the normalised direction;
+ * the closest hit per mesh (the earliest triangle on equal t); the meshes folded in array order -- RXR_LIST_CHUNK_OPACITY /
+ * _CHUNK_TERRAIN / _STATIC / _DYNAMIC replace the best hit when closer, RXR_LIST_CHUNK the same unless the hit's profile id equals
+ * the best's, RXR_LIST_OVERLAY replaces it whenever it hits.  Per ray: t (FLT_MAX on a miss), mesh (the index into the
+ * rxr_set_meshes array -- which recovers profile_id and geometry_source -- or UINT32_MAX on a miss), triangle (mesh-local; 0 on a
+ * miss), hitpoint = origin + dir * t with the caller's un-normalised dir ((0,0,0) on a miss).  RXR_INTERSECT_FULL adds what
+ * Batch3D::intersect(ray, false) computes: the interpolated uv and the interpolated, normalised normal facing against dir (zeros
+ * on a miss); the choice of hit is the same.  NULL required pointers: RXR_ERR_INVALID; n_rays == 0 does nothing; no meshes
+ * registered: every ray misses.  An intersect changes no frame state: a frame uploaded before it renders as it would have.  Nothing
+ * of this is part of Rasterizer::rasterize. */
+#define RXR_INTERSECT_FULL (1u << 0)   /* Batch3D::intersect(ray, false): uv + normal as well */
+/* host arrays, blocking: origins / dirs [n][3]; hitpoint [n][3], uv [n][2], normal [n][3] may be NULL.  Multi-device handles: member 0. */
+int rxr_intersect(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n_rays, uint32_t flags, float *t, uint32_t *mesh,
+                  uint32_t *triangle, float *hitpoint, float *uv, float *normal);
+/* the same on DEVICE arrays, queued on hip_stream (NULL = the context's stream; asynchronous).  Multi-device handles:
+ * RXR_ERR_UNSUPPORTED (use rxr_member). */
+int rxr_intersect_to(rxr_ctx *ctx, const float *dev_origins, const float *dev_dirs, uint32_t n_rays, uint32_t flags, float *dev_t,
+                     uint32_t *dev_mesh, uint32_t *dev_triangle, float *dev_hitpoint, float *dev_uv, float *dev_normal, void *hip_stream);
+/* Rasterizer::screen_ray (src/rasterizer.rs:1843-1870) for every pixel (x, y) of [x0, x0+w) x [y0, y0+h), row-major, into device
+ * arrays [w*h][3]: inverse_view / inverse_projection are column-major 4x4 matrices, width / height the viewport.  Queued on
+ * hip_stream (NULL = the context's stream).  Multi-device handles: RXR_ERR_UNSUPPORTED. */
+int rxr_screen_rays_to(rxr_ctx *ctx, const float *inverse_view, const float *inverse_projection, float width, float height,
+                       uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, float *dev_origins, float *dev_dirs, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

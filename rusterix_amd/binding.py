@@ -457,6 +457,12 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         camera_firstp=fn("camera_firstp", None, pf, pf, f32, f32, f32, f32, f32, pf, pf),
     )
 
+    # ray picking (product host library only: the oracle has no such symbols, and loading it must keep working)
+    has_intersect = hasattr(lib, prefix + "scene_intersect")
+    if has_intersect:
+        L.scene_intersect = fn("scene_intersect", i32, vp, pf, pf, u32, u32, pf, pu, pu, pf, pf, pf)
+        L.rasterizer_screen_ray = fn("rasterizer_screen_ray", None, vp, f32, f32, pf, pf)
+
     def tile_args(tile: Tile):
         n = len(tile.textures)
         frames = (pb * n)(*[_bp(t.data) for t in tile.textures])
@@ -741,6 +747,34 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         def num_dynamic_lights(self):
             return L.scene_num_dynamic_lights(self._h)
 
+        def intersect(self, origins, dirs, full=False):
+            """Scene::intersect (reference src/scene.rs:216-276) for every ray of origins / dirs ([n][3]), on the device
+            (rxr_intersect, include/rxr.h).  Returns a dict of numpy arrays: t ([n], f32::MAX on a miss), mesh ([n], the batch's
+            position in the order chunks (opacity, batches, terrain per chunk), static, dynamic, overlay; 0xFFFFFFFF on a miss),
+            triangle ([n]), hitpoint ([n][3]) and, with full=True (Batch3D::intersect(ray, false)), uv ([n][2]) and normal ([n][3])."""
+            if not has_intersect:
+                raise NotImplementedError(f"{name}: no ray intersection in this library")
+            o = np.ascontiguousarray(np.asarray(origins, np.float32).reshape(-1, 3))
+            d = np.ascontiguousarray(np.asarray(dirs, np.float32).reshape(-1, 3))
+            if o.shape != d.shape:
+                raise ValueError("origins and dirs must have the same number of rays")
+            n = o.shape[0]
+            out = dict(t=np.zeros(n, np.float32), mesh=np.zeros(n, np.uint32), triangle=np.zeros(n, np.uint32),
+                       hitpoint=np.zeros((n, 3), np.float32))
+            if full:
+                out["uv"] = np.zeros((n, 2), np.float32)
+                out["normal"] = np.zeros((n, 3), np.float32)
+            rc = L.scene_intersect(self._h, _fp(o), _fp(d), n, 1 if full else 0, _fp(out["t"]), _up(out["mesh"]), _up(out["triangle"]),
+                                   _fp(out["hitpoint"]), _fp(out["uv"]) if full else None, _fp(out["normal"]) if full else None)
+            if rc != 0:
+                msg = ""
+                if hasattr(lib, prefix + "last_error"):
+                    f = getattr(lib, prefix + "last_error")
+                    f.restype = C.c_char_p
+                    msg = (f() or b"").decode()
+                raise RasterizeError(rc, msg)
+            return out
+
         def projected_batch3d(self, list_kind, index, chunk=-1):
             """Outputs of clip_and_project for one batch (after rasterize): dict of numpy arrays."""
             nv, nt, hn = C.c_uint32(), C.c_uint32(), C.c_uint32()
@@ -884,6 +918,15 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
             iv, ip, cp = np.zeros(16, np.float32), np.zeros(16, np.float32), np.zeros(3, np.float32)
             L.rasterizer_get_derived(self._h, _fp(iv), _fp(ip), _fp(cp))
             return iv, ip, cp
+
+        def screen_ray(self, x, y):
+            """Rasterizer::screen_ray (reference src/rasterizer.rs:1843-1870): (origin, dir) as numpy arrays; the viewport is that of
+            the last rasterize (0 x 0 before, as in the reference)."""
+            if not has_intersect:
+                raise NotImplementedError(f"{name}: no screen_ray in this library")
+            o, d = np.zeros(3, np.float32), np.zeros(3, np.float32)
+            L.rasterizer_screen_ray(self._h, float(x), float(y), _fp(o), _fp(d))
+            return o, d
 
         def project(self, scene, width, height):
             """Host-side `scene.project(..)` only (reference src/scene.rs:154-200)."""

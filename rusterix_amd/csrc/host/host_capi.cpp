@@ -65,6 +65,11 @@ int rxh_get_light_math_exact() { return light_math_exact() ? 1 : 0; }
 
 // ---- scene ----------------------------------------------------------------------------------------
 void *rxh_scene_new() { return new Scene(); }
+// Scene::intersect for n rays (rxr_intersect's arrays and flags, include/rxr.h); RXR_OK or a negative rxr_status
+int rxh_scene_intersect(void *s, const float *origins, const float *dirs, uint32_t n, uint32_t flags, float *t, uint32_t *mesh,
+                        uint32_t *triangle, float *hitpoint, float *uv, float *normal) {
+    return ((Scene *)s)->intersect(origins, dirs, n, flags, t, mesh, triangle, hitpoint, uv, normal);
+}
 void rxh_scene_free(void *s) { delete (Scene *)s; }
 void rxh_scene_set_animation_frame(void *s, uint64_t f) { ((Scene *)s)->animation_frame = (size_t)f; }
 void rxh_scene_set_background(void *s, int kind) { ((Scene *)s)->background = (uint32_t)kind; }
@@ -311,6 +316,8 @@ void rxh_rasterizer_get_derived(void *r, float *inv_view16, float *inv_proj16, f
     memcpy(inv_proj16, x->inverse_projection_matrix.m, 64);
     camera_pos3[0] = x->camera_pos.x; camera_pos3[1] = x->camera_pos.y; camera_pos3[2] = x->camera_pos.z;
 }
+// Rasterizer::screen_ray (src/rasterizer.rs:1843-1870): origin3 / dir3 receive the ray
+void rxh_rasterizer_screen_ray(void *r, float x, float y, float *origin3, float *dir3) { ((Rasterizer *)r)->screen_ray(x, y, origin3, dir3); }
 int rxh_rasterizer_rasterize(void *r, void *scene, uint8_t *pixels, uint32_t w, uint32_t h, uint32_t tile_size, void *assets) {
     return ((Rasterizer *)r)->rasterize(*(Scene *)scene, pixels, w, h, tile_size, *(Assets *)assets);
 }

@@ -496,6 +496,7 @@ bool g_device_edges = !(getenv("RXR_HOST_EDGES") && atoi(getenv("RXR_HOST_EDGES"
 thread_local bool t_frame_edgeless = true;
 int g_light_math = RXR_LIGHT_MATH_RELAXED;  // the library's default
 uint64_t g_mesh_fingerprint = 0;
+uint64_t g_mesh_geometry_fingerprint = 0;  // what rxr_intersect reads of the registered meshes (Scene::intersect)
 uint64_t g_mesh2d_fingerprint = 0;
 }  // namespace
 
@@ -516,7 +517,7 @@ namespace {
 void drop_context_locked() {
     if (g_ctx) rxr_destroy(g_ctx);
     g_ctx = nullptr;
-    g_mesh_fingerprint = 0;
+    g_mesh_fingerprint = g_mesh_geometry_fingerprint = 0;
     g_mesh2d_fingerprint = 0;
     g_tex_static_gen = g_tex_dynamic_gen = 0;
     g_shaders_gen = g_shader_env_gen = 0;
@@ -666,6 +667,117 @@ rxr_batch2d view2d(const Batch2D &b, int chunk, const SequenceSlots &slots) {
 }
 
 }  // namespace
+
+namespace {
+
+// The scene's 3D batches as object-space meshes in submission order -- per chunk opacity, chunk, terrain; then static, dynamic, overlay
+// (the order of Rasterizer::upload's frame and of Scene::intersect, src/scene.rs:216-276) -- and two FNV-1a fingerprints: `full` over
+// everything rxr_set_meshes copies (transforms travel per frame), `geometry` over what rxr_intersect reads of it.  slots == nullptr
+// (an intersect without a frame): sources are left unresolved; they are not read by rxr_intersect.  false: a batch with triangles but
+// without normals (clip_and_project panics at batch3d.rs:605, and rxr_set_meshes refuses it).
+bool scene_meshes(const Scene &scene, const SequenceSlots *slots, std::vector<rxr_mesh3d> &meshes, std::vector<float> *transforms,
+                  uint64_t &full, uint64_t &geometry) {
+    full = geometry = 1469598103934665603ull;
+    auto mix = [](uint64_t &fp, const void *p, size_t n) {
+        const uint8_t *q = (const uint8_t *)p;
+        for (size_t i = 0; i < n; ++i) fp = (fp ^ q[i]) * 1099511628211ull;
+    };
+    auto add = [&](const Batch3D &b, uint32_t list, int chunk) -> bool {
+        if (!b.indices.empty() && b.normals.size() / 3 < b.vertex_count()) return false;  // batch3d.rs:605 panics
+        rxr_mesh3d m{};
+        m.vertices = b.vertices.data();
+        m.indices = b.indices.data();
+        m.uvs = b.uvs.data();
+        m.normals = b.normals.empty() ? nullptr : b.normals.data();
+        m.n_vertices = (uint32_t)b.vertex_count();
+        m.n_triangles = (uint32_t)b.triangle_count();
+        memcpy(m.transform_3d, b.transform_3d.m, 64);
+        m.cull_mode = (uint32_t)b.cull_mode_;
+        m.repeat_mode = b.repeat_mode_;
+        if (slots) m.source = slots->resolve(b.source_);
+        m.ambient_color[0] = b.ambient_color_.x; m.ambient_color[1] = b.ambient_color_.y; m.ambient_color[2] = b.ambient_color_.z;
+        m.shader = b.shader_;
+        m.has_profile_id = b.has_profile_id ? 1u : 0u;
+        m.profile_id = b.profile_id_;
+        m.list = list;
+        m.chunk = chunk;
+        meshes.push_back(m);
+        if (transforms) transforms->insert(transforms->end(), b.transform_3d.m, b.transform_3d.m + 16);
+        const uint32_t meta[12] = {m.n_vertices, m.n_triangles, m.cull_mode, m.repeat_mode, m.source.kind, m.source.index,
+                                   (uint32_t)m.shader, m.has_profile_id, m.profile_id, m.list, (uint32_t)m.chunk,
+                                   (uint32_t)b.normals.size()};
+        mix(full, meta, sizeof(meta));
+        mix(full, m.source.pixel, 4);
+        mix(full, m.ambient_color, 12);
+        mix(full, &b.geometry_stamp, 8);  // geometry identity (Batch3D::touch)
+        const uint32_t gmeta[7] = {m.n_vertices, m.n_triangles, m.has_profile_id, m.profile_id, m.list, (uint32_t)m.chunk,
+                                   (uint32_t)b.normals.size()};
+        mix(geometry, gmeta, sizeof(gmeta));
+        mix(geometry, &b.geometry_stamp, 8);
+        return true;
+    };
+    bool ok = true;
+    for (size_t c = 0; c < scene.chunks.size(); ++c) {
+        for (const Batch3D &b : scene.chunks[c].batches3d_opacity) ok = ok && add(b, RXR_LIST_CHUNK_OPACITY, (int)c);
+        for (const Batch3D &b : scene.chunks[c].batches3d) ok = ok && add(b, RXR_LIST_CHUNK, (int)c);
+        for (const Batch3D &b : scene.chunks[c].terrain_batch3d) ok = ok && add(b, RXR_LIST_CHUNK_TERRAIN, (int)c);
+    }
+    for (const Batch3D &b : scene.d3_static) ok = ok && add(b, RXR_LIST_STATIC, -1);
+    for (const Batch3D &b : scene.d3_dynamic) ok = ok && add(b, RXR_LIST_DYNAMIC, -1);
+    for (const Batch3D &b : scene.d3_overlay) ok = ok && add(b, RXR_LIST_OVERLAY, -1);
+    return ok;
+}
+
+// rxr_set_meshes + the two fingerprints of what the context now holds (full: 0 = not known, the next upload registers again)
+int register_meshes(rxr_ctx *ctx, const std::vector<rxr_mesh3d> &meshes, uint64_t full, uint64_t geometry) {
+    const int rc = rxr_set_meshes(ctx, meshes.data(), (uint32_t)meshes.size());
+    if (rc != RXR_OK) {
+        g_error = rxr_last_error(ctx);
+        g_mesh_fingerprint = g_mesh_geometry_fingerprint = 0;
+        return rc;
+    }
+    g_mesh_fingerprint = full;
+    g_mesh_geometry_fingerprint = geometry;
+    return RXR_OK;
+}
+
+}  // namespace
+
+int Scene::intersect(const float *origins, const float *dirs, uint32_t n, uint32_t flags, float *t, uint32_t *mesh, uint32_t *triangle,
+                     float *hitpoint, float *uv, float *normal) const {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::string err;
+    rxr_ctx *ctx = context(&err);
+    if (!ctx) return RXR_ERR_NO_DEVICE;
+    // registered again only when the geometry changed: rxr_set_meshes drops a frame that was uploaded but not yet rendered
+    std::vector<rxr_mesh3d> meshes;
+    uint64_t full = 0, geometry = 0;
+    if (!scene_meshes(*this, nullptr, meshes, nullptr, full, geometry)) {
+        g_error = "Scene::intersect: a batch with triangles but without normals cannot be registered (rxr_set_meshes)";
+        return RXR_ERR_INVALID;
+    }
+    if (geometry != g_mesh_geometry_fingerprint || !g_mesh_geometry_fingerprint) {
+        int rc = register_meshes(ctx, meshes, 0, geometry);  // (sources unresolved: the next device-projected upload registers again)
+        if (rc != RXR_OK) return rc;
+    }
+    const int rc = rxr_intersect(ctx, origins, dirs, n, flags, t, mesh, triangle, hitpoint, uv, normal);
+    if (rc != RXR_OK) g_error = rxr_last_error(ctx);
+    return rc;
+}
+
+void Rasterizer::screen_ray(float x, float y, float origin[3], float dir[3]) const {
+    const float ndc_x = 2.0f * (x / width) - 1.0f;
+    const float ndc_y = 1.0f - 2.0f * (y / height);  // flip y
+    Vec4 view_near = inverse_projection_matrix * Vec4{ndc_x, ndc_y, -1.0f, 1.0f};
+    Vec4 view_far = inverse_projection_matrix * Vec4{ndc_x, ndc_y, 1.0f, 1.0f};
+    view_near = view_near / view_near.w;
+    view_far = view_far / view_far.w;
+    const Vec4 world_near = inverse_view_matrix * view_near, world_far = inverse_view_matrix * view_far;
+    const Vec3 o{world_near.x, world_near.y, world_near.z}, target{world_far.x, world_far.y, world_far.z};
+    const Vec3 d = rvek::normalized(target - o);
+    origin[0] = o.x, origin[1] = o.y, origin[2] = o.z;
+    dir[0] = d.x, dir[1] = d.y, dir[2] = d.z;
+}
 
 int Rasterizer::upload(Scene &scene, size_t w, size_t h, size_t tile_size, const Assets &assets) {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
@@ -875,62 +987,14 @@ int Rasterizer::upload(Scene &scene, size_t w, size_t h, size_t tile_size, const
     std::vector<rxr_mesh3d> meshes;
     std::vector<float> mesh_transforms;
     if (on_device) {
-        uint64_t fp = 1469598103934665603ull;  // FNV-1a over what rxr_set_meshes copies (transforms travel per frame)
-        auto mix = [&](const void *p, size_t n) {
-            const uint8_t *q = (const uint8_t *)p;
-            for (size_t i = 0; i < n; ++i) fp = (fp ^ q[i]) * 1099511628211ull;
-        };
-        auto add = [&](const Batch3D &b, uint32_t list, int chunk) -> bool {
-            if (!b.indices.empty() && b.normals.size() / 3 < b.vertex_count()) return false;  // batch3d.rs:605 panics
-            rxr_mesh3d m{};
-            m.vertices = b.vertices.data();
-            m.indices = b.indices.data();
-            m.uvs = b.uvs.data();
-            m.normals = b.normals.empty() ? nullptr : b.normals.data();
-            m.n_vertices = (uint32_t)b.vertex_count();
-            m.n_triangles = (uint32_t)b.triangle_count();
-            memcpy(m.transform_3d, b.transform_3d.m, 64);
-            m.cull_mode = (uint32_t)b.cull_mode_;
-            m.repeat_mode = b.repeat_mode_;
-            m.source = slots.resolve(b.source_);
-            m.ambient_color[0] = b.ambient_color_.x; m.ambient_color[1] = b.ambient_color_.y; m.ambient_color[2] = b.ambient_color_.z;
-            m.shader = b.shader_;
-            m.has_profile_id = b.has_profile_id ? 1u : 0u;
-            m.profile_id = b.profile_id_;
-            m.list = list;
-            m.chunk = chunk;
-            meshes.push_back(m);
-            mesh_transforms.insert(mesh_transforms.end(), b.transform_3d.m, b.transform_3d.m + 16);
-            const uint32_t meta[12] = {m.n_vertices, m.n_triangles, m.cull_mode, m.repeat_mode, m.source.kind, m.source.index,
-                                       (uint32_t)m.shader, m.has_profile_id, m.profile_id, m.list, (uint32_t)m.chunk,
-                                       (uint32_t)b.normals.size()};
-            mix(meta, sizeof(meta));
-            mix(m.source.pixel, 4);
-            mix(m.ambient_color, 12);
-            mix(&b.geometry_stamp, 8);  // geometry identity (Batch3D::touch)
-            return true;
-        };
-        bool ok = true;
-        for (size_t c = 0; c < scene.chunks.size(); ++c) {
-            for (const Batch3D &b : scene.chunks[c].batches3d_opacity) ok = ok && add(b, RXR_LIST_CHUNK_OPACITY, (int)c);
-            for (const Batch3D &b : scene.chunks[c].batches3d) ok = ok && add(b, RXR_LIST_CHUNK, (int)c);
-            for (const Batch3D &b : scene.chunks[c].terrain_batch3d) ok = ok && add(b, RXR_LIST_CHUNK_TERRAIN, (int)c);
-        }
-        for (const Batch3D &b : scene.d3_static) ok = ok && add(b, RXR_LIST_STATIC, -1);
-        for (const Batch3D &b : scene.d3_dynamic) ok = ok && add(b, RXR_LIST_DYNAMIC, -1);
-        for (const Batch3D &b : scene.d3_overlay) ok = ok && add(b, RXR_LIST_OVERLAY, -1);
-        if (!ok) {
+        uint64_t fp = 0, fp_geometry = 0;
+        if (!scene_meshes(scene, &slots, meshes, &mesh_transforms, fp, fp_geometry)) {
             g_error = "clip_and_project: batch without normals (the reference panics at batch3d.rs:605)";
             return RXR_ERR_INVALID;
         }
         if (fp != g_mesh_fingerprint) {
-            int rc = rxr_set_meshes(ctx, meshes.data(), (uint32_t)meshes.size());
-            if (rc != RXR_OK) {
-                g_error = rxr_last_error(ctx);
-                g_mesh_fingerprint = 0;
-                return rc;
-            }
-            g_mesh_fingerprint = fp;
+            int rc = register_meshes(ctx, meshes, fp, fp_geometry);
+            if (rc != RXR_OK) return rc;
         }
         b3.clear();
     }

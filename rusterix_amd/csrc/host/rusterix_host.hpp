@@ -252,6 +252,11 @@ public:
     std::vector<const Batch3D *> batches3d_in_order() const;
     // the 2D half only (src/scene.rs:163-187); used when the 3D half runs on the device
     void project_2d(const Mat3 *m2d);
+    // src/scene.rs:216-276 for n rays at once, on the device (rxr_intersect, include/rxr.h): registers the 3D batches with
+    // rxr_set_meshes unless the context already holds this geometry, whether or not device projection is on.  `mesh` indexes the
+    // batches in the order of batches3d_in_order().  Returns RXR_OK or a negative rxr_status; there is no CPU path.
+    int intersect(const float *origins, const float *dirs, uint32_t n, uint32_t flags, float *t, uint32_t *mesh, uint32_t *triangle,
+                  float *hitpoint, float *uv, float *normal) const;
 };
 
 // src/rasterizer.rs:35-193
@@ -291,6 +296,8 @@ public:
     // the same up to and including the host->device hand-over (project + flatten + rxr_upload_frame);
     // callers then drive rxr_render_rows / rxr_render_rows_to themselves (bench, multi-GPU host)
     int upload(Scene &scene, size_t width, size_t height, size_t tile_size, const Assets &assets);
+    // :1843-1870 (width / height: those of the last rasterize / upload, 0 before, as in the reference)
+    void screen_ray(float x, float y, float origin[3], float dir[3]) const;
 };
 
 // the process-wide device context.  Every function that uses it holds one process-wide lock for its whole duration, so

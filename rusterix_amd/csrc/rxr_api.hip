@@ -68,6 +68,10 @@ int rxr_quiesce(rxr_ctx *ctx) {
     if (ctx->last_stream && ctx->last_stream != ctx->stream) HIPCHK(ctx, hipStreamSynchronize(ctx->last_stream));
     if (ctx->copy_stream) HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->isect_pending) {  // an intersect on the caller's stream (rxr_intersect_to) reads the meshes and its scratch
+        HIPCHK(ctx, hipEventSynchronize(ctx->ev_isect));
+        ctx->isect_pending = false;
+    }
     return RXR_OK;
 }
 
@@ -252,7 +256,8 @@ void rxr_destroy(rxr_ctx *ctx) {
     DevBuf *bufs[] = {&ctx->d_stripes, &ctx->d_obj, &ctx->d_proj_out, &ctx->d_proj_misc, &ctx->d_tex, &ctx->d_texels, &ctx->d_frame, &ctx->d_tri_setup, &ctx->d_tri_shade, &ctx->d_tri_box, &ctx->d_bin_count, &ctx->d_bins, &ctx->d_bin2d_count, &ctx->d_bins2d,
                       &ctx->d_list2d, &ctx->d_large2d,
                       &ctx->d_list, &ctx->d_large, &ctx->d_counters, &ctx->d_fb,
-                      &ctx->d_vm_code, &ctx->d_programs, &ctx->d_patterns, &ctx->d_pattern_data, &ctx->d_palette};
+                      &ctx->d_vm_code, &ctx->d_programs, &ctx->d_patterns, &ctx->d_pattern_data, &ctx->d_palette,
+                      &ctx->d_isect_tris, &ctx->d_isect_misc, &ctx->d_isect_keys, &ctx->d_isect_io};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     rxr_jit_drop(ctx);
@@ -265,6 +270,7 @@ void rxr_destroy(rxr_ctx *ctx) {
     if (ctx->ev2) (void)hipEventDestroy(ctx->ev2);
     if (ctx->ev_upload) (void)hipEventDestroy(ctx->ev_upload);
     if (ctx->ev_render) (void)hipEventDestroy(ctx->ev_render);
+    if (ctx->ev_isect) (void)hipEventDestroy(ctx->ev_isect);
     for (hipEvent_t ev : ctx->ev_band)
         if (ev) (void)hipEventDestroy(ev);
     if (ctx->copy_stream) {
@@ -362,6 +368,8 @@ int rxr_set_meshes(rxr_ctx *ctx, const rxr_mesh3d *meshes, uint32_t n_meshes) {
     }
     ctx->meshes.clear();
     ctx->has_frame = false;
+    ctx->meshes_valid = false;  // (rxr_intersect.hip: until this call completes)
+    ctx->isect_ready = false;
     size_t vin = 0, tin = 0, vout = 0, tout = 0;
     for (uint32_t i = 0; i < n_meshes; ++i) {
         const rxr_mesh3d &m = meshes[i];
@@ -495,6 +503,7 @@ int rxr_set_meshes(rxr_ctx *ctx, const rxr_mesh3d *meshes, uint32_t n_meshes) {
     rxr_launch_proj_static(&PP, ctx->stream);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->meshes_valid = true;
     return RXR_OK;
 }
 

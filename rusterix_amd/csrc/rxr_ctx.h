@@ -214,6 +214,19 @@ struct rxr_ctx {
     uint32_t n_patterns = 0, n_normal_patterns = 0, n_palette = 0;
     bool frame_uses_programs = false;
 
+    // ray picking (rxr_intersect.hip): buffers of its own -- an intersect never touches the frame state (has_frame, the bins, the
+    // counters).  d_isect_tris: (p0, edge1, edge2) per registered triangle; d_isect_misc: the segments and per-mesh profile ids
+    // (isect_host: their host copy, kept alive for the asynchronous upload); d_isect_keys: per ray and segment the (t, triangle)
+    // minimum; d_isect_io: rxr_intersect's device copies of the caller's host arrays.
+    DevBuf d_isect_tris, d_isect_misc, d_isect_keys, d_isect_io;
+    std::vector<uint32_t> isect_host;
+    bool meshes_valid = true;        // false while / after an rxr_set_meshes that did not complete
+    bool isect_ready = false;        // d_isect_tris / d_isect_misc describe the current meshes (rxr_set_meshes clears it)
+    uint32_t isect_nseg = 0, isect_stride = 0;
+    size_t isect_off_pid = 0;        // words into d_isect_misc
+    hipEvent_t ev_isect = nullptr;   // recorded behind the last intersect's launches (on whichever stream they ran)
+    bool isect_pending = false;      // ... and not yet waited for (rxr_quiesce)
+
     FrameStream fstream;    // rxr_stream_begin .. rxr_upload_frame
     int last_upload_streamed = 0;  // 0 plain, 1 streamed (copied), 2 streamed out of page-locked arrays
 

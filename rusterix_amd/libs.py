@@ -70,6 +70,9 @@ def rxr_abi():
         "rxr_profile_begin": (i32, [vp, u32]),
         "rxr_profile_stride": (i32, [vp, u32]),
         "rxr_profile_read": (i32, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u32, C.POINTER(u32)]),
+        "rxr_intersect": (i32, [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
+        "rxr_intersect_to": (i32, [vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
+        "rxr_screen_rays_to": (i32, [vp, vp, vp, C.c_float, C.c_float, u32, u32, u32, u32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
