@@ -46,7 +46,8 @@ namespace {
 constexpr uint32_t ISECT_WG = 256;
 constexpr uint32_t ISECT_FEW_RAYS = 64;             // up to this many rays in a batch: a thread per triangle
 constexpr uint32_t ISECT_RAYS_PER_Y = 8;            // ... each workgroup row of k_isect_by_tri tests this many rays
-constexpr uint64_t ISECT_KEYS_MAX = 8ull << 20;     // keys (8 B) of one batch of rays: 64 MiB of scratch at most
+constexpr uint64_t ISECT_KEYS_MAX = 8ull << 20;     // keys (8 B) of one batch of rays: 64 MiB of scratch -- more only beyond 32 768 segments,
+                                                    // where a batch stays at ISECT_WG rays (ISECT_WG * nseg keys: 67.6 MB at 33 000 segments)
 constexpr unsigned long long NO_HIT = ~0ull;
 
 enum : uint32_t { SEG_PLAIN = 0, SEG_CHUNK_PID = 1, SEG_OVERLAY = 2 };

@@ -2,7 +2,8 @@
 against the numpy restatement of Scene::intersect (tests/intersect_ref.py), bit for bit: t, mesh, triangle, hitpoint and, in full
 mode, uv and normal -- on the product scenes, chunk scenes whose profile ids decide the winner, overlays, a transformed mesh, the
 1 M-triangle grid and adversarial rays.  Every scene runs twice: all rays in one call (a thread per ray once there are more than 64)
-and in calls of 16 (a thread per triangle)."""
+and in calls of 16 (a thread per triangle).  The kernels' thresholds -- ray counts, ray batches, segment ends, meshes without triangles,
+two streams -- and seeded scenes are in tests/test_gpu_intersect_fuzz.py."""
 import ctypes as C
 
 import numpy as np
@@ -25,13 +26,7 @@ def plain_context(product):
     product.lib.rxh_set_device_projection(0)
 
 
-def same(a, b):
-    """bitwise equality; any NaN equals any NaN (the device's default NaN is positive, x86's negative)"""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.dtype == np.float32:
-        nan = np.isnan(a) & np.isnan(b)
-        return bool(np.all(nan | (a.view(np.uint32) == b.view(np.uint32))))
-    return bool(np.array_equal(a, b))
+same = R.same   # bitwise equality; any NaN equals any NaN
 
 
 def assert_same(got, ref, label=""):
@@ -282,6 +277,8 @@ def test_screen_rays_and_pick_buffer(product, plain_context):
     assert (ref["mesh"] != R.MISS).mean() > 0.5
     sub = np.arange(0, n, 997)
     assert_same({k: v[sub] for k, v in ref.items()}, R.intersect(meshes, ho[sub], hd[sub], full=True), "pick buffer vs numpy")
+    # ... and every ray of the buffer against the vectorised reference
+    assert_same(got, R.intersect_many(meshes, ho, hd, full=True), "the whole pick buffer vs numpy")
 
 
 def test_new_meshes_are_hit_no_stale_records(product, plain_context):

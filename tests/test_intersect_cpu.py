@@ -123,3 +123,103 @@ def test_intersect_kernels_do_not_spill(tmp_path):
         assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)) == 0, f"{name} uses scratch"
         assert int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", body).group(1)) <= 64, f"{name}: more than 64 VGPRs"
     assert not re.search(r"^\s+scratch_\w+", isa, flags=re.M), "scratch instructions in the intersect kernels"
+
+
+# ---- the vectorised reference and the seeded generator (tests/pick_fuzz.py) -------------------------------------------------------
+
+from tests import pick_fuzz as P  # noqa: E402
+
+
+def assert_bits(got, ref, label):
+    assert set(got) == set(ref), label
+    bad = P.differences(got, ref, label)
+    assert bad is None, bad
+
+
+@pytest.mark.parametrize("seed", P.SEEDS)
+def test_intersect_many_equals_intersect(seed):
+    """every output of both modes, bit for bit, on the generator's scenes and rays (the per-ray side sets the ray count: the whole
+    parametrised test takes about a minute); a small max_pairs makes several ray blocks"""
+    meshes = P.random_pick_scene(seed)
+    o, d = P.random_rays(meshes, seed, 3000)
+    o, d = o[:240], d[:240]
+    recs = [R.tri_records(m) for m in meshes]
+    for full in (False, True):
+        ref = R.intersect(meshes, o, d, full=full, records=recs)
+        assert_bits(R.intersect_many(meshes, o, d, full=full), ref, f"seed {seed} full={full}")
+        assert_bits(R.intersect_many(meshes, o, d, full=full, max_pairs=50_000), ref, f"seed {seed} full={full} (small blocks)")
+
+
+def test_intersect_many_on_the_adversarial_rays_and_hand_cases():
+    from tests.test_gpu_intersect import adversarial_rays
+
+    api = rusterix_amd.load()
+    v, i, uv, n = api.Batch3D.from_box(3, 3, 3, 1, 1, 1).with_computed_normals().geometry()
+    box = dict(vertices=v, indices=i, uvs=uv, normals=n, list=R.LIST_STATIC, has_pid=False, pid=0)
+    o, d = adversarial_rays(np.random.default_rng(5))
+    for meshes in ([quad(0.0), box],
+                   [quad(0.0), quad(5.0, list=R.LIST_OVERLAY), quad(2.0), quad(3.0, list=R.LIST_OVERLAY), quad(-0.5, list=R.LIST_DYNAMIC)],
+                   [quad(5.0, list=R.LIST_CHUNK, has_pid=True, pid=7), quad(0.0, list=R.LIST_CHUNK, has_pid=True, pid=7)],
+                   [quad(0.0), quad(0.0)], []):
+        for full in (False, True):
+            assert_bits(R.intersect_many(meshes, o, d, full=full), R.intersect(meshes, o, d, full=full), f"{len(meshes)} meshes full={full}")
+    # an accepted t of +inf beats a rejected triangle and loses to every finite t (huge coordinates)
+    far = [quad(0.0), quad(1.0)]
+    oo = np.array([[0.5, 0.25, -3e38]], np.float32)
+    dd = np.array([[0.0, 0.0, 1.0]], np.float32)
+    assert_bits(R.intersect_many(far, oo, dd, full=True), R.intersect(far, oo, dd, full=True), "huge")
+    empty = R.intersect_many([quad(0.0)], np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), full=True)
+    assert empty["t"].shape == (0,) and empty["normal"].shape == (0, 3)
+
+
+def _empty_meshes_around_a_plain_run(meshes):
+    """a plain run with a mesh without triangles right before it, inside it and right after it"""
+    n = [len(m["indices"]) for m in meshes]
+    for _, _, m0, m1, rule in P.segments(meshes):
+        if rule == "plain" and m0 > 0 and n[m0 - 1] == 0 and 0 in n[m0:m1] and m1 < len(meshes) and n[m1] == 0:
+            return True
+    return False
+
+
+def test_generator_gives_the_device_something_to_decide():
+    """tests/test_gpu_intersect_fuzz.py compares the device with intersect_many on these seeds: here the reference alone shows that
+    the scenes and rays exercise hits, many winners, the overlay rule, the profile-id rule, ties, meshes without triangles and
+    segment ends on 1024-triangle boundaries"""
+    overlay_behind = pid_decided = ties = 0
+    holes = aligned = False
+    for seed in P.SEEDS:
+        meshes = P.random_pick_scene(seed)
+        assert 5 <= len(meshes) <= 60 and sum(len(m["indices"]) for m in meshes) <= P.MAX_TRIANGLES + 300, seed
+        for a, b in zip(meshes, meshes[1:]):   # rxr_set_meshes order: chunks (opacity, batches, terrain), static, dynamic, overlay
+            key = lambda m: (0, m["chunk"], m["list"]) if m["list"] <= R.LIST_CHUNK_TERRAIN else (1, m["list"], 0)
+            assert key(a) <= key(b), seed
+        o, d = P.random_rays(meshes, seed, 3000)
+        ref = R.intersect_many(meshes, o, d)
+        hit = ref["mesh"] != R.MISS
+        assert hit.mean() >= 0.30, (seed, hit.mean())
+        assert len(np.unique(ref["mesh"][hit])) >= min(5, len(meshes)), (seed, np.unique(ref["mesh"][hit]))
+        # every mesh alone: its own closest t per ray
+        alone = [R.intersect_many([dict(m, list=R.LIST_STATIC)], o, d) for m in meshes]
+        t_alone = np.stack([np.where(a["mesh"] != R.MISS, a["t"], np.float32(np.inf)) for a in alone])     # [mesh, ray]
+        hit_alone = np.stack([a["mesh"] != R.MISS for a in alone])
+        is_overlay = np.array([m["list"] == R.LIST_OVERLAY for m in meshes])
+        win = np.where(hit, ref["mesh"], 0).astype(np.int64)
+        overlay_behind += int((hit & is_overlay[win] & ((t_alone < ref["t"][None, :]) & hit_alone).any(axis=0)).sum())
+        ties += int((hit & (((t_alone == ref["t"][None, :]) & hit_alone).sum(axis=0) >= 2)).sum())
+        no_pid = R.intersect_many([dict(m, has_pid=False) for m in meshes], o, d)
+        pid_decided += int((no_pid["mesh"] != ref["mesh"]).sum())
+        holes |= _empty_meshes_around_a_plain_run(meshes)
+        aligned |= any(end % 1024 == 0 for _, end, _, _, _ in P.segments(meshes)[:-1])
+    assert overlay_behind >= 20 and pid_decided >= 20 and ties >= 20, (overlay_behind, pid_decided, ties)
+    assert holes and aligned, (holes, aligned)
+
+
+def test_segments_and_batches_restate_the_kernel_file():
+    k = P.kernel_constants()
+    assert k == dict(ISECT_WG=256, ISECT_FEW_RAYS=64, ISECT_RAYS_PER_Y=8, ISECT_KEYS_MAX=8 << 20), k
+    assert P.expected_batches(32768, 300, k) == [27904, 4864]
+    assert P.expected_batches(600, 33000, k) == [256, 256, 88]
+    assert P.expected_batches(64000, 5, k) == [64000]
+    ms = [quad(0.0), dict(quad(0.0), indices=np.zeros((0, 3), np.uint32)), quad(1.0, list=R.LIST_CHUNK),
+          quad(2.0, list=R.LIST_CHUNK, has_pid=True, pid=3), quad(3.0, list=R.LIST_OVERLAY), quad(4.0, has_pid=True, pid=3)]
+    assert P.segments(ms) == [(0, 4, 0, 3, "plain"), (4, 6, 3, 4, "pid"), (6, 8, 4, 5, "overlay"), (8, 10, 5, 6, "plain")]
