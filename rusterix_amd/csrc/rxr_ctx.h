@@ -1,4 +1,4 @@
-// rxr_ctx.h -- the context object behind the C ABI (private to rxr_api.hip and rxr_multi.hip).
+// rxr_ctx.h -- the context object behind the C ABI (private to the host files: rxr_api.hip, rxr_upload.hip, rxr_multi.hip, rxr_intersect.hip).
 //
 // A plain context is one HIP device: its streams, the resident textures / meshes / programs, the frame blob and the
 // device scratch.  A multi-device context (rxr_create_multi) is a handle whose `group` lists one plain context per
@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstdlib>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -262,14 +263,47 @@ struct rxr_ctx {
     rxr_stats stats{};
 };
 
-// ---- helpers shared by the two translation units (defined in rxr_api.hip) -------------------------
+// ---- helpers shared by the host translation units (defined in rxr_api.hip) ------------------------
 int rxr_fail(rxr_ctx *ctx, int code, const std::string &msg);
 int rxr_ensure(rxr_ctx *ctx, DevBuf &b, size_t bytes);
+int rxr_ensure_stage(rxr_ctx *ctx, size_t bytes);  // the same for the pinned staging blob (ctx->h_stage)
 // waits until nothing queued by this context -- on its own streams or on the caller's stream of the last render -- is
 // still running: the precondition for rewriting the staging blob, the frame blob or any scratch buffer
 int rxr_quiesce(rxr_ctx *ctx);
 // one render launch sequence of a plain context (rxr_api.hip)
 extern "C" int rxr_render_spec(rxr_ctx *ctx, const RenderSpec &spec, void *dev_pixels, hipStream_t s);
+
+// ---- defined here: what rxr_api.hip and rxr_upload.hip both need ----------------------------------
+// sparse frames (rxr_ctx::content_row0 / 1, row spans): the empty tiles a clamp must save before its fill launches pay (RXR_CONTENT_MIN_TILES
+// overrides it -- the tests use small frames)
+static inline size_t content_min_tiles() {
+    const char *e = getenv("RXR_CONTENT_MIN_TILES");
+    return e ? (size_t)atol(e) : 8192u;
+}
+
+// Execution fields whose lanes the raster loops do not (all) assign before each call (rasterizer.rs:773-785, :1259-1298,
+// :1637-1662): a read sees what an EARLIER fragment's program left there unless this invocation wrote the field first
+enum : uint32_t { PF_UV = 1, PF_ROUGHNESS = 2, PF_METALLIC = 4, PF_OPACITY = 8, PF_BUMP = 16, PF_NORMAL = 32, PF_HITPOINT = 64, PF_EMISSIVE = 128 };
+// DevProgram.flags
+enum : uint32_t {
+    PG_WRITES_OPACITY = 1,     // contains SetOpacity: an opaque-pass batch running it needs the program in the visibility loop
+    PG_WRITES_EMISSIVE = 2,    // contains SetEmissive (anywhere, callees included)
+    PG_ASSIGNS_EMISSIVE = 4,   // `shade` executes a SetEmissive on EVERY path to its end (definite assignment, see PurityCheck)
+};
+
+static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+static inline uint32_t pack_px(const uint8_t p[4]) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+
+// the cursor that lays a blob out: take(bytes) is where the next section starts; sections are 256-byte aligned, an empty one keeps 16 bytes
+struct BlobCursor {
+    size_t o = 0;
+    size_t operator()(size_t bytes) {
+        size_t at = o;
+        o = align_up(o + (bytes ? bytes : 16), 256);
+        return at;
+    }
+};
 
 #define HIPCHK(ctx, call)                                                                                  \
     do {                                                                                                   \

@@ -3,7 +3,7 @@
 // The reference projects a scene's batches with rayon (`par_iter_mut` over chunks and batch lists, src/scene.rs:162-211) and walks
 // the screen tiles with `par_iter` (src/rasterizer.rs:274).  The tiles went to the GPU; what stays on the host per frame -- one
 // `clip_and_project` per batch (host mirror, rusterix_host.cpp) and the flattening of the projected batches into the pinned staging
-// blob (rxr_upload_frame, rxr_api.hip) -- is independent per batch and runs through this pool.
+// blob (rxr_upload_frame, rxr_upload.hip) -- is independent per batch and runs through this pool.
 //
 //   rxr_parallel::run(n_items, weight, [&](size_t i) { ... });
 //

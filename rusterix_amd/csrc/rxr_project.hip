@@ -3,7 +3,7 @@
 //
 // Same exactness rules as rxr_kernels.hip: -ffp-contract=off, IEEE division, fmaf only where vek's
 // Mat4 * Vec4 fuses.  The host half that remains per frame is two Mat4 * Mat4 products and the 8-corner
-// AABB frustum test per mesh (rxr_api.hip); everything per vertex / per triangle happens here.
+// AABB frustum test per mesh (rxr_upload.hip); everything per vertex / per triangle happens here.
 //
 // Ordering: the reference appends the vertices / fan triangles created by near-plane clipping after
 // the originals, in the order of the original triangles (:627-686).  Triangle order is the tie-break
@@ -615,7 +615,7 @@ __device__ __forceinline__ uint32_t sat_px(float x, uint32_t hi) {
 }
 // Rust `x as isize` narrowed to i32 for the Bresenham end points (:1785-1788); false beyond +-2^30
 __device__ __forceinline__ bool to_isize32(float x, int32_t &out) {
-    if (!(x == x)) {  // (NaN: refused like a coordinate out of range -- rxr_api.hip to_isize32 says why)
+    if (!(x == x)) {  // (NaN: refused like a coordinate out of range -- rxr_upload.hip to_isize32 says why)
         out = 0;
         return false;
     }
