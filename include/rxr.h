@@ -660,6 +660,42 @@ int rxr_intersect_to(rxr_ctx *ctx, const float *dev_origins, const float *dev_di
 int rxr_screen_rays_to(rxr_ctx *ctx, const float *inverse_view, const float *inverse_projection, float width, float height,
                        uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, float *dev_origins, float *dev_dirs, void *hip_stream);
 
+/* ---- running a program over an image: the shader-texture bake (rusterix_amd/csrc/rxr_bake.hip) -------------------------------
+ * Rusteria::shade (rusteria/src/lib.rs:161-210) over a width x height RenderBuffer, as Chunk::add_shader runs it at 64 x 64 for
+ * chunk.shader_textures[i] (src/chunk.rs:104-122) and the rsia tool at any size.  Texel (x, y), row-major, top row first:
+ * uv = (x / width, 1 - y / height, 0), color = 0, every other Execution field at its Execution::new value (roughness 0.5, the
+ * rest 0: the bake sets neither time nor hitpoint), Execution::shade, pixel = (color.x, color.y, color.z, 1) with -0.0 stored as
+ * +0.0 (RenderBuffer::accum_from at accum == 1, rusteria/src/renderbuffer.rs:64-85).  The bytes are RenderBuffer::as_rgba_bytes
+ * (:88-107, :152-155): (c.powf(0.4545) * 255.0) as u8 per colour channel -- the cast saturates, truncates and maps NaN to 0 --
+ * and 255 for alpha; powf comes from the device math library, so a channel whose exact value lies within a few ulp of an integer
+ * may differ from a host's libm by one step.  Texture::generate_normals (chunk.rs:119) only fills Texture.data_ext, which the
+ * rasterizer never reads: not computed.
+ * Which programs: those rxr_set_shaders accepts that, in addition, never read roughness, metallic, opacity, normal or bump
+ * before the same invocation has written it when the program writes that field anywhere (the reference keeps one Execution per
+ * 80 x 80 tile and resets only uv and color between texels, so such a read would see the previous texel's value; a field that is
+ * only read holds its constant).  Anything else: RXR_ERR_UNSUPPORTED.  A program without `shade` (shade_index -1; add_shader
+ * pushes None and bakes nothing, chunk.rs:107-109) or an index outside the set: RXR_ERR_INVALID.
+ * A bake always runs the interpreter and changes no frame, scratch or compiled-program state: a frame uploaded before it renders
+ * as it would have. */
+/* validation only, no context: the status and, in `message`, the reason for program `program` of `set` (everything
+ * rxr_check_shaders refuses for the set, plus the rule above for that program) */
+int rxr_check_bake(const rxr_shader_set *set, uint32_t program, char *message, uint32_t message_capacity);
+/* n bakes of width x height each, bake i over programs[i] of the resident set (rxr_set_shaders; a program may repeat), in ONE
+ * launch.  pixels: n * width * height * 4 floats (RenderBuffer.pixels), rgba: n * width * height * 4 bytes (as_rgba_bytes); either
+ * may be NULL.  width, height in [1, RXR_BAKE_MAX_DIM] and n * width * height <= RXR_BAKE_MAX_TEXELS, else RXR_ERR_INVALID; n == 0
+ * does nothing.  Host memory, blocking; a program that does what makes the reference panic (or exceeds the interpreter's
+ * instruction bound): RXR_ERR_INVALID, the message names the program and the texel.  Multi-device handles: member 0.
+ * Replaces: rs.shade + as_rgba_bytes in Chunk::add_shader, src/chunk.rs:110-116. */
+#define RXR_BAKE_MAX_DIM 16384u
+#define RXR_BAKE_MAX_TEXELS (1u << 28)
+int rxr_bake_shaders(rxr_ctx *ctx, const uint32_t *programs, uint32_t n, uint32_t width, uint32_t height, float *pixels, uint8_t *rgba);
+/* the same into DEVICE memory (its first and last byte are checked to be device memory of the context's device), queued on hip_stream (NULL = the context's stream);
+ * `programs` is host memory and is read before the call returns.  Asynchronous: a program fault is reported by the next
+ * rxr_synchronize (RXR_ERR_INVALID).  Multi-device handles: RXR_ERR_UNSUPPORTED (use rxr_member).
+ * Replaces: Rusteria::shade, rusteria/src/lib.rs:161-210. */
+int rxr_bake_shaders_to(rxr_ctx *ctx, const uint32_t *programs, uint32_t n, uint32_t width, uint32_t height, float *dev_pixels,
+                        uint8_t *dev_rgba, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -463,6 +463,27 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         L.scene_intersect = fn("scene_intersect", i32, vp, pf, pf, u32, u32, pf, pu, pu, pf, pf, pf)
         L.rasterizer_screen_ray = fn("rasterizer_screen_ray", None, vp, f32, f32, pf, pf)
 
+    # the shader-texture bake (product host library only, like ray picking)
+    has_bake = hasattr(lib, prefix + "scene_bake_shaders")
+    if has_bake:
+        L.scene_bake_shaders = fn("scene_bake_shaders", i32, vp, vp, pu, u32, u32, u32, pf, pb)
+        L.chunk_add_shader_baked = fn("chunk_add_shader_baked", i32, vp, i32, vp, u32, i32, u32, C.POINTER(pu), pu, u32)
+        L.chunk_shader_texture = fn("chunk_shader_texture", i32, vp, i32, u32, pu, pu, pb)
+
+    def last_error():
+        if not hasattr(lib, prefix + "last_error"):
+            return ""
+        f = getattr(lib, prefix + "last_error")
+        f.restype = C.c_char_p
+        return (f() or b"").decode()
+
+    def program_args(program: Program):
+        n = len(program.functions)
+        arrs = [np.asarray(f, np.uint32) if len(f) else np.zeros(1, np.uint32) for f in program.functions]
+        ptrs = (pu * max(n, 1))(*[_up(a) for a in arrs])
+        lens = (C.c_uint32 * max(n, 1))(*[len(f) for f in program.functions])
+        return arrs, ptrs, lens, n
+
     def tile_args(tile: Tile):
         n = len(tile.textures)
         frames = (pb * n)(*[_bp(t.data) for t in tile.textures])
@@ -643,15 +664,45 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
             L.chunk_set_terrain_batch2d(self._scene._h, self.index, b._h)
             return self
 
-        def add_shader(self, program: Program, baked_texture=None):
-            """chunk.add_shader (reference src/chunk.rs:84-131) without the compiler and the 64x64 bake: the program and
-            the texture the reference would have baked from it (or None) are given directly; returns the shader index"""
+        def add_shader(self, program: Program, baked_texture=None, bake=False, assets=None):
+            """chunk.add_shader (reference src/chunk.rs:84-131) without the compiler; returns the shader index.  By default also
+            without the 64x64 bake: the texture the reference would have baked from the program (or None) is given directly.
+            With bake=True the texture is baked on the device (rxr_bake_shaders, include/rxr.h) with the pattern banks and the
+            palette of `assets` (None: empty ones) -- 64 x 64, or None for a program without `shade`, as in the reference; read it
+            back with shader_texture(index).  A program the device cannot bake raises RasterizeError and is not added."""
+            if bake:
+                if baked_texture is not None:
+                    raise ValueError("bake=True and baked_texture exclude each other")
+                if not has_bake:
+                    raise NotImplementedError(f"{name}: no shader bake in this library")
+                if assets is None:
+                    assets = Assets()
+                keep, ptrs, lens, n = program_args(program)
+                idx = L.chunk_add_shader_baked(self._scene._h, self.index, assets._h, program.globals, program.shade_index,
+                                               program.shade_locals, ptrs, lens, n)
+                if idx < 0:
+                    raise RasterizeError(idx, last_error())
+                return idx
             idx = self._scene.add_program(program, chunk=self.index)
             if baked_texture is None:
                 L.chunk_add_shader_texture(self._scene._h, self.index, None, 0, 0)
             else:
                 L.chunk_add_shader_texture(self._scene._h, self.index, _bp(baked_texture.data), baked_texture.width, baked_texture.height)
             return idx
+
+        def shader_texture(self, index):
+            """chunk.shader_textures[index] as a Texture, or None (a program without `shade`)"""
+            if not has_bake:
+                raise NotImplementedError(f"{name}: no shader bake in this library")
+            w, h = C.c_uint32(), C.c_uint32()
+            rc = L.chunk_shader_texture(self._scene._h, self.index, index, C.byref(w), C.byref(h), None)
+            if rc < 0:
+                raise IndexError("no such shader texture")
+            if rc == 0:
+                return None
+            data = np.zeros(w.value * h.value * 4, np.uint8)
+            L.chunk_shader_texture(self._scene._h, self.index, index, C.byref(w), C.byref(h), _bp(data))
+            return Texture(data, w.value, h.value)
 
         def add_occluder(self, mn, mx, occlusion):
             L.chunk_add_occluder(self._scene._h, self.index, mn[0], mn[1], mx[0], mx[1], occlusion)
@@ -773,6 +824,29 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
                     f.restype = C.c_char_p
                     msg = (f() or b"").decode()
                 raise RasterizeError(rc, msg)
+            return out
+
+        def bake_shaders(self, programs, width, height, assets=None, pixels=True, rgba=True):
+            """Rusteria::shade over a width x height RenderBuffer (reference rusteria/src/lib.rs:161-210) for every program index
+            of `programs`, in one device launch (rxr_bake_shaders, include/rxr.h).  An index counts through scene.shaders first,
+            then every chunk's shaders in chunk order.  Returns a dict: pixels ([n][height][width][4] float32, RenderBuffer.pixels)
+            and rgba ([n][height][width][4] uint8, RenderBuffer::as_rgba_bytes), each only if asked for."""
+            if not has_bake:
+                raise NotImplementedError(f"{name}: no shader bake in this library")
+            if assets is None:
+                assets = Assets()
+            progs = np.ascontiguousarray(np.asarray(programs, np.uint32).reshape(-1))
+            n = progs.shape[0]
+            out = {}
+            if pixels:
+                out["pixels"] = np.zeros((n, height, width, 4), np.float32)
+            if rgba:
+                out["rgba"] = np.zeros((n, height, width, 4), np.uint8)
+            rc = L.scene_bake_shaders(self._h, assets._h, _up(progs) if n else None, n, width, height,
+                                      _fp(out["pixels"]) if pixels and out["pixels"].size else None,
+                                      _bp(out["rgba"]) if rgba and out["rgba"].size else None)
+            if rc != 0:
+                raise RasterizeError(rc, last_error())
             return out
 
         def projected_batch3d(self, list_kind, index, chunk=-1):

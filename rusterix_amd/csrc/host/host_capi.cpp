@@ -126,6 +126,32 @@ void rxh_chunk_add_shader_texture(void *s, int chunk, const uint8_t *rgba, uint3
     c.shader_textures.push_back(std::move(t));
     c.shader_texture_present.push_back(rgba ? 1 : 0);
 }
+// Chunk::add_shader with the bake (Scene::chunk_add_shader): the shader index in the chunk, or a negative rxr_status
+int rxh_chunk_add_shader_baked(void *s, int chunk, void *assets, uint32_t n_globals, int32_t shade_index, uint32_t shade_locals,
+                               const uint32_t *const *fn_words, const uint32_t *fn_lens, uint32_t n_functions) {
+    Program p;
+    p.globals = n_globals;
+    p.shade_index = shade_index;
+    p.shade_locals = shade_locals;
+    for (uint32_t i = 0; i < n_functions; ++i) p.user_functions.emplace_back(fn_words[i], fn_words[i] + fn_lens[i]);
+    if (chunk < 0) return RXR_ERR_INVALID;
+    return ((Scene *)s)->chunk_add_shader((size_t)chunk, std::move(p), *(const Assets *)assets);
+}
+// chunks[chunk].shader_textures[index]: 1 and its size if present, 0 for None, -1 for a bad index; rgba (may be NULL) receives w * h * 4 bytes
+int rxh_chunk_shader_texture(void *s, int chunk, uint32_t index, uint32_t *w, uint32_t *h, uint8_t *rgba) {
+    Scene *sc = (Scene *)s;
+    if (chunk < 0 || (size_t)chunk >= sc->chunks.size() || index >= sc->chunks[chunk].shader_textures.size()) return -1;
+    const Chunk &c = sc->chunks[chunk];
+    if (!c.shader_texture_present[index]) return 0;
+    *w = c.shader_textures[index].width;
+    *h = c.shader_textures[index].height;
+    if (rgba) memcpy(rgba, c.shader_textures[index].data.data(), c.shader_textures[index].data.size());
+    return 1;
+}
+// Scene::bake_shaders (rxr_bake_shaders' arrays, include/rxr.h); RXR_OK or a negative rxr_status
+int rxh_scene_bake_shaders(void *s, void *assets, const uint32_t *programs, uint32_t n, uint32_t width, uint32_t height, float *pixels, uint8_t *rgba) {
+    return ((Scene *)s)->bake_shaders(*(const Assets *)assets, programs, n, width, height, pixels, rgba);
+}
 void rxh_chunk_add_light(void *s, int chunk, const rxr_light *l) { ((Scene *)s)->chunks[chunk].lights.push_back(*l); }
 // scene.add_shader (src/scene.rs:104-134) minus the parser / compiler; chunk >= 0: that chunk's shaders
 int rxh_scene_add_program(void *s, int chunk, uint32_t n_globals, int32_t shade_index, uint32_t shade_locals,

@@ -743,6 +743,97 @@ int register_meshes(rxr_ctx *ctx, const std::vector<rxr_mesh3d> &meshes, uint64_
 
 }  // namespace
 
+namespace {
+
+// Makes the scene's Rusteria programs, the pattern banks and the palette of `assets` the context's resident set (rxr_set_shaders) unless
+// they already are.  One table: scene.shaders first, then every chunk's shaders; chunk_program_base[c] is where chunk c's begin
+// (rxr_chunk.program_base points into it).
+int ensure_shaders(rxr_ctx *ctx, const Scene &scene, const Assets &assets, std::vector<uint32_t> &chunk_program_base) {
+    std::vector<const Program *> all_programs;
+    for (const Program &p : scene.shaders) all_programs.push_back(&p);
+    chunk_program_base.assign(scene.chunks.size(), 0);
+    for (size_t c = 0; c < scene.chunks.size(); ++c) {
+        chunk_program_base[c] = (uint32_t)all_programs.size();
+        for (const Program &p : scene.chunks[c].shaders) all_programs.push_back(&p);
+    }
+    if (g_shaders_gen != scene.shaders_generation || g_shader_env_gen != assets.shader_env_generation) {
+        std::vector<std::vector<rxr_function>> fns(all_programs.size());
+        std::vector<rxr_program> progs(all_programs.size());
+        for (size_t i = 0; i < all_programs.size(); ++i) {
+            const Program &p = *all_programs[i];
+            for (const auto &f : p.user_functions) fns[i].push_back(rxr_function{f.data(), (uint32_t)f.size()});
+            progs[i] = rxr_program{p.globals, p.shade_index, p.shade_locals, fns[i].data(), (uint32_t)fns[i].size()};
+        }
+        auto views = [](const std::vector<Pattern> &src) {
+            std::vector<rxr_pattern> v;
+            for (const Pattern &t : src) v.push_back(rxr_pattern{t.rgb.data(), t.width, t.height});
+            return v;
+        };
+        std::vector<rxr_pattern> pv = views(assets.patterns), pn = views(assets.patterns_normal);
+        rxr_shader_set set{};
+        set.programs = progs.data();
+        set.n_programs = (uint32_t)progs.size();
+        set.patterns = pv.data();
+        set.n_patterns = (uint32_t)pv.size();
+        set.normal_patterns = pn.data();
+        set.n_normal_patterns = (uint32_t)pn.size();
+        set.palette_rgb = assets.palette_rgb.data();
+        set.palette_present = assets.palette_present.data();
+        set.n_palette = (uint32_t)assets.palette_present.size();
+        int rc = rxr_set_shaders(ctx, &set);
+        if (rc != RXR_OK) {
+            g_error = rxr_last_error(ctx);
+            g_shaders_gen = 0;
+            return rc;
+        }
+        g_shaders_gen = scene.shaders_generation;
+        g_shader_env_gen = assets.shader_env_generation;
+    }
+    return RXR_OK;
+}
+
+}  // namespace
+
+int Scene::bake_shaders(const Assets &assets, const uint32_t *programs, uint32_t n, uint32_t width, uint32_t height, float *pixels, uint8_t *rgba) const {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::string err;
+    rxr_ctx *ctx = context(&err);
+    if (!ctx) return RXR_ERR_NO_DEVICE;
+    std::vector<uint32_t> chunk_program_base;
+    int rc = ensure_shaders(ctx, *this, assets, chunk_program_base);
+    if (rc != RXR_OK) return rc;
+    rc = rxr_bake_shaders(ctx, programs, n, width, height, pixels, rgba);
+    if (rc != RXR_OK) g_error = rxr_last_error(ctx);
+    return rc;
+}
+
+int Scene::chunk_add_shader(size_t chunk, Program program, const Assets &assets) {
+    if (chunk >= chunks.size()) {
+        g_error = "Chunk::add_shader: no such chunk";
+        return RXR_ERR_INVALID;
+    }
+    const bool has_shade = program.shade_index >= 0;
+    chunks[chunk].shaders.push_back(std::move(program));
+    shaders_generation = next_generation();
+    Texture tex;
+    if (has_shade) {   // chunk.rs:107-122: 64 x 64, as_rgba_bytes
+        uint32_t index = (uint32_t)shaders.size();   // the program's place in the context's table (ensure_shaders)
+        for (size_t c = 0; c < chunk; ++c) index += (uint32_t)chunks[c].shaders.size();
+        index += (uint32_t)chunks[chunk].shaders.size() - 1u;
+        tex.width = tex.height = 64;
+        tex.data.resize((size_t)64 * 64 * 4);
+        const int rc = bake_shaders(assets, &index, 1, 64, 64, nullptr, tex.data.data());
+        if (rc != RXR_OK) {   // nothing is added: the caller bakes elsewhere or does without the program
+            chunks[chunk].shaders.pop_back();
+            shaders_generation = next_generation();
+            return rc;
+        }
+    }
+    chunks[chunk].shader_textures.push_back(std::move(tex));
+    chunks[chunk].shader_texture_present.push_back(has_shade ? 1 : 0);
+    return (int)chunks[chunk].shaders.size() - 1;
+}
+
 int Scene::intersect(const float *origins, const float *dirs, uint32_t n, uint32_t flags, float *t, uint32_t *mesh, uint32_t *triangle,
                      float *hitpoint, float *uv, float *normal) const {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
@@ -904,46 +995,10 @@ int Rasterizer::upload(Scene &scene, size_t w, size_t h, size_t tile_size, const
     }
 
     // Rusteria programs, patterns, palette: re-sent only when they changed
-    // one table: scene.shaders first, then every chunk's shaders (rxr_chunk.program_base points into it)
-    std::vector<const Program *> all_programs;
-    for (const Program &p : scene.shaders) all_programs.push_back(&p);
-    std::vector<uint32_t> chunk_program_base(scene.chunks.size(), 0);
-    for (size_t c = 0; c < scene.chunks.size(); ++c) {
-        chunk_program_base[c] = (uint32_t)all_programs.size();
-        for (const Program &p : scene.chunks[c].shaders) all_programs.push_back(&p);
-    }
-    if (g_shaders_gen != scene.shaders_generation || g_shader_env_gen != assets.shader_env_generation) {
-        std::vector<std::vector<rxr_function>> fns(all_programs.size());
-        std::vector<rxr_program> progs(all_programs.size());
-        for (size_t i = 0; i < all_programs.size(); ++i) {
-            const Program &p = *all_programs[i];
-            for (const auto &f : p.user_functions) fns[i].push_back(rxr_function{f.data(), (uint32_t)f.size()});
-            progs[i] = rxr_program{p.globals, p.shade_index, p.shade_locals, fns[i].data(), (uint32_t)fns[i].size()};
-        }
-        auto views = [](const std::vector<Pattern> &src) {
-            std::vector<rxr_pattern> v;
-            for (const Pattern &t : src) v.push_back(rxr_pattern{t.rgb.data(), t.width, t.height});
-            return v;
-        };
-        std::vector<rxr_pattern> pv = views(assets.patterns), pn = views(assets.patterns_normal);
-        rxr_shader_set set{};
-        set.programs = progs.data();
-        set.n_programs = (uint32_t)progs.size();
-        set.patterns = pv.data();
-        set.n_patterns = (uint32_t)pv.size();
-        set.normal_patterns = pn.data();
-        set.n_normal_patterns = (uint32_t)pn.size();
-        set.palette_rgb = assets.palette_rgb.data();
-        set.palette_present = assets.palette_present.data();
-        set.n_palette = (uint32_t)assets.palette_present.size();
-        int rc = rxr_set_shaders(ctx, &set);
-        if (rc != RXR_OK) {
-            g_error = rxr_last_error(ctx);
-            g_shaders_gen = 0;
-            return rc;
-        }
-        g_shaders_gen = scene.shaders_generation;
-        g_shader_env_gen = assets.shader_env_generation;
+    std::vector<uint32_t> chunk_program_base;
+    {
+        int rc = ensure_shaders(ctx, scene, assets, chunk_program_base);
+        if (rc != RXR_OK) return rc;
     }
 
     // flatten in submission order (:314-405, :503-552)

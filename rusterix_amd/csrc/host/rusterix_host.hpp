@@ -257,6 +257,14 @@ public:
     // batches in the order of batches3d_in_order().  Returns RXR_OK or a negative rxr_status; there is no CPU path.
     int intersect(const float *origins, const float *dirs, uint32_t n, uint32_t flags, float *t, uint32_t *mesh, uint32_t *triangle,
                   float *hitpoint, float *uv, float *normal) const;
+    // Rusteria::shade + RenderBuffer::as_rgba_bytes (rusteria/src/lib.rs:161-210, renderbuffer.rs:88-107) on the device (rxr_bake_shaders,
+    // include/rxr.h): n bakes of width x height; programs[i] indexes scene.shaders followed by every chunk's shaders in chunk order (the
+    // table Rasterizer::upload makes resident, which this call makes resident too when it is not).  Returns RXR_OK or a negative rxr_status.
+    int bake_shaders(const Assets &assets, const uint32_t *programs, uint32_t n, uint32_t width, uint32_t height, float *pixels, uint8_t *rgba) const;
+    // Chunk::add_shader (src/chunk.rs:84-131) behind the compiler: pushes the program onto chunks[chunk].shaders and the 64 x 64 texture
+    // baked from it on the device onto shader_textures (None for a program without `shade`, which is not baked); the bytes are host memory.
+    // Returns the shader's index in the chunk or a negative rxr_status (a program the device cannot bake is not added).
+    int chunk_add_shader(size_t chunk, Program program, const Assets &assets);
 };
 
 // src/rasterizer.rs:35-193

@@ -63,6 +63,11 @@ int rxr_quiesce(rxr_ctx *ctx) {
         HIPCHK(ctx, hipEventSynchronize(ctx->ev_isect));
         ctx->isect_pending = false;
     }
+    if (ctx->bake_pending) {  // a bake on the caller's stream (rxr_bake_shaders_to) reads the programs and its job list
+        HIPCHK(ctx, hipEventSynchronize(ctx->ev_bake));
+        ctx->bake_pending = false;
+    }
+    ctx->bake_jobs_used = 0;  // (every queued bake has run: the ring of program lists starts over)
     return RXR_OK;
 }
 
@@ -176,7 +181,8 @@ void rxr_destroy(rxr_ctx *ctx) {
                       &ctx->d_list2d, &ctx->d_large2d,
                       &ctx->d_list, &ctx->d_large, &ctx->d_counters, &ctx->d_fb,
                       &ctx->d_vm_code, &ctx->d_programs, &ctx->d_patterns, &ctx->d_pattern_data, &ctx->d_palette,
-                      &ctx->d_isect_tris, &ctx->d_isect_misc, &ctx->d_isect_keys, &ctx->d_isect_io};
+                      &ctx->d_isect_tris, &ctx->d_isect_misc, &ctx->d_isect_keys, &ctx->d_isect_io,
+                      &ctx->d_bake_io, &ctx->d_bake_jobs, &ctx->d_bake_fault};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     rxr_jit_drop(ctx);
@@ -190,6 +196,9 @@ void rxr_destroy(rxr_ctx *ctx) {
     if (ctx->ev_upload) (void)hipEventDestroy(ctx->ev_upload);
     if (ctx->ev_render) (void)hipEventDestroy(ctx->ev_render);
     if (ctx->ev_isect) (void)hipEventDestroy(ctx->ev_isect);
+    if (ctx->ev_bake) (void)hipEventDestroy(ctx->ev_bake);
+    if (ctx->h_bake_fault) (void)hipHostFree(ctx->h_bake_fault);
+    if (ctx->h_bake_jobs) (void)hipHostFree(ctx->h_bake_jobs);
     for (hipEvent_t ev : ctx->ev_band)
         if (ev) (void)hipEventDestroy(ev);
     if (ctx->copy_stream) {
@@ -1022,6 +1031,7 @@ int rxr_synchronize(rxr_ctx *ctx) {
         if (qrc != RXR_OK) return qrc;
         const uint32_t launches = ctx->launches_since_sync;
         ctx->launches_since_sync = 0;
+        if (ctx->h_bake_fault && ctx->h_bake_fault[0]) return rxr_bake_report_fault(ctx);  // a queued bake's program faulted (rxr_bake.hip)
         if (!ctx->rendered) return RXR_OK;
         uint32_t *hc = ctx->h_counters;
         if (hc[HS_VM_FAULT] == VMF_JIT_PALETTE_MISS) {
@@ -1647,7 +1657,7 @@ namespace {
 // validates every program of the set and flattens them into one code stream; no device involved.
 // Returns RXR_OK or the status + message rxr_set_shaders / rxr_check_shaders report.
 int flatten_programs(const rxr_shader_set *set, std::vector<uint32_t> &code, std::vector<DevProgram> &progs, std::vector<uint32_t> &field_reads,
-                     std::string &err) {
+                     std::string &err, std::vector<uint32_t> *field_writes_out = nullptr) {
     auto bad = [&](int st, const std::string &m) {
         err = m;
         return st;
@@ -1692,6 +1702,7 @@ int flatten_programs(const rxr_shader_set *set, std::vector<uint32_t> &code, std
                       ((at_exit & PF_EMISSIVE) ? PG_ASSIGNS_EMISSIVE : 0u);
         }
         field_reads.push_back(ru);
+        if (field_writes_out) field_writes_out->push_back(wr);   // PF_* this program writes anywhere (the bake's rule, rxr_bake_refusal)
         progs.push_back(d);
     }
     // uv.z, roughness.yz, metallic.yz, opacity.yz and bump are never assigned by the raster loops: once ANY program of the
@@ -1830,6 +1841,31 @@ int rxr_check_shaders(const rxr_shader_set *set, uint32_t *code_words, char *mes
     return rc;
 }
 
+int rxr_check_bake(const rxr_shader_set *set, uint32_t program, char *message, uint32_t message_capacity) {
+    std::vector<uint32_t> code, reads, writes;
+    std::vector<DevProgram> progs;
+    std::string err;
+    int rc = set ? flatten_programs(set, code, progs, reads, err, &writes) : RXR_ERR_INVALID;
+    if (rc == RXR_OK) {
+        if (program >= progs.size()) {
+            rc = RXR_ERR_INVALID;
+            err = "program index out of range";
+        } else if (progs[program].shade_entry == 0xFFFFFFFFu) {
+            rc = RXR_ERR_INVALID;
+            err = "the program has no shade function (shade_index -1): Chunk::add_shader bakes nothing for it";
+        } else if (const char *why = rxr_bake_refusal(reads[program], writes[program])) {
+            rc = RXR_ERR_UNSUPPORTED;
+            err = why;
+        }
+    }
+    if (message && message_capacity) {
+        size_t n = std::min<size_t>(err.size(), message_capacity - 1);
+        memcpy(message, err.data(), n);
+        message[n] = 0;
+    }
+    return rc;
+}
+
 int rxr_set_shaders(rxr_ctx *ctx, const rxr_shader_set *set) {
     if (!ctx) return RXR_ERR_INVALID;
     if (ctx->group) return rxr_group_set_shaders(ctx, set);
@@ -1842,6 +1878,7 @@ int rxr_set_shaders(rxr_ctx *ctx, const rxr_shader_set *set) {
     ctx->programs.clear();
     ctx->programs_static = false;
     ctx->program_field_reads.clear();
+    ctx->program_field_writes.clear();
     ctx->n_patterns = ctx->n_normal_patterns = ctx->n_palette = 0;
     if (!set) return RXR_OK;
     if ((set->n_programs && !set->programs) || (set->n_patterns && !set->patterns) || (set->n_normal_patterns && !set->normal_patterns) ||
@@ -1853,10 +1890,10 @@ int rxr_set_shaders(rxr_ctx *ctx, const rxr_shader_set *set) {
         std::vector<uint32_t> code;
     } fl;
     std::vector<DevProgram> progs;
-    std::vector<uint32_t> field_reads;  // per program: PF_* read before written
+    std::vector<uint32_t> field_reads, field_writes;  // per program: PF_* read before written / written anywhere
     {
         std::string err;
-        int frc = flatten_programs(set, fl.code, progs, field_reads, err);
+        int frc = flatten_programs(set, fl.code, progs, field_reads, err, &field_writes);
         if (frc != RXR_OK) return rxr_fail(ctx, frc, "rxr_set_shaders: " + err);
     }
     {
@@ -1931,6 +1968,7 @@ int rxr_set_shaders(rxr_ctx *ctx, const rxr_shader_set *set) {
     }
     ctx->programs = std::move(progs);
     ctx->program_field_reads = std::move(field_reads);
+    ctx->program_field_writes = std::move(field_writes);
     ctx->n_patterns = set->n_patterns;
     ctx->n_normal_patterns = set->n_normal_patterns;
     ctx->n_palette = set->n_palette;

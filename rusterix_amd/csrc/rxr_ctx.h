@@ -211,6 +211,7 @@ struct rxr_ctx {
     DevBuf d_vm_code, d_programs, d_patterns, d_pattern_data, d_palette;
     std::vector<DevProgram> programs;
     std::vector<uint32_t> program_field_reads;  // PF_* each program reads before writing (see rxr_set_shaders)
+    std::vector<uint32_t> program_field_writes; // PF_* each program writes anywhere (rxr_bake_refusal)
     std::vector<uint32_t> program_flags;        // PG_* per program (see rxr_set_shaders)
     uint32_t n_patterns = 0, n_normal_patterns = 0, n_palette = 0;
     bool frame_uses_programs = false;
@@ -227,6 +228,18 @@ struct rxr_ctx {
     size_t isect_off_pid = 0;        // words into d_isect_misc
     hipEvent_t ev_isect = nullptr;   // recorded behind the last intersect's launches (on whichever stream they ran)
     bool isect_pending = false;      // ... and not yet waited for (rxr_quiesce)
+
+    // shader-texture bakes (rxr_bake.hip): buffers of their own, like the intersect's -- a bake touches neither the frame state nor the
+    // compiled programs.  d_bake_jobs: the program index per bake of the launches in flight (a ring of bake_jobs_cap words, filled
+    // through its page-locked twin h_bake_jobs); d_bake_io: rxr_bake_shaders' device copies of the caller's host arrays;
+    // d_bake_fault: BAKE_FAULT_WORDS words, sticky (the first faulting texel wins) until the host has reported them; h_bake_fault:
+    // their pinned host copy, refreshed behind every bake.
+    DevBuf d_bake_io, d_bake_jobs, d_bake_fault;
+    uint32_t *h_bake_fault = nullptr, *h_bake_jobs = nullptr;
+    size_t bake_jobs_cap = 0;        // words
+    size_t bake_jobs_used = 0;       // ... of which launches since the last rxr_quiesce may still read this many
+    hipEvent_t ev_bake = nullptr;    // recorded behind the last bake's launches (on whichever stream they ran)
+    bool bake_pending = false;       // ... and not yet waited for (rxr_quiesce)
 
     FrameStream fstream;    // rxr_stream_begin .. rxr_upload_frame
     int last_upload_streamed = 0;  // 0 plain, 1 streamed (copied), 2 streamed out of page-locked arrays
@@ -290,6 +303,22 @@ enum : uint32_t {
     PG_WRITES_EMISSIVE = 2,    // contains SetEmissive (anywhere, callees included)
     PG_ASSIGNS_EMISSIVE = 4,   // `shade` executes a SetEmissive on EVERY path to its end (definite assignment, see PurityCheck)
 };
+
+// The bake's acceptance rule (include/rxr.h, rxr_bake_shaders) on top of rxr_set_shaders': Rusteria::shade keeps one Execution per
+// tile and resets only uv and color between texels (rusteria/src/lib.rs:177-195), so roughness, metallic, opacity, normal and bump
+// carry over from texel to texel -- a program that writes one of them must not read it before the same invocation wrote it.  `reads`:
+// PF_* read before written, `writes`: PF_* written anywhere, both from the definite-assignment walk of rxr_set_shaders (PurityCheck).
+// (For the raster loops `normal` is assigned before every call and therefore not part of rxr_set_shaders' own rule.)
+static inline const char *rxr_bake_refusal(uint32_t reads, uint32_t writes) {
+    if (reads & writes & (PF_ROUGHNESS | PF_METALLIC | PF_OPACITY | PF_NORMAL | PF_BUMP))
+        return "bake: the program reads roughness / metallic / opacity / normal / bump before writing it and writes that field (Rusteria::shade "
+               "resets only uv and color between texels: the read would see the previous texel's value)";
+    return nullptr;
+}
+// rxr_bake.hip: turns the pinned fault words of a bake into RXR_ERR_INVALID + message and clears them (streams idle)
+// (the device's words: the VMF_* code, then the program, the bake of the call and the texel it happened in; _SCRATCH: the interpreter's own report)
+enum : uint32_t { BAKE_FAULT_CODE = 0, BAKE_FAULT_PROGRAM, BAKE_FAULT_JOB, BAKE_FAULT_X, BAKE_FAULT_Y, BAKE_FAULT_SCRATCH, BAKE_FAULT_WORDS = 8 };
+int rxr_bake_report_fault(rxr_ctx *ctx);
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
