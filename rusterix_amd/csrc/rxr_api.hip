@@ -32,11 +32,11 @@ extern "C" void rxr_launch_bin2d_fill(const RasterParams *P, hipStream_t s);
 extern "C" void rxr_launch_fill(const RasterParams *P, hipStream_t s);
 extern "C" void rxr_launch_blockscan(const RasterParams *P, hipStream_t s);
 extern "C" void rxr_launch_blockscan2d(const RasterParams *P, hipStream_t s);
-extern "C" void rxr_launch_raster(const RasterParams *P, hipStream_t s);
+extern "C" const char *rxr_launch_raster(const RasterParams *P, hipStream_t s);
 extern "C" void rxr_launch_fill_words(uint32_t *dst, uint64_t n_words, uint32_t value, hipStream_t s);
 extern "C" void rxr_launch_fill_outside_spans(const RasterParams *P, hipStream_t s);
 extern "C" void rxr_launch_spans_from_meshes(const RasterParams *P, uint32_t n_tile_rows, const uint32_t *d2_box, uint2 *host_copy, hipStream_t s);
-extern "C" void rxr_launch_raster_grid(const RasterParams *P, uint32_t grid_x, hipStream_t s);
+extern "C" const char *rxr_launch_raster_grid(const RasterParams *P, uint32_t grid_x, hipStream_t s);
 extern "C" int rxr_raster_takes_spans(const RasterParams *P);
 extern "C" void rxr_launch_selftest_math(uint64_t seed, uint32_t blocks, uint32_t iters, unsigned long long *mismatch, hipStream_t s);
 
@@ -849,6 +849,7 @@ static int render_impl(rxr_ctx *ctx, const RenderSpec &spec, void *dev_pixels, h
         }
     }
     if (slot) slot->raster_first = slot->n;
+    ctx->last_raster_kernel = "";  // (a frame that launches none: empty, or only filled)
     if (n_raster_bands > 1u && spec.tile_stride == 1u && !spec.compact) {
         if (band_row_of)
             for (uint32_t k = 0; k <= n_raster_bands; ++k) band_row_of[k] = k ? spec.row1 : spec.row0;  // (a frame without content: one band of filled rows)
@@ -864,10 +865,10 @@ static int render_impl(rxr_ctx *ctx, const RenderSpec &spec, void *dev_pixels, h
                 band_row_of[k] = k ? P.row0 : spec.row0;
                 band_row_of[k + 1u] = k + 1u < n_raster_bands ? P.row1 : spec.row1;
             }
-            if (P.tiles_y && !rxr_jit_launch(ctx, &P, s)) rxr_launch_raster_grid(&P, use_spans ? widest_span(P.tile_y0, P.tiles_y) : 0u, s);
+            if (P.tiles_y && !rxr_jit_launch(ctx, &P, s)) ctx->last_raster_kernel = rxr_launch_raster_grid(&P, use_spans ? widest_span(P.tile_y0, P.tiles_y) : 0u, s);
             if (band_events) HIPCHK(ctx, hipEventRecord(band_events[k], s));
         }
-    } else if (!rxr_jit_launch(ctx, &P, s)) rxr_launch_raster_grid(&P, use_spans ? widest_span(P.tile_y0, P.tiles_y) : 0u, s);
+    } else if (!rxr_jit_launch(ctx, &P, s)) ctx->last_raster_kernel = rxr_launch_raster_grid(&P, use_spans ? widest_span(P.tile_y0, P.tiles_y) : 0u, s);
     HIPCHK(ctx, hipGetLastError());
     ctx->scratch_dirty = false;  // the raster launch that hands the bins back is queued
     ctx->scratch2d_dirty = false;
@@ -2073,6 +2074,12 @@ extern "C" int rxr_debug_stream_info(rxr_ctx *ctx) { return (ctx && !ctx->group)
 // tests: how many launch sequences rxr_synchronize has rendered again after a list overflow (a plain context or a member)
 extern "C" uint32_t rxr_debug_rerenders(rxr_ctx *ctx) { return (ctx && !ctx->group) ? ctx->rerenders : 0u; }
 
+// tests: the symbol name of the raster kernel of the context's most recent raster launch ("k_raster_rows_cut_rl", "k_raster_jit", ...;
+// "" when the last frame launched none); a multi-device handle answers for member 0
+extern "C" const char *rxr_debug_last_raster_kernel(rxr_ctx *ctx) {
+    if (ctx && ctx->group) ctx = rxr_member(ctx, 0);
+    return ctx ? ctx->last_raster_kernel : "";
+}
 extern "C" const char *rxr_debug_jit_info(rxr_ctx *ctx) {
     if (!ctx) return "";
     if (ctx->group) return rxr_member(ctx, 0) ? rxr_member(ctx, 0)->jit_info.c_str() : "";

@@ -264,6 +264,7 @@ struct rxr_ctx {
     bool last_had_prepass = false, last_had_prepass2d = false;
     uint32_t launches_since_sync = 0;   // renders queued since rxr_synchronize last drained the streams
     uint32_t rerenders = 0;             // launches rendered again by rxr_synchronize after a list overflow
+    const char *last_raster_kernel = "";  // symbol name of the last raster launch's kernel (rxr_debug_last_raster_kernel: tests); a static string
     RenderSpec last_spec{};
     void *last_out = nullptr;
     hipStream_t last_stream = nullptr;

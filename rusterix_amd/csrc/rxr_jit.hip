@@ -1148,6 +1148,8 @@ int rxr_jit_build(rxr_ctx *ctx, const std::vector<uint32_t> &code, const std::ve
 }
 
 namespace {
+// the two kernels of a code object (rxr_kernels.hip under RXR_JIT): looked up and reported (rxr_ctx.last_raster_kernel) by these names
+const char *const k_jit_name = "k_raster_jit", *const k_jit_cut_name = "k_raster_jit_cut";
 // slot 0 / 1 / 2 = template level 2 / 7 / 8
 bool ensure_level(rxr_ctx *ctx, int slot) {
     if (ctx->jit_fn[slot]) return true;
@@ -1181,7 +1183,7 @@ bool ensure_level(rxr_ctx *ctx, int slot) {
     hipFunction_t fn = nullptr;
     hipError_t e = hipSetDevice(ctx->device);
     if (e == hipSuccess) e = hipModuleLoadData(&mod, obj.data());
-    if (e == hipSuccess) e = hipModuleGetFunction(&fn, mod, "k_raster_jit");
+    if (e == hipSuccess) e = hipModuleGetFunction(&fn, mod, k_jit_name);
     if (e != hipSuccess) {
         if (mod) (void)hipModuleUnload(mod);
         ctx->jit_failed[slot] = true;
@@ -1193,7 +1195,7 @@ bool ensure_level(rxr_ctx *ctx, int slot) {
     hipFunction_t fn_cut = nullptr;
     ctx->jit_fn_cut[slot] = nullptr;
     if (levels[slot] != 2) {  // (template level 2 has none)
-        if (hipModuleGetFunction(&fn_cut, mod, "k_raster_jit_cut") == hipSuccess) ctx->jit_fn_cut[slot] = (void *)fn_cut;
+        if (hipModuleGetFunction(&fn_cut, mod, k_jit_cut_name) == hipSuccess) ctx->jit_fn_cut[slot] = (void *)fn_cut;
         else (void)hipGetLastError();   // (a code object of an older build in the disk cache: the plain kernel serves; the error must not stay behind)
     }
     char msg[200];
@@ -1217,6 +1219,7 @@ bool rxr_jit_launch(rxr_ctx *ctx, const RasterParams *P, hipStream_t s) {
     // (frames with cut-out or profiled batches: rounds in row mode around them -- binned frames only, the others never reach that code)
     const bool cut = P->split_rounds && ctx->jit_fn_cut[slot] && P->fused_small == 0u && (P->flags & RXR_FLAG_D3_ACTIVE);
     const hipFunction_t kernel = (hipFunction_t)(cut ? ctx->jit_fn_cut[slot] : ctx->jit_fn[slot]);
+    ctx->last_raster_kernel = cut ? k_jit_cut_name : k_jit_name;
     hipEvent_t e0, e1;
     if (rxr_launch_times && rxr_launch_pair(&e0, &e1))  // (kernel timing, rxr_launch.h; this form takes the grid in THREADS)
         return hipExtModuleLaunchKernel(kernel, P->tiles_x * RXR_TILE_THREADS, P->tiles_y, 1, RXR_TILE_THREADS, 1, 1, 0, s, nullptr, config,

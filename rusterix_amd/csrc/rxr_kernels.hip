@@ -4033,10 +4033,27 @@ extern "C" int rxr_raster_takes_spans(const RasterParams *P) {
     return 1;
 }
 // grid_x: workgroups per tile row (0: tiles_x; with RasterParams.row_spans the widest span of the launch's rows)
-extern "C" void rxr_launch_raster_grid(const RasterParams *P, uint32_t grid_x, hipStream_t s);
-extern "C" void rxr_launch_raster(const RasterParams *P, hipStream_t s) { rxr_launch_raster_grid(P, 0u, s); }
-extern "C" void rxr_launch_raster_grid(const RasterParams *P, uint32_t grid_x, hipStream_t s) {
-    if (P->tiles_x * P->tiles_y == 0) return;
+// Returns the symbol name of the kernel it launched ("" when there was nothing to launch): rxr_debug_last_raster_kernel hands it to the
+// tests (tests/test_gpu_routes.py pins every kernel below to a scene of its own).  RXR_RASTER is the one place a name comes from.
+//   fact (rxr_upload.hip, phase RasterParams; render_impl for fused_small)               kernel
+//   kernel_level 5 / 4 + plain_programs / 4 / 3 / 2                                       k_raster_vm_v / _p / _sv / _s / k_raster_vm
+//   kernel_level 1 (chunk textures, RXR_MIN_KERNEL_LEVEL=1)                               k_raster_chunk   [_cut: split_rounds, binned] [_rl]
+//   fused_small 1 (RXR_SMALL_MODE=1, at most RXR_STAGE_TRIS triangles)                    k_raster_fused
+//   binned 3D frame (fused_small 0), RXR_PAIR_TILES=1, no opacity pass, tile_stride 1     k_raster_pair    [_rl]
+//   binned, split_rounds (cut-out texels, profiled batches under an opacity pass)         k_raster_rows_cut [_rl]
+//   binned, row_spans (sparse frame)                                                      k_raster_rows_sp / k_raster_rows_rl_sp
+//   binned                                                                                k_raster_rows    [_rl]
+//   small frame (fused_small 2), no 3D pass, RXR_NO_ROWS                                  k_raster         [_rl]
+//   _rl: relaxed_lights (demoted to exact on large or non-finite light parameters), n_lights > 0, 3D pass active
+#define RXR_RASTER(kernel, grid)                                   \
+    do {                                                           \
+        RXR_LAUNCH(kernel, grid, dim3(RXR_TILE_THREADS), s, *P);   \
+        return #kernel;                                            \
+    } while (0)
+extern "C" const char *rxr_launch_raster_grid(const RasterParams *P, uint32_t grid_x, hipStream_t s);
+extern "C" const char *rxr_launch_raster(const RasterParams *P, hipStream_t s) { return rxr_launch_raster_grid(P, 0u, s); }
+extern "C" const char *rxr_launch_raster_grid(const RasterParams *P, uint32_t grid_x, hipStream_t s) {
+    if (P->tiles_x * P->tiles_y == 0) return "";
     if (!grid_x || !P->row_spans) grid_x = P->tiles_x;
 #if RXR_XCD_GROUP
     grid_x = P->tiles_x;  // (this tuning build's column mapping ignores the spans: every column is rastered, the fills are overwritten)
@@ -4047,18 +4064,18 @@ extern "C" void rxr_launch_raster_grid(const RasterParams *P, uint32_t grid_x, h
 #endif
     const bool rl = P->relaxed_lights && P->n_lights && (P->flags & RXR_FLAG_D3_ACTIVE);  // (frames without a 3D light loop: one kernel for both modes)
     const bool no_rows = getenv("RXR_NO_ROWS") != nullptr;  // tuning knob: binned scenes walk every candidate per pixel (k_raster)
-    if (P->kernel_level >= 5u) RXR_LAUNCH(k_raster_vm_v, tiles, dim3(RXR_TILE_THREADS), s, *P);
-    else if (P->kernel_level == 4u && P->plain_programs) RXR_LAUNCH(k_raster_vm_p, tiles, dim3(RXR_TILE_THREADS), s, *P);
-    else if (P->kernel_level == 4u) RXR_LAUNCH(k_raster_vm_sv, tiles, dim3(RXR_TILE_THREADS), s, *P);
-    else if (P->kernel_level == 3u) RXR_LAUNCH(k_raster_vm_s, tiles, dim3(RXR_TILE_THREADS), s, *P);
-    else if (P->kernel_level == 2u) RXR_LAUNCH(k_raster_vm, tiles, dim3(RXR_TILE_THREADS), s, *P);
+    if (P->kernel_level >= 5u) RXR_RASTER(k_raster_vm_v, tiles);
+    else if (P->kernel_level == 4u && P->plain_programs) RXR_RASTER(k_raster_vm_p, tiles);
+    else if (P->kernel_level == 4u) RXR_RASTER(k_raster_vm_sv, tiles);
+    else if (P->kernel_level == 3u) RXR_RASTER(k_raster_vm_s, tiles);
+    else if (P->kernel_level == 2u) RXR_RASTER(k_raster_vm, tiles);
     else if (P->kernel_level == 1u) {
         const bool cut = P->split_rounds && P->fused_small == 0u && (P->flags & RXR_FLAG_D3_ACTIVE);  // (binned frames: the others never reach scan_lists_rows)
-        if (cut && rl) RXR_LAUNCH(k_raster_chunk_cut_rl, tiles, dim3(RXR_TILE_THREADS), s, *P);
-        else if (cut) RXR_LAUNCH(k_raster_chunk_cut, tiles, dim3(RXR_TILE_THREADS), s, *P);
-        else if (rl) RXR_LAUNCH(k_raster_chunk_rl, tiles, dim3(RXR_TILE_THREADS), s, *P);
-        else RXR_LAUNCH(k_raster_chunk, tiles, dim3(RXR_TILE_THREADS), s, *P);
-    } else if (P->fused_small == 1u) RXR_LAUNCH(k_raster_fused, tiles, dim3(RXR_TILE_THREADS), s, *P);
+        if (cut && rl) RXR_RASTER(k_raster_chunk_cut_rl, tiles);
+        else if (cut) RXR_RASTER(k_raster_chunk_cut, tiles);
+        else if (rl) RXR_RASTER(k_raster_chunk_rl, tiles);
+        else RXR_RASTER(k_raster_chunk, tiles);
+    } else if (P->fused_small == 1u) RXR_RASTER(k_raster_fused, tiles);
     else if (P->fused_small == 0u && (P->flags & RXR_FLAG_D3_ACTIVE) && !no_rows) {
         // two tiles per workgroup (raster_tile_pair): opt-in.  Built in round 3 as the 16 x 32-tile experiment the round-2 verdict asked to
         // repeat on a build that passes parity: it does pass (tests/test_gpu_rows.py runs it), and it LOSES -- 1 M-triangle grid 555 ->
@@ -4069,17 +4086,18 @@ extern "C" void rxr_launch_raster_grid(const RasterParams *P, uint32_t grid_x, h
         const bool pairs_on = pt && pt[0] == '1';
         if (pairs_on && !P->has_opacity && P->tile_stride == 1u && !RXR_XCD_GROUP) {
             const dim3 pairs(P->tiles_x, (P->tiles_y + 1u) / 2u);
-            if (rl) RXR_LAUNCH(k_raster_pair_rl, pairs, dim3(RXR_TILE_THREADS), s, *P);
-            else RXR_LAUNCH(k_raster_pair, pairs, dim3(RXR_TILE_THREADS), s, *P);
+            if (rl) RXR_RASTER(k_raster_pair_rl, pairs);
+            else RXR_RASTER(k_raster_pair, pairs);
         } else if (P->split_rounds) {  // (these two look the row spans up themselves when there are any: SPANS)
-            if (rl) RXR_LAUNCH(k_raster_rows_cut_rl, tiles, dim3(RXR_TILE_THREADS), s, *P);
-            else RXR_LAUNCH(k_raster_rows_cut, tiles, dim3(RXR_TILE_THREADS), s, *P);
+            if (rl) RXR_RASTER(k_raster_rows_cut_rl, tiles);
+            else RXR_RASTER(k_raster_rows_cut, tiles);
         } else if (P->row_spans) {
-            if (rl) RXR_LAUNCH(k_raster_rows_rl_sp, tiles, dim3(RXR_TILE_THREADS), s, *P);
-            else RXR_LAUNCH(k_raster_rows_sp, tiles, dim3(RXR_TILE_THREADS), s, *P);
-        } else if (rl) RXR_LAUNCH(k_raster_rows_rl, tiles, dim3(RXR_TILE_THREADS), s, *P);
-        else RXR_LAUNCH(k_raster_rows, tiles, dim3(RXR_TILE_THREADS), s, *P);
-    } else if (rl) RXR_LAUNCH(k_raster_rl, tiles, dim3(RXR_TILE_THREADS), s, *P);
-    else RXR_LAUNCH(k_raster, tiles, dim3(RXR_TILE_THREADS), s, *P);
+            if (rl) RXR_RASTER(k_raster_rows_rl_sp, tiles);
+            else RXR_RASTER(k_raster_rows_sp, tiles);
+        } else if (rl) RXR_RASTER(k_raster_rows_rl, tiles);
+        else RXR_RASTER(k_raster_rows, tiles);
+    } else if (rl) RXR_RASTER(k_raster_rl, tiles);
+    else RXR_RASTER(k_raster, tiles);
 }
+#undef RXR_RASTER
 #endif  // !RXR_JIT

@@ -61,6 +61,7 @@ def rxr_abi():
         "rxr_stream_batch3d": (i32, [vp, u32, vp]),
         "rxr_debug_stream_info": (i32, [vp]),
         "rxr_debug_rerenders": (u32, [vp]),
+        "rxr_debug_last_raster_kernel": (C.c_char_p, [vp]),
         "rxr_render_download": (i32, [vp, vp]),
         "rxr_download_rows": (i32, [vp, vp, u32, u32]),
         "rxr_synchronize": (i32, [vp]),

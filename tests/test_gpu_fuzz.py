@@ -10,10 +10,13 @@ import pytest
 
 from rusterix_amd import binding as B
 from rusterix_amd import scenes
+from tests.routes import last_raster_kernel
 
 pytestmark = pytest.mark.gpu
 
 TOLERANCE = 1
+BINNED_CHUNK_KERNELS = ("k_raster_chunk", "k_raster_chunk_rl", "k_raster_chunk_cut", "k_raster_chunk_cut_rl", "k_raster_vm_sv", "k_raster_vm_p",
+                        "k_raster_vm_v", "k_raster_jit", "k_raster_jit_cut")
 
 
 def random_texture(rng, w, h, alpha_mode):
@@ -230,6 +233,9 @@ def test_random_chunk_scene_binned(oracle, product, seed):
     batches or full-alpha candidates in a round -- the walk"""
     w, h = 168, 104
     got = scenes.render(build_chunks(product, 200 + seed, w, h, dense=40))
+    # a chunk kernel, or -- no program of this generator writes `opacity` -- an interpreter kernel without calls in the visibility loop,
+    # or the compiled kernels once the background compiler is done: never the plain kernels of feature level 0, never k_raster_vm / _vm_s
+    assert last_raster_kernel(product) in BINNED_CHUNK_KERNELS, f"seed {seed}: drawn by {last_raster_kernel(product)}"
     ref = scenes.render(build_chunks(oracle, 200 + seed, w, h, dense=40))
     diff = np.abs(got.astype(np.int16) - ref.astype(np.int16)).max(axis=2)
     bad = np.argwhere(diff > TOLERANCE)

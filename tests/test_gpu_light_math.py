@@ -19,6 +19,7 @@ import pytest
 import rusterix_amd
 from rusterix_amd import binding as B
 from rusterix_amd import scenes
+from tests.routes import last_raster_kernel
 from tests.test_gpu_parity import _light, assert_exact, scene_2d
 
 pytestmark = pytest.mark.gpu
@@ -109,14 +110,20 @@ SCENES = {
 }
 
 
+RELAXED_TWIN = {"k_raster_rows_sp": "k_raster_rows_rl_sp"}   # (every other relaxed kernel is its exact twin's name + "_rl")
+
+
 @pytest.mark.parametrize("name", list(SCENES))
 def test_both_modes_against_the_oracle(oracle, product, light_math, name):
     build = SCENES[name]
     ref = scenes.render(build(oracle)).copy()
     light_math(True)
     exact = scenes.render(build(product)).copy()
+    exact_kernel = last_raster_kernel(product)
     light_math(False)
     relaxed = scenes.render(build(product)).copy()
+    # the two frames really come from the two arithmetic modes' kernels (every scene here has lights and a 3D pass at feature level 0 or 1)
+    assert not exact_kernel.endswith("_rl") and last_raster_kernel(product) == RELAXED_TWIN.get(exact_kernel, exact_kernel + "_rl"), (exact_kernel, last_raster_kernel(product))
     n = ref.shape[0] * ref.shape[1]
     lit_pixels = int((ref[..., :3].max(axis=2) > 0).sum())
     assert lit_pixels > n // 10, f"{name}: the scene shows nothing"

@@ -14,6 +14,7 @@ import pytest
 from rusterix_amd import binding as B
 from rusterix_amd import scenes
 from tests.test_gpu_fuzz import random_texture
+from tests.routes import assert_route
 
 pytestmark = pytest.mark.gpu
 
@@ -192,6 +193,7 @@ def test_pairs_of_tiles_per_workgroup(oracle, product, monkeypatch, variant):
     monkeypatch.setenv("RXR_PAIR_TILES", "1")
     for seed, (w, h) in enumerate([(203, 131), (240, 176), (97, 33)]):   # 9, 11 and 3 tile rows: the last pair is half empty
         got = scenes.render(build(product, seed, w, h, variant))
+        assert_route(product, "k_raster_pair", f"{variant} seed {seed}")
         ref = scenes.render(build(oracle, seed, w, h, variant))
         diff = (got != ref).any(axis=2)
         assert not diff.any(), f"{variant} seed {seed}: {int(diff.sum())} pixels differ; first {np.argwhere(diff)[:3].tolist()}"
@@ -219,9 +221,11 @@ def test_rounds_run_in_row_mode_around_cut_out_and_profiled_candidates(oracle, p
 
     ref = scenes.render(build(oracle)).copy()
     got = scenes.render(build(product)).copy()
+    assert_route(product, "k_raster_rows_cut", "cut-out / profiled batches")
     assert np.array_equal(got, ref), f"{(got != ref).any(axis=2).sum()} pixels differ from the oracle"
     monkeypatch.setenv("RXR_NO_SPLIT_ROUNDS", "1")
     plain_kernels = scenes.render(build(product)).copy()
+    assert_route(product, "k_raster_rows", "RXR_NO_SPLIT_ROUNDS")
     assert np.array_equal(plain_kernels, ref)
     monkeypatch.delenv("RXR_NO_SPLIT_ROUNDS")
     solid = scenes.render(scenes.box_grid_scene(product, n=20, width=640, height=360))

@@ -10,6 +10,7 @@ import pytest
 import rusterix_amd
 from rusterix_amd import binding as B
 from rusterix_amd import scenes
+from tests.routes import assert_route
 from rusterix_amd.binding import Program
 from tests import test_gpu_shaders as S
 
@@ -339,9 +340,11 @@ def test_compiled_programs_on_a_binned_frame_with_cut_out_batches(oracle, produc
     the plain compiled kernel (RXR_NO_SPLIT_ROUNDS)"""
     build = lambda api: scenes.box_grid_scene(api, n=20, width=640, height=360, shader=True, cutout_every=3)   # noqa: E731
     got, info = three_ways(oracle, product, monkeypatch, build)
+    assert_route(product, "k_raster_jit_cut", "the compiled frame with cut-out batches")   # (the last product frame of three_ways)
     monkeypatch.setenv("RXR_SHADER_JIT", "1")
     monkeypatch.setenv("RXR_NO_SPLIT_ROUNDS", "1")
     plain = scenes.render(build(product)).copy()
+    assert_route(product, "k_raster_jit", "RXR_NO_SPLIT_ROUNDS")
     assert jit_info(product).startswith("compiled:")
     assert np.array_equal(plain, got)
     solid = scenes.render(scenes.box_grid_scene(oracle, n=20, width=640, height=360, shader=True))

@@ -11,6 +11,7 @@ import pytest
 from rusterix_amd import binding as B
 from rusterix_amd import scenes
 from rusterix_amd.binding import Program
+from tests.routes import assert_route
 
 pytestmark = pytest.mark.gpu
 
@@ -462,11 +463,19 @@ def test_static_and_dynamic_stack_pointer_agree(oracle, product, seed, monkeypat
         prog = ProgramGen(rng, n_locals=int(rng.integers(3, 6)), n_functions=0).program()
         build = lambda api: rect_scene(api, prog, time=0.5)   # noqa: E731
     ref = scenes.render(build(oracle)).copy()
-    monkeypatch.delenv("RXR_VM_NO_STATIC", raising=False)
-    static = scenes.render(build(product)).copy()
-    monkeypatch.setenv("RXR_VM_NO_STATIC", "1")
-    dynamic = scenes.render(build(product)).copy()
-    assert np.array_equal(static, ref) and np.array_equal(dynamic, ref)
+    monkeypatch.setenv("RXR_SHADER_JIT", "0")   # (the interpreter kernels are what this test is about)
+    # no program here writes `opacity`: on its own the frame takes the kernels without interpreter calls in the visibility loop (k_raster_vm_p
+    # static, k_raster_vm_v dynamic); RXR_VM_VIS_CALLS sends it to the ones the docstring names (k_raster_vm_s static, k_raster_vm dynamic)
+    for vis_calls, static_kernel, dynamic_kernel in ((False, "k_raster_vm_p", "k_raster_vm_v"), (True, "k_raster_vm_s", "k_raster_vm")):
+        if vis_calls:
+            monkeypatch.setenv("RXR_VM_VIS_CALLS", "1")
+        monkeypatch.delenv("RXR_VM_NO_STATIC", raising=False)
+        static = scenes.render(build(product)).copy()
+        assert_route(product, static_kernel, "static stack pointer")
+        monkeypatch.setenv("RXR_VM_NO_STATIC", "1")
+        dynamic = scenes.render(build(product)).copy()
+        assert_route(product, dynamic_kernel, "RXR_VM_NO_STATIC")
+        assert np.array_equal(static, ref) and np.array_equal(dynamic, ref)
 
 
 @pytest.mark.parametrize("scene", ["grid", "cube", "cube-calls", "rows-cutout"])
@@ -508,10 +517,18 @@ def test_visibility_with_and_without_interpreter_calls_agree(oracle, product, sc
             return scenes._result(api, scene, assets, setup, 219, 140, 40, "rows-cutout-program")
         tol = 0
     ref = scenes.render(build(oracle)).copy()
+    monkeypatch.setenv("RXR_SHADER_JIT", "0")   # (the interpreter kernels are what this test is about)
+    calls = scene == "cube-calls"
     monkeypatch.delenv("RXR_VM_VIS_CALLS", raising=False)
     level4 = scenes.render(build(product)).copy()
+    assert_route(product, "k_raster_vm_v" if calls else "k_raster_vm_p", scene)   # (none of these frames needs the chunk paths: level 4 is vm_p)
+    monkeypatch.setenv("RXR_NO_PLAIN_PROGRAMS", "1")
+    with_chunk_paths = scenes.render(build(product)).copy()
+    assert_route(product, "k_raster_vm_v" if calls else "k_raster_vm_sv", scene + ", RXR_NO_PLAIN_PROGRAMS")
+    monkeypatch.delenv("RXR_NO_PLAIN_PROGRAMS")
     monkeypatch.setenv("RXR_VM_VIS_CALLS", "1")
     level3 = scenes.render(build(product)).copy()
-    for name, got in (("level 4", level4), ("level 3", level3)):
+    assert_route(product, "k_raster_vm" if calls else "k_raster_vm_s", scene + ", RXR_VM_VIS_CALLS")
+    for name, got in (("level 4", level4), ("level 4 with the chunk paths", with_chunk_paths), ("level 3", level3)):
         diff = np.abs(got.astype(np.int16) - ref.astype(np.int16)).max(axis=2)
         assert (diff > tol).sum() <= (5 if tol else 0), f"{scene} {name}: {(diff > tol).sum()} pixels differ (max {diff.max()})"

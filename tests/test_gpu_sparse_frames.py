@@ -17,6 +17,7 @@ import pytest
 import rusterix_amd
 from rusterix_amd import binding as B
 from rusterix_amd import scenes
+from tests.routes import assert_route, last_raster_kernel
 
 W = H = 480
 BOUNDARY = 320            # a multiple of 16 (the device's bin tiles) and of every reference tile size below
@@ -246,6 +247,7 @@ def test_boundary_frames_leave_clean_scratch(product, projection, monkeypatch, a
     assert_scratch_clean(product, cfg.name)
     info = content_info(product)
     assert info[3] == (2 if device else 1), f"the frame did not take its row spans: {info}"
+    assert_route(product, "k_raster_rows_sp", cfg.name)
     if blockscan == "0":
         assert bin_entries(product) > 0, "the frame did not go through the general pipeline"
     assert_exact(got, ref, f"{cfg.name} vs oracle")
@@ -254,6 +256,7 @@ def test_boundary_frames_leave_clean_scratch(product, projection, monkeypatch, a
     no_spans = scenes.render(cfg).copy()
     assert_scratch_clean(product, f"{cfg.name} without row spans")
     assert content_info(product)[3] == 0
+    assert_route(product, "k_raster_rows", cfg.name + " without row spans")
     monkeypatch.delenv("RXR_ROW_SPANS")
     assert_exact(got, no_spans, f"{cfg.name}: row spans on vs off")
     bands = render_bands(product, cfg, [(0, 37), (37, BOUNDARY + 10), (BOUNDARY + 10, H)])
@@ -362,6 +365,8 @@ def test_sparse_frame_sequences(oracle, product, projection, monkeypatch, block)
             frames += 1
             with_spans += content_info(product)[3] != 0
             general += bin_entries(product) > 0
+            if content_info(product)[3] != 0 and bin_entries(product) > 0:   # (a binned frame under row spans: a kernel that looks them up)
+                assert last_raster_kernel(product) in ("k_raster_rows_sp", "k_raster_rows_rl_sp", "k_raster_rows_cut", "k_raster_rows_cut_rl"), what
             monkeypatch.setenv("RXR_ROW_SPANS", "0")
             no_spans = scenes.render(cfg).copy()
             monkeypatch.delenv("RXR_ROW_SPANS")

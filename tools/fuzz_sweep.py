@@ -18,6 +18,7 @@ from tests import test_gpu_fuzz as F  # noqa: E402
 from tests import test_gpu_rows as R  # noqa: E402
 from tests import test_gpu_shaders as S  # noqa: E402
 from tests import test_gpu_shader_jit as J  # noqa: E402
+from tests.routes import last_raster_kernel  # noqa: E402
 
 prod, orc = rusterix_amd.load(), load_oracle()
 DEVPROJ = "--device-projection" in sys.argv
@@ -31,6 +32,7 @@ if DEVPROJ:
     prod.lib.rxh_set_device_projection(1)
 bad = []
 refused = []
+routes = {}   # raster kernel (rxr_debug_last_raster_kernel) -> frames it drew: which kernels the sweep actually feeds
 
 
 def check(tag, got, ref, tol, max_bad):
@@ -45,6 +47,8 @@ def compare(tag, build, tol, max_bad):
     a parity failure: the shim would render it on the CPU"""
     try:
         got = scenes.render(build(prod))
+        kernel = last_raster_kernel(prod)
+        routes[kernel] = routes.get(kernel, 0) + 1
     except B.RasterizeError as e:
         if e.code != B.RXR_ERR_UNSUPPORTED:
             raise
@@ -79,6 +83,7 @@ for s in range(first, first + n):
     if (s - first) % 20 == 19:
         print(f"... {s - first + 1} seeds, {len(bad)} failures so far", flush=True)
 print("device projection" if DEVPROJ else "host projection", "seeds", first, "..", first + n - 1, "failures:", len(bad), "refused frames / programs:", len(refused), refused[:4])
+print("routes:", " ".join(f"{k or '(none)'}={v}" for k, v in sorted(routes.items(), key=lambda kv: -kv[1])))
 for b in bad[:20]:
     print("  ", b)
 sys.exit(1 if bad else 0)
