@@ -2069,6 +2069,17 @@ extern "C" int rxr_debug_download_bytes(rxr_ctx *ctx, uint64_t *out2) {
     out2[1] = ctx->last_host_fill_bytes;
     return 0;
 }
+// tests: the device projection's two ticket words (rxr_project.h) after the context's streams have drained: out2[0] = k_proj_scan's
+// arrival counter (0 between frames: the workgroup that arrives last hands it back), out2[1] = "a triangle of the last device-projected
+// frame appends" (proj_init_item clears it, clip_count_item raises it: 0 lets k_proj_scan and k_clip_emit leave at once)
+extern "C" int rxr_debug_projection_ticket(rxr_ctx *ctx, uint32_t *out2) {
+    if (!ctx || ctx->group || !out2 || ctx->meshes.empty() || !ctx->PP.ticket) return -1;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = rxr_quiesce(ctx);
+    if (rc != RXR_OK) return rc;
+    HIPCHK(ctx, hipMemcpy(out2, ctx->PP.ticket, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
 extern "C" int rxr_debug_stream_info(rxr_ctx *ctx) { return (ctx && !ctx->group) ? ctx->last_upload_streamed : -1; }
 
 // tests: how many launch sequences rxr_synchronize has rendered again after a list overflow (a plain context or a member)

@@ -1,7 +1,8 @@
 """Counts on either side of the device's internal thresholds (none of which the reference has): the light loop's chunks of 64 lights, the
 small-scene path's 128 triangles (RXR_STAGE_TRIS), the 2D pass's 128 primitives before it bins, the per-triangle batch table's 16 384
-triangles (RXR_TRI_INFO_MAX), the one-workgroup device projection's 1024 vertices / triangles, a scene without any batch, batches
-without triangles -- against the oracle."""
+triangles (RXR_TRI_INFO_MAX), the one-workgroup device projection's 1024 vertices / triangles with NOTHING clipped (every triangle lies
+in front of the near plane: the append tables are all zero; tests/test_gpu_projection_clip.py crosses the same limits, and the scan's
+chunks and rounds, with triangles that append), a scene without any batch, batches without triangles -- against the oracle."""
 import ctypes as C
 
 import numpy as np
