@@ -696,6 +696,61 @@ int rxr_bake_shaders(rxr_ctx *ctx, const uint32_t *programs, uint32_t n, uint32_
 int rxr_bake_shaders_to(rxr_ctx *ctx, const uint32_t *programs, uint32_t n, uint32_t width, uint32_t height, float *dev_pixels,
                         uint8_t *dev_rgba, void *hip_stream);
 
+/* ---- terrain chunk textures: Terrain::bake_chunk (rusterix_amd/csrc/rxr_terrain.hip) --------------------------------------------
+ * chunk.terrain_texture, the texture every RXR_SOURCE_TERRAIN batch samples (src/chunk.rs:135-151), as Terrain::bake_chunk
+ * (src/terrain/mod.rs:318-369) makes it for build_chunk_at (:372-399, modifiers == false): side x side RGBA8 with
+ * side = chunk_size * pixels_per_tile, row-major, top row first.  Texel (x, y) of chunk (cx, cy):
+ *   tile = (cx * chunk_size) as f32 + (x as f32 / pixels_per_tile as f32), world = tile * scale, the blend mode that of the cell
+ *   at floor(tile) (:336-344); None: sample_source(world) (:197-245), its alpha included; Blend(r): sample_source_blended_radius
+ *   (world, r) (:247-298); BlendOffset(r, off) and Custom(r, _, off): the same at world + off.  Integer texels in, integer bytes
+ *   out, every f32 operation once and in the reference's order (no libm): the bytes are the reference's bytes.
+ * The quirks are kept: sample_source's cell is floor(world / scale), not floor(tile); its uv is x - trunc(x), plus 1.0 when
+ * negative, which can be exactly 1.0; no source is the 135 / 120 checker by cell parity; a blended texel without a valid tap --
+ * radius 0 included, whose only weight is 0 / 0 -- is the checker with the colours swapped (120 / 135), taken at the position the
+ * function was given; a tap exactly on the rim counts with weight 0; a blended texel has alpha 255.
+ * process_batch_modifiers (modifiers == true) needs the map and the ShapeFX graph: host only, not part of this. */
+#define RXR_TERRAIN_BLEND_NONE 0u     /* TerrainBlendMode::None                         (src/terrain/chunk.rs:13-18) */
+#define RXR_TERRAIN_BLEND_RADIUS 1u   /* Blend(r): sample_source_blended_radius(world_pos, r)                        */
+#define RXR_TERRAIN_BLEND_OFFSET 2u   /* BlendOffset(r, off) and Custom(r, _, off): ...(world_pos + off, r)          */
+/* cell_blend[i] = kind | radius << 8, radius 0..255 (the reference's u8) */
+#define RXR_TERRAIN_MAX_CELLS (1u << 22)  /* cells of the bounding rectangle of one terrain                          */
+#define RXR_TERRAIN_MAX_STEPS 64u         /* ceil(radius / (min(scale) * 0.5)): (2 * 64 + 1)^2 = 16 641 taps a texel */
+/* validation only, no context: the status rxr_set_terrain would return and, in `message`, the reason.  RXR_ERR_INVALID: a scale
+ * that is not finite and > 0 (the reference never leaves its tap loop at scale 0), chunk_size < 1, a non-finite offset, a texture
+ * index outside [-1, n_textures), a zero-sized or NULL texture, an unknown blend kind (or bits above the radius), a bounding
+ * rectangle of more than RXR_TERRAIN_MAX_CELLS cells, a NULL array.  RXR_ERR_UNSUPPORTED: a cell whose steps exceed
+ * RXR_TERRAIN_MAX_STEPS (the host bakes such a terrain itself). */
+int rxr_check_terrain(const float scale[2], int32_t chunk_size, const int32_t *cell_xy, const int32_t *cell_texture,
+                      const uint32_t *cell_blend, const float *cell_offset, uint32_t n_cells, const rxr_texture *textures,
+                      uint32_t n_textures, char *message, uint32_t message_capacity);
+/* makes a terrain resident (it stays until the next call; n_cells == 0 removes it: every texel is then a checker texel).  The
+ * caller flattens Terrain.chunks' `sources` and `blend_modes` maps (src/terrain/chunk.rs:29-31) into one cell list.
+ * cell_texture: -1 wherever sample_source falls through to the checker (get_source is None, the variant is neither TileId nor
+ * MaterialId, the lookup or textures.first() failed), else the index of that first texture in `textures`.  A coordinate given
+ * twice: the later entry wins.  The library keeps a dense grid over the cells' bounding rectangle; cells outside it have no
+ * source and blend None.  Arrays are read before the call returns.  A refused call leaves the resident terrain as it was.
+ * Replaces: Terrain::get_source / get_blend_mode, src/terrain/mod.rs:115-145. */
+int rxr_set_terrain(rxr_ctx *ctx, const float scale[2], int32_t chunk_size,
+                    const int32_t *cell_xy,       /* [n_cells][2] world tile coordinates                                  */
+                    const int32_t *cell_texture,  /* [n_cells] index into `textures`, or -1                               */
+                    const uint32_t *cell_blend,   /* [n_cells]                                                            */
+                    const float *cell_offset,     /* [n_cells][2], read for RXR_TERRAIN_BLEND_OFFSET cells; NULL = zeros  */
+                    uint32_t n_cells, const rxr_texture *textures, uint32_t n_textures);
+/* n chunks in one call: bake i is side * side * 4 bytes at rgba + i * side * side * 4 -- the bytes of the Texture bake_chunk
+ * returns for chunk_coords[i].  RXR_ERR_INVALID: no rxr_set_terrain yet, pixels_per_tile < 1, side > RXR_BAKE_MAX_DIM,
+ * n * side * side > RXR_BAKE_MAX_TEXELS, or chunk_coords[i] * chunk_size outside i32 (the reference overflows).  n == 0 does
+ * nothing.  Host memory, blocking.  The call is split into launches of bounded work (texels x taps; RXR_TERRAIN_LAUNCH_TAPS in
+ * the environment, read at each call, overrides the bound).  Leaves frame state, scratch and the textures of rxr_set_textures
+ * alone.  Multi-device handles: member 0, for rxr_set_terrain as well.
+ * Replaces: Terrain::bake_chunk, src/terrain/mod.rs:318-369. */
+int rxr_bake_terrain(rxr_ctx *ctx, const int32_t *chunk_coords, uint32_t n, int32_t pixels_per_tile, uint8_t *rgba);
+/* the same into DEVICE memory (its first and last byte are checked to be memory of the context's device; 4-byte aligned), queued
+ * on hip_stream (NULL = the context's stream); chunk_coords is host memory and is read before the call returns.  Asynchronous.
+ * Multi-device handles: RXR_ERR_UNSUPPORTED (use rxr_member).
+ * Replaces: the rayon rows of Terrain::bake_chunk, src/terrain/mod.rs:331-366. */
+int rxr_bake_terrain_to(rxr_ctx *ctx, const int32_t *chunk_coords, uint32_t n, int32_t pixels_per_tile, uint8_t *dev_rgba,
+                        void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,9 @@ class RxrLight(C.Structure):
     ]
 
 
+TERRAIN_BLEND_NONE, TERRAIN_BLEND_RADIUS, TERRAIN_BLEND_OFFSET = 0, 1, 2   # include/rxr.h RXR_TERRAIN_BLEND_*
+
+
 class RasterizeError(RuntimeError):
     def __init__(self, code, msg=""):
         super().__init__(f"rasterize failed with status {code}: {msg}")
@@ -470,6 +473,19 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         L.chunk_add_shader_baked = fn("chunk_add_shader_baked", i32, vp, i32, vp, u32, i32, u32, C.POINTER(pu), pu, u32)
         L.chunk_shader_texture = fn("chunk_shader_texture", i32, vp, i32, u32, pu, pu, pb)
 
+    # terrain chunk textures (product host library only, like the shader bake)
+    has_terrain = hasattr(lib, prefix + "terrain_new")
+    if has_terrain:
+        pi = C.POINTER(C.c_int32)
+        L.terrain_new = fn("terrain_new", vp, f32, f32, i32)
+        L.terrain_free = fn("terrain_free", None, vp)
+        L.terrain_set_source = fn("terrain_set_source", None, vp, i32, i32, pb, u32, u32)
+        L.terrain_set_blend_mode = fn("terrain_set_blend_mode", None, vp, i32, i32, u32, u32, f32, f32)
+        L.terrain_bake_chunk = fn("terrain_bake_chunk", i32, vp, i32, i32, i32, pb)
+        L.terrain_bake_chunks = fn("terrain_bake_chunks", i32, vp, pi, u32, i32, pb)
+        L.terrain_build_chunk_at = fn("terrain_build_chunk_at", i32, vp, i32, i32, i32, vp, i32)
+        L.chunk_terrain_texture = fn("chunk_terrain_texture", i32, vp, i32, pu, pu, pb)
+
     def last_error():
         if not hasattr(lib, prefix + "last_error"):
             return ""
@@ -704,6 +720,18 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
             L.chunk_shader_texture(self._scene._h, self.index, index, C.byref(w), C.byref(h), _bp(data))
             return Texture(data, w.value, h.value)
 
+        def terrain_texture(self):
+            """chunk.terrain_texture as a Texture, or None"""
+            if not has_terrain:
+                raise NotImplementedError(f"{name}: no terrain bake in this library")
+            w, h = C.c_uint32(), C.c_uint32()
+            rc = L.chunk_terrain_texture(self._scene._h, self.index, C.byref(w), C.byref(h), None)
+            if rc <= 0:
+                return None
+            data = np.zeros(w.value * h.value * 4, np.uint8)
+            L.chunk_terrain_texture(self._scene._h, self.index, C.byref(w), C.byref(h), _bp(data))
+            return Texture(data, w.value, h.value)
+
         def add_occluder(self, mn, mx, occlusion):
             L.chunk_add_occluder(self._scene._h, self.index, mn[0], mn[1], mx[0], mx[1], occlusion)
             return self
@@ -864,6 +892,64 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
             L.scene_batch3d_copy(self._h, list_kind, chunk, index, _fp(pv), _fp(uv), _fp(nr), _up(idx), _fp(ed), _fp(bb))
             return dict(projected_vertices=pv, clipped_uvs=uv, clipped_normals=nr, clipped_indices=idx, edges=ed,
                         bounding_box=bb, has_normals=bool(hn.value))
+
+    class Terrain:
+        """reference src/terrain/mod.rs: what Terrain::bake_chunk reads.  A cell's source is given as the Texture sample_source would
+        sample (tile.textures.first() behind the TileId / MaterialId lookup), or None for a source that resolves to none."""
+
+        def __init__(self, scale=(1.0, 1.0), chunk_size=16):
+            if not has_terrain:
+                raise NotImplementedError(f"{name}: no terrain bake in this library")
+            self.scale, self.chunk_size = (float(scale[0]), float(scale[1])), int(chunk_size)
+            self._h = L.terrain_new(self.scale[0], self.scale[1], self.chunk_size)
+
+        def __del__(self):
+            if getattr(self, "_h", None):
+                L.terrain_free(self._h)
+                self._h = None
+
+        def set_source(self, x, y, texture):
+            """Terrain::set_source (:133-137)"""
+            if texture is None:
+                L.terrain_set_source(self._h, x, y, None, 0, 0)
+            else:
+                L.terrain_set_source(self._h, x, y, _bp(texture.data), texture.width, texture.height)
+            return self
+
+        def set_blend_mode(self, x, y, kind, radius=0, offset=(0.0, 0.0)):
+            """Terrain::set_blend_mode (:127-130); kind: TERRAIN_BLEND_NONE / _RADIUS (Blend(r)) / _OFFSET (BlendOffset(r, off), Custom)"""
+            L.terrain_set_blend_mode(self._h, x, y, kind, radius, offset[0], offset[1])
+            return self
+
+        def _side(self, pixels_per_tile):
+            return max(self.chunk_size * int(pixels_per_tile), 0)
+
+        def bake_chunk(self, coord, pixels_per_tile):
+            """Terrain::bake_chunk (:318-369) on the CPU (the host's worker pool): a Texture"""
+            side = self._side(pixels_per_tile)
+            data = np.zeros(max(side * side * 4, 4), np.uint8)
+            rc = L.terrain_bake_chunk(self._h, coord[0], coord[1], pixels_per_tile, _bp(data))
+            if rc != 0:
+                raise RasterizeError(rc, last_error())
+            return Texture(data[:side * side * 4], side, side)
+
+        def bake_chunks(self, coords, pixels_per_tile):
+            """the same for every chunk of `coords` in one device call (rxr_bake_terrain, include/rxr.h): [n][side][side][4] uint8"""
+            cc = np.ascontiguousarray(np.asarray(coords, np.int32).reshape(-1, 2))
+            side = self._side(pixels_per_tile)
+            out = np.zeros((cc.shape[0], side, side, 4), np.uint8)
+            rc = L.terrain_bake_chunks(self._h, cc.ctypes.data_as(C.POINTER(C.c_int32)), cc.shape[0], pixels_per_tile,
+                                       _bp(out) if out.size else None)
+            if rc != 0:
+                raise RasterizeError(rc, last_error())
+            return out
+
+        def build_chunk_at(self, coord, pixels_per_tile, chunk):
+            """Terrain::build_chunk_at (:372-399) without modifiers: chunk.terrain_texture baked on the device"""
+            rc = L.terrain_build_chunk_at(self._h, coord[0], coord[1], pixels_per_tile, chunk._scene._h, chunk.index)
+            if rc != 0:
+                raise RasterizeError(rc, last_error())
+            return chunk
 
     class Assets:
         """reference src/server/assets.rs (`tile_list`, `.textures(..)` builder)."""
@@ -1079,7 +1165,7 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
 
     return types.SimpleNamespace(
         name=name, lib=lib, prefix=prefix, raw=L,
-        Scene=Scene, Batch3D=Batch3D, Batch2D=Batch2D, Chunk=Chunk, Assets=Assets, Rasterizer=Rasterizer,
+        Scene=Scene, Batch3D=Batch3D, Batch2D=Batch2D, Chunk=Chunk, Assets=Assets, Rasterizer=Rasterizer, Terrain=Terrain,
         D3OrbitCamera=D3OrbitCamera, D3FirstPCamera=D3FirstPCamera,
         # shared value types
         Texture=Texture, Tile=Tile, Light=Light, PixelSource=PixelSource, RenderMode=RenderMode,

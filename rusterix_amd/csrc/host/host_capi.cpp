@@ -3,6 +3,7 @@
 // C ABI of include/rxr.h to the HIP kernels; there is no CPU path here.
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "rusterix_host.hpp"
 
@@ -151,6 +152,56 @@ int rxh_chunk_shader_texture(void *s, int chunk, uint32_t index, uint32_t *w, ui
 // Scene::bake_shaders (rxr_bake_shaders' arrays, include/rxr.h); RXR_OK or a negative rxr_status
 int rxh_scene_bake_shaders(void *s, void *assets, const uint32_t *programs, uint32_t n, uint32_t width, uint32_t height, float *pixels, uint8_t *rgba) {
     return ((Scene *)s)->bake_shaders(*(const Assets *)assets, programs, n, width, height, pixels, rgba);
+}
+// ---- terrain (rusterix::Terrain) --------------------------------------------------------------------
+void *rxh_terrain_new(float scale_x, float scale_y, int32_t chunk_size) {
+    Terrain *t = new Terrain();
+    t->scale[0] = scale_x;
+    t->scale[1] = scale_y;
+    t->chunk_size = chunk_size;
+    return t;
+}
+void rxh_terrain_free(void *t) { delete (Terrain *)t; }
+// Terrain::set_source behind the asset lookup: the texture the source resolves to; rgba == NULL: a source without one
+void rxh_terrain_set_source(void *t, int32_t x, int32_t y, const uint8_t *rgba, uint32_t w, uint32_t h) {
+    if (!rgba) return ((Terrain *)t)->set_source(x, y, nullptr);
+    Texture tex;
+    tex.width = w;
+    tex.height = h;
+    tex.data.assign(rgba, rgba + (size_t)w * h * 4);
+    ((Terrain *)t)->set_source(x, y, &tex);
+}
+// Terrain::set_blend_mode; kind: RXR_TERRAIN_BLEND_* (include/rxr.h)
+void rxh_terrain_set_blend_mode(void *t, int32_t x, int32_t y, uint32_t kind, uint32_t radius, float offset_x, float offset_y) {
+    ((Terrain *)t)->set_blend_mode(x, y, kind, radius, offset_x, offset_y);
+}
+// Terrain::bake_chunk on the CPU: side * side * 4 bytes; RXR_OK or a negative rxr_status
+int rxh_terrain_bake_chunk(void *t, int32_t cx, int32_t cy, int32_t ppt, uint8_t *rgba) {
+    std::vector<uint8_t> out;
+    const int rc = ((Terrain *)t)->bake_chunk(cx, cy, ppt, out);
+    if (rc == RXR_OK) memcpy(rgba, out.data(), out.size());
+    return rc;
+}
+// the same for n chunks on the device (rxr_bake_terrain)
+int rxh_terrain_bake_chunks(void *t, const int32_t *coords, uint32_t n, int32_t ppt, uint8_t *rgba) {
+    return ((Terrain *)t)->bake_chunks(coords, n, ppt, rgba);
+}
+// Terrain::build_chunk_at without modifiers: chunks[chunk].terrain_texture from the device's bake
+int rxh_terrain_build_chunk_at(void *t, int32_t cx, int32_t cy, int32_t ppt, void *s, int chunk) {
+    Scene *sc = (Scene *)s;
+    if (chunk < 0 || (size_t)chunk >= sc->chunks.size()) return RXR_ERR_INVALID;
+    return ((Terrain *)t)->build_chunk_at(cx, cy, ppt, sc->chunks[chunk]);
+}
+// chunks[chunk].terrain_texture: 1 and its size if present, 0 for None; rgba (may be NULL) receives w * h * 4 bytes
+int rxh_chunk_terrain_texture(void *s, int chunk, uint32_t *w, uint32_t *h, uint8_t *rgba) {
+    Scene *sc = (Scene *)s;
+    if (chunk < 0 || (size_t)chunk >= sc->chunks.size()) return -1;
+    const Chunk &c = sc->chunks[chunk];
+    if (!c.has_terrain_texture) return 0;
+    *w = c.terrain_texture.width;
+    *h = c.terrain_texture.height;
+    if (rgba) memcpy(rgba, c.terrain_texture.data.data(), c.terrain_texture.data.size());
+    return 1;
 }
 void rxh_chunk_add_light(void *s, int chunk, const rxr_light *l) { ((Scene *)s)->chunks[chunk].lights.push_back(*l); }
 // scene.add_shader (src/scene.rs:104-134) minus the parser / compiler; chunk >= 0: that chunk's shaders

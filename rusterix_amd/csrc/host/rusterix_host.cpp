@@ -488,6 +488,7 @@ std::vector<int> g_devices;  // more than one entry: rxr_create_multi
 std::string g_error;
 uint64_t g_tex_static_gen = 0, g_tex_dynamic_gen = 0;
 uint64_t g_shaders_gen = 0, g_shader_env_gen = 0;
+uint64_t g_terrain_gen = 0;   // the Terrain::generation the context's resident terrain was registered from (0: none)
 // (RXR_DEVICE_PROJECTION=1 in the environment makes device projection the initial choice, as in the Rust shim: shim/.../lib.rs)
 bool g_device_projection = [] { const char *e = getenv("RXR_DEVICE_PROJECTION"); return e && e[0] == '1'; }();
 bool g_device_edges = !(getenv("RXR_HOST_EDGES") && atoi(getenv("RXR_HOST_EDGES")) != 0);
@@ -521,6 +522,7 @@ void drop_context_locked() {
     g_mesh2d_fingerprint = 0;
     g_tex_static_gen = g_tex_dynamic_gen = 0;
     g_shaders_gen = g_shader_env_gen = 0;
+    g_terrain_gen = 0;
 }
 }  // namespace
 
@@ -854,6 +856,200 @@ int Scene::intersect(const float *origins, const float *dirs, uint32_t n, uint32
     const int rc = rxr_intersect(ctx, origins, dirs, n, flags, t, mesh, triangle, hitpoint, uv, normal);
     if (rc != RXR_OK) g_error = rxr_last_error(ctx);
     return rc;
+}
+
+// ---- Terrain --------------------------------------------------------------------------------------
+namespace {
+int32_t div_euclid(int32_t a, int32_t b) {
+    int32_t q = a / b;
+    if (a % b < 0) q -= 1;   // (b > 0)
+    return q;
+}
+// Rust's `x as i32` / `x as usize` / `x as u8`: saturating, NaN -> 0
+int32_t as_i32(float x) {
+    if (x != x) return 0;
+    if (x <= -2147483648.0f) return INT32_MIN;
+    if (x >= 2147483648.0f) return INT32_MAX;
+    return (int32_t)x;
+}
+size_t as_usize(float x) {
+    if (!(x > 0.0f)) return 0;
+    if (x >= 18446744073709551616.0f) return SIZE_MAX;
+    return (size_t)x;
+}
+uint8_t as_u8(float x) {
+    if (!(x > 0.0f)) return 0;
+    if (x >= 255.0f) return 255;
+    return (uint8_t)x;
+}
+
+// the read side of a Terrain for one bake
+struct TerrainSampler {
+    const Terrain &t;
+    const Terrain::Cell *cell(int32_t x, int32_t y) const {
+        auto it = t.cells.find({x, y});
+        return it == t.cells.end() ? nullptr : &it->second;
+    }
+    // sample_source, src/terrain/mod.rs:197-245
+    bool sample_source(float wx, float wy, uint8_t px[4]) const {
+        const float qx = wx / t.scale[0], qy = wy / t.scale[1];
+        const int32_t x = as_i32(std::floor(qx)), y = as_i32(std::floor(qy));
+        float u = qx - std::trunc(qx), v = qy - std::trunc(qy);   // f32::fract
+        if (u < 0.0f) u = u + 1.0f;
+        if (v < 0.0f) v = v + 1.0f;
+        const Terrain::Cell *c = cell(x, y);
+        if (c && c->has_source && c->texture >= 0) {
+            const Texture &tex = t.textures[(size_t)c->texture];   // Texture::sample_nearest, src/texture.rs:307-323
+            size_t tx = as_usize(std::round(u * ((float)tex.width - 1.0f))), ty = as_usize(std::round(v * ((float)tex.height - 1.0f)));
+            tx = std::min<size_t>(tx, tex.width - 1);
+            ty = std::min<size_t>(ty, tex.height - 1);
+            memcpy(px, tex.data.data() + (ty * tex.width + tx) * 4, 4);
+            return true;
+        }
+        const uint8_t g = (((x & 1) ^ (y & 1)) == 0) ? 135 : 120;
+        px[0] = px[1] = px[2] = g;
+        px[3] = 255;
+        return false;
+    }
+    // sample_source_blended_radius, :247-298
+    void blended(float wx, float wy, float radius, uint8_t px[4]) const {
+        Vec3 sum{0.0f, 0.0f, 0.0f};
+        float weight_sum = 0.0f;
+        const float step = std::min(t.scale[0], t.scale[1]) * 0.5f;
+        const float radius_squared = radius * radius;
+        const int32_t steps = as_i32(std::ceil(radius / step));
+        for (int32_t dy = -steps; dy <= steps; ++dy)
+            for (int32_t dx = -steps; dx <= steps; ++dx) {
+                const float ox = (float)dx * step, oy = (float)dy * step;
+                const float dist2 = ox * ox + oy * oy;
+                if (dist2 > radius_squared) continue;
+                uint8_t p[4];
+                if (sample_source(wx + ox, wy + oy, p)) {
+                    const float tt = 1.0f - (dist2 / radius_squared);
+                    const float weight = tt * tt;
+                    sum += Vec3{(float)p[0], (float)p[1], (float)p[2]} * weight;
+                    weight_sum += weight;
+                }
+            }
+        if (weight_sum > 0.0f) {
+            const Vec3 avg = sum / weight_sum;
+            px[0] = as_u8(std::round(avg.x));
+            px[1] = as_u8(std::round(avg.y));
+            px[2] = as_u8(std::round(avg.z));
+        } else {
+            const int32_t x = as_i32(std::floor(wx / t.scale[0])), y = as_i32(std::floor(wy / t.scale[1]));
+            px[0] = px[1] = px[2] = (((x ^ y) & 1) == 0) ? 120 : 135;
+        }
+        px[3] = 255;
+    }
+};
+}  // namespace
+
+void Terrain::set_source(int32_t x, int32_t y, const Texture *texture) {
+    Cell &c = cells[{x, y}];
+    c.has_source = true;
+    c.texture = -1;
+    if (texture && texture->width && texture->height) {
+        size_t i = 0;
+        for (; i < textures.size(); ++i)
+            if (textures[i].width == texture->width && textures[i].height == texture->height && textures[i].data == texture->data) break;
+        if (i == textures.size()) textures.push_back(*texture);
+        c.texture = (int32_t)i;
+    }
+    chunks.insert({div_euclid(x, chunk_size), div_euclid(y, chunk_size)});
+    touch();
+}
+
+void Terrain::set_blend_mode(int32_t x, int32_t y, uint32_t kind, uint32_t radius, float offset_x, float offset_y) {
+    Cell &c = cells[{x, y}];
+    c.blend = kind == RXR_TERRAIN_BLEND_NONE ? RXR_TERRAIN_BLEND_NONE : (kind | (radius & 255u) << 8);
+    c.offset[0] = kind == RXR_TERRAIN_BLEND_OFFSET ? offset_x : 0.0f;
+    c.offset[1] = kind == RXR_TERRAIN_BLEND_OFFSET ? offset_y : 0.0f;
+    chunks.insert({div_euclid(x, chunk_size), div_euclid(y, chunk_size)});
+    touch();
+}
+
+void Terrain::flatten(std::vector<int32_t> &xy, std::vector<int32_t> &texture, std::vector<uint32_t> &blend, std::vector<float> &offset) const {
+    for (const auto &kv : cells) {
+        xy.push_back(kv.first.first);
+        xy.push_back(kv.first.second);
+        texture.push_back(kv.second.has_source ? kv.second.texture : -1);
+        blend.push_back(kv.second.blend);
+        offset.push_back(kv.second.offset[0]);
+        offset.push_back(kv.second.offset[1]);
+    }
+}
+
+int Terrain::bake_chunk(int32_t cx, int32_t cy, int32_t ppt, std::vector<uint8_t> &rgba) const {
+    if (!(std::isfinite(scale[0]) && std::isfinite(scale[1]) && scale[0] > 0.0f && scale[1] > 0.0f) || chunk_size < 1 || ppt < 1) {
+        g_error = "Terrain::bake_chunk: scale must be finite and > 0, chunk_size and pixels_per_tile at least 1";
+        return RXR_ERR_INVALID;
+    }
+    const int64_t min_x = (int64_t)cx * chunk_size, min_y = (int64_t)cy * chunk_size, side = (int64_t)chunk_size * ppt;
+    if (min_x < INT32_MIN || min_x > INT32_MAX || min_y < INT32_MIN || min_y > INT32_MAX || side > RXR_BAKE_MAX_DIM) {
+        g_error = "Terrain::bake_chunk: chunk coordinates or texture size out of range";
+        return RXR_ERR_INVALID;
+    }
+    std::lock_guard<std::recursive_mutex> lk(g_mu);   // (the worker pool runs one job at a time)
+    rgba.assign((size_t)side * side * 4, 0);
+    const TerrainSampler S{*this};
+    rxr_parallel::run((size_t)side, (size_t)side * side * 16, [&](size_t y) {   // :331-366, one row per item
+        uint8_t *line = rgba.data() + y * (size_t)side * 4;
+        for (int64_t x = 0; x < side; ++x) {
+            const float tile_x = (float)(int32_t)min_x + ((float)x / (float)ppt), tile_y = (float)(int32_t)min_y + ((float)y / (float)ppt);
+            const float world_x = tile_x * scale[0], world_y = tile_y * scale[1];
+            const Cell *c = S.cell(as_i32(std::floor(tile_x)), as_i32(std::floor(tile_y)));
+            const uint32_t kind = c ? (c->blend & 255u) : RXR_TERRAIN_BLEND_NONE;
+            uint8_t *px = line + x * 4;
+            if (kind == RXR_TERRAIN_BLEND_NONE) (void)S.sample_source(world_x, world_y, px);
+            else if (kind == RXR_TERRAIN_BLEND_RADIUS) S.blended(world_x, world_y, (float)((c->blend >> 8) & 255u), px);
+            else S.blended(world_x + c->offset[0], world_y + c->offset[1], (float)((c->blend >> 8) & 255u), px);
+        }
+    });
+    return RXR_OK;
+}
+
+int Terrain::bake_chunks(const int32_t *coords, uint32_t n, int32_t ppt, uint8_t *rgba) const {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::string err;
+    rxr_ctx *ctx = context(&err);
+    if (!ctx) return RXR_ERR_NO_DEVICE;
+    if (g_terrain_gen != generation) {
+        std::vector<int32_t> xy, texture;
+        std::vector<uint32_t> blend;
+        std::vector<float> offset;
+        flatten(xy, texture, blend, offset);
+        std::vector<rxr_texture> tex;
+        for (const Texture &t : textures) tex.push_back(rxr_texture{t.data.data(), t.width, t.height});
+        const int rc = rxr_set_terrain(ctx, scale, chunk_size, xy.data(), texture.data(), blend.data(), offset.data(), (uint32_t)texture.size(), tex.data(),
+                                       (uint32_t)tex.size());
+        if (rc != RXR_OK) {
+            g_error = rxr_last_error(ctx);
+            return rc;
+        }
+        g_terrain_gen = generation;
+    }
+    const int rc = rxr_bake_terrain(ctx, coords, n, ppt, rgba);
+    if (rc != RXR_OK) g_error = rxr_last_error(ctx);
+    return rc;
+}
+
+int Terrain::build_chunk_at(int32_t cx, int32_t cy, int32_t ppt, Chunk &chunk) const {
+    if (chunk_size < 1 || ppt < 1 || (int64_t)chunk_size * ppt > RXR_BAKE_MAX_DIM) {
+        g_error = "Terrain::build_chunk_at: chunk_size and pixels_per_tile must be at least 1 and their product at most RXR_BAKE_MAX_DIM";
+        return RXR_ERR_INVALID;
+    }
+    const uint32_t side = (uint32_t)(chunk_size * ppt);
+    Texture baked;
+    baked.width = baked.height = side;
+    baked.data.resize((size_t)side * side * 4);
+    const int32_t coord[2] = {cx, cy};
+    const int rc = bake_chunks(coord, 1, ppt, baked.data.data());
+    if (rc != RXR_OK) return rc;
+    if (!chunks.count({cx, cy})) return RXR_OK;   // :383-391: baked, but the terrain has no chunk there: nothing is set
+    chunk.terrain_texture = std::move(baked);
+    chunk.has_terrain_texture = true;
+    return RXR_OK;
 }
 
 void Rasterizer::screen_ray(float x, float y, float origin[3], float dir[3]) const {

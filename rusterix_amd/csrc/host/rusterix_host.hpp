@@ -14,6 +14,7 @@
 #pragma once
 #include <cstdint>
 #include <map>
+#include <set>
 #include <string>
 #include <functional>
 #include <new>
@@ -265,6 +266,41 @@ public:
     // baked from it on the device onto shader_textures (None for a program without `shade`, which is not baked); the bytes are host memory.
     // Returns the shader's index in the chunk or a negative rxr_status (a program the device cannot bake is not added).
     int chunk_add_shader(size_t chunk, Program program, const Assets &assets);
+};
+
+// src/terrain/mod.rs, src/terrain/chunk.rs: what Terrain::bake_chunk reads -- `sources` and `blend_modes` per cell, behind the asset
+// lookup: a cell's source is the texture sample_source would sample (tile.textures.first()), or a source without one (a PixelSource
+// that is neither TileId nor MaterialId, or whose lookup fails: the checker, as for no source at all)
+class Terrain {
+public:
+    struct Cell {
+        bool has_source = false;
+        int32_t texture = -1;                         // index into `textures`
+        uint32_t blend = RXR_TERRAIN_BLEND_NONE;      // kind | radius << 8 (include/rxr.h)
+        float offset[2] = {0.0f, 0.0f};
+    };
+    float scale[2] = {1.0f, 1.0f};                    // :22
+    int32_t chunk_size = 16;                          // :24
+    std::map<std::pair<int32_t, int32_t>, Cell> cells;            // keyed (x, y), world tile coordinates
+    std::set<std::pair<int32_t, int32_t>> chunks;                 // Terrain.chunks' keys (get_or_create_chunk, :43-51)
+    std::vector<Texture> textures;                                // de-duplicated by content
+    uint64_t generation = next_generation();                      // re-stamped by every mutator; code that edits the fields calls touch()
+    void touch() { generation = next_generation(); }
+
+    void set_source(int32_t x, int32_t y, const Texture *texture);   // :133-137; nullptr: a source without a texture
+    void set_blend_mode(int32_t x, int32_t y, uint32_t kind, uint32_t radius, float offset_x, float offset_y);   // :127-130
+    // Terrain::bake_chunk (:318-369) on the CPU, rows over the host's worker pool as the reference's run over rayon: side * side * 4
+    // bytes, side = chunk_size * pixels_per_tile.  RXR_OK, or RXR_ERR_INVALID for a scale that is not finite and > 0, chunk_size < 1 or
+    // pixels_per_tile < 1.  No bound on the radius.
+    int bake_chunk(int32_t cx, int32_t cy, int32_t pixels_per_tile, std::vector<uint8_t> &rgba) const;
+    // the same for n chunks on the device (rxr_set_terrain when the terrain changed since it was registered, then rxr_bake_terrain,
+    // include/rxr.h): n * side * side * 4 bytes.  RXR_OK or a negative rxr_status; there is no fall-back to the CPU.
+    int bake_chunks(const int32_t *coords, uint32_t n, int32_t pixels_per_tile, uint8_t *rgba) const;
+    // Terrain::build_chunk_at (:372-399) with modifiers == false: bakes on the device and sets chunk.terrain_texture -- unless the
+    // terrain has no chunk at `coord`, as in the reference.  RXR_OK or a negative rxr_status.
+    int build_chunk_at(int32_t cx, int32_t cy, int32_t pixels_per_tile, Chunk &chunk) const;
+    // the cell list of rxr_set_terrain
+    void flatten(std::vector<int32_t> &xy, std::vector<int32_t> &texture, std::vector<uint32_t> &blend, std::vector<float> &offset) const;
 };
 
 // src/rasterizer.rs:35-193

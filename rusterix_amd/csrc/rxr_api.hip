@@ -68,6 +68,10 @@ int rxr_quiesce(rxr_ctx *ctx) {
         ctx->bake_pending = false;
     }
     ctx->bake_jobs_used = 0;  // (every queued bake has run: the ring of program lists starts over)
+    if (ctx->terrain_pending) {  // a terrain bake on the caller's stream (rxr_bake_terrain_to) reads the resident terrain
+        HIPCHK(ctx, hipEventSynchronize(ctx->ev_terrain));
+        ctx->terrain_pending = false;
+    }
     return RXR_OK;
 }
 
@@ -182,7 +186,8 @@ void rxr_destroy(rxr_ctx *ctx) {
                       &ctx->d_list, &ctx->d_large, &ctx->d_counters, &ctx->d_fb,
                       &ctx->d_vm_code, &ctx->d_programs, &ctx->d_patterns, &ctx->d_pattern_data, &ctx->d_palette,
                       &ctx->d_isect_tris, &ctx->d_isect_misc, &ctx->d_isect_keys, &ctx->d_isect_io,
-                      &ctx->d_bake_io, &ctx->d_bake_jobs, &ctx->d_bake_fault};
+                      &ctx->d_bake_io, &ctx->d_bake_jobs, &ctx->d_bake_fault,
+                      &ctx->d_terrain_cells, &ctx->d_terrain_tex, &ctx->d_terrain_texels, &ctx->d_terrain_weights, &ctx->d_terrain_io};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     rxr_jit_drop(ctx);
@@ -197,6 +202,7 @@ void rxr_destroy(rxr_ctx *ctx) {
     if (ctx->ev_render) (void)hipEventDestroy(ctx->ev_render);
     if (ctx->ev_isect) (void)hipEventDestroy(ctx->ev_isect);
     if (ctx->ev_bake) (void)hipEventDestroy(ctx->ev_bake);
+    if (ctx->ev_terrain) (void)hipEventDestroy(ctx->ev_terrain);
     if (ctx->h_bake_fault) (void)hipHostFree(ctx->h_bake_fault);
     if (ctx->h_bake_jobs) (void)hipHostFree(ctx->h_bake_jobs);
     for (hipEvent_t ev : ctx->ev_band)

@@ -241,6 +241,21 @@ struct rxr_ctx {
     hipEvent_t ev_bake = nullptr;    // recorded behind the last bake's launches (on whichever stream they ran)
     bool bake_pending = false;       // ... and not yet waited for (rxr_quiesce)
 
+    // terrain chunk textures (rxr_terrain.hip): the resident terrain of rxr_set_terrain and the bake's buffers, all its own.
+    // d_terrain_cells: the dense grid (TerrainCell per cell of the bounding rectangle); d_terrain_tex / _texels: the source textures'
+    // records and packed texels; d_terrain_weights: 256 table offsets by radius, then one tap-weight table per radius in use;
+    // d_terrain_io: rxr_bake_terrain's device copy of the caller's host array.  terrain_blend: the grid's blend words on the host
+    // (the work estimate that splits a call into launches reads them).
+    DevBuf d_terrain_cells, d_terrain_tex, d_terrain_texels, d_terrain_weights, d_terrain_io;
+    std::vector<uint32_t> terrain_blend;
+    bool terrain_set = false;
+    float terrain_scale[2] = {1.0f, 1.0f};
+    int32_t terrain_chunk_size = 0, terrain_x0 = 0, terrain_y0 = 0;
+    uint32_t terrain_gw = 0, terrain_gh = 0, terrain_max_steps = 0;
+    hipEvent_t ev_terrain = nullptr;  // recorded behind the last terrain bake's launches (on whichever stream they ran)
+    bool terrain_pending = false;     // ... and not yet waited for (rxr_quiesce)
+    uint32_t terrain_launches = 0;    // k_terrain_bake launches of the last bake call (rxr_debug_terrain_launches)
+
     FrameStream fstream;    // rxr_stream_begin .. rxr_upload_frame
     int last_upload_streamed = 0;  // 0 plain, 1 streamed (copied), 2 streamed out of page-locked arrays
 
