@@ -22,15 +22,9 @@
 // compiler's sequence with the no-op instructions removed, so the result is the same float; outside
 // the window it is the compiler's code.  tests/test_gpu_exact_math.py checks bit equality over
 // billions of operand pairs, including the window edges and every special value.
-//
-// RXR_EXACT_FAST=0 compiles the plain operators instead (A/B measurements).
 #pragma once
 #ifndef RXR_JIT
 #include <hip/hip_runtime.h>
-#endif
-
-#ifndef RXR_EXACT_FAST
-#define RXR_EXACT_FAST 1
 #endif
 
 namespace rxm {
@@ -88,14 +82,11 @@ __device__ __forceinline__ float sqrt_core(float x) {
 // n / d for one numerator.  Only cheaper than `/` when the window test is cheap for the caller, so it
 // takes the caller's knowledge: `ok` must imply in_window(n) && in_window(d) for this lane.
 __device__ __forceinline__ float div1_known(float n, float d, bool ok) {
-#if RXR_EXACT_FAST
     if (wave_all(ok)) return div_chain(n, d, rcp_refined(d));
-#endif
     return n / d;
 }
 
 __device__ __forceinline__ void div2(float n0, float n1, float d, float &q0, float &q1) {
-#if RXR_EXACT_FAST
     float lo = fminf(__builtin_fabsf(n0), __builtin_fabsf(n1)), hi = fmaxf(__builtin_fabsf(n0), __builtin_fabsf(n1));
     if (wave_all(in_window(d) && lo >= WIN_LO && hi <= WIN_HI)) {
         float r = rcp_refined(d);
@@ -103,7 +94,6 @@ __device__ __forceinline__ void div2(float n0, float n1, float d, float &q0, flo
         q1 = div_chain(n1, d, r);
         return;
     }
-#endif
     q0 = n0 / d;
     q1 = n1 / d;
 }
@@ -112,20 +102,17 @@ __device__ __forceinline__ void div2(float n0, float n1, float d, float &q0, flo
 // row-mode round): r = denominator_part(d).  The same instructions on the same operands: the same quotients.
 __device__ __forceinline__ float denominator_part(float d) { return in_window(d) ? rcp_refined(d) : 0.0f; }  // (never 0 inside the window)
 __device__ __forceinline__ void div2_pre(float n0, float n1, float d, float r, float &q0, float &q1) {
-#if RXR_EXACT_FAST
     float lo = fminf(__builtin_fabsf(n0), __builtin_fabsf(n1)), hi = fmaxf(__builtin_fabsf(n0), __builtin_fabsf(n1));
     if (wave_all(r != 0.0f && lo >= WIN_LO && hi <= WIN_HI)) {
         q0 = div_chain(n0, d, r);
         q1 = div_chain(n1, d, r);
         return;
     }
-#endif
     q0 = n0 / d;
     q1 = n1 / d;
 }
 
 __device__ __forceinline__ void div3(float n0, float n1, float n2, float d, float &q0, float &q1, float &q2) {
-#if RXR_EXACT_FAST
     float lo = __builtin_fminf(__builtin_fminf(__builtin_fabsf(n0), __builtin_fabsf(n1)), __builtin_fabsf(n2));
     float hi = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(n0), __builtin_fabsf(n1)), __builtin_fabsf(n2));
     if (wave_all(in_window(d) && lo >= WIN_LO && hi <= WIN_HI)) {
@@ -135,7 +122,6 @@ __device__ __forceinline__ void div3(float n0, float n1, float n2, float d, floa
         q2 = div_chain(n2, d, r);
         return;
     }
-#endif
     q0 = n0 / d;
     q1 = n1 / d;
     q2 = n2 / d;
@@ -143,7 +129,6 @@ __device__ __forceinline__ void div3(float n0, float n1, float n2, float d, floa
 
 // (n0, n1, n2, d) / d: the perspective divide of a Vec4 by its own w (d / d is exactly 1 in the window)
 __device__ __forceinline__ void div3_self(float n0, float n1, float n2, float d, float &q0, float &q1, float &q2, float &qd) {
-#if RXR_EXACT_FAST
     float lo = __builtin_fminf(__builtin_fminf(__builtin_fabsf(n0), __builtin_fabsf(n1)), __builtin_fabsf(n2));
     float hi = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(n0), __builtin_fabsf(n1)), __builtin_fabsf(n2));
     if (wave_all(in_window(d) && lo >= WIN_LO && hi <= WIN_HI)) {
@@ -154,7 +139,6 @@ __device__ __forceinline__ void div3_self(float n0, float n1, float n2, float d,
         qd = 1.0f;
         return;
     }
-#endif
     q0 = n0 / d;
     q1 = n1 / d;
     q2 = n2 / d;
@@ -162,10 +146,8 @@ __device__ __forceinline__ void div3_self(float n0, float n1, float n2, float d,
 }
 
 __device__ __forceinline__ float sqrt_exact(float x) {
-#if RXR_EXACT_FAST
     // 2^-96 <= x < inf  (bits in [0x0f800000, 0x7f800000))
     if (wave_all((__float_as_uint(x) - 0x0f800000u) < (0x7f800000u - 0x0f800000u))) return sqrt_core(x);
-#endif
     return sqrtf(x);
 }
 
@@ -175,7 +157,6 @@ __device__ __forceinline__ float sqrt_exact(float x) {
 // rounding, so only their lower bound is tested.
 __device__ __forceinline__ void normalize3(float x, float y, float z, float &ox, float &oy, float &oz, float &mag) {
     float m2 = (x * x + y * y) + z * z;
-#if RXR_EXACT_FAST
     float lo = __builtin_fminf(__builtin_fminf(__builtin_fabsf(x), __builtin_fabsf(y)), __builtin_fabsf(z));
     if (wave_all(sq_in_window(m2) && lo >= WIN_LO)) {
         float m = sqrt_core(m2);
@@ -186,7 +167,6 @@ __device__ __forceinline__ void normalize3(float x, float y, float z, float &ox,
         mag = m;
         return;
     }
-#endif
     float m = sqrtf(m2);
     ox = x / m;
     oy = y / m;
@@ -222,7 +202,6 @@ __device__ __forceinline__ void normalize3_relaxed(float x, float y, float z, fl
 __device__ __forceinline__ uint32_t zero_or_window_key(float x) { return (__float_as_uint(x) & 0x7FFFFFFFu) - 1u; }  // 0 -> 0xFFFFFFFF
 __device__ __forceinline__ void normalize3_z(float x, float y, float z, float &ox, float &oy, float &oz) {
     float m2 = (x * x + y * y) + z * z;
-#if RXR_EXACT_FAST
     uint32_t k = min(min(zero_or_window_key(x), zero_or_window_key(y)), zero_or_window_key(z));
     if (wave_all(sq_in_window(m2) && k >= 0x2B800000u /* 2^-40 */ - 1u)) {
         float m = sqrt_core(m2);
@@ -232,7 +211,6 @@ __device__ __forceinline__ void normalize3_z(float x, float y, float z, float &o
         oz = __builtin_amdgcn_div_fixupf(div_chain(z, m, r), m, z);
         return;
     }
-#endif
     float m = sqrtf(m2);
     ox = x / m;
     oy = y / m;
@@ -243,23 +221,16 @@ __device__ __forceinline__ void normalize3_z(float x, float y, float z, float &o
 // truncates toward zero, clamps to [0, 2^32 - 1] and turns NaN into 0 -- exactly the cast.  C's `(uint32_t)x` is undefined out
 // of range, so the compiler may not be asked for it; the instruction is named directly.  Checked against the compare-and-
 // select form over a strided sweep of ALL float bit patterns in every test run (rxr_selftest_math, kind 10).
-// RXR_HW_SAT_CVT=0 compiles the compare-and-select form (A-B runs).
-#ifndef RXR_HW_SAT_CVT
-#define RXR_HW_SAT_CVT 1
-#endif
+// sat_u32_ref is that compare-and-select form.
 __device__ __forceinline__ uint32_t sat_u32_ref(float x) {
     if (!(x > 0.0f)) return 0u;  // NaN, negatives, zero
     if (x >= 4294967296.0f) return 0xFFFFFFFFu;
     return (uint32_t)x;
 }
 __device__ __forceinline__ uint32_t sat_u32(float x) {
-#if RXR_HW_SAT_CVT
     uint32_t r;
     asm("v_cvt_u32_f32_e32 %0, %1" : "=v"(r) : "v"(x));
     return r;
-#else
-    return sat_u32_ref(x);
-#endif
 }
 
 // Maximum over the 64 lanes of a wave of NON-NEGATIVE floats (+0, denormals, normals, +inf: their order is the order of their bit
@@ -302,12 +273,10 @@ __device__ __forceinline__ unsigned int wave_inclusive_add(unsigned int v) {
 
 // exp2f(k * log2f(x)) as the reference's pow32_fast computes it (rasterizer.rs:1895-1901)
 __device__ __forceinline__ float pow_exp2_log2(float x, float k) {
-#if RXR_EXACT_FAST
     // log2f scales arguments below 2^-126, exp2f arguments below -126; NaN takes neither branch
     float lg = __builtin_amdgcn_logf(x);
     float y = k * lg;
     if (wave_all(!(x < 0x1p-126f) && !(y < -126.0f))) return __builtin_amdgcn_exp2f(y);
-#endif
     return exp2f(k * log2f(x));
 }
 

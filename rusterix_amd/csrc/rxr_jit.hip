@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "rxr_ctx.h"
+#include "rxr_route.h"
 
 #include <dirent.h>
 #include <dlfcn.h>
@@ -1217,7 +1218,7 @@ bool rxr_jit_launch(rxr_ctx *ctx, const RasterParams *P, hipStream_t s) {
     size_t size = sizeof(params);
     void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &params, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
     // (frames with cut-out or profiled batches: rounds in row mode around them -- binned frames only, the others never reach that code)
-    const bool cut = P->split_rounds && ctx->jit_fn_cut[slot] && P->fused_small == 0u && (P->flags & RXR_FLAG_D3_ACTIVE);
+    const bool cut = ctx->jit_fn_cut[slot] && rxr_route::rounds_cut(P->split_rounds != 0u, P->fused_small, (P->flags & RXR_FLAG_D3_ACTIVE) != 0u);
     const hipFunction_t kernel = (hipFunction_t)(cut ? ctx->jit_fn_cut[slot] : ctx->jit_fn[slot]);
     ctx->last_raster_kernel = cut ? k_jit_cut_name : k_jit_name;
     hipEvent_t e0, e1;

@@ -33,12 +33,10 @@
 #include <cstring>
 
 #include "rxr_launch.h"
+#include "rxr_route.h"
 #endif
 
-// 1: TriShade's two spare words carry the batch's texture descriptor (make_setup, shade3d_begin); 0: A-B runs
-#ifndef RXR_DESC_IN_TRISHADE
-#define RXR_DESC_IN_TRISHADE 1
-#endif
+// TriShade's two spare words carry the batch's texture descriptor (make_setup, shade3d_begin)
 #define TS_DESC_VALID 0x80000000u
 
 #include "rxr_device.h"
@@ -54,16 +52,8 @@
 #ifndef RXR_VM_WAVES_PER_SIMD
 #define RXR_VM_WAVES_PER_SIMD 6
 #endif
-// 1: the opaque pass calls the out-of-line interpreter too (A-B runs: slower, 304 vs 236 us on the probe)
-#ifndef RXR_VM_ALWAYS_CALL
-#define RXR_VM_ALWAYS_CALL 0
-#endif
 #ifndef RXR_VEK_FUSED_MATVEC
 #define RXR_VEK_FUSED_MATVEC 1
-#endif
-// 0 (A-B runs only: emissive programs then render wrongly): the opaque pass does not carry a program's emissive to the encode step
-#ifndef RXR_VM_EMISSIVE
-#define RXR_VM_EMISSIVE 1
 #endif
 
 // -DRXR_PHASE_TIMING=1 (tuning builds only): per-phase wave-cycle totals of the raster kernel, read with
@@ -113,15 +103,8 @@ struct f3 {
 // load is unclobbered and issues it as a VECTOR load plus v_readfirstlane -- for the lights that was an L2 round trip per light and
 // wave on the critical path of the light loop (seen in the ISA: global_load_dwordx4 ... s_waitcnt vmcnt ... v_readfirstlane).
 // Only fields that are used are loaded.  The tables (lights, linedefs) are written by the upload and never by a kernel.
-#ifndef RXR_UNIFORM_2D_BATCH
-#define RXR_UNIFORM_2D_BATCH 1
-#endif
-#ifndef RXR_UNIFORM_SCALAR_LOADS
-#define RXR_UNIFORM_SCALAR_LOADS 1
-#endif
 template <class T>
 __device__ __forceinline__ T uniform_record(const T *table, uint32_t i) {
-#if RXR_UNIFORM_SCALAR_LOADS
     // word by word: a struct has no copy constructor from another address space; the loads are merged again (s_load_dwordx16 ...)
     static_assert(sizeof(T) % 4 == 0 && alignof(T) >= 4, "records of 32-bit fields");
     typedef const uint32_t __attribute__((address_space(4))) *word_ptr;
@@ -131,9 +114,6 @@ __device__ __forceinline__ T uniform_record(const T *table, uint32_t i) {
 #pragma unroll
     for (uint32_t k = 0; k < sizeof(T) / 4; ++k) dst[k] = src[k];
     return out;
-#else
-    return table[i];
-#endif
 }
 // the first 32 bytes of a record in ONE scalar load (the word-by-word form above lets the compiler fetch the fields where they are first used:
 // several dependent scalar-cache round trips when the uses sit behind one another's branches)
@@ -487,12 +467,8 @@ __device__ __forceinline__ void fragment_uv(const TriShade &S, float alpha, floa
     rxm::div2(iu, iv, irw, u, v);
 }
 
-#ifndef RXR_DESC_ONE_LOAD
-#define RXR_DESC_ONE_LOAD 1  // (0: the texture descriptor's words fetched where they are first used -- A-B measurements)
-#endif
 // texel base of a texture: the resident pool, or this frame's chunk textures in the frame blob
 __device__ __forceinline__ const uint32_t *texel_base(const RasterParams &P, const DevTexDesc &d) {
-#if RXR_DESC_ONE_LOAD
     // both bases as scalars, then a select: written as `c ? P.frame_texels : P.texels` the compiler selects between the two ADDRESSES
     // inside the parameter block and loads the pointer per lane -- one more dependent round trip in front of every texel
     // (as integers, and back through the global address space: a pointer that has been through the asm is a FLAT pointer to the
@@ -501,9 +477,6 @@ __device__ __forceinline__ const uint32_t *texel_base(const RasterParams &P, con
     asm volatile("" : "+v"(ft), "+v"(rt));  // ("v": the out-of-line interpreter sites receive P through vector registers)
     typedef const uint32_t __attribute__((address_space(1))) *global_words;
     return (const uint32_t *)(global_words)((d.all_opaque & 2u) ? ft : rt);
-#else
-    return (d.all_opaque & 2u) ? P.frame_texels : P.texels;
-#endif
 }
 
 // Chunk::sample_terrain_texture(world_pos, Vec2::one()) (chunk.rs:133-151) with Texture::get_pixel (texture.rs:527-538)
@@ -554,7 +527,6 @@ template <int X> inline constexpr bool lvl1 = X >= 1 && X != 8 && X != 9;  // (9
 // comes through the scalar cache like the batch header itself (uniform_record)
 template <int X, bool UNIFORM = false>
 __device__ __forceinline__ uint32_t batch_texel(const RasterParams &P, const DevBatch &B, float u, float v, float wx, float wy, const f3 *world3 = nullptr) {
-#if RXR_DESC_ONE_LOAD
     if constexpr (!UNIFORM && !lvl1<X>) {
         // tex, pixel and repeat_mode are neighbours in the header: one 16-byte load instead of one word now and another, behind
         // the descriptor's round trip, when the sampler wants the repeat mode
@@ -569,7 +541,6 @@ __device__ __forceinline__ uint32_t batch_texel(const RasterParams &P, const Dev
         asm volatile("" : "+v"(d.offset), "+v"(d.w), "+v"(d.h), "+v"(d.all_opaque));
         return sample_texture(d, texel_base(P, d), u, v, P.sample_mode, repeat);
     }
-#endif
     if (B.tex < 0) return B.pixel;
     if constexpr (lvl1<X>) {
         if (B.flags & DB_TERRAIN) {
@@ -582,16 +553,12 @@ __device__ __forceinline__ uint32_t batch_texel(const RasterParams &P, const Dev
         const DevTexDesc d = uniform_record(P.tex, (uint32_t)B.tex);
         return sample_texture(d, texel_base(P, d), u, v, P.sample_mode, B.repeat_mode);
     } else {
-#if RXR_DESC_ONE_LOAD
         // the descriptor in ONE 16-byte load: left to itself the compiler fetches its four words where they are first used --
         // all_opaque, then w, then h and offset, three dependent round trips between the batch header and the texel
         const uint4 raw = *reinterpret_cast<const uint4 *>(&P.tex[B.tex]);
         DevTexDesc d{raw.x, raw.y, raw.z, raw.w};
         asm volatile("" : "+v"(d.offset), "+v"(d.w), "+v"(d.h), "+v"(d.all_opaque));
         static_assert(sizeof(DevTexDesc) == 16, "one 16-byte load");
-#else
-        const DevTexDesc &d = P.tex[B.tex];
-#endif
         return sample_texture(d, texel_base(P, d), u, v, P.sample_mode, B.repeat_mode);
     }
 }
@@ -706,9 +673,7 @@ __device__ __forceinline__ void shade3d_begin(const RasterParams &P, const TriSh
 
     uint32_t texel;
     bool desc_in_record = false;  // wave-uniform
-#if RXR_DESC_IN_TRISHADE
     if constexpr (!lvl1<X> || X == 1) desc_in_record = rxm::wave_all((S.pad[1] & TS_DESC_VALID) != 0u);  // (terrain batches leave the words zero: make_setup)
-#endif
     if (desc_in_record) {  // (make_setup: the descriptor as the record carries it -- the same sampler on the same words)
         const uint32_t p0 = S.pad[0], p1 = S.pad[1];
         const DevTexDesc d{p0, p1 & 0x1FFFu, (p1 >> 13) & 0x1FFFu, (p1 >> 28) & 3u};
@@ -739,16 +704,15 @@ __device__ __forceinline__ void shade3d_begin(const RasterParams &P, const TriSh
             io.uv.y = v / 4.0f;
             io.hitpoint = rxvm::mk(world.x, world.y, world.z);
             io.time = rxvm::splat(P.time);
-            if constexpr (vm_level<X>::inline_site && !RXR_VM_ALWAYS_CALL) rxvm::shade_inline<vm_level<X>::ssp>(P, B.program_plus1 - 1u, io, rxvm::stack_block());
+            // (calling the out-of-line interpreter from the opaque pass too was slower: 304 vs 236 us on the probe)
+            if constexpr (vm_level<X>::inline_site) rxvm::shade_inline<vm_level<X>::ssp>(P, B.program_plus1 - 1u, io, rxvm::stack_block());
             else rxvm::shade_call<vm_level<X>::ssp>(P, B.program_plus1 - 1u, io);  // X == 3 / 5: from the visibility loop's alpha test
             base = mk3(io.color.x, io.color.y, io.color.z);  // :1319-1323
             normal = mk3(io.normal.x, io.normal.y, io.normal.z);
             rough = rclamp(io.roughness.x, 0.0f, 1.0f);
             metal = rclamp(io.metallic.x, 0.0f, 1.0f);
             F.opacity = io.opacity.x;  // :1403
-#if RXR_VM_EMISSIVE
             F.emis = mk3(io.emissive.x, io.emissive.y, io.emissive.z);  // :1323
-#endif
         }
     }
 
@@ -800,15 +764,9 @@ __device__ __forceinline__ void shade3d_begin(const RasterParams &P, const TriSh
 // RL: the relaxed arithmetic of RXR_LIGHT_MATH=relaxed for POINT lights (every quantity is continuous in the fragment's position
 // there: the range test, the smoothstep and the Lambert / specular cut-offs all meet their neighbours at zero, so an error of a
 // few ulp moves a channel by at most one step); spot, area and daylight lights have hard cut-offs and stay exact in both modes.
-#ifndef RXR_RL_POW6
-#define RXR_RL_POW6 1   // (0: exp2(6 log2 x) also below feature level 2 -- A-B measurements)
-#endif
-#ifndef RXR_RL_TABLE
-#define RXR_RL_TABLE 1  // (0: the light's constants from its rxr_light record in the loop -- A-B measurements)
-#endif
-#ifndef RXR_RL_FOLD
-#define RXR_RL_FOLD 1   // (0: the light direction formed and normalised first -- A-B measurements)
-#endif
+// Three A-B variants of the relaxed point-light term were tried against what stands below and are retired: the light's
+// constants read from its rxr_light record in the loop (now its LightFast record), the light direction formed and normalised
+// first (now folded into the dot products), and exp2(6 log2 x) below feature level 2 (now three multiplies).
 template <int X, bool RL = false>
 __device__ __forceinline__ void shade3d_lights(const RasterParams &P, bool hit, Frag &F) {
     const unsigned long long hitmask = __ballot(hit);
@@ -855,8 +813,7 @@ __device__ __forceinline__ void shade3d_lights(const RasterParams &P, bool hit, 
         unsigned long long ss_ok_mask = 0ull;
         // lights of this step that have a LightFast record (relaxed mode): one bit per light, tested by the scalar unit in the loop
         unsigned long long fast_mask = 0ull;
-        constexpr bool table_cull = RL && RXR_RL_TABLE;
-        if constexpr (table_cull) {
+        if constexpr (RL) {
             // Everything the step needs of a light -- position, range, whether its type is culled at all, whether it has a fast
             // record -- comes from its LightFast record in ONE round of loads (the general form below reads start / end, the fast flag,
             // the type and then position / range in four dependent round trips, each behind the previous one's branch); the
@@ -911,21 +868,27 @@ __device__ __forceinline__ void shade3d_lights(const RasterParams &P, bool hit, 
             const uint32_t li = base_i + (uint32_t)li_lane;
             todo &= todo - 1ull;
             // (read where the exact kernels have always read it; the relaxed kernels want it only behind their fast path)
-            constexpr bool table_path = RL && RXR_RL_TABLE;
             float ss_r = 0.0f;
             bool ss_fast = false;
-            if constexpr (!table_path) {
+            if constexpr (!RL) {
                 ss_r = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ss_rcp), li_lane));
                 ss_fast = (ss_ok_mask >> li_lane) & 1ull;
             }
             if (!hit) continue;
-#if RXR_RL_TABLE
             if constexpr (RL) {
-                // The whole point-light term in relaxed arithmetic (see the block below, which this one replaces: the same
-                // expressions) with every fragment-independent factor read from the light's LightFast record -- made by the host
-                // with the frame, fetched through the scalar cache: no VALU instruction on a wave-uniform operand is left in the loop.
+                // The whole point-light term in relaxed arithmetic: fused multiply-adds, one v_rsq_f32 per normalisation, the half
+                // vector never normalised (n.h = n.(l + v) * rsq(|l + v|^2)), and the scalar factors gathered before they meet the
+                // colour:  lit += (kd + f * spec) * (colour * flicker) * (intensity * (n.l)^2).  Every operand stays within a few ulp
+                // of the reference's; a fragment outside the range, behind the light (n.l = 0) or without a specular lobe contributes
+                // exactly what it contributes there: nothing.  Magnitudes outside the window (zero, denormal, infinite, NaN) leave
+                // through the exact path below.
+                // Every fragment-independent factor is read from the light's LightFast record -- made by the host with the frame,
+                // fetched through the scalar cache: no VALU instruction on a wave-uniform operand is left in the loop.
                 // t = clamp((distance - end) / (start - end)) as ONE fused multiply-add, distance * ss_r + (-end * ss_r); colour,
-                // intensity and flicker arrive as one product.
+                // intensity and flicker arrive as one product.  The range test and the full-intensity test ARE the clamp of the
+                // smoothstep: beyond the end distance t = 0 and the term is exactly +0 added to lit; inside the start distance t = 1
+                // and the smoothstep is exactly 1.  No compare, no select, no divergent branch (the wave-level culling has already
+                // dropped the lights that reach no fragment of the wave).  The clamps are output modifiers of the multiplies.
                 if ((fast_mask >> li_lane) & 1ull) {
                     const LightFast LF = uniform_record_x8(P.lights_fast, li);  // one s_load_dwordx8
                     const f3 d = sub3(mk3(LF.pos[0], LF.pos[1], LF.pos[2]), F.world);
@@ -934,12 +897,17 @@ __device__ __forceinline__ void shade3d_lights(const RasterParams &P, bool hit, 
                         const float inv = __builtin_amdgcn_rsqf(m2);
                         const float t = __builtin_amdgcn_fmed3f(fmaf(m2 * inv, LF.ss_r, LF.c0), 0.0f, 1.0f);
                         const float ss = t * t * fmaf(-2.0f, t, 3.0f);
+                        // max(n.l, 0) and max(n.h, 0) as clamps to [0, 1] (both are cosines: at most 1 + 2 ulp); l = d / |d| is never
+                        // formed: n.l = (n.d) / |d| and l + v = d / |d| + v as one fused multiply-add per component
                         const float ndl = __builtin_amdgcn_fmed3f(fmaf(F.normal.z, d.z, fmaf(F.normal.y, d.y, F.normal.x * d.x)) * inv, 0.0f, 1.0f);
                         const f3 hu = mk3(fmaf(d.x, inv, F.view_dir.x), fmaf(d.y, inv, F.view_dir.y), fmaf(d.z, inv, F.view_dir.z));
                         const float hh = fmaf(hu.z, hu.z, fmaf(hu.y, hu.y, hu.x * hu.x));  // 0 (l = -v: n.h = NaN -> 0 below) or >= 1e-15
                         const float ndh = __builtin_amdgcn_fmed3f(fmaf(F.normal.z, hu.z, fmaf(F.normal.y, hu.y, F.normal.x * hu.x)) * __builtin_amdgcn_rsqf(hh), 0.0f, 1.0f);
+                        // Below feature level 2 no program sets roughness: rough = 0.5, shininess = 2 / 0.25 - 2 = 6 exactly, and the
+                        // reference's powf(n.h, 6) is three multiplies (each within half an ulp: closer to powf than exp2(6 log2 x),
+                        // whose v_log_f32 error the exponent multiplies by six) instead of two quarter-rate transcendentals
                         float spec;
-                        if constexpr (X < 2) {  // rough = 0.5: shininess = 6 exactly (see below)
+                        if constexpr (X < 2) {
                             const float ndh2 = ndh * ndh;
                             spec = ndh2 * ndh2 * ndh2;
                         } else {
@@ -953,8 +921,7 @@ __device__ __forceinline__ void shade3d_lights(const RasterParams &P, bool hit, 
                     }
                 }
             }
-#endif
-            if constexpr (table_path) {
+            if constexpr (RL) {
                 ss_r = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ss_rcp), li_lane));
                 ss_fast = (ss_ok_mask >> li_lane) & 1ull;
             }
@@ -966,54 +933,6 @@ __device__ __forceinline__ void shade3d_lights(const RasterParams &P, bool hit, 
                 // (lp - world).normalized(): |world - lp| and |lp - world| are the same float
                 if (!L.emitting) continue;
                 f3 d = sub3(lp, F.world);
-                if constexpr (RL && !RXR_RL_TABLE) {
-                    // The whole point-light term in relaxed arithmetic: fused multiply-adds, one v_rsq_f32 per normalisation, the
-                    // half vector never normalised (n.h = n.(l + v) * rsq(|l + v|^2)), and the scalar factors gathered before they
-                    // meet the colour:  lit += (kd + f * spec) * (colour * flicker) * (intensity * (n.l)^2).  Every operand stays
-                    // within a few ulp of the reference's; a fragment outside the range, behind the light (n.l = 0) or without a
-                    // specular lobe contributes exactly what it contributes there: nothing.  Magnitudes outside the window (zero,
-                    // denormal, infinite, NaN) leave through the exact path below.
-                    const float m2 = fmaf(d.z, d.z, fmaf(d.y, d.y, d.x * d.x));
-                    // (ss_fast: start - end is a window value; the fused form also wants start < end, as every real light has it)
-                    if (rxm::wave_all(rxm::sq_in_window(m2)) && ss_fast && L.start_distance < L.end_distance) {
-                        const float inv = __builtin_amdgcn_rsqf(m2);
-                        const float distance = m2 * inv;
-                        // The range test and the full-intensity test ARE the clamp of the smoothstep: beyond the end distance
-                        // t = 0 and the term below is exactly +0 added to lit; inside the start distance t = 1 and the smoothstep
-                        // is exactly 1.  No compare, no select, no divergent branch (the wave-level culling has already dropped
-                        // the lights that reach no fragment of the wave).  The clamps are output modifiers of the multiplies.
-                        const float t = __builtin_amdgcn_fmed3f((distance - L.end_distance) * ss_r, 0.0f, 1.0f);
-                        const float intensity = L.intensity * (t * t * fmaf(-2.0f, t, 3.0f));
-                        // max(n.l, 0) and max(n.h, 0) as clamps to [0, 1] (both are cosines: at most 1 + 2 ulp)
-#if RXR_RL_FOLD
-                        // l = d / |d| is never formed: n.l = (n.d) / |d| and l + v = d / |d| + v as one fused multiply-add per component
-                        const float ndl = __builtin_amdgcn_fmed3f(fmaf(F.normal.z, d.z, fmaf(F.normal.y, d.y, F.normal.x * d.x)) * inv, 0.0f, 1.0f);
-                        const f3 hu = mk3(fmaf(d.x, inv, F.view_dir.x), fmaf(d.y, inv, F.view_dir.y), fmaf(d.z, inv, F.view_dir.z));
-#else
-                        const f3 l = scale3(d, inv);
-                        const float ndl = __builtin_amdgcn_fmed3f(fmaf(F.normal.z, l.z, fmaf(F.normal.y, l.y, F.normal.x * l.x)), 0.0f, 1.0f);
-                        const f3 hu = add3(l, F.view_dir);
-#endif
-                        const float hh = fmaf(hu.z, hu.z, fmaf(hu.y, hu.y, hu.x * hu.x));  // 0 (l = -v: n.h = NaN -> 0 below) or >= 1e-15
-                        const float ndh = __builtin_amdgcn_fmed3f(fmaf(F.normal.z, hu.z, fmaf(F.normal.y, hu.y, F.normal.x * hu.x)) * __builtin_amdgcn_rsqf(hh), 0.0f, 1.0f);
-                        // Below feature level 2 no program sets roughness: rough = 0.5, shininess = 2 / 0.25 - 2 = 6 exactly, and the
-                        // reference's powf(n.h, 6) is three multiplies (each within half an ulp: closer to powf than exp2(6 log2 x),
-                        // whose v_log_f32 error the exponent multiplies by six) instead of two quarter-rate transcendentals
-                        float spec;
-                        if constexpr (X < 2 && RXR_RL_POW6) {
-                            const float ndh2 = ndh * ndh;
-                            spec = ndh2 * ndh2 * ndh2;
-                        } else {
-                            spec = __builtin_amdgcn_exp2f(rl_shininess * __builtin_amdgcn_logf(ndh));  // (0 for n.h = 0)
-                        }
-                        const f3 cf = apply_flicker(L, 1.0f, P.hash_anim);  // wave-uniform
-                        const float s = intensity * ndl * ndl;
-                        F.lit.x = fmaf(fmaf(rl_f.x, spec, rl_kd.x), cf.x * s, F.lit.x);
-                        F.lit.y = fmaf(fmaf(rl_f.y, spec, rl_kd.y), cf.y * s, F.lit.y);
-                        F.lit.z = fmaf(fmaf(rl_f.z, spec, rl_kd.z), cf.z * s, F.lit.z);
-                        continue;
-                    }
-                }
                 float distance;
                 ldir = norm3_fast(d, distance);
                 if (distance >= L.end_distance) continue;
@@ -1042,7 +961,7 @@ __device__ __forceinline__ void shade3d_lights(const RasterParams &P, bool hit, 
             // (relaxed kernels: the general path is the rare one -- its light-independent factors (f0, kd, the Fresnel term) must not
             // be hoisted in front of the loop, where every wave would pay for them: the empty asm ties them to this iteration)
             float rough_g = rough, metal_g = metal;
-            if constexpr (table_path) asm volatile("" : "+v"(rough_g), "+v"(metal_g));
+            if constexpr (RL) asm volatile("" : "+v"(rough_g), "+v"(metal_g));
             F.lit = add3(F.lit, shade_fast_brdf<RL>(F.base, rough_g, metal_g, F.normal, F.view_dir, ldir, radiance, n_dot_l));  // (continuous for every light type)
         }
     }
@@ -1053,9 +972,7 @@ __device__ __forceinline__ void shade3d_lights(const RasterParams &P, bool hit, 
 template <int X, bool RL = false>
 __device__ __forceinline__ uint32_t shade3d_end(const Frag &F) {
     f3 lit = F.lit;
-#if RXR_VM_EMISSIVE
     if constexpr (X >= 2) lit = add3(lit, F.emis);
-#endif
     if constexpr (RL) {  // linear_to_srgb_fast (:26-33) with v_sqrt_f32 (1 ulp) for the correctly rounded root
         const float sx = __builtin_amdgcn_sqrtf(lit.x), sy = __builtin_amdgcn_sqrtf(lit.y), sz = __builtin_amdgcn_sqrtf(lit.z);
         return pack4(f32_to_u8_saturated(1.055f * sx - 0.055f * sx * sx), f32_to_u8_saturated(1.055f * sy - 0.055f * sy * sy),
@@ -1138,7 +1055,7 @@ __device__ __forceinline__ uint32_t fragment2d(const RasterParams &P, const Prim
     float gy = ((float)py - P.fheight / 2.0f) - (P.translationd2[1] - P.fheight / 2.0f);
     float wx = gx / P.scaled2, wy = gy / P.scaled2;
 
-    uint32_t texel = batch_texel<X, RXR_UNIFORM_2D_BATCH != 0>(P, B, u, v, wx, wy);  // 2D terrain: chunk.sample_terrain_texture(world, ..), :749-751
+    uint32_t texel = batch_texel<X, true>(P, B, u, v, wx, wy);  // 2D terrain: chunk.sample_terrain_texture(world, ..), :749-751
     if constexpr (X >= 2) {
         if (B.program_plus1 && P.programs[B.program_plus1 - 1u].shade_entry != 0xFFFFFFFFu) {  // :760-797
             const float INV_255 = 1.0f / 255.0f;  // pixel_to_vec4, lib.rs:52-62
@@ -1354,7 +1271,6 @@ __device__ __forceinline__ bool make_setup(const RasterParams &P, uint32_t t, Tr
         for (int k = 0; k < 3; ++k) H.n0[k] = H.n1[k] = H.n2[k] = 0.0f;
     }
     H.pad[0] = H.pad[1] = 0;
-#if RXR_DESC_IN_TRISHADE
     // The batch's texture descriptor rides in the record's two spare words (TS_DESC_VALID | w | h << 13 | repeat mode << 26 | the
     // descriptor's two flag bits << 28; the texel offset in the other word): the shading pass goes from the winner's record -- whose
     // load it has long issued -- straight to the texels, instead of batch header -> descriptor -> texels: two dependent round trips
@@ -1367,7 +1283,6 @@ __device__ __forceinline__ bool make_setup(const RasterParams &P, uint32_t t, Tr
             H.pad[1] = TS_DESC_VALID | d.w | (d.h << 13) | (B.repeat_mode << 26) | ((d.all_opaque & 3u) << 28);
         }
     }
-#endif
     // Bilinear sampling turns a NaN texture coordinate into NaN in EVERY channel (texture.rs:414-460: v00 + dx * (v10 - v00)), alpha
     // included, and `NaN as u8` is 0: such a fragment is not written (:1408) even when every texel of its texture is opaque -- the one
     // case in which a batch without DB_ALPHA_TEST needs the per-fragment test all the same.  A coordinate is NaN only when the
@@ -1477,9 +1392,6 @@ __device__ __forceinline__ uint32_t wave_bin_finish(uint32_t raw, uint32_t first
 // The records leave through LDS: a thread's own 96 + 80 bytes are eleven 16-byte stores at a stride of 96 / 80 bytes across the
 // wave (every store instruction touches 64 cache lines, a sixth of each); transposed, the workgroup's 256 records are one
 // contiguous 24 KB / 20 KB block that consecutive lanes write 16 bytes at a time.
-#ifndef RXR_SETUP_TRANSPOSE
-#define RXR_SETUP_TRANSPOSE 1
-#endif
 // device-projected frames: true (uniformly) for a workgroup whose 256 slots all lie behind the live triangles of one mesh.  The
 // pools are capacity based (3 slots per input triangle): an unclipped scene leaves two thirds of them unused, and k_setup3d /
 // k_fill used to walk them all (1 M-triangle grid: 161 us instead of 87).  Such a workgroup writes and reads nothing; the bin
@@ -1518,7 +1430,6 @@ extern "C" __global__ void __launch_bounds__(256) k_setup3d(RasterParams P) {
         live = make_setup(P, t, S, H);
         P.tri_box[t] = make_uint2(S.bx, S.by);
     }
-#if RXR_SETUP_TRANSPOSE
     {
         // (a triangle that can never be a candidate -- culled, clipped away, empty box -- has bx = by = 0: the lists skip it and
         // the implicit-list path rejects its empty box; its other fields are whatever make_setup got to, zero at the least)
@@ -1556,17 +1467,6 @@ extern "C" __global__ void __launch_bounds__(256) k_setup3d(RasterParams P) {
             if (k < n_here * 5u) dst[k] = xpose[k];
         }
     }
-#else
-    if (t < P.n_tris3d) {
-        if (live) {
-            P.tri_shade[t] = H;
-            P.tri_setup[t] = S;
-        } else {
-            // never a candidate: the lists skip it and the implicit-list path rejects its empty box
-            *reinterpret_cast<uint2 *>(&P.tri_setup[t].bx) = make_uint2(0u, 0u);
-        }
-    }
-#endif
     if (P.blockscan_cap) {  // uniform: k_blockscan bins this launch -- every wave leaves it the union of its 64 triangles' bin ranges
         uint32_t gx0 = 0xFFFFu, gx1 = 0u, gy0 = 0xFFFFu, gy1 = 0u;  // (empty: x0 > x1)
         if (live) {
@@ -2187,9 +2087,6 @@ __device__ __forceinline__ int front_lookup(const Vis &v, int t) {
 // shared-reciprocal sequences of rxr_exact_math.h (the same floats as `/`; a wave with an operand outside the window, e.g. a
 // barycentric that is exactly zero, takes the plain operators).  Must be called in wave-uniform-or-divergent control flow
 // alike: the window vote counts active lanes only.
-#ifndef RXR_FAST_BARY
-#define RXR_FAST_BARY 1
-#endif
 // PRE: (pre_acx, pre_acy, pre_r) = (v2x - v0x, v2y - v0y, rxm::denominator_part(area)) -- what the expressions need of the TRIANGLE
 // alone -- computed once per candidate of a row-mode round by the thread that prepares it (rows_round) instead of by every pixel
 // item: the same operations on the same operands, so the same floats.
@@ -2202,20 +2099,11 @@ __device__ __forceinline__ void bary_depth(float v0x, float v0y, float v1x, floa
     const float apx = fx - v0x, apy = fy - v0y;
     const float acx = PRE ? pre_acx : v2x - v0x, acy = PRE ? pre_acy : v2y - v0y;
     const float na = pcx * pby - pcy * pbx, nb = acx * apy - acy * apx;
-#if RXR_FAST_BARY
     if constexpr (PRE) rxm::div2_pre(na, nb, area, pre_r, alpha, beta);
     else rxm::div2(na, nb, area, alpha, beta);
-#else
-    alpha = na / area;
-    beta = nb / area;
-#endif
     const float gamma = 1.0f - alpha - beta;
     const float one_over_z = iz0 * alpha + iz1 * beta + iz2 * gamma;
-#if RXR_FAST_BARY
     z = rxm::div1_known(1.0f, one_over_z, rxm::in_window(one_over_z));
-#else
-    z = 1.0f / one_over_z;
-#endif
 }
 
 // one candidate triangle against this lane's pixel (rasterizer.rs:1020-1060 + the :1408 alpha rule)
@@ -2288,15 +2176,12 @@ __device__ __forceinline__ void visit(const RasterParams &P, const TriSetup &S, 
             float u, v;
             fragment_uv(H, alpha, beta, gamma, u, v);
             uint32_t texel;
-#if RXR_DESC_IN_TRISHADE
             // (the candidate is the same for every lane, and so is its record: the descriptor it carries -- make_setup -- leads straight to
             // the texels; through the batch header and the descriptor table every cut-out candidate of a tile cost two more round trips)
             if (H.pad[1] & TS_DESC_VALID) {
                 const DevTexDesc d{H.pad[0], H.pad[1] & 0x1FFFu, (H.pad[1] >> 13) & 0x1FFFu, (H.pad[1] >> 28) & 3u};
                 texel = sample_texture(d, texel_base(P, d), u, v, P.sample_mode, (H.pad[1] >> 26) & 3u);
-            } else
-#endif
-            {
+            } else {
                 const DevBatch &B = P.batches3d[S.batch];
                 texel = batch_texel<X>(P, B, u, v, 0.0f, 0.0f);  // never a terrain batch: those carry DB_FULL_ALPHA
             }
@@ -2369,9 +2254,6 @@ __device__ __forceinline__ bool tile_inside_edges(const float *ea, const float *
     }
     return inside;
 }
-#ifndef RXR_COVER_FAST
-#define RXR_COVER_FAST 1
-#endif
 #define RXR_COVER_BIT 0x80000000u
 // candidate R of the opaque pass, already known to meet the tile: covering and plain (visit_cover)?
 __device__ __forceinline__ bool covers_plainly(const TriSetup &R, uint32_t tile_x0, uint32_t tile_y0px) {
@@ -2420,19 +2302,6 @@ __device__ __forceinline__ uint32_t z_order_bits(float z) {
 }
 // z_buffer starts at 1.0 and only `z < 1.0` is ever written (:1060): no key at or above this one is a hit
 #define RXR_ZKEY_INIT (0xBF800000ull << 32)
-// row mode when the candidates' clipped boxes cover on average less than this many of the tile's 256 pixels
-#ifndef RXR_ROWS_INLINE
-#define RXR_ROWS_INLINE __forceinline__
-#endif
-#ifndef RXR_RESOLVE_INLINE
-#define RXR_RESOLVE_INLINE __forceinline__
-#endif
-#ifndef RXR_ROWS_PRE
-#define RXR_ROWS_PRE 1   // (0: every pixel item derives its triangle's own operands of bary_depth -- A-B measurements)
-#endif
-#ifndef RXR_ROWS_OWNER_DIRECT
-#define RXR_ROWS_OWNER_DIRECT 1  // (0: the chunk owners by binary search behind a barrier of their own -- A-B measurements)
-#endif
 // A round goes to the pixel-parallel walk when its candidates' clipped boxes average more than this many pixels (a whole tile is 256: at 256
 // no round of candidates without cut-outs does).  128 until the end of round 4, chosen when row mode still ran every box pixel through
 // bary_depth; with the fragment compaction row mode also wins on LARGE triangles -- A-B-A-B 128 against 256: the teapot 25.2 -> 24.6 us,
@@ -2444,7 +2313,7 @@ __device__ __forceinline__ uint32_t z_order_bits(float z) {
 // Fragment compaction (north-star: "wavefront ballot/prefix-sum for fragment compaction").  A candidate covers a third of its
 // clipped pixel box on the 1 M-triangle grid (measured on the scene: 34 candidates, 1 880 box pixels and 700 fragments per non-empty
 // tile), so with Edges::evaluate and the depth arithmetic in one pass two lanes in three sit out bary_depth -- two exact quotients, a
-// reciprocal and the ds_min_u64 -- and every box pixel pays the owner search and the decode of its item.  With RXR_ROWS_COMPACT
+// reciprocal and the ds_min_u64 -- and every box pixel pays the owner search and the decode of its item.  With the compaction
 //   (a) an item is a run of up to FOUR pixels of one row of a candidate's clipped box: one owner search, one decode and one fetch of the
 //       edge coefficients per run, and b*y per run instead of per pixel (the same products: the same floats);
 //   (b) the items only evaluate the edge functions.  The survivors of each of the four pixel slots are counted with one ballot and take
@@ -2455,43 +2324,24 @@ __device__ __forceinline__ uint32_t z_order_bits(float z) {
 // The same expressions per fragment, and the arg-min is order-independent: exact by construction.  The rings alias the 2D pass's sort
 // buffer, idle during the 3D passes: no LDS is added.  First tried with one-pixel items, a queue shared by the workgroup, an LDS add
 // per wave and pass and a barrier in front of the drain: 4 % fewer VALU instructions and 1.5 % SLOWER (profiles/r04).
-#ifndef RXR_ROWS_COMPACT
-#define RXR_ROWS_COMPACT 1
-#endif
-// k_blockscan's lists: this many entries of a tile's list are fetched together with its length (0: the offsets and, behind them, the ids).
-// Measured with 64 (profiles/r04/prefetch_ids_ab_c5.txt, A-B-A-B on one box): the 1 M-triangle frame 0.574 -> 0.591 ms -- more than half of
-// its tiles are empty and fetch 256 bytes of stale slots for nothing, and the others wait for the ids in the prologue instead of behind
-// the first barrier.  Off; the knob stays for scenes without empty tiles.
-#ifndef RXR_ROWS_PREFETCH_IDS
-#define RXR_ROWS_PREFETCH_IDS 0
-#endif
-#ifndef RXR_ROWS_DIAG
-#define RXR_ROWS_DIAG 0
-#endif
-#ifndef RXR_ROWS_UNROLL_PX
-#define RXR_ROWS_UNROLL_PX 0  // (A-B knob: the four pixel slots of an item as straight-line code, five copies of the drain)
-#endif
 #define RXR_ROWS_RING 128u  // entries per wave: fewer than 64 left over + at most 64 from one pixel slot
 static_assert(RXR_ROWS_RING * 4u * (RXR_TILE_THREADS / 64) <= RXR_SORT2D_MAX * 4u, "the four rings live in the 2D pass's sort buffer");
 
 // One round of row mode over the `n` records staged in st (ids in st.ids).  Returns false (uniformly) without having
 // done anything when the round is better served by the pixel-parallel walk.
 //
-// RXR_ROWS_PIXEL_ITEMS (default): the work items are the PIXELS of the candidates' clipped boxes, not their rows.  With a row
+// Pixel items (PIX): the work items are the PIXELS of the candidates' clipped boxes, not their rows.  With a row
 // per thread every wave runs its x loop as often as its widest row needs (a tile of the 1 M-triangle grid: ~95 rows of 1..16
 // pixels in two of the four waves, the other two idle) -- most lanes wait most of the time.  With a pixel per thread the
 // ~380 box pixels of such a tile are two passes of all four waves, each lane evaluating exactly the expressions of visit()
 // once.  The owner of item i is found without a search per lane: the prefix sums of the box areas are in LDS, every
 // 64-item chunk looks its first owner up once (a parallel binary search, one chunk per thread) and a lane steps forward
 // from there (runs of one candidate are ~20 items long).
-#ifndef RXR_ROWS_PIXEL_ITEMS
-#define RXR_ROWS_PIXEL_ITEMS 1
-#endif
 // INDIRECT: candidate k's record is st.tri[rl.slot[k] * 6] (scan_lists_rows) instead of st.tri[k * 6]
 // PIX: pixel items (above); false = one item per row with an x loop, which the interpreter kernels with programs in their visibility
 // loop keep (levels 2 - 5).  The others (6 / 7 / 9) take pixel items WITH the compaction since the end of round 4: pixel items alone had
 // cost k_raster_vm_sv 3-4 % on the 1 M-triangle grid in round 3 (its register budget is spent on the interpreter); as 4-pixel runs with
-// the per-wave rings they save k_raster_vm_p 7 % and k_raster_vm_sv 6 % (scan_lists_rows, RXR_ROWS_PIXEL_ITEMS_VM)
+// the per-wave rings they save k_raster_vm_p 7 % and k_raster_vm_sv 6 % (scan_lists_rows)
 // SPLIT: a round that holds candidates row mode cannot take -- cut-outs, whose fragments need a texel (:1408); candidates with a profile id
 // in a frame with an opacity pass (:1044-1048) -- still runs in row mode for all the others; the ones left over are named in rl.cut and
 // the caller walks them (scan_lists_rows).  Without SPLIT such a round is refused as a whole (returns false), as until the end of round
@@ -2499,8 +2349,8 @@ static_assert(RXR_ROWS_RING * 4u * (RXR_TILE_THREADS / 64) <= RXR_SORT2D_MAX * 4
 // eight 3.2 times.
 // Returns 0 (refused), 1 (done) or -- SPLIT only -- 2 (done, and rl.cut names candidates that are left to walk).
 template <bool INDIRECT, bool PIX, uint32_t TH = RXR_TILE_H, bool COMPACT = false, bool SPLIT = false>
-__device__ RXR_ROWS_INLINE uint32_t rows_round(const RasterParams &P, Stage &st, RowLdsT<TH> &rl, uint32_t n, uint32_t tile_x0, uint32_t tile_y0px,
-                                           uint32_t *queue = nullptr) {
+__device__ __forceinline__ uint32_t rows_round(const RasterParams &P, Stage &st, RowLdsT<TH> &rl, uint32_t n, uint32_t tile_x0, uint32_t tile_y0px,
+                                               uint32_t *queue = nullptr) {
     static_assert(TH == 16 || TH == 32, "the bit fields of `geo` and the exact short division hold for offsets below 512");
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     // clipped pixel box of staged candidate `tid`
@@ -2591,7 +2441,6 @@ __device__ RXR_ROWS_INLINE uint32_t rows_round(const RasterParams &P, Stage &st,
         if constexpr (COMPACT) asm volatile("" : "+v"(tl));
         rl.row_start[tl] = start;
         rl.raw[tl] = geo;                            // (the list entries' ids have moved to st.ids by now)
-#if RXR_ROWS_PRE
         // The round is row mode from here on: nothing reads the staged record's pixel box and flags again, and their words take what
         // bary_depth needs of the triangle alone (its PRE form) -- once per candidate instead of once per pixel item.
         if (area) {
@@ -2602,39 +2451,22 @@ __device__ RXR_ROWS_INLINE uint32_t rows_round(const RasterParams &P, Stage &st,
             W.bflags = __float_as_uint(r);
             if constexpr (COMPACT) W.profile_id = st.ids[tl];  // (row mode never reads the profile: no candidate of the round has one that matters) the queue names records
         }
-#endif
         // first owner of every 64-item chunk (area_total <= 128 * 128: at most 256 chunks): item 64 c belongs to the one candidate
         // WITH pixels whose range [start, start + area) holds it -- that candidate knows, so it writes the chunk's entry itself
         // (usually none or one: ~20 items per candidate) instead of a binary search over the prefix by one thread per chunk behind
         // another barrier.  Candidates without pixels in front of it share its start; the item loop steps over them as before.
-#if RXR_ROWS_OWNER_DIRECT
         for (uint32_t c = (start + 63u) >> 6; (c << 6) < start + mine; ++c) rl.chunk_owner[c] = (uint8_t)tl;
-#endif
     }
     if (tid == 0) rl.row_start[n] = n_items;
     __syncthreads();
-#if !RXR_ROWS_OWNER_DIRECT
-    // the largest k with row_start[k] <= chunk * 64
-    if (tid * 64u < n_items) {
-        uint32_t lo = 0, hi = n;
-        while (hi - lo > 1u) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (rl.row_start[mid] <= tid * 64u) lo = mid;
-            else hi = mid;
-        }
-        rl.chunk_owner[tid] = (uint8_t)lo;
-    }
-    __syncthreads();
-#endif
     if constexpr (COMPACT) {
-    static_assert(!COMPACT || RXR_ROWS_PRE, "the drain reads the PRE operands and the triangle id from the staged record");
+    // (the drain reads the PRE operands and the triangle id from the staged record)
     uint32_t *const ring = queue + wave * RXR_ROWS_RING;
     uint32_t head = 0, fill = 0;  // wave-uniform
     // (c) entries [head, head + m) of this wave's ring on lanes 0 .. m-1: barycentric_weights_3d, the depth and the merge, as visit()
+    // (two diagnostic builds -- this drain without its z-buffer traffic, and no drain at all -- located the kernel's LDS bank conflicts
+    // here: profiles/r04/lds_conflict_sources_c5.txt)
     auto drain = [&](uint32_t m) {
-#if RXR_ROWS_DIAG == 2
-        return;  // (diagnostic build: where do the LDS bank conflicts come from?  wrong frames)
-#endif
         if (lane < m) {
             const uint32_t e = ring[(head + lane) & (RXR_ROWS_RING - 1u)];
             // words 8 .. 23 of the staged record as four 16-byte reads (ds_read_b128: 64 banks, 16 lanes per LDS cycle -- the lanes of a drain
@@ -2647,12 +2479,7 @@ __device__ RXR_ROWS_INLINE uint32_t rows_round(const RasterParams &P, Stage &st,
             const float fx = (float)((e >> 8) & (SPLIT ? 0x7Fu : 0xFFu)) + ((float)tile_x0 + 0.5f), fy = (float)((e >> 16) & 0xFFu) + ((float)tile_y0px + 0.5f);  // (exact sums: the item's own fx, fy)
             float alpha, beta, z;
             bary_depth<true>(q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w, q4.x, q4.y, q4.z, fx, fy, alpha, beta, z, q5.x, q5.y, q5.z);
-#if RXR_ROWS_DIAG == 1
-            if (z == 12345.678f)  // (diagnostic build: the drain without its z-buffer traffic -- never true, but the arithmetic above stays)
-#else
-            if (z < 1.0f)  // never closer than the cleared buffer; also NaN
-#endif
-            {
+            if (z < 1.0f) {  // never closer than the cleared buffer; also NaN
                 const unsigned long long key = ((unsigned long long)z_order_bits(z + 0.0f) << 32) | __float_as_uint(q5.w);  // -0 -> +0: they compare equal
                 unsigned long long *const cell = &rl.key[TH == 16 ? (e >> 24) : ((e >> 16) & 0xFFu) * RXR_TILE_W + ((e >> 8) & (SPLIT ? 0x7Fu : 0xFFu))];
                 // (cells only ever decrease: a stale value is merely conservative.  A relaxed workgroup-scope atomic load, so that the
@@ -2701,11 +2528,8 @@ __device__ RXR_ROWS_INLINE uint32_t rows_round(const RasterParams &P, Stage &st,
             entry = sl | (lx << 8) | (ly << 16) | ((ly * RXR_TILE_W + lx) << 24) | (SPLIT ? ((g >> 31) << 15) : 0u);   // (bit 15: a cut-out candidate's item)
             static_assert(RXR_STAGE_TRIS <= 256 && RXR_TILE_W == 16 && TH <= 32, "bit fields of a ring entry");
         }
-#if RXR_ROWS_UNROLL_PX
-#pragma unroll
-#else
+        // (the four pixel slots as straight-line code -- five copies of the drain -- were tried and retired)
 #pragma unroll 1
-#endif
         for (uint32_t px = 0; px < 4u; ++px) {
             // Edges::evaluate (edge.rs:28-36)
             const float r0 = a0 * fx + t0 + c0;
@@ -2752,12 +2576,8 @@ __device__ RXR_ROWS_INLINE uint32_t rows_round(const RasterParams &P, Stage &st,
         if ((r0 < 0.0f) || (r1 < 0.0f) || (r2 < 0.0f)) continue;
         // barycentric_weights_3d and depth, as visit()
         float alpha, beta, z;
-#if RXR_ROWS_PRE
         bary_depth<true>(S.v0x, S.v0y, S.v1x, S.v1y, S.v2x, S.v2y, S.area, S.iz0, S.iz1, S.iz2, fx, fy, alpha, beta, z, __uint_as_float(S.bx),
                          __uint_as_float(S.by), __uint_as_float(S.bflags));
-#else
-        bary_depth(S.v0x, S.v0y, S.v1x, S.v1y, S.v2x, S.v2y, S.area, S.iz0, S.iz1, S.iz2, fx, fy, alpha, beta, z);
-#endif
         if (!(z < 1.0f)) continue;  // never closer than the cleared buffer; also NaN
         const unsigned long long key = ((unsigned long long)z_order_bits(z + 0.0f) << 32) | t;  // -0 -> +0: they compare equal
         unsigned long long *const cell = &rl.key[ly * RXR_TILE_W + lx];
@@ -2821,7 +2641,7 @@ __device__ RXR_ROWS_INLINE uint32_t rows_round(const RasterParams &P, Stage &st,
 
 // after the last round: this lane's pixel takes the z-buffer's winner if it beats what the pixel-parallel rounds found
 // (the winner's shading record is fetched together with its set-up record: one memory latency instead of two)
-__device__ RXR_RESOLVE_INLINE void rows_resolve(const RasterParams &P, const RowLds &rl, uint32_t lx, uint32_t ly, float fx, float fy, Vis &vis,
+__device__ __forceinline__ void rows_resolve(const RasterParams &P, const RowLds &rl, uint32_t lx, uint32_t ly, float fx, float fy, Vis &vis,
                                                 TriShade &shade, int &shade_of) {
     const unsigned long long key = rl.key[ly * RXR_TILE_W + lx];
     if (key >= RXR_ZKEY_INIT) return;
@@ -2910,7 +2730,7 @@ __device__ __forceinline__ void scan_lists(const RasterParams &P, Stage &st, uin
         __syncthreads();
         // 4. walk (or, for rounds of small triangles, the rows of their boxes: rows_round)
         if constexpr (!OPACITY && X == 0) {
-            if (rl != nullptr && rows_round<false, RXR_ROWS_PIXEL_ITEMS != 0>(P, st, *rl, n, tile_x0, tile_y0px)) continue;
+            if (rl != nullptr && rows_round<false, true>(P, st, *rl, n, tile_x0, tile_y0px)) continue;
         }
         for (uint32_t k = 0; k < n; ++k) {
             const TriSetup &S = *reinterpret_cast<const TriSetup *>(&st.tri[k * 6u]);
@@ -2932,16 +2752,15 @@ __device__ __forceinline__ void scan_lists(const RasterParams &P, Stage &st, uin
 template <int X, bool SPLITR = false>
 __device__ __forceinline__ void scan_lists_rows(const RasterParams &P, Stage &st, RowLds &rl, bool row_mode, uint32_t b0, uint32_t b1,
                                                 uint32_t tile_x0, uint32_t tile_y0px, uint32_t px, uint32_t py, float fx, float fy, Vis &vis,
-                                                int surf_profile, const Vis *opf, uint32_t *queue, uint32_t pre_n PHASE_PARAM) {
+                                                int surf_profile, const Vis *opf, uint32_t *queue PHASE_PARAM) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t n_large = min(P.counters[CNT_LARGE], P.n_tris3d);
     const uint32_t total = n_large + (b1 - b0);
     const float4 *g4 = reinterpret_cast<const float4 *>(P.tri_setup);
     for (uint32_t base = 0; base < total; base += RXR_STAGE_TRIS) {
         const uint32_t m = min(total - base, (uint32_t)RXR_STAGE_TRIS);
-        // 1. ids of the round's list entries (the first pre_n entries of this tile's own list are in rl.raw already: raster_tile fetched
-        // them together with the list's length)
-        if (tid < m && !(base == 0u && n_large == 0u && tid < pre_n)) {
+        // 1. ids of the round's list entries
+        if (tid < m) {
             const uint32_t e = base + tid;
             rl.raw[tid] = e < n_large ? P.large_list[e] : P.bin_list[b0 + (e - n_large)];
         }
@@ -2980,15 +2799,13 @@ __device__ __forceinline__ void scan_lists_rows(const RasterParams &P, Stage &st
         __syncthreads();
         // 4. the rows of the candidates' boxes, or the walk
         PHASE_MARK(1);
-#ifndef RXR_ROWS_PIXEL_ITEMS_VM
-#define RXR_ROWS_PIXEL_ITEMS_VM 1   // (0: the interpreter kernel of plain program sets keeps row items, as until the end of round 4 -- A-B runs)
-#endif
-        constexpr bool pixel_items = (RXR_ROWS_PIXEL_ITEMS != 0) && (X < 2 || X == 8 || ((X == 9 || X == 6 || X == 7) && RXR_ROWS_PIXEL_ITEMS_VM != 0));
+        // (levels 6 / 7 / 9 kept row items until the end of round 4; levels 2 - 5 still do: rows_round, PIX)
+        constexpr bool pixel_items = X < 2 || X == 8 || X == 9 || X == 6 || X == 7;
         if constexpr (SPLITR) {
             // the candidates every pixel walks: all of the round when row mode refuses it (0), else the ones row mode left over (2: cut-outs;
             // profiled ones under an opacity pass -- rows_round SPLIT wrote their bits in front of its barriers; their records are untouched)
             unsigned long long walk_lo = n >= 64u ? ~0ull : ((1ull << n) - 1ull), walk_hi = n > 64u ? (n >= 128u ? ~0ull : ((1ull << (n - 64u)) - 1ull)) : 0ull;
-            const uint32_t rows_ret = row_mode ? rows_round<true, pixel_items, RXR_TILE_H, pixel_items && (RXR_ROWS_COMPACT != 0), pixel_items>(P, st, rl, n, tile_x0, tile_y0px, queue) : 0u;
+            const uint32_t rows_ret = row_mode ? rows_round<true, pixel_items, RXR_TILE_H, pixel_items, pixel_items>(P, st, rl, n, tile_x0, tile_y0px, queue) : 0u;
             if (rows_ret) {
                 walk_lo = walk_hi = 0ull;
                 if (pixel_items && rows_ret == 2u) {  // (uniform)
@@ -3015,7 +2832,7 @@ __device__ __forceinline__ void scan_lists_rows(const RasterParams &P, Stage &st
             }
             PHASE_MARK(10);
         } else {
-            if (row_mode && rows_round<true, pixel_items, RXR_TILE_H, pixel_items && (RXR_ROWS_COMPACT != 0)>(P, st, rl, n, tile_x0, tile_y0px, queue)) {
+            if (row_mode && rows_round<true, pixel_items, RXR_TILE_H, pixel_items>(P, st, rl, n, tile_x0, tile_y0px, queue)) {
                 PHASE_MARK(7);
                 continue;
             }
@@ -3064,7 +2881,7 @@ __device__ __forceinline__ void scan_implicit(const RasterParams &P, Stage &st, 
     }
     // (the survivors keep their order: the walk below is in ascending submission index)
     bool cover = false;
-    if constexpr (!OPACITY && RXR_COVER_FAST) {
+    if constexpr (!OPACITY) {
         if (keep) cover = covers_plainly(*reinterpret_cast<const TriSetup *>(&st.tri[tid * 6u]), tile_x0, tile_y0px);
     }
     if (keep) st.ids[off + before] = tid | (cover ? RXR_COVER_BIT : 0u);
@@ -3169,12 +2986,8 @@ __device__ __forceinline__ uint32_t prim2d_pixel(const RasterParams &P, const Pr
     in = in && !(r0 < 0.0f) && !(r1 < 0.0f) && !(r2 < 0.0f);
     if (in) {
         // (the primitive is the same for every lane: its batch header comes through the scalar cache, not as a vector load per wave)
-#if RXR_UNIFORM_2D_BATCH
         const DevBatch B = uniform_record(P.batches2d, T.batch_kind >> 2);
         color = fragment2d<X>(P, T, B, px, py, fx, fy, color);
-#else
-        color = fragment2d<X>(P, T, P.batches2d[T.batch_kind >> 2], px, py, fx, fy, color);
-#endif
     }
     return color;
 }
@@ -3205,15 +3018,9 @@ __device__ __forceinline__ uint32_t walk_prims2d(const RasterParams &P, Stage &s
 
 }  // namespace
 
-// tuning knobs: occupancy bound of k_raster and the pixel footprint of a wave
+// tuning knob: occupancy bound of k_raster
 #ifndef RXR_RASTER_WAVES_PER_SIMD
 #define RXR_RASTER_WAVES_PER_SIMD 8  // bench frame (4K, 16 lights), built without SLP vectorisation: unbounded (67 VGPRs) 217 us, 7: 211, 8: 210
-#endif
-#ifndef RXR_XCD_GROUP
-#define RXR_XCD_GROUP 0
-#endif
-#ifndef RXR_WAVE_8X8
-#define RXR_WAVE_8X8 0
 #endif
 
 // does the union of the 2D primitives' pixel boxes reach this tile?  The box is a launch constant (host-built Prim2D records) or, for
@@ -3342,26 +3149,9 @@ __device__ __forceinline__ uint32_t pass2d(const RasterParams &P, Stage &stage, 
     return color;
 }
 
+// (A retired measurement: N useless full-rate VALU instructions per wave in front of the light loop or in front of the visibility scan.
+// A kernel bound by VALU issue pays their issue cycles, one bound by latency does not: profiles/r03/bench_kernel_experiments.txt.)
 // LDS of the fused instantiation only
-// Measurement knobs (0 in every product build): N useless full-rate VALU instructions per wave in front of the light loop
-// (RXR_PAD_VALU) or in front of the visibility scan (RXR_PAD_VALU_EARLY).  A kernel bound by VALU issue pays their issue cycles, one
-// bound by latency does not: profiles/r03/bench_kernel_experiments.txt.
-#ifndef RXR_PAD_VALU
-#define RXR_PAD_VALU 0
-#endif
-#ifndef RXR_PAD_VALU_EARLY
-#define RXR_PAD_VALU_EARLY 0
-#endif
-template <int N>
-__device__ __forceinline__ void valu_pad(float &carrier) {
-    if constexpr (N > 0) {
-        float pad = carrier;
-#pragma unroll
-        for (int i = 0; i < N; ++i) asm volatile("v_add_f32 %0, %0, %0" : "+v"(pad));
-        carrier = (pad != pad) ? pad : carrier;
-    }
-}
-
 template <bool F>
 struct ShadeStore {
     StageShade s;
@@ -3388,26 +3178,16 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
     __shared__ uint32_t s_sort[RXR_SORT2D_MAX];  // the gathered candidates of a binned 2D pass; during the 3D passes row mode's fragment queue
     // 2-D grid, no integer division in front of every tile.  Workgroups go to the eight XCDs round robin in launch order
     // (x fastest), and every XCD has its own L2: with column = blockIdx.x, horizontally adjacent tiles -- which share the records
-    // of the triangles that straddle them -- always sit on different XCDs.  RXR_XCD_GROUP = G > 0 hands each XCD groups of G
-    // adjacent columns instead (block x stands for column (q / G) * 8G + (x & 7) * G + q % G, q = x / 8; the grid is padded to
+    // of the triangles that straddle them -- always sit on different XCDs.  Tried and retired: handing each XCD groups of G
+    // adjacent columns instead (block x stands for column (q / G) * 8G + (x & 7) * G + q % G, q = x / 8; the grid padded to
     // a multiple of 8G columns).  Measured (tools/try_cfg_parity.sh, one box): the 1 M-triangle grid's frame 0.706 ms plain, 0.708 /
     // 0.700 / 0.700 ms with G = 2 / 4 / 8 -- nothing beyond noise, the raster kernels are bound by instruction issue and
     // dependent latencies, not by L2 misses -- while the bench frame loses 1 / 5 / 7 % (neighbouring columns differ in cost, and
     // round robin by single columns is the finest balance there is).  Whole vertical bands per XCD lose far more: grid 561 ->
-    // 810 us, bench frame 199 -> 217 us.  Hence G = 0: the hardware's own round robin.
-#if RXR_XCD_GROUP
-    constexpr uint32_t G = RXR_XCD_GROUP;
-    static_assert((G & (G - 1u)) == 0u, "power of two");
-    const uint32_t q = blockIdx.x >> 3;
-    const uint32_t tx = (q / G) * (8u * G) + (blockIdx.x & 7u) * G + (q % G), ty = blockIdx.y;
-    if (tx >= P.tiles_x) return;  // (workgroup-uniform; the padding columns)
-#else
-#ifndef RXR_FLIP_TILE_ROWS
-#define RXR_FLIP_TILE_ROWS 0
-#endif
-    // (RXR_FLIP_TILE_ROWS: dispatch the launch's bottom tile rows first -- an A-B knob for frames whose expensive tiles are at the bottom)
+    // 810 us, bench frame 199 -> 217 us.  Hence the hardware's own round robin.
+    // (dispatching the launch's bottom tile rows first, for frames whose expensive tiles are at the bottom, was an A-B variant too: retired)
     uint32_t tx = blockIdx.x;
-    const uint32_t ty = RXR_FLIP_TILE_ROWS ? gridDim.y - 1u - blockIdx.y : blockIdx.y;
+    const uint32_t ty = blockIdx.y;
     if constexpr (SPANS) {
         if (P.row_spans) {  // (uniform; sparse frames only: see RasterParams.row_spans)
             const uint2 span = uniform_record(P.row_spans, P.tile_y0 + ty);
@@ -3415,17 +3195,11 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
             if (tx >= span.y) return;  // (the whole workgroup, in front of every barrier)
         }
     }
-#endif
     const uint32_t bin = (ty + P.bin_row0) * P.tiles_x + tx;
     const uint32_t tid = threadIdx.x;
     const uint32_t tile_x0 = tx * RXR_TILE_W, tile_y0px = (P.tile_y0 + ty * P.tile_stride) * RXR_TILE_H;
-#if RXR_WAVE_8X8
-    // wave w owns the 8x8 quadrant (w & 1, w >> 1) of the tile
-    const uint32_t lx = ((tid >> 6) & 1u) * 8u + (tid & 7u), ly = (tid >> 7) * 8u + ((tid >> 3) & 7u);
-#else
-    // wave w owns rows 4w .. 4w+3 of the tile (16 x 4 pixels: 64-byte row segments on the store)
+    // wave w owns rows 4w .. 4w+3 of the tile (16 x 4 pixels: 64-byte row segments on the store; an 8x8 quadrant per wave was tried and retired)
     const uint32_t lx = tid & (RXR_TILE_W - 1), ly = tid / RXR_TILE_W;
-#endif
     const uint32_t px = tile_x0 + lx;
     const uint32_t py = tile_y0px + ly;
     const float fx = (float)px + 0.5f, fy = (float)py + 0.5f;  // rasterizer.rs:1022
@@ -3454,24 +3228,14 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
         uint32_t b0 = 0, b1 = 0;
         uint32_t my_bin_count = 0;
         const bool rows_binned = ROWS && P.fused_small == 0u;  // (k_raster_chunk / k_raster_vm also serve small scenes)
-        uint32_t pre_n = 0u;  // (rows_binned, k_blockscan's lists) entries at the head of this tile's list that were fetched before its length was known
         if (rows_binned) {
             // every thread reads the (uniform) list bounds itself: no LDS round trip and no barrier in front of the first
             // list fetch; the bin count is handed back zeroed after the scan, when every thread has long read it
             my_bin_count = P.bin_count[bin];
-            uint32_t start;
-#if RXR_ROWS_PREFETCH_IDS
-            if (P.blockscan_cap) {  // (uniform) k_blockscan: bin b owns the slots [b * cap, (b + 1) * cap) -- no offsets to fetch, and the first
-                                    // entries can travel in the same round trip as the count instead of behind it: count -> ids -> records
-                                    // becomes (count, ids) -> records.  Slots behind the count hold stale ids; nothing uses them (pre_n).
-                start = bin * P.blockscan_cap;
-                if constexpr (ROWS) {  // (straight into the round's id table: nothing else has touched it yet, and no register carries them)
-                    if (tid < (uint32_t)RXR_ROWS_PREFETCH_IDS) row_store.r.raw[tid] = P.bin_list[min(start + tid, P.list_capacity - 1u)];
-                }
-                pre_n = min(min((uint32_t)RXR_ROWS_PREFETCH_IDS, P.blockscan_cap), P.list_capacity - min(start, P.list_capacity));
-            } else
-#endif
-                start = P.chunk_base[bin / RXR_SCAN_CHUNK] + P.bin_offset[bin];
+            // (k_blockscan's lists, tried and retired: the first 64 row ids fetched into LDS in the same round trip as the count.  The 1 M-triangle
+            // frame 0.574 -> 0.591 ms -- more than half of its tiles are empty and fetch 256 bytes of stale slots for nothing, and the others wait
+            // for the ids in the prologue instead of behind the first barrier: profiles/r04/prefetch_ids_ab_c5.txt)
+            const uint32_t start = P.chunk_base[bin / RXR_SCAN_CHUNK] + P.bin_offset[bin];
             b0 = min(start, P.list_capacity);
             b1 = min(start + my_bin_count, P.list_capacity);
         } else if (!fused && P.fused_small == 0u) {  // (s_bin[0..1]: this tile's 3D list)
@@ -3508,7 +3272,6 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
         }
         Vis vis;
         vis.zmin = 1.0f; vis.best = -1; vis.alpha = 0.0f; vis.beta = 0.0f; vis.slot = 0; vis.batch = 0;
-        valu_pad<RXR_PAD_VALU_EARLY>(vis.alpha);
         TriShade HS;     // shading record of the winner
         int hs_of = -1;  // triangle whose record HS already holds (row mode fetches it early)
         uint32_t win_flags = 0u;  // the winner's batch flags, where the visibility pass had them at hand (scan_implicit)
@@ -3525,7 +3288,7 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
                 const bool row_mode = true;
                 if (row_mode) row_store.r.key[ly * RXR_TILE_W + lx] = RXR_ZKEY_INIT;  // own cell; published by the barriers of the first staging round
                 scan_lists_rows<X, SPLITR>(P, stage, row_store.r, row_mode, b0, b1, tile_x0, tile_y0px, px, py, fx, fy, vis, surf_profile, &op,
-                                   s_sort, pre_n PHASE_ARG);
+                                   s_sort PHASE_ARG);
                 if (tid == 0 && my_bin_count) P.bin_count[bin] = 0u;  // (a non-empty list went through the barriers of a round)
                 PHASE_MARK(1);
                 if (row_mode) rows_resolve(P, row_store.r, lx, ly, fx, fy, vis, HS, hs_of);  // (the last round ended with a barrier)
@@ -3558,7 +3321,6 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
             shade3d_begin<X, RL>(P, HS, vis.batch, vis.alpha, vis.beta, vis.zmin, fx, fy, F, have_flags, win_flags);
         }
         PHASE_MARK(2);
-        valu_pad<RXR_PAD_VALU>(F.rough);
         if (P.n_lights) shade3d_lights<X, RL>(P, hit, F);  // wave-uniform call
         PHASE_MARK(3);
         color = hit ? shade3d_end<X, RL>(F) : pack4(0u, 0u, 0u, 255u);
@@ -3601,11 +3363,7 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
         // first line of the kernel to this one, `ly` was SPILLED by the 64-register kernels -- a scratch store and load per thread for a shift)
         uint32_t tid_again = threadIdx.x;
         asm volatile("" : "+v"(tid_again));
-#if RXR_WAVE_8X8
-        const uint32_t ly_again = (tid_again >> 7) * 8u + ((tid_again >> 3) & 7u);
-#else
         const uint32_t ly_again = tid_again / RXR_TILE_W;
-#endif
         const int64_t row = P.compact ? (int64_t)(ty * RXR_TILE_H + ly_again) : (int64_t)py - P.out_base_row;
         P.out[(size_t)row * P.out_row_stride + px] = color;
     }
@@ -3791,14 +3549,7 @@ extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_JIT_WAVES_PER
 extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_JIT_WAVES_PER_SIMD) k_raster_jit_cut(RasterParams) { raster_tile<false, RXR_JIT_LEVEL, true, false, true, true>(kernarg_params_early()); }
 #endif
 #else
-#ifndef RXR_RASTER_KERNARG_IN_PLACE
-#define RXR_RASTER_KERNARG_IN_PLACE 1
-#endif
-#if RXR_RASTER_KERNARG_IN_PLACE
 extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_RASTER_WAVES_PER_SIMD) k_raster(RasterParams) { raster_tile<false, 0>(kernarg_params_early()); }
-#else
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_RASTER_WAVES_PER_SIMD) k_raster(RasterParams P) { raster_tile<false, 0>(P); }
-#endif
 extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS) k_raster_fused(RasterParams) { raster_tile<true, 0>(kernarg_params_early()); }
 // RXR_LIGHT_MATH=relaxed (RasterParams.relaxed_lights): the same kernels with the relaxed light loop (shade3d_lights<X, true>)
 extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_RASTER_WAVES_PER_SIMD) k_raster_rl(RasterParams) { raster_tile<false, 0, false, true>(kernarg_params_early()); }
@@ -3806,14 +3557,7 @@ extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_RASTER_WAVES_
 #ifndef RXR_ROWS_WAVES_PER_SIMD
 #define RXR_ROWS_WAVES_PER_SIMD 8  // C5: unbounded (87 VGPRs, 5 waves) 797 us, 6: 718, 7: 727; with the parameter block in place 6: 654, 8: 628
 #endif
-#ifndef RXR_ROWS_KERNARG_IN_PLACE
-#define RXR_ROWS_KERNARG_IN_PLACE 1
-#endif
-#if RXR_ROWS_KERNARG_IN_PLACE
 extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_ROWS_WAVES_PER_SIMD) k_raster_rows(RasterParams) { raster_tile<false, 0, true>(kernarg_params_early()); }
-#else
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_ROWS_WAVES_PER_SIMD) k_raster_rows(RasterParams P) { raster_tile<false, 0, true>(P); }
-#endif
 extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_ROWS_WAVES_PER_SIMD) k_raster_rows_rl(RasterParams) { raster_tile<false, 0, true, true>(kernarg_params_early()); }
 // ... and for sparse frames (RasterParams.row_spans)
 extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_ROWS_WAVES_PER_SIMD) k_raster_rows_sp(RasterParams) { raster_tile<false, 0, true, false, true>(kernarg_params_early()); }
@@ -4019,85 +3763,63 @@ extern "C" void rxr_launch_fill_outside_spans(const RasterParams *P, hipStream_t
     if (!P->row_spans || !P->tiles_y) return;
     RXR_LAUNCH(k_fill_outside_spans, dim3(P->tiles_y, RXR_TILE_H), dim3(256), s, *P);
 }
-// does the kernel rxr_launch_raster_grid would pick for this launch look RasterParams.row_spans up?  (the host asks before it narrows
-// the grid and fills outside the spans: the choice below mirrors the launcher's)
-extern "C" int rxr_raster_takes_spans(const RasterParams *P) {
-#if RXR_XCD_GROUP
-    return 0;
-#endif
-    if (P->kernel_level >= 1u) return 1;
-    if (P->fused_small != 0u || !(P->flags & RXR_FLAG_D3_ACTIVE)) return 0;   // k_raster / k_raster_rl / k_raster_fused: small scenes
-    if (getenv("RXR_NO_ROWS")) return 0;
-    const char *pt = getenv("RXR_PAIR_TILES");
-    if (pt && pt[0] == '1' && !P->has_opacity && P->tile_stride == 1u) return 0;  // (the pair kernels do not)
-    return 1;
+// the route of a launch (rxr_route.h); spans: is -- or, for the host's question, would be -- the span table attached?
+static rxr_route::Choice raster_route_of(const RasterParams *P, bool spans) {
+    rxr_route::Facts f;
+    f.kernel_level = P->kernel_level;
+    f.plain_programs = P->plain_programs != 0;
+    f.fused_small = P->fused_small;
+    f.d3_active = (P->flags & RXR_FLAG_D3_ACTIVE) != 0;
+    f.split_rounds = P->split_rounds != 0;
+    f.spans = spans;
+    f.rl = P->relaxed_lights && P->n_lights;
+    f.has_opacity = P->has_opacity != 0;
+    f.tile_stride = P->tile_stride;
+    f.no_rows = getenv("RXR_NO_ROWS") != nullptr;  // tuning knob
+    const char *pt = getenv("RXR_PAIR_TILES");     // (both read per launch: the tests switch them)
+    f.pairs_on = pt && pt[0] == '1';
+    return rxr_route::raster_route(f);
 }
+// would the kernel of this launch look RasterParams.row_spans up if the table were attached?  (the host asks before it attaches the
+// table, narrows the grid and fills outside the spans)
+extern "C" int rxr_raster_takes_spans(const RasterParams *P) { return raster_route_of(P, true).takes_spans ? 1 : 0; }
 // grid_x: workgroups per tile row (0: tiles_x; with RasterParams.row_spans the widest span of the launch's rows)
 // Returns the symbol name of the kernel it launched ("" when there was nothing to launch): rxr_debug_last_raster_kernel hands it to the
-// tests (tests/test_gpu_routes.py pins every kernel below to a scene of its own).  RXR_RASTER is the one place a name comes from.
-//   fact (rxr_upload.hip, phase RasterParams; render_impl for fused_small)               kernel
-//   kernel_level 5 / 4 + plain_programs / 4 / 3 / 2                                       k_raster_vm_v / _p / _sv / _s / k_raster_vm
-//   kernel_level 1 (chunk textures, RXR_MIN_KERNEL_LEVEL=1)                               k_raster_chunk   [_cut: split_rounds, binned] [_rl]
-//   fused_small 1 (RXR_SMALL_MODE=1, at most RXR_STAGE_TRIS triangles)                    k_raster_fused
-//   binned 3D frame (fused_small 0), RXR_PAIR_TILES=1, no opacity pass, tile_stride 1     k_raster_pair    [_rl]
-//   binned, split_rounds (cut-out texels, profiled batches under an opacity pass)         k_raster_rows_cut [_rl]
-//   binned, row_spans (sparse frame)                                                      k_raster_rows_sp / k_raster_rows_rl_sp
-//   binned                                                                                k_raster_rows    [_rl]
-//   small frame (fused_small 2), no 3D pass, RXR_NO_ROWS                                  k_raster         [_rl]
-//   _rl: relaxed_lights (demoted to exact on large or non-finite light parameters), n_lights > 0, 3D pass active
-#define RXR_RASTER(kernel, grid)                                   \
-    do {                                                           \
-        RXR_LAUNCH(kernel, grid, dim3(RXR_TILE_THREADS), s, *P);   \
-        return #kernel;                                            \
-    } while (0)
+// tests (tests/test_gpu_routes.py pins every kernel to a scene of its own).
 extern "C" const char *rxr_launch_raster_grid(const RasterParams *P, uint32_t grid_x, hipStream_t s);
 extern "C" const char *rxr_launch_raster(const RasterParams *P, hipStream_t s) { return rxr_launch_raster_grid(P, 0u, s); }
 extern "C" const char *rxr_launch_raster_grid(const RasterParams *P, uint32_t grid_x, hipStream_t s) {
     if (P->tiles_x * P->tiles_y == 0) return "";
     if (!grid_x || !P->row_spans) grid_x = P->tiles_x;
-#if RXR_XCD_GROUP
-    grid_x = P->tiles_x;  // (this tuning build's column mapping ignores the spans: every column is rastered, the fills are overwritten)
-    const uint32_t pad = 8u * RXR_XCD_GROUP;
-    const dim3 tiles(pad * ((grid_x + pad - 1u) / pad), P->tiles_y);  // (see raster_tile: groups of adjacent columns per XCD)
-#else
-    const dim3 tiles(grid_x, P->tiles_y);  // tiles_y <= 2048 (frames of at most 32768 rows)
-#endif
-    const bool rl = P->relaxed_lights && P->n_lights && (P->flags & RXR_FLAG_D3_ACTIVE);  // (frames without a 3D light loop: one kernel for both modes)
-    const bool no_rows = getenv("RXR_NO_ROWS") != nullptr;  // tuning knob: binned scenes walk every candidate per pixel (k_raster)
-    if (P->kernel_level >= 5u) RXR_RASTER(k_raster_vm_v, tiles);
-    else if (P->kernel_level == 4u && P->plain_programs) RXR_RASTER(k_raster_vm_p, tiles);
-    else if (P->kernel_level == 4u) RXR_RASTER(k_raster_vm_sv, tiles);
-    else if (P->kernel_level == 3u) RXR_RASTER(k_raster_vm_s, tiles);
-    else if (P->kernel_level == 2u) RXR_RASTER(k_raster_vm, tiles);
-    else if (P->kernel_level == 1u) {
-        const bool cut = P->split_rounds && P->fused_small == 0u && (P->flags & RXR_FLAG_D3_ACTIVE);  // (binned frames: the others never reach scan_lists_rows)
-        if (cut && rl) RXR_RASTER(k_raster_chunk_cut_rl, tiles);
-        else if (cut) RXR_RASTER(k_raster_chunk_cut, tiles);
-        else if (rl) RXR_RASTER(k_raster_chunk_rl, tiles);
-        else RXR_RASTER(k_raster_chunk, tiles);
-    } else if (P->fused_small == 1u) RXR_RASTER(k_raster_fused, tiles);
-    else if (P->fused_small == 0u && (P->flags & RXR_FLAG_D3_ACTIVE) && !no_rows) {
-        // two tiles per workgroup (raster_tile_pair): opt-in.  Built in round 3 as the 16 x 32-tile experiment the round-2 verdict asked to
-        // repeat on a build that passes parity: it does pass (tests/test_gpu_rows.py runs it), and it LOSES -- 1 M-triangle grid 555 ->
-        // 654 us at 8 waves per SIMD (817 / 697 / 668 at 7 / 6 / 5), teapot 29 -> 46 us (profiles/r03/pair_tiles_experiment.txt): what the
-        // pair saves in per-tile instructions it pays in spills (the two shading passes share one register budget) and in a per-workgroup
-        // latency chain that is twice as long.  RXR_PAIR_TILES=1 selects it.
-        const char *pt = getenv("RXR_PAIR_TILES");  // (read per launch: the tests switch it)
-        const bool pairs_on = pt && pt[0] == '1';
-        if (pairs_on && !P->has_opacity && P->tile_stride == 1u && !RXR_XCD_GROUP) {
-            const dim3 pairs(P->tiles_x, (P->tiles_y + 1u) / 2u);
-            if (rl) RXR_RASTER(k_raster_pair_rl, pairs);
-            else RXR_RASTER(k_raster_pair, pairs);
-        } else if (P->split_rounds) {  // (these two look the row spans up themselves when there are any: SPANS)
-            if (rl) RXR_RASTER(k_raster_rows_cut_rl, tiles);
-            else RXR_RASTER(k_raster_rows_cut, tiles);
-        } else if (P->row_spans) {
-            if (rl) RXR_RASTER(k_raster_rows_rl_sp, tiles);
-            else RXR_RASTER(k_raster_rows_sp, tiles);
-        } else if (rl) RXR_RASTER(k_raster_rows_rl, tiles);
-        else RXR_RASTER(k_raster_rows, tiles);
-    } else if (rl) RXR_RASTER(k_raster_rl, tiles);
-    else RXR_RASTER(k_raster, tiles);
+    // route id -> kernel and its symbol name: RXR_RASTER is the one place a name comes from
+    struct Entry {
+        rxr_route::Route id;
+        void (*kernel)(RasterParams);
+        const char *name;
+    };
+#define RXR_RASTER(kernel, id) {rxr_route::id, kernel, #kernel}
+    static constexpr Entry table[] = {
+        RXR_RASTER(k_raster, RASTER), RXR_RASTER(k_raster_fused, FUSED), RXR_RASTER(k_raster_rl, RASTER_RL),
+        RXR_RASTER(k_raster_rows, ROWS), RXR_RASTER(k_raster_rows_rl, ROWS_RL), RXR_RASTER(k_raster_rows_sp, ROWS_SP),
+        RXR_RASTER(k_raster_rows_rl_sp, ROWS_RL_SP), RXR_RASTER(k_raster_rows_cut, ROWS_CUT), RXR_RASTER(k_raster_rows_cut_rl, ROWS_CUT_RL),
+        RXR_RASTER(k_raster_pair, PAIR), RXR_RASTER(k_raster_pair_rl, PAIR_RL),
+        RXR_RASTER(k_raster_chunk, CHUNK), RXR_RASTER(k_raster_chunk_rl, CHUNK_RL), RXR_RASTER(k_raster_chunk_cut, CHUNK_CUT),
+        RXR_RASTER(k_raster_chunk_cut_rl, CHUNK_CUT_RL),
+        RXR_RASTER(k_raster_vm, VM), RXR_RASTER(k_raster_vm_s, VM_S), RXR_RASTER(k_raster_vm_sv, VM_SV), RXR_RASTER(k_raster_vm_p, VM_P),
+        RXR_RASTER(k_raster_vm_v, VM_V),
+    };
+    static_assert(sizeof(table) / sizeof(table[0]) == rxr_route::N_ROUTES, "one entry per route");
+    static_assert([] {
+        for (int i = 0; i < rxr_route::N_ROUTES; ++i)
+            if (table[i].id != i) return false;
+        return true;
+    }(), "in the order of the enum");
+    const rxr_route::Choice c = raster_route_of(P, P->row_spans != nullptr);
+    const Entry &e = table[c.route];
+    // tiles_y <= 2048 (frames of at most 32768 rows)
+    const dim3 grid = c.pair_grid ? dim3(P->tiles_x, (P->tiles_y + 1u) / 2u) : dim3(grid_x, P->tiles_y);
+    RXR_LAUNCH(e.kernel, grid, dim3(RXR_TILE_THREADS), s, *P);
+    return e.name;
 }
 #undef RXR_RASTER
 #endif  // !RXR_JIT
