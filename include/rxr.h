@@ -751,6 +751,48 @@ int rxr_bake_terrain(rxr_ctx *ctx, const int32_t *chunk_coords, uint32_t n, int3
 int rxr_bake_terrain_to(rxr_ctx *ctx, const int32_t *chunk_coords, uint32_t n, int32_t pixels_per_tile, uint8_t *dev_rgba,
                         void *hip_stream);
 
+/* ---- terrain picks: Terrain::ray_terrain_hit (rusterix_amd/csrc/rxr_terrain_hit.hip) ---------------------------------------------
+ * "Ray / terrain hit used for editing" (src/terrain/mod.rs:427-479), exact to the bit.  The reference does not intersect the terrain
+ * mesh: it marches the height field in up to RXR_TERRAIN_MARCH_STEPS steps of 0.1 along the caller's UN-NORMALISED dir with nearest
+ * sampling (sample_height, :148-152: round half away from zero, in WORLD coordinates -- the scale is not applied) and refines the
+ * first step with point.y - height < 0.01 by four bisections over bilinear samples (sample_height_bilinear, :155-173).  Kept as it
+ * is: t advances by repeated f32 addition (t_10 = 1.0000001, not 1.0); step 0 is always tested, step k >= 1 iff t_k <= max_distance,
+ * a NaN max_distance never leaves; `low` of the bisection starts at max(t_k - 0.1, 0); grid_pos divides by the scale although the
+ * heights were looked up without it. */
+#define RXR_TERRAIN_MARCH_STEPS 1500u
+/* validation only, no context: the status rxr_set_terrain_heights would return and, in `message`, the reason.  RXR_ERR_INVALID: a
+ * scale that is not finite and > 0, a bounding rectangle of more than RXR_TERRAIN_MAX_CELLS cells, a coordinate outside +-2^30, a
+ * NULL array with n_cells > 0. */
+int rxr_check_terrain_heights(const float scale[2], const int32_t *cell_xy, const float *cell_height, uint32_t n_cells,
+                              char *message, uint32_t message_capacity);
+/* makes a terrain's heights resident (they stay until the next call; n_cells == 0 registers the empty terrain, a plane at 0).
+ * cell_height[i] is what Terrain::get_height returns for cell_xy[i] (the caller flattens chunk.processed_heights where a chunk has
+ * them, else chunk.heights, src/terrain/chunk.rs:81-95); any f32 bit pattern is legal.  A coordinate given twice: the later entry wins.  The library keeps a dense f32 grid over the cells' bounding
+ * rectangle; cells outside it and cells not listed are 0.0, the reference's answer.  Independent of rxr_set_terrain: buffers and
+ * scale of its own; either may be registered without the other.  Arrays are read before the call returns.  A refused call leaves
+ * the resident heights as they were.  Multi-device handles: member 0.
+ * Replaces: Terrain::get_height, src/terrain/mod.rs:82-89. */
+int rxr_set_terrain_heights(rxr_ctx *ctx, const float scale[2], const int32_t *cell_xy /* [n_cells][2] world cell coordinates */,
+                            const float *cell_height /* [n_cells] */, uint32_t n_cells);
+/* n rays against the resident heights, one max_distance for all.  origins / dirs [n][3], dirs un-normalised, as rxr_intersect takes
+ * them.  Per ray: hit (1 or 0; required); t = t_hit IN UNITS OF THE CALLER'S dir (FLT_MAX on a miss) -- rxr_intersect's t is along
+ * the NORMALISED direction: multiply this one by |dir| before taking the nearer of a mesh hit and a terrain hit; world_pos [n][3] =
+ * TerrainHit.world_pos, whose [1] is TerrainHit.height; grid_pos [n][2] = TerrainHit.grid_pos (zeros on a miss).  t, world_pos and
+ * grid_pos may be NULL.  Where the reference's world_pos is a NaN (NaN or infinite ray components, NaN heights) this one is a NaN;
+ * its sign and payload are the device's.  RXR_ERR_INVALID: no rxr_set_terrain_heights yet, or a NULL required pointer; n_rays == 0 does nothing.
+ * Host memory, blocking.  A few rays (a click) run one ray per wave, more run one ray per lane (RXR_TERRAIN_HIT_ROUTE=lane|wave in
+ * the environment, read at each call, forces one; the bytes are the same); the call is split into launches of a
+ * bounded number of rays (RXR_TERRAIN_HIT_LAUNCH_RAYS overrides the bound).  Changes no frame, scratch, bake or picking state.
+ * Multi-device handles: member 0.
+ * Replaces: Terrain::ray_terrain_hit, src/terrain/mod.rs:427-479. */
+int rxr_terrain_hits(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n_rays, float max_distance, uint32_t *hit,
+                     float *t, float *world_pos, int32_t *grid_pos);
+/* the same on DEVICE arrays (each given array's first and last byte are checked to be memory of the context's device; 4-byte
+ * aligned), queued on hip_stream (NULL = the context's stream): the rays of rxr_screen_rays_to go straight in.  Asynchronous.
+ * Multi-device handles: RXR_ERR_UNSUPPORTED (use rxr_member). */
+int rxr_terrain_hits_to(rxr_ctx *ctx, const float *dev_origins, const float *dev_dirs, uint32_t n_rays, float max_distance,
+                        uint32_t *dev_hit, float *dev_t, float *dev_world_pos, int32_t *dev_grid_pos, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -485,6 +485,16 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         L.terrain_bake_chunks = fn("terrain_bake_chunks", i32, vp, pi, u32, i32, pb)
         L.terrain_build_chunk_at = fn("terrain_build_chunk_at", i32, vp, i32, i32, i32, vp, i32)
         L.chunk_terrain_texture = fn("chunk_terrain_texture", i32, vp, i32, pu, pu, pb)
+    # terrain heights and the editor's pick (product host library only)
+    has_terrain_hit = hasattr(lib, prefix + "terrain_ray_hits")
+    if has_terrain_hit:
+        L.terrain_set_height = fn("terrain_set_height", None, vp, i32, i32, f32)
+        L.terrain_get_height = fn("terrain_get_height", f32, vp, i32, i32)
+        L.terrain_sample_height = fn("terrain_sample_height", f32, vp, f32, f32)
+        L.terrain_sample_height_bilinear = fn("terrain_sample_height_bilinear", f32, vp, f32, f32)
+        L.terrain_ray_hit = fn("terrain_ray_hit", i32, vp, pf, pf, f32, pf, pf, pi)
+        L.terrain_ray_hits_cpu = fn("terrain_ray_hits_cpu", None, vp, pf, pf, u32, f32, pu, pf, pf, pi)
+        L.terrain_ray_hits = fn("terrain_ray_hits", i32, vp, pf, pf, u32, f32, pu, pf, pf, pi)
 
     def last_error():
         if not hasattr(lib, prefix + "last_error"):
@@ -950,6 +960,68 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
             if rc != 0:
                 raise RasterizeError(rc, last_error())
             return chunk
+
+        # ---- heights and the editor's pick (:82-95, :148-173, :427-479) ----
+        @staticmethod
+        def _need_hit():
+            if not has_terrain_hit:
+                raise NotImplementedError(f"{name}: no terrain pick in this library")
+
+        def set_height(self, x, y, height):
+            """Terrain::set_height (:92-95)"""
+            self._need_hit()
+            L.terrain_set_height(self._h, x, y, height)
+            return self
+
+        def get_height(self, x, y):
+            self._need_hit()
+            return np.float32(L.terrain_get_height(self._h, x, y))
+
+        def sample_height(self, x, y):
+            self._need_hit()
+            return np.float32(L.terrain_sample_height(self._h, x, y))
+
+        def sample_height_bilinear(self, x, y):
+            self._need_hit()
+            return np.float32(L.terrain_sample_height_bilinear(self._h, x, y))
+
+        def ray_terrain_hit(self, origin, dir, max_distance):
+            """Terrain::ray_terrain_hit (:427-479) on the CPU for one ray: None, or a dict of t (t_hit, in units of `dir`), world_pos
+            ([3] float32), grid_pos ([2] int32) and height"""
+            self._need_hit()
+            o, d = np.asarray(origin, np.float32).reshape(3).copy(), np.asarray(dir, np.float32).reshape(3).copy()
+            t, wp, gp = np.zeros(1, np.float32), np.zeros(3, np.float32), np.zeros(2, np.int32)
+            if not L.terrain_ray_hit(self._h, _fp(o), _fp(d), max_distance, _fp(t), _fp(wp), gp.ctypes.data_as(C.POINTER(C.c_int32))):
+                return None
+            return dict(t=t[0], world_pos=wp, grid_pos=gp, height=wp[1])
+
+        def _hits(self, origins, dirs, max_distance, device):
+            self._need_hit()
+            o = np.ascontiguousarray(np.asarray(origins, np.float32).reshape(-1, 3))
+            d = np.ascontiguousarray(np.asarray(dirs, np.float32).reshape(-1, 3))
+            if o.shape != d.shape:
+                raise ValueError("origins and dirs must have the same shape")
+            n = o.shape[0]
+            m = max(n, 1)
+            hit, t = np.zeros(m, np.uint32), np.zeros(m, np.float32)
+            wp, gp = np.zeros((m, 3), np.float32), np.zeros((m, 2), np.int32)
+            args = (self._h, _fp(o) if n else None, _fp(d) if n else None, n, max_distance, _up(hit), _fp(t), _fp(wp), gp.ctypes.data_as(C.POINTER(C.c_int32)))
+            if device:
+                rc = L.terrain_ray_hits(*args)
+                if rc != 0:
+                    raise RasterizeError(rc, last_error())
+            else:
+                L.terrain_ray_hits_cpu(*args)
+            return dict(hit=hit[:n], t=t[:n], world_pos=wp[:n], grid_pos=gp[:n])
+
+        def ray_terrain_hits(self, origins, dirs, max_distance):
+            """ray_terrain_hit for [n][3] origins and dirs in one device call (rxr_terrain_hits, include/rxr.h): a dict of hit ([n]
+            uint32, 1 or 0), t ([n], f32::MAX on a miss), world_pos ([n][3], [.., 1] is the height) and grid_pos ([n][2] int32)"""
+            return self._hits(origins, dirs, max_distance, True)
+
+        def ray_terrain_hits_cpu(self, origins, dirs, max_distance):
+            """the same arrays from the CPU ray_terrain_hit over the host's worker pool"""
+            return self._hits(origins, dirs, max_distance, False)
 
     class Assets:
         """reference src/server/assets.rs (`tile_list`, `.textures(..)` builder)."""

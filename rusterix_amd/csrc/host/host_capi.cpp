@@ -175,6 +175,30 @@ void rxh_terrain_set_source(void *t, int32_t x, int32_t y, const uint8_t *rgba, 
 void rxh_terrain_set_blend_mode(void *t, int32_t x, int32_t y, uint32_t kind, uint32_t radius, float offset_x, float offset_y) {
     ((Terrain *)t)->set_blend_mode(x, y, kind, radius, offset_x, offset_y);
 }
+// Terrain::set_height / get_height
+void rxh_terrain_set_height(void *t, int32_t x, int32_t y, float height) { ((Terrain *)t)->set_height(x, y, height); }
+float rxh_terrain_get_height(void *t, int32_t x, int32_t y) { return ((Terrain *)t)->get_height(x, y); }
+float rxh_terrain_sample_height(void *t, float x, float y) { return ((Terrain *)t)->sample_height(x, y); }
+float rxh_terrain_sample_height_bilinear(void *t, float x, float y) { return ((Terrain *)t)->sample_height_bilinear(x, y); }
+// Terrain::ray_terrain_hit on the CPU: 1 and t_hit, world_pos[3], grid_pos[2] for Some, 0 for None
+int rxh_terrain_ray_hit(void *t, const float *origin, const float *dir, float max_distance, float *t_hit, float *world_pos, int32_t *grid_pos) {
+    Terrain::Hit h;
+    if (!((Terrain *)t)->ray_terrain_hit(origin, dir, max_distance, h)) return 0;
+    *t_hit = h.t;
+    memcpy(world_pos, h.world_pos, sizeof h.world_pos);
+    memcpy(grid_pos, h.grid_pos, sizeof h.grid_pos);
+    return 1;
+}
+// the same for n rays over the host's worker pool, in the layout of rxr_terrain_hits
+void rxh_terrain_ray_hits_cpu(void *t, const float *origins, const float *dirs, uint32_t n, float max_distance, uint32_t *hit, float *t_hit, float *world_pos,
+                              int32_t *grid_pos) {
+    ((Terrain *)t)->ray_terrain_hits_cpu(origins, dirs, n, max_distance, hit, t_hit, world_pos, grid_pos);
+}
+// ... and on the device (rxr_terrain_hits); RXR_OK or a negative rxr_status
+int rxh_terrain_ray_hits(void *t, const float *origins, const float *dirs, uint32_t n, float max_distance, uint32_t *hit, float *t_hit, float *world_pos,
+                         int32_t *grid_pos) {
+    return ((Terrain *)t)->ray_terrain_hits(origins, dirs, n, max_distance, hit, t_hit, world_pos, grid_pos);
+}
 // Terrain::bake_chunk on the CPU: side * side * 4 bytes; RXR_OK or a negative rxr_status
 int rxh_terrain_bake_chunk(void *t, int32_t cx, int32_t cy, int32_t ppt, uint8_t *rgba) {
     std::vector<uint8_t> out;

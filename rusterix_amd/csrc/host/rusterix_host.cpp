@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -489,6 +490,7 @@ std::string g_error;
 uint64_t g_tex_static_gen = 0, g_tex_dynamic_gen = 0;
 uint64_t g_shaders_gen = 0, g_shader_env_gen = 0;
 uint64_t g_terrain_gen = 0;   // the Terrain::generation the context's resident terrain was registered from (0: none)
+uint64_t g_heights_gen = 0;   // the Terrain::heights_generation the context's resident heights were registered from (0: none)
 // (RXR_DEVICE_PROJECTION=1 in the environment makes device projection the initial choice, as in the Rust shim: shim/.../lib.rs)
 bool g_device_projection = [] { const char *e = getenv("RXR_DEVICE_PROJECTION"); return e && e[0] == '1'; }();
 bool g_device_edges = !(getenv("RXR_HOST_EDGES") && atoi(getenv("RXR_HOST_EDGES")) != 0);
@@ -523,6 +525,7 @@ void drop_context_locked() {
     g_tex_static_gen = g_tex_dynamic_gen = 0;
     g_shaders_gen = g_shader_env_gen = 0;
     g_terrain_gen = 0;
+    g_heights_gen = 0;
 }
 }  // namespace
 
@@ -1050,6 +1053,149 @@ int Terrain::build_chunk_at(int32_t cx, int32_t cy, int32_t ppt, Chunk &chunk) c
     chunk.terrain_texture = std::move(baked);
     chunk.has_terrain_texture = true;
     return RXR_OK;
+}
+
+// ---- heights and the editor's pick ----
+void Terrain::set_height(int32_t x, int32_t y, float height) {
+    heights[{x, y}] = height;
+    chunks.insert({div_euclid(x, chunk_size), div_euclid(y, chunk_size)});
+    heights_generation = next_generation();
+}
+
+void Terrain::flatten_heights(std::vector<int32_t> &xy, std::vector<float> &height) const {
+    for (const auto &kv : heights) {
+        xy.push_back(kv.first.first);
+        xy.push_back(kv.first.second);
+        height.push_back(kv.second);
+    }
+}
+
+const Terrain::HeightGrid &Terrain::height_grid() const {
+    HeightGrid &g = height_grid_;
+    if (g.generation == heights_generation) return g;
+    g = HeightGrid{};
+    if (!heights.empty()) {
+        int64_t lo[2] = {INT32_MAX, INT32_MAX}, hi[2] = {INT32_MIN, INT32_MIN};
+        for (const auto &kv : heights) {
+            lo[0] = std::min<int64_t>(lo[0], kv.first.first);
+            hi[0] = std::max<int64_t>(hi[0], kv.first.first);
+            lo[1] = std::min<int64_t>(lo[1], kv.first.second);
+            hi[1] = std::max<int64_t>(hi[1], kv.first.second);
+        }
+        const int64_t w = hi[0] - lo[0] + 1, h = hi[1] - lo[1] + 1;
+        if (w * h <= (int64_t)RXR_TERRAIN_MAX_CELLS) {   // (else w == 0: get_height reads the map)
+            g.x0 = lo[0];
+            g.y0 = lo[1];
+            g.w = w;
+            g.h = h;
+            g.cells.assign((size_t)(w * h), 0.0f);
+            for (const auto &kv : heights) g.cells[(size_t)((kv.first.second - lo[1]) * w + (kv.first.first - lo[0]))] = kv.second;
+        }
+    }
+    g.generation = heights_generation;
+    return g;
+}
+
+float Terrain::get_height(int32_t x, int32_t y) const {
+    const HeightGrid &g = height_grid();
+    if (g.w || heights.empty()) {
+        const int64_t gx = (int64_t)x - g.x0, gy = (int64_t)y - g.y0;
+        return (gx >= 0 && gy >= 0 && gx < g.w && gy < g.h) ? g.cells[(size_t)(gy * g.w + gx)] : 0.0f;
+    }
+    auto it = heights.find({x, y});
+    return it == heights.end() ? 0.0f : it->second;
+}
+
+float Terrain::sample_height(float x, float y) const { return get_height(as_i32(std::round(x)), as_i32(std::round(y))); }
+
+float Terrain::sample_height_bilinear(float x, float y) const {
+    const int32_t x0 = as_i32(std::floor(x)), y0 = as_i32(std::floor(y));
+    const int32_t x1 = (int32_t)((uint32_t)x0 + 1u), y1 = (int32_t)((uint32_t)y0 + 1u);   // (wraps, as a release build does)
+    const float tx = x - (float)x0, ty = y - (float)y0;
+    const float h00 = get_height(x0, y0), h10 = get_height(x1, y0), h01 = get_height(x0, y1), h11 = get_height(x1, y1);
+    const float h0 = h00 * (1.0f - tx) + h10 * tx;
+    const float h1 = h01 * (1.0f - tx) + h11 * tx;
+    return h0 * (1.0f - ty) + h1 * ty;
+}
+
+bool Terrain::ray_terrain_hit(const float origin[3], const float dir[3], float max_distance, Hit &hit) const {
+    const Vec3 o{origin[0], origin[1], origin[2]}, d{dir[0], dir[1], dir[2]};
+    float t = 0.0f;
+    const float step_size = 0.1f;
+    for (int i = 0; i < (int)RXR_TERRAIN_MARCH_STEPS; ++i) {
+        const Vec3 point = o + d * t;
+        const float terrain_height = sample_height(point.x, point.z);
+        if (point.y - terrain_height < 0.01f) {
+            float low = std::fmax(t - step_size, 0.0f), high = t;
+            for (int j = 0; j < 4; ++j) {
+                const float mid = (low + high) * 0.5f;
+                const Vec3 point_mid = o + d * mid;
+                if (point_mid.y - sample_height_bilinear(point_mid.x, point_mid.z) < 0.01f) high = mid;
+                else low = mid;
+            }
+            const float t_hit = (low + high) * 0.5f;
+            const Vec3 hit_point = o + d * t_hit;
+            const float terrain_hit_height = sample_height_bilinear(hit_point.x, hit_point.z);
+            hit.t = t_hit;
+            hit.world_pos[0] = hit_point.x;
+            hit.world_pos[1] = terrain_hit_height;
+            hit.world_pos[2] = hit_point.z;
+            hit.grid_pos[0] = as_i32(std::floor(hit_point.x / scale[0]));
+            hit.grid_pos[1] = as_i32(std::floor(hit_point.z / scale[1]));
+            hit.height = terrain_hit_height;
+            return true;
+        }
+        t += step_size;
+        if (t > max_distance) break;
+    }
+    return false;
+}
+
+namespace {
+void store_hit(bool found, const Terrain::Hit &h, size_t i, uint32_t *hit, float *t, float *world_pos, int32_t *grid_pos) {
+    hit[i] = found ? 1u : 0u;
+    if (t) t[i] = found ? h.t : FLT_MAX;
+    for (int a = 0; a < 3; ++a)
+        if (world_pos) world_pos[3 * i + a] = found ? h.world_pos[a] : 0.0f;
+    for (int a = 0; a < 2; ++a)
+        if (grid_pos) grid_pos[2 * i + a] = found ? h.grid_pos[a] : 0;
+}
+}  // namespace
+
+void Terrain::ray_terrain_hits_cpu(const float *origins, const float *dirs, uint32_t n, float max_distance, uint32_t *hit, float *t, float *world_pos,
+                                   int32_t *grid_pos) const {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);   // (the worker pool runs one job at a time)
+    (void)height_grid();                              // (built once, before the workers read it)
+    const size_t per = 256, items = ((size_t)n + per - 1) / per;
+    rxr_parallel::run(items, (size_t)n * 1500, [&](size_t item) {
+        for (size_t i = item * per; i < std::min<size_t>((item + 1) * per, n); ++i) {
+            Hit h;
+            const bool found = ray_terrain_hit(origins + 3 * i, dirs + 3 * i, max_distance, h);
+            store_hit(found, h, i, hit, t, world_pos, grid_pos);
+        }
+    });
+}
+
+int Terrain::ray_terrain_hits(const float *origins, const float *dirs, uint32_t n, float max_distance, uint32_t *hit, float *t, float *world_pos,
+                              int32_t *grid_pos) const {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::string err;
+    rxr_ctx *ctx = context(&err);
+    if (!ctx) return RXR_ERR_NO_DEVICE;
+    if (g_heights_gen != heights_generation) {
+        std::vector<int32_t> xy;
+        std::vector<float> height;
+        flatten_heights(xy, height);
+        const int rc = rxr_set_terrain_heights(ctx, scale, xy.data(), height.data(), (uint32_t)height.size());
+        if (rc != RXR_OK) {
+            g_error = rxr_last_error(ctx);
+            return rc;
+        }
+        g_heights_gen = heights_generation;
+    }
+    const int rc = rxr_terrain_hits(ctx, origins, dirs, n, max_distance, hit, t, world_pos, grid_pos);
+    if (rc != RXR_OK) g_error = rxr_last_error(ctx);
+    return rc;
 }
 
 void Rasterizer::screen_ray(float x, float y, float origin[3], float dir[3]) const {

@@ -301,6 +301,44 @@ public:
     int build_chunk_at(int32_t cx, int32_t cy, int32_t pixels_per_tile, Chunk &chunk) const;
     // the cell list of rxr_set_terrain
     void flatten(std::vector<int32_t> &xy, std::vector<int32_t> &texture, std::vector<uint32_t> &blend, std::vector<float> &offset) const;
+
+    // ---- heights and the editor's pick (:82-95, :148-173, :427-479) ----
+    // TerrainHit (src/terrain/mod.rs:11-16); `t` is t_hit, which the reference computes and drops
+    struct Hit {
+        float t = 0.0f;
+        float world_pos[3] = {0.0f, 0.0f, 0.0f};
+        int32_t grid_pos[2] = {0, 0};
+        float height = 0.0f;
+    };
+    std::map<std::pair<int32_t, int32_t>, float> heights;         // what get_height returns per cell, keyed (x, y)
+    uint64_t heights_generation = next_generation();              // re-stamped by set_height alone: a height edit does not re-register the bake's terrain
+    void set_height(int32_t x, int32_t y, float height);          // :92-95
+    float get_height(int32_t x, int32_t y) const;                 // :82-89: 0.0 for a cell that does not exist
+    float sample_height(float x, float y) const;                  // :148-152
+    float sample_height_bilinear(float x, float y) const;         // :155-173
+    // Terrain::ray_terrain_hit (:427-479) on the CPU, a plain transcription: false for None
+    bool ray_terrain_hit(const float origin[3], const float dir[3], float max_distance, Hit &hit) const;
+    // the same for n rays on the device (rxr_set_terrain_heights when the heights changed since they were registered, then
+    // rxr_terrain_hits, include/rxr.h); t, world_pos and grid_pos may be null.  RXR_OK or a negative rxr_status; there is no fall-back
+    // to the CPU.
+    int ray_terrain_hits(const float *origins, const float *dirs, uint32_t n, float max_distance, uint32_t *hit, float *t, float *world_pos,
+                         int32_t *grid_pos) const;
+    // the same on the CPU over the host's worker pool (what tools/terrain_hit_bench.py measures the device against)
+    void ray_terrain_hits_cpu(const float *origins, const float *dirs, uint32_t n, float max_distance, uint32_t *hit, float *t, float *world_pos,
+                              int32_t *grid_pos) const;
+    // the cell list of rxr_set_terrain_heights
+    void flatten_heights(std::vector<int32_t> &xy, std::vector<float> &height) const;
+
+private:
+    // get_height's answers as a dense grid over the cells' bounding rectangle, rebuilt when heights_generation moved (the CPU march
+    // looks a cell up 1500 times a ray)
+    struct HeightGrid {
+        uint64_t generation = 0;
+        int64_t x0 = 0, y0 = 0, w = 0, h = 0;
+        std::vector<float> cells;
+    };
+    mutable HeightGrid height_grid_;
+    const HeightGrid &height_grid() const;
 };
 
 // src/rasterizer.rs:35-193

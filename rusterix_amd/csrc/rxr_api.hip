@@ -72,6 +72,10 @@ int rxr_quiesce(rxr_ctx *ctx) {
         HIPCHK(ctx, hipEventSynchronize(ctx->ev_terrain));
         ctx->terrain_pending = false;
     }
+    if (ctx->heights_pending) {  // a terrain pick on the caller's stream (rxr_terrain_hits_to) reads the resident heights
+        HIPCHK(ctx, hipEventSynchronize(ctx->ev_heights));
+        ctx->heights_pending = false;
+    }
     return RXR_OK;
 }
 
@@ -187,7 +191,8 @@ void rxr_destroy(rxr_ctx *ctx) {
                       &ctx->d_vm_code, &ctx->d_programs, &ctx->d_patterns, &ctx->d_pattern_data, &ctx->d_palette,
                       &ctx->d_isect_tris, &ctx->d_isect_misc, &ctx->d_isect_keys, &ctx->d_isect_io,
                       &ctx->d_bake_io, &ctx->d_bake_jobs, &ctx->d_bake_fault,
-                      &ctx->d_terrain_cells, &ctx->d_terrain_tex, &ctx->d_terrain_texels, &ctx->d_terrain_weights, &ctx->d_terrain_io};
+                      &ctx->d_terrain_cells, &ctx->d_terrain_tex, &ctx->d_terrain_texels, &ctx->d_terrain_weights, &ctx->d_terrain_io,
+                      &ctx->d_heights, &ctx->d_heights_tk, &ctx->d_heights_io};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     rxr_jit_drop(ctx);
@@ -203,6 +208,7 @@ void rxr_destroy(rxr_ctx *ctx) {
     if (ctx->ev_isect) (void)hipEventDestroy(ctx->ev_isect);
     if (ctx->ev_bake) (void)hipEventDestroy(ctx->ev_bake);
     if (ctx->ev_terrain) (void)hipEventDestroy(ctx->ev_terrain);
+    if (ctx->ev_heights) (void)hipEventDestroy(ctx->ev_heights);
     if (ctx->h_bake_fault) (void)hipHostFree(ctx->h_bake_fault);
     if (ctx->h_bake_jobs) (void)hipHostFree(ctx->h_bake_jobs);
     for (hipEvent_t ev : ctx->ev_band)

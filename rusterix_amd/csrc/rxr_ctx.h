@@ -256,6 +256,19 @@ struct rxr_ctx {
     bool terrain_pending = false;     // ... and not yet waited for (rxr_quiesce)
     uint32_t terrain_launches = 0;    // k_terrain_bake launches of the last bake call (rxr_debug_terrain_launches)
 
+    // terrain picks (rxr_terrain_hit.hip): the resident heights of rxr_set_terrain_heights, independent of the resident terrain above.
+    // d_heights: the dense f32 grid over the cells' bounding rectangle; d_heights_tk: the 1500 values t_k of the march; d_heights_io:
+    // rxr_terrain_hits' device copies of the caller's host arrays.
+    DevBuf d_heights, d_heights_tk, d_heights_io;
+    bool heights_set = false;
+    float heights_scale[2] = {1.0f, 1.0f};
+    int32_t heights_x0 = 0, heights_y0 = 0;
+    uint32_t heights_gw = 0, heights_gh = 0;
+    hipEvent_t ev_heights = nullptr;  // recorded behind the last hit call's launches (on whichever stream they ran)
+    bool heights_pending = false;     // ... and not yet waited for (rxr_quiesce)
+    uint32_t heights_launches = 0;    // march launches of the last hit call (rxr_debug_terrain_hit_kernel)
+    const char *heights_kernel = "";  // ... and their kernel's symbol name; a static string
+
     FrameStream fstream;    // rxr_stream_begin .. rxr_upload_frame
     int last_upload_streamed = 0;  // 0 plain, 1 streamed (copied), 2 streamed out of page-locked arrays
 

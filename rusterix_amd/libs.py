@@ -82,6 +82,12 @@ def rxr_abi():
         "rxr_bake_terrain": (i32, [vp, vp, u32, i32, vp]),
         "rxr_bake_terrain_to": (i32, [vp, vp, u32, i32, vp, vp]),
         "rxr_debug_terrain_launches": (u32, [vp]),
+        "rxr_check_terrain_heights": (i32, [vp, vp, vp, u32, C.c_char_p, u32]),
+        "rxr_set_terrain_heights": (i32, [vp, vp, vp, vp, u32]),
+        "rxr_terrain_hits": (i32, [vp, vp, vp, u32, C.c_float, vp, vp, vp, vp]),
+        "rxr_terrain_hits_to": (i32, [vp, vp, vp, u32, C.c_float, vp, vp, vp, vp, vp]),
+        "rxr_debug_terrain_hit_kernel": (C.c_char_p, [vp, C.POINTER(u32)]),
+        "rxr_debug_terrain_hit_few_rays": (u32, []),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -126,6 +126,52 @@ pub fn invalidate_device_caches() {
     }
 }
 
+// ---- terrain picks (include/rxr.h rxr_set_terrain_heights / rxr_terrain_hits) -----------------------------------
+/// Makes `terrain`'s heights resident: per chunk the cells of `processed_heights` where the chunk has them, else of `heights`
+/// (what `TerrainChunk::get_height` reads, src/terrain/chunk.rs:81-95), at world cell = chunk.origin + local.  Call it again after
+/// an edit.  False when there is no device context or the library refuses the terrain (the caller then asks the CPU).
+pub fn set_terrain_heights(terrain: &Terrain) -> bool {
+    let mut guard = STATE.lock().unwrap();
+    let st = guard.get_or_insert_with(Caches::default);
+    if st.ctx.is_none() && !st.tried {
+        st.tried = true;
+        st.ctx = create_context();
+    }
+    let Some(ctx) = &st.ctx else { return false };
+    let (mut xy, mut height) = (Vec::<i32>::new(), Vec::<f32>::new());
+    for chunk in terrain.chunks.values() {
+        let cells = chunk.processed_heights.as_ref().unwrap_or(&chunk.heights);
+        for (&(lx, ly), &h) in cells {
+            xy.extend_from_slice(&[chunk.origin.x + lx, chunk.origin.y + ly]);
+            height.push(h);
+        }
+    }
+    let scale = [terrain.scale.x, terrain.scale.y];
+    unsafe { rxr_set_terrain_heights(ctx.0, scale.as_ptr(), xy.as_ptr(), height.as_ptr(), height.len() as u32) == RXR_OK }
+}
+
+/// `Terrain::ray_terrain_hit` (src/terrain/mod.rs:427-479) for every ray in one device call against the heights of the last
+/// `set_terrain_heights`; one `max_distance` for all.  `None`: no device context, or the library's error status.
+pub fn terrain_ray_hits(rays: &[Ray], max_distance: f32) -> Option<Vec<Option<TerrainHit>>> {
+    let guard = STATE.lock().unwrap();
+    let ctx = guard.as_ref()?.ctx.as_ref()?;
+    let n = rays.len();
+    let origins: Vec<f32> = rays.iter().flat_map(|r| [r.origin.x, r.origin.y, r.origin.z]).collect();
+    let dirs: Vec<f32> = rays.iter().flat_map(|r| [r.dir.x, r.dir.y, r.dir.z]).collect();
+    let (mut hit, mut world, mut grid) = (vec![0u32; n], vec![0f32; 3 * n], vec![0i32; 2 * n]);
+    let rc = unsafe {
+        rxr_terrain_hits(ctx.0, origins.as_ptr(), dirs.as_ptr(), n as u32, max_distance, hit.as_mut_ptr(), std::ptr::null_mut(), world.as_mut_ptr(), grid.as_mut_ptr())
+    };
+    if rc != RXR_OK {
+        return None;
+    }
+    Some((0..n).map(|i| (hit[i] != 0).then(|| TerrainHit {
+        world_pos: Vec3::new(world[3 * i], world[3 * i + 1], world[3 * i + 2]),
+        grid_pos: Vec2::new(grid[2 * i], grid[2 * i + 1]),
+        height: world[3 * i + 1],
+    })).collect())
+}
+
 // ---- NodeOp tree -> the word stream of include/rxr.h ------------------------------------------------------------
 /// Depth-first serialisation of `Program.user_functions[i]` (rusteria/src/node/nodeop.rs:12-103): opcode = the variant's
 /// position in the enum, payloads as documented in include/rxr.h.  Block lengths are in words.

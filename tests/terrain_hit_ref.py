@@ -1,0 +1,232 @@
+"""Ground truth of the terrain pick: Terrain::ray_terrain_hit (reference src/terrain/mod.rs:427-479) with sample_height (:148-152),
+sample_height_bilinear (:155-173) and get_height (:82-89) restated in numpy float32 -- vectorised over rays, a Python loop over the
+1500 steps, every operation once and in the reference's order.  np.round rounds half to even and numpy casts do not saturate: the
+helpers of tests/terrain_ref.py (`round_away`, `as_i32`) handle both.
+
+HeightSpec is the neutral description the tests build terrains with: it answers the reference (`hits`), makes the mirror's Terrain
+(`product`) and the arrays of rxr_set_terrain_heights (`arrays`)."""
+import numpy as np
+
+from tests.terrain_ref import as_i32, round_away
+
+F = np.float32
+STEPS = 1500                     # RXR_TERRAIN_MARCH_STEPS
+F32_MAX = np.finfo(np.float32).max
+RXR_OK, RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED = 0, -1, -4
+
+
+def march_table():
+    """t_k, k = 0..1499: t_0 = 0, t_{k+1} = fl(t_k + 0.1f) (:428-429, :473)"""
+    out = np.zeros(STEPS, F)
+    t = F(0.0)
+    for k in range(STEPS):
+        out[k] = t
+        t = F(t + F(0.1))
+    return out
+
+
+TK = march_table()
+
+
+def steps_tested(max_distance):
+    """K: steps 0 .. K-1 are tested (:473-476: after step k, t becomes t_{k+1} and the loop leaves when it exceeds max_distance)"""
+    k = 1
+    while k < STEPS and not (TK[k] > F(max_distance)):
+        k += 1
+    return k
+
+
+def wrap_i32(v):
+    return ((v + 2 ** 31) % 2 ** 32) - 2 ** 31
+
+
+class HeightSpec:
+    def __init__(self, scale=(1.0, 1.0), chunk_size=16):
+        self.scale = (F(scale[0]), F(scale[1]))
+        self.chunk_size = int(chunk_size)
+        self.heights = {}        # (x, y) -> f32
+        self._grid = None
+
+    def height(self, x, y, h):
+        self.heights[(int(x), int(y))] = F(h)
+        self._grid = None
+        return self
+
+    # ---- the consumers -----------------------------------------------------------------------------------------------------------
+    def product(self, api):
+        t = api.Terrain((float(self.scale[0]), float(self.scale[1])), self.chunk_size)
+        for (x, y), h in self.heights.items():
+            t.set_height(x, y, float(h))
+        return t
+
+    def arrays(self):
+        """the arguments of rxr_check_terrain_heights / rxr_set_terrain_heights behind ctx, as a dict (which keeps the arrays alive) and a tuple"""
+        keys = sorted(self.heights)
+        n = len(keys)
+        xy = np.array(keys, np.int32).reshape(n, 2)
+        h = np.array([self.heights[k] for k in keys], np.float32)
+        scale = np.array(self.scale, np.float32)
+        keep = dict(xy=xy, h=h, scale=scale)
+        return keep, (scale.ctypes.data, xy.ctypes.data if n else None, h.ctypes.data if n else None, n)
+
+    # ---- the reference -----------------------------------------------------------------------------------------------------------
+    def _dense(self):
+        if self._grid is None:
+            if not self.heights:
+                self._grid = (0, 0, np.zeros((0, 0), F))
+            else:
+                xs, ys = [k[0] for k in self.heights], [k[1] for k in self.heights]
+                x0, y0 = min(xs), min(ys)
+                g = np.zeros((max(ys) - y0 + 1, max(xs) - x0 + 1), F)
+                for (x, y), h in self.heights.items():
+                    g[y - y0, x - x0] = h
+                self._grid = (x0, y0, g)
+        return self._grid
+
+    def get_height(self, x, y):
+        """:82-89 for int64 arrays of cells: 0.0 where no cell exists"""
+        x0, y0, g = self._dense()
+        out = np.zeros(np.shape(x), F)
+        if g.size:
+            gx, gy = x - x0, y - y0
+            inside = (gx >= 0) & (gy >= 0) & (gx < g.shape[1]) & (gy < g.shape[0])
+            out[inside] = g[gy[inside], gx[inside]]
+        return out
+
+    def sample_height(self, x, y):
+        return self.get_height(as_i32(round_away(x)), as_i32(round_away(y)))
+
+    def sample_height_bilinear(self, x, y):
+        x0, y0 = as_i32(np.floor(x)), as_i32(np.floor(y))
+        x1, y1 = wrap_i32(x0 + 1), wrap_i32(y0 + 1)          # (a release build wraps)
+        tx, ty = (x - x0.astype(F)).astype(F), (y - y0.astype(F)).astype(F)
+        h00, h10, h01, h11 = self.get_height(x0, y0), self.get_height(x1, y0), self.get_height(x0, y1), self.get_height(x1, y1)
+        h0 = ((h00 * (F(1) - tx)).astype(F) + (h10 * tx).astype(F)).astype(F)
+        h1 = ((h01 * (F(1) - tx)).astype(F) + (h11 * tx).astype(F)).astype(F)
+        return ((h0 * (F(1) - ty)).astype(F) + (h1 * ty).astype(F)).astype(F)
+
+    def hits(self, origins, dirs, max_distance):
+        """:427-479 for [n][3] origins and dirs: a dict of hit (uint32), step (the coarse step k, -1 on a miss), t (t_hit, f32::MAX on a
+        miss), world_pos [n][3] and grid_pos [n][2] (zeros on a miss) -- the layout of rxr_terrain_hits plus `step`"""
+        o = np.ascontiguousarray(np.asarray(origins, F).reshape(-1, 3))
+        d = np.ascontiguousarray(np.asarray(dirs, F).reshape(-1, 3))
+        n = o.shape[0]
+        step = np.full(n, -1, np.int64)
+        max_distance = F(max_distance)
+        with np.errstate(invalid="ignore", over="ignore"):
+            pending = np.arange(n)
+            t = F(0.0)
+            for k in range(STEPS):
+                if not len(pending):
+                    break
+                op, dp = o[pending], d[pending]
+                p = (op + (dp * t).astype(F)).astype(F)
+                h = self.sample_height(p[:, 0], p[:, 2])
+                found = (p[:, 1] - h).astype(F) < F(0.01)
+                step[pending[found]] = k
+                pending = pending[~found]
+                t = F(t + F(0.1))
+                if t > max_distance:
+                    break
+            out = dict(hit=(step >= 0).astype(np.uint32), step=step, t=np.full(n, F32_MAX, F), world_pos=np.zeros((n, 3), F), grid_pos=np.zeros((n, 2), np.int32))
+            m = np.flatnonzero(step >= 0)
+            if len(m):
+                om, dm = o[m], d[m]
+                high = TK[step[m]]
+                low = np.maximum((high - F(0.1)).astype(F), F(0.0))
+                for _ in range(4):
+                    mid = ((low + high).astype(F) * F(0.5)).astype(F)
+                    pm = (om + (dm * mid[:, None]).astype(F)).astype(F)
+                    below = (pm[:, 1] - self.sample_height_bilinear(pm[:, 0], pm[:, 2])).astype(F) < F(0.01)
+                    high = np.where(below, mid, high)
+                    low = np.where(below, low, mid)
+                t_hit = ((low + high).astype(F) * F(0.5)).astype(F)
+                q = (om + (dm * t_hit[:, None]).astype(F)).astype(F)
+                hh = self.sample_height_bilinear(q[:, 0], q[:, 2])
+                out["t"][m] = t_hit
+                out["world_pos"][m] = np.stack([q[:, 0], hh, q[:, 2]], axis=1)
+                out["grid_pos"][m, 0] = as_i32(np.floor((q[:, 0] / self.scale[0]).astype(F))).astype(np.int32)
+                out["grid_pos"][m, 1] = as_i32(np.floor((q[:, 2] / self.scale[1]).astype(F))).astype(np.int32)
+        return out
+
+
+KEYS = ("hit", "t", "world_pos", "grid_pos")
+
+
+def bits(a):
+    """the array's words for a bitwise comparison (-0.0 is not 0.0).  Every NaN becomes ONE pattern first: which sign and payload an
+    invalid operation (inf * 0, inf - inf) or a NaN operand leaves is the hardware's choice -- x86 makes 0xFFC00000 of inf * 0, the
+    device 0x7FC00000 -- and Rust leaves it open too, so the reference has no bits to offer there.  A NaN only ever reaches
+    world_pos: no comparison or cast of the march depends on which NaN it sees."""
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind == "f":
+        a = np.where(np.isnan(a), F(np.nan), a).astype(F)
+    return a.view(np.uint32) if a.dtype.itemsize == 4 else a
+
+
+def first_difference(got, want):
+    """'' when every array of KEYS is equal bit for bit, else the first differing ray as text"""
+    for key in KEYS:
+        g, w = bits(got[key]), bits(want[key])
+        if g.shape != w.shape:
+            return f"{key}: shape {g.shape} against {w.shape}"
+        if not np.array_equal(g, w):
+            bad = np.flatnonzero((g != w).reshape(g.shape[0], -1).any(axis=1))
+            i = int(bad[0])
+            extra = f", reference step {int(want['step'][i])}" if "step" in want else ""
+            return f"{key}: {len(bad)} rays differ; first ray {i}: got {got[key][i]!r}, want {want[key][i]!r}{extra}"
+    return ""
+
+
+# ---- rays and terrains the CPU and the GPU tests share -----------------------------------------------------------------------------
+VERTICAL_STEPS = [0, 1, 2, 3, 63, 64, 65, 127, 128, 255, 256, 1000, 1499]
+
+
+def vertical_rays(steps=VERTICAL_STEPS, extra=F(0.005)):
+    """rays straight down from (0.2, t_k + 0.005, 0.2): over the plane at 0 the first step whose test holds is exactly k"""
+    o = np.array([[0.2, F(TK[k] + extra), 0.2] for k in steps], F)
+    d = np.tile(np.array([0.0, -1.0, 0.0], F), (len(steps), 1))
+    return o, d
+
+
+def fuzz_spec(seed, scale=(1.0, 1.0)):
+    """heights uniform in [-2, 3] on a 13 x 13 grid at (-6, -6), a quarter of the cells zeroed"""
+    rng = np.random.default_rng(500 + seed)
+    s = HeightSpec(scale)
+    for y in range(-6, 7):
+        for x in range(-6, 7):
+            h = rng.uniform(-2.0, 3.0)
+            s.height(x, y, 0.0 if rng.random() < 0.25 else h)
+    return s
+
+
+FUZZ_MAX_DISTANCE = [5.0, 20.0, 60.0, 200.0, 1.0, float("nan")]
+
+
+def fuzz_rays(seed, n=2000):
+    """origins uniform in [-8, 8] x [0.5, 8] x [-8, 8], dirs uniform in [-1, 1]^3; returns (origins, dirs, max_distance)"""
+    rng = np.random.default_rng(900 + seed)
+    o = np.stack([rng.uniform(-8, 8, n), rng.uniform(0.5, 8, n), rng.uniform(-8, 8, n)], axis=1).astype(F)
+    d = rng.uniform(-1, 1, (n, 3)).astype(F)
+    return o, d, FUZZ_MAX_DISTANCE[seed % len(FUZZ_MAX_DISTANCE)]
+
+
+_fuzz_cache = {}
+
+
+def fuzz_case(seed):
+    """(spec, origins, dirs, max_distance, reference answers), computed once per process"""
+    if seed not in _fuzz_cache:
+        spec = fuzz_spec(seed)
+        o, d, md = fuzz_rays(seed)
+        _fuzz_cache[seed] = (spec, o, d, md, spec.hits(o, d, md))
+    return _fuzz_cache[seed]
+
+
+def walls_spec():
+    """two walls of height 5 across x at x = 3 and x = 7 (z in [-2, 2]) on the plane at 0"""
+    s = HeightSpec()
+    for z in range(-2, 3):
+        s.height(3, z, 5.0)
+        s.height(7, z, 5.0)
+    return s

@@ -7,7 +7,7 @@ mkdir -p build/variants build/obj_variant_$name
 C=rusterix_amd/csrc
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -fPIC -Wno-unused-function -Iinclude"
 pids=()
-for f in rxr_api rxr_upload rxr_multi rxr_kernels rxr_project rxr_selftest rxr_jit rxr_intersect rxr_bake rxr_terrain; do
+for f in rxr_api rxr_upload rxr_multi rxr_kernels rxr_project rxr_selftest rxr_jit rxr_intersect rxr_bake rxr_terrain rxr_terrain_hit; do
   /opt/rocm/bin/hipcc $FLAGS "$@" -c -o build/obj_variant_$name/$f.o $C/$f.hip 2>&1 | grep -i "error" -A5 &
   pids+=($!)
 done
