@@ -19,7 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "rxr_ctx.h"
+#include "rxr_query.h"
 
 thread_local LaunchTimes *rxr_launch_times = nullptr;  // rxr_launch.h: the profiling slot of the render this thread is queueing
 extern "C" void rxr_launch_proj_static(const ProjectParams *P, hipStream_t s);
@@ -59,23 +59,12 @@ int rxr_quiesce(rxr_ctx *ctx) {
     if (ctx->last_stream && ctx->last_stream != ctx->stream) HIPCHK(ctx, hipStreamSynchronize(ctx->last_stream));
     if (ctx->copy_stream) HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->isect_pending) {  // an intersect on the caller's stream (rxr_intersect_to) reads the meshes and its scratch
-        HIPCHK(ctx, hipEventSynchronize(ctx->ev_isect));
-        ctx->isect_pending = false;
-    }
-    if (ctx->bake_pending) {  // a bake on the caller's stream (rxr_bake_shaders_to) reads the programs and its job list
-        HIPCHK(ctx, hipEventSynchronize(ctx->ev_bake));
-        ctx->bake_pending = false;
-    }
+    for (QueryLane &q : ctx->lane)  // a device query on the caller's stream (rxr_ctx.h: Q_*) reads resident data and its scratch
+        if (q.pending) {
+            HIPCHK(ctx, hipEventSynchronize(q.ev));
+            q.pending = false;
+        }
     ctx->bake_jobs_used = 0;  // (every queued bake has run: the ring of program lists starts over)
-    if (ctx->terrain_pending) {  // a terrain bake on the caller's stream (rxr_bake_terrain_to) reads the resident terrain
-        HIPCHK(ctx, hipEventSynchronize(ctx->ev_terrain));
-        ctx->terrain_pending = false;
-    }
-    if (ctx->heights_pending) {  // a terrain pick on the caller's stream (rxr_terrain_hits_to) reads the resident heights
-        HIPCHK(ctx, hipEventSynchronize(ctx->ev_heights));
-        ctx->heights_pending = false;
-    }
     return RXR_OK;
 }
 
@@ -189,12 +178,16 @@ void rxr_destroy(rxr_ctx *ctx) {
                       &ctx->d_list2d, &ctx->d_large2d,
                       &ctx->d_list, &ctx->d_large, &ctx->d_counters, &ctx->d_fb,
                       &ctx->d_vm_code, &ctx->d_programs, &ctx->d_patterns, &ctx->d_pattern_data, &ctx->d_palette,
-                      &ctx->d_isect_tris, &ctx->d_isect_misc, &ctx->d_isect_keys, &ctx->d_isect_io,
-                      &ctx->d_bake_io, &ctx->d_bake_jobs, &ctx->d_bake_fault,
-                      &ctx->d_terrain_cells, &ctx->d_terrain_tex, &ctx->d_terrain_texels, &ctx->d_terrain_weights, &ctx->d_terrain_io,
-                      &ctx->d_heights, &ctx->d_heights_tk, &ctx->d_heights_io};
+                      &ctx->d_isect_tris, &ctx->d_isect_misc, &ctx->d_isect_keys,
+                      &ctx->d_bake_jobs, &ctx->d_bake_fault,
+                      &ctx->d_terrain_cells, &ctx->d_terrain_tex, &ctx->d_terrain_texels, &ctx->d_terrain_weights,
+                      &ctx->d_heights, &ctx->d_heights_tk};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
+    for (QueryLane &q : ctx->lane) {
+        if (q.io.p) (void)hipFree(q.io.p);
+        if (q.ev) (void)hipEventDestroy(q.ev);
+    }
     rxr_jit_drop(ctx);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
@@ -205,10 +198,6 @@ void rxr_destroy(rxr_ctx *ctx) {
     if (ctx->ev2) (void)hipEventDestroy(ctx->ev2);
     if (ctx->ev_upload) (void)hipEventDestroy(ctx->ev_upload);
     if (ctx->ev_render) (void)hipEventDestroy(ctx->ev_render);
-    if (ctx->ev_isect) (void)hipEventDestroy(ctx->ev_isect);
-    if (ctx->ev_bake) (void)hipEventDestroy(ctx->ev_bake);
-    if (ctx->ev_terrain) (void)hipEventDestroy(ctx->ev_terrain);
-    if (ctx->ev_heights) (void)hipEventDestroy(ctx->ev_heights);
     if (ctx->h_bake_fault) (void)hipHostFree(ctx->h_bake_fault);
     if (ctx->h_bake_jobs) (void)hipHostFree(ctx->h_bake_jobs);
     for (hipEvent_t ev : ctx->ev_band)
@@ -1846,11 +1835,7 @@ int rxr_check_shaders(const rxr_shader_set *set, uint32_t *code_words, char *mes
     std::string err;
     int rc = set ? flatten_programs(set, code, progs, reads, err) : RXR_ERR_INVALID;
     if (code_words) *code_words = (uint32_t)code.size();
-    if (message && message_capacity) {
-        size_t n = std::min<size_t>(err.size(), message_capacity - 1);
-        memcpy(message, err.data(), n);
-        message[n] = 0;
-    }
+    rxr_copy_message(err, message, message_capacity);
     return rc;
 }
 
@@ -1871,11 +1856,7 @@ int rxr_check_bake(const rxr_shader_set *set, uint32_t program, char *message, u
             err = why;
         }
     }
-    if (message && message_capacity) {
-        size_t n = std::min<size_t>(err.size(), message_capacity - 1);
-        memcpy(message, err.data(), n);
-        message[n] = 0;
-    }
+    rxr_copy_message(err, message, message_capacity);
     return rc;
 }
 

@@ -30,7 +30,7 @@
 #include <string>
 #include <vector>
 
-#include "rxr_ctx.h"
+#include "rxr_query.h"
 #include "rxr_vm.h"
 
 struct BakeArgs {
@@ -94,20 +94,18 @@ extern "C" __global__ __launch_bounds__(RXR_TILE_THREADS) void k_bake_s(BakeArgs
 
 namespace {
 
-int fail(rxr_ctx *ctx, int code, const std::string &msg) { return rxr_fail(ctx, code, msg); }
-
 // the argument checks both entry points share; `who` starts the message
 int bake_check(rxr_ctx *ctx, const char *who, const uint32_t *programs, uint32_t n, uint32_t width, uint32_t height) {
     const std::string w = who;
-    if (n && !programs) return fail(ctx, RXR_ERR_INVALID, w + ": NULL program list");
+    if (n && !programs) return rxr_fail(ctx, RXR_ERR_INVALID, w + ": NULL program list");
     if (!width || !height || width > RXR_BAKE_MAX_DIM || height > RXR_BAKE_MAX_DIM)
-        return fail(ctx, RXR_ERR_INVALID, w + ": width and height must lie in [1, " + std::to_string(RXR_BAKE_MAX_DIM) + "]");
+        return rxr_fail(ctx, RXR_ERR_INVALID, w + ": width and height must lie in [1, " + std::to_string(RXR_BAKE_MAX_DIM) + "]");
     if ((uint64_t)n * width * height > RXR_BAKE_MAX_TEXELS)
-        return fail(ctx, RXR_ERR_INVALID, w + ": more than " + std::to_string(RXR_BAKE_MAX_TEXELS) + " texels in one call");
-    if (n && ctx->programs.empty()) return fail(ctx, RXR_ERR_INVALID, w + ": no shader set is resident (rxr_set_shaders)");
+        return rxr_fail(ctx, RXR_ERR_INVALID, w + ": more than " + std::to_string(RXR_BAKE_MAX_TEXELS) + " texels in one call");
+    if (n && ctx->programs.empty()) return rxr_fail(ctx, RXR_ERR_INVALID, w + ": no shader set is resident (rxr_set_shaders)");
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t p = programs[i];
-        auto refuse = [&](int code, const char *why) { return fail(ctx, code, w + ": programs[" + std::to_string(i) + "] = " + std::to_string(p) + ": " + why); };
+        auto refuse = [&](int code, const char *why) { return rxr_fail(ctx, code, w + ": programs[" + std::to_string(i) + "] = " + std::to_string(p) + ": " + why); };
         if (p >= ctx->programs.size()) return refuse(RXR_ERR_INVALID, "no such program in the resident set");
         if (ctx->programs[p].shade_entry == 0xFFFFFFFFu)
             return refuse(RXR_ERR_INVALID, "the program has no shade function (shade_index -1): Chunk::add_shader bakes nothing for it");
@@ -118,7 +116,6 @@ int bake_check(rxr_ctx *ctx, const char *who, const uint32_t *programs, uint32_t
 
 // the whole bake into device arrays, queued on `s`
 int bake_run(rxr_ctx *ctx, const uint32_t *programs, uint32_t n, uint32_t width, uint32_t height, float *dev_pixels, uint8_t *dev_rgba, hipStream_t s) {
-    if (!ctx->ev_bake) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_bake, hipEventDisableTiming));
     if (!ctx->h_bake_fault) {
         HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_bake_fault, BAKE_FAULT_WORDS * sizeof(uint32_t), hipHostMallocDefault));
         memset(ctx->h_bake_fault, 0, BAKE_FAULT_WORDS * sizeof(uint32_t));
@@ -148,7 +145,7 @@ int bake_run(rxr_ctx *ctx, const uint32_t *programs, uint32_t n, uint32_t width,
     uint32_t *d_jobs = (uint32_t *)ctx->d_bake_jobs.p + ctx->bake_jobs_used;
     ctx->bake_jobs_used += n;
     memcpy(h_jobs, programs, (size_t)n * sizeof(uint32_t));
-    if (ctx->bake_pending) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_bake, 0));  // (a bake on another stream: the fault words' host copy is refreshed in order)
+    if ((rc = rxr_query_begin(ctx, ctx->lane[Q_BAKE], s)) != RXR_OK) return rc;  // (a bake on another stream: the fault words' host copy is refreshed in order)
     HIPCHK(ctx, hipMemcpyAsync(d_jobs, h_jobs, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     BakeArgs A{};
     A.vm_code = (const uint32_t *)ctx->d_vm_code.p;
@@ -172,20 +169,7 @@ int bake_run(rxr_ctx *ctx, const uint32_t *programs, uint32_t n, uint32_t width,
     hipLaunchKernelGGL(ctx->programs_static ? k_bake_s : k_bake, grid, dim3(RXR_TILE_THREADS), 0, s, A);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_bake_fault, ctx->d_bake_fault.p, BAKE_FAULT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipEventRecord(ctx->ev_bake, s));
-    ctx->bake_pending = true;
-    return RXR_OK;
-}
-
-// a range of device memory on the context's device?
-bool on_device(const rxr_ctx *ctx, const void *p, size_t bytes) {
-    hipPointerAttribute_t a0{}, a1{};
-    const hipError_t e0 = hipPointerGetAttributes(&a0, p), e1 = hipPointerGetAttributes(&a1, (const uint8_t *)p + bytes - 1);
-    if (e0 != hipSuccess || e1 != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a0.type == hipMemoryTypeDevice && a1.type == hipMemoryTypeDevice && a0.device == ctx->device && a1.device == ctx->device;
+    return rxr_query_end(ctx, ctx->lane[Q_BAKE], s);
 }
 
 }  // namespace
@@ -211,24 +195,17 @@ extern "C" {
 
 int rxr_bake_shaders(rxr_ctx *ctx, const uint32_t *programs, uint32_t n, uint32_t width, uint32_t height, float *pixels, uint8_t *rgba) {
     if (!ctx) return RXR_ERR_INVALID;
-    if (ctx->group) {
-        rxr_ctx *m0 = rxr_member(ctx, 0);
-        const int rc = rxr_bake_shaders(m0, programs, n, width, height, pixels, rgba);
-        return rc == RXR_OK ? rc : fail(ctx, rc, rxr_last_error(m0));
-    }
+    if (ctx->group) return rxr_as_member0(ctx, [&](rxr_ctx *m) { return rxr_bake_shaders(m, programs, n, width, height, pixels, rgba); });
     int rc = bake_check(ctx, "rxr_bake_shaders", programs, n, width, height);
     if (rc != RXR_OK) return rc;
     if (!n) return RXR_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t texels = (size_t)n * width * height, b_px = pixels ? texels * 16 : 0, b_rgba = rgba ? texels * 4 : 0;
-    if ((rc = rxr_ensure(ctx, ctx->d_bake_io, std::max<size_t>(b_px + b_rgba, 256))) != RXR_OK) return rc;
-    uint8_t *io = (uint8_t *)ctx->d_bake_io.p;
-    hipStream_t s = ctx->stream;
-    if ((rc = bake_run(ctx, programs, n, width, height, b_px ? (float *)io : nullptr, b_rgba ? io + b_px : nullptr, s)) != RXR_OK) return rc;
-    if (b_px) HIPCHK(ctx, hipMemcpyAsync(pixels, io, b_px, hipMemcpyDeviceToHost, s));
-    if (b_rgba) HIPCHK(ctx, hipMemcpyAsync(rgba, io + b_px, b_rgba, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    ctx->bake_pending = false;   // (ev_bake lies behind on this very stream)
+    const size_t texels = (size_t)n * width * height;
+    QueryIO io{ctx, ctx->lane[Q_BAKE]};
+    const unsigned i_px = io.out(pixels, texels * 16), i_rgba = io.out(rgba, texels * 4);
+    if ((rc = io.upload()) != RXR_OK) return rc;
+    if ((rc = bake_run(ctx, programs, n, width, height, io.dev<float>(i_px), io.dev<uint8_t>(i_rgba), ctx->stream)) != RXR_OK) return rc;
+    if ((rc = io.download()) != RXR_OK) return rc;
     if (ctx->h_bake_fault[BAKE_FAULT_CODE]) return rxr_bake_report_fault(ctx);
     return RXR_OK;
 }
@@ -236,16 +213,16 @@ int rxr_bake_shaders(rxr_ctx *ctx, const uint32_t *programs, uint32_t n, uint32_
 int rxr_bake_shaders_to(rxr_ctx *ctx, const uint32_t *programs, uint32_t n, uint32_t width, uint32_t height, float *dev_pixels,
                         uint8_t *dev_rgba, void *hip_stream) {
     if (!ctx) return RXR_ERR_INVALID;
-    if (ctx->group) return fail(ctx, RXR_ERR_UNSUPPORTED, "rxr_bake_shaders_to on a multi-device context: device pointers and streams belong to ONE device (use rxr_member)");
+    if (ctx->group) return rxr_fail(ctx, RXR_ERR_UNSUPPORTED, "rxr_bake_shaders_to on a multi-device context: device pointers and streams belong to ONE device (use rxr_member)");
     int rc = bake_check(ctx, "rxr_bake_shaders_to", programs, n, width, height);
     if (rc != RXR_OK) return rc;
     if (!n || (!dev_pixels && !dev_rgba)) return RXR_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t texels = (size_t)n * width * height;
     if (((uintptr_t)dev_pixels & 15u) || ((uintptr_t)dev_rgba & 3u))
-        return fail(ctx, RXR_ERR_INVALID, "rxr_bake_shaders_to: dev_pixels must be 16-byte aligned and dev_rgba 4-byte aligned");
-    if ((dev_pixels && !on_device(ctx, dev_pixels, texels * 16)) || (dev_rgba && !on_device(ctx, dev_rgba, texels * 4)))
-        return fail(ctx, RXR_ERR_INVALID, "rxr_bake_shaders_to: an output array is not device memory of the context's device (or is too small)");
+        return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_bake_shaders_to: dev_pixels must be 16-byte aligned and dev_rgba 4-byte aligned");
+    if ((dev_pixels && !rxr_on_device(ctx, dev_pixels, texels * 16)) || (dev_rgba && !rxr_on_device(ctx, dev_rgba, texels * 4)))
+        return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_bake_shaders_to: an output array is not device memory of the context's device (or is too small)");
     return bake_run(ctx, programs, n, width, height, dev_pixels, dev_rgba, hip_stream ? (hipStream_t)hip_stream : ctx->stream);
 }
 

@@ -21,6 +21,21 @@ struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
 };
+// One device query's lane (rxr_query.h): its calls run on whichever stream the caller names, ordered among themselves by `ev`
+struct QueryLane {
+    hipEvent_t ev = nullptr;   // recorded behind the last call's launches (on whichever stream they ran)
+    bool pending = false;      // ... and not yet waited for (rxr_quiesce)
+    DevBuf io;                 // the blocking form's device copies of the caller's host arrays (QueryIO)
+};
+// The lanes of rxr_ctx::lane.  rxr_quiesce waits for every one -- a call queued on the caller's stream may still be reading what
+// the lane's comment names -- and rxr_destroy releases every one
+enum : uint32_t {
+    Q_ISECT,     // rxr_intersect_to: the meshes and its scratch
+    Q_BAKE,      // rxr_bake_shaders_to: the programs and its job list
+    Q_TERRAIN,   // rxr_bake_terrain_to: the resident terrain
+    Q_HEIGHTS,   // rxr_terrain_hits_to: the resident heights
+    Q_LANES
+};
 #define RXR_MAX_TILE_ROWS 2048u   // frames of at most 32768 rows
 
 struct TileRange {
@@ -216,56 +231,47 @@ struct rxr_ctx {
     uint32_t n_patterns = 0, n_normal_patterns = 0, n_palette = 0;
     bool frame_uses_programs = false;
 
+    QueryLane lane[Q_LANES];         // the four device queries below: stream ordering and staging (rxr_query.h)
+
     // ray picking (rxr_intersect.hip): buffers of its own -- an intersect never touches the frame state (has_frame, the bins, the
     // counters).  d_isect_tris: (p0, edge1, edge2) per registered triangle; d_isect_misc: the segments and per-mesh profile ids
     // (isect_host: their host copy, kept alive for the asynchronous upload); d_isect_keys: per ray and segment the (t, triangle)
-    // minimum; d_isect_io: rxr_intersect's device copies of the caller's host arrays.
-    DevBuf d_isect_tris, d_isect_misc, d_isect_keys, d_isect_io;
+    // minimum.
+    DevBuf d_isect_tris, d_isect_misc, d_isect_keys;
     std::vector<uint32_t> isect_host;
     bool meshes_valid = true;        // false while / after an rxr_set_meshes that did not complete
     bool isect_ready = false;        // d_isect_tris / d_isect_misc describe the current meshes (rxr_set_meshes clears it)
     uint32_t isect_nseg = 0, isect_stride = 0;
     size_t isect_off_pid = 0;        // words into d_isect_misc
-    hipEvent_t ev_isect = nullptr;   // recorded behind the last intersect's launches (on whichever stream they ran)
-    bool isect_pending = false;      // ... and not yet waited for (rxr_quiesce)
 
     // shader-texture bakes (rxr_bake.hip): buffers of their own, like the intersect's -- a bake touches neither the frame state nor the
     // compiled programs.  d_bake_jobs: the program index per bake of the launches in flight (a ring of bake_jobs_cap words, filled
-    // through its page-locked twin h_bake_jobs); d_bake_io: rxr_bake_shaders' device copies of the caller's host arrays;
-    // d_bake_fault: BAKE_FAULT_WORDS words, sticky (the first faulting texel wins) until the host has reported them; h_bake_fault:
-    // their pinned host copy, refreshed behind every bake.
-    DevBuf d_bake_io, d_bake_jobs, d_bake_fault;
+    // through its page-locked twin h_bake_jobs); d_bake_fault: BAKE_FAULT_WORDS words, sticky (the first faulting texel wins) until
+    // the host has reported them; h_bake_fault: their pinned host copy, refreshed behind every bake.
+    DevBuf d_bake_jobs, d_bake_fault;
     uint32_t *h_bake_fault = nullptr, *h_bake_jobs = nullptr;
     size_t bake_jobs_cap = 0;        // words
     size_t bake_jobs_used = 0;       // ... of which launches since the last rxr_quiesce may still read this many
-    hipEvent_t ev_bake = nullptr;    // recorded behind the last bake's launches (on whichever stream they ran)
-    bool bake_pending = false;       // ... and not yet waited for (rxr_quiesce)
 
     // terrain chunk textures (rxr_terrain.hip): the resident terrain of rxr_set_terrain and the bake's buffers, all its own.
     // d_terrain_cells: the dense grid (TerrainCell per cell of the bounding rectangle); d_terrain_tex / _texels: the source textures'
-    // records and packed texels; d_terrain_weights: 256 table offsets by radius, then one tap-weight table per radius in use;
-    // d_terrain_io: rxr_bake_terrain's device copy of the caller's host array.  terrain_blend: the grid's blend words on the host
-    // (the work estimate that splits a call into launches reads them).
-    DevBuf d_terrain_cells, d_terrain_tex, d_terrain_texels, d_terrain_weights, d_terrain_io;
+    // records and packed texels; d_terrain_weights: 256 table offsets by radius, then one tap-weight table per radius in use.
+    // terrain_blend: the grid's blend words on the host (the work estimate that splits a call into launches reads them).
+    DevBuf d_terrain_cells, d_terrain_tex, d_terrain_texels, d_terrain_weights;
     std::vector<uint32_t> terrain_blend;
     bool terrain_set = false;
     float terrain_scale[2] = {1.0f, 1.0f};
     int32_t terrain_chunk_size = 0, terrain_x0 = 0, terrain_y0 = 0;
     uint32_t terrain_gw = 0, terrain_gh = 0, terrain_max_steps = 0;
-    hipEvent_t ev_terrain = nullptr;  // recorded behind the last terrain bake's launches (on whichever stream they ran)
-    bool terrain_pending = false;     // ... and not yet waited for (rxr_quiesce)
     uint32_t terrain_launches = 0;    // k_terrain_bake launches of the last bake call (rxr_debug_terrain_launches)
 
     // terrain picks (rxr_terrain_hit.hip): the resident heights of rxr_set_terrain_heights, independent of the resident terrain above.
-    // d_heights: the dense f32 grid over the cells' bounding rectangle; d_heights_tk: the 1500 values t_k of the march; d_heights_io:
-    // rxr_terrain_hits' device copies of the caller's host arrays.
-    DevBuf d_heights, d_heights_tk, d_heights_io;
+    // d_heights: the dense f32 grid over the cells' bounding rectangle; d_heights_tk: the 1500 values t_k of the march.
+    DevBuf d_heights, d_heights_tk;
     bool heights_set = false;
     float heights_scale[2] = {1.0f, 1.0f};
     int32_t heights_x0 = 0, heights_y0 = 0;
     uint32_t heights_gw = 0, heights_gh = 0;
-    hipEvent_t ev_heights = nullptr;  // recorded behind the last hit call's launches (on whichever stream they ran)
-    bool heights_pending = false;     // ... and not yet waited for (rxr_quiesce)
     uint32_t heights_launches = 0;    // march launches of the last hit call (rxr_debug_terrain_hit_kernel)
     const char *heights_kernel = "";  // ... and their kernel's symbol name; a static string
 

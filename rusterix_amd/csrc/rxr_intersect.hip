@@ -39,7 +39,7 @@
 #include <vector>
 
 #include "../../include/rusterix_vek.hpp"  // (RXR_VEK_FUSED_MATVEC: the screen rays' Mat4 * Vec4 follows the host's choice)
-#include "rxr_ctx.h"
+#include "rxr_query.h"
 
 namespace {
 
@@ -335,8 +335,6 @@ __global__ __launch_bounds__(ISECT_WG) void k_screen_rays(ScreenRayArgs S) {
     S.dirs[3 * i] = d.x, S.dirs[3 * i + 1] = d.y, S.dirs[3 * i + 2] = d.z;
 }
 
-int fail(rxr_ctx *ctx, int code, const std::string &msg) { return rxr_fail(ctx, code, msg); }
-
 // the segments and per-triangle records of the current meshes (once per rxr_set_meshes), queued on `s`
 int isect_prepare(rxr_ctx *ctx, hipStream_t s) {
     if (ctx->isect_ready) return RXR_OK;
@@ -390,11 +388,9 @@ int isect_prepare(rxr_ctx *ctx, hipStream_t s) {
 
 // the whole intersect on device arrays, queued on `s`
 int isect_run(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n, uint32_t flags, const IsectOut &out, hipStream_t s) {
-    if (!ctx->meshes_valid) return fail(ctx, RXR_ERR_INVALID, "rxr_intersect: the last rxr_set_meshes failed: no meshes are registered");
-    if (!ctx->ev_isect) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_isect, hipEventDisableTiming));
-    if (ctx->isect_pending) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_isect, 0));  // (the scratch of an intersect on another stream)
-    int rc = isect_prepare(ctx, s);
-    if (rc != RXR_OK) return rc;
+    if (!ctx->meshes_valid) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_intersect: the last rxr_set_meshes failed: no meshes are registered");
+    int rc = rxr_query_begin(ctx, ctx->lane[Q_ISECT], s);  // (the scratch of an intersect on another stream)
+    if (rc != RXR_OK || (rc = isect_prepare(ctx, s)) != RXR_OK) return rc;
     const uint32_t ntri = ctx->PP.n_tris_in, nseg = ctx->isect_nseg;
     uint32_t per_batch = n;
     if (nseg && (uint64_t)n * nseg > ISECT_KEYS_MAX)
@@ -439,9 +435,7 @@ int isect_run(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n,
         hipLaunchKernelGGL(k_isect_fold, dim3((nr + ISECT_WG - 1) / ISECT_WG), dim3(ISECT_WG), 0, s, A, r0, nr, O);
         HIPCHK(ctx, hipGetLastError());
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev_isect, s));
-    ctx->isect_pending = true;
-    return RXR_OK;
+    return rxr_query_end(ctx, ctx->lane[Q_ISECT], s);
 }
 
 }  // namespace
@@ -451,53 +445,37 @@ extern "C" {
 int rxr_intersect(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n_rays, uint32_t flags, float *t, uint32_t *mesh,
                   uint32_t *triangle, float *hitpoint, float *uv, float *normal) {
     if (!ctx) return RXR_ERR_INVALID;
-    if (!origins || !dirs || !t || !mesh || !triangle) return fail(ctx, RXR_ERR_INVALID, "rxr_intersect: NULL ray or output array");
-    if (flags & ~RXR_INTERSECT_FULL) return fail(ctx, RXR_ERR_INVALID, "rxr_intersect: unknown flags");
-    if (ctx->group) {
-        rxr_ctx *m0 = rxr_member(ctx, 0);
-        const int rc = rxr_intersect(m0, origins, dirs, n_rays, flags, t, mesh, triangle, hitpoint, uv, normal);
-        return rc == RXR_OK ? rc : fail(ctx, rc, rxr_last_error(m0));
-    }
+    if (!origins || !dirs || !t || !mesh || !triangle) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_intersect: NULL ray or output array");
+    if (flags & ~RXR_INTERSECT_FULL) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_intersect: unknown flags");
+    if (ctx->group) return rxr_as_member0(ctx, [&](rxr_ctx *m) { return rxr_intersect(m, origins, dirs, n_rays, flags, t, mesh, triangle, hitpoint, uv, normal); });
     if (!n_rays) return RXR_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const bool full = (flags & RXR_INTERSECT_FULL) != 0;
-    // device copies: rays in, then t, mesh, triangle, hitpoint, uv, normal
     const size_t n = n_rays;
-    const size_t b_rays = n * 12, b_t = n * 4, b_hp = hitpoint ? n * 12 : 0, b_uv = full && uv ? n * 8 : 0, b_nrm = full && normal ? n * 12 : 0;
-    const size_t off_d = b_rays, off_t = 2 * b_rays, off_m = off_t + b_t, off_tri = off_m + b_t, off_hp = off_tri + b_t;
-    const size_t off_uv = off_hp + b_hp, off_nrm = off_uv + b_uv, total = off_nrm + b_nrm;
-    int rc = rxr_ensure(ctx, ctx->d_isect_io, total);
+    QueryIO io{ctx, ctx->lane[Q_ISECT]};
+    const unsigned i_o = io.in(origins, n * 12), i_d = io.in(dirs, n * 12);
+    const unsigned i_t = io.out(t, n * 4), i_m = io.out(mesh, n * 4), i_tri = io.out(triangle, n * 4), i_hp = io.out(hitpoint, n * 12);
+    const unsigned i_uv = io.out(full ? uv : nullptr, n * 8), i_nrm = io.out(full ? normal : nullptr, n * 12);
+    int rc = io.upload();
     if (rc != RXR_OK) return rc;
-    uint8_t *io = (uint8_t *)ctx->d_isect_io.p;
-    hipStream_t s = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(io, origins, b_rays, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(io + off_d, dirs, b_rays, hipMemcpyHostToDevice, s));
     IsectOut O{};
-    O.t = (float *)(io + off_t);
-    O.mesh = (uint32_t *)(io + off_m);
-    O.tri = (uint32_t *)(io + off_tri);
-    O.hitpoint = b_hp ? (float *)(io + off_hp) : nullptr;
-    O.uv = b_uv ? (float *)(io + off_uv) : nullptr;
-    O.normal = b_nrm ? (float *)(io + off_nrm) : nullptr;
-    if ((rc = isect_run(ctx, (const float *)io, (const float *)(io + off_d), n_rays, flags, O, s)) != RXR_OK) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(t, O.t, b_t, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(mesh, O.mesh, b_t, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipMemcpyAsync(triangle, O.tri, b_t, hipMemcpyDeviceToHost, s));
-    if (b_hp) HIPCHK(ctx, hipMemcpyAsync(hitpoint, O.hitpoint, b_hp, hipMemcpyDeviceToHost, s));
-    if (b_uv) HIPCHK(ctx, hipMemcpyAsync(uv, O.uv, b_uv, hipMemcpyDeviceToHost, s));
-    if (b_nrm) HIPCHK(ctx, hipMemcpyAsync(normal, O.normal, b_nrm, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    ctx->isect_pending = false;
-    return RXR_OK;
+    O.t = io.dev<float>(i_t);
+    O.mesh = io.dev<uint32_t>(i_m);
+    O.tri = io.dev<uint32_t>(i_tri);
+    O.hitpoint = io.dev<float>(i_hp);
+    O.uv = io.dev<float>(i_uv);
+    O.normal = io.dev<float>(i_nrm);
+    if ((rc = isect_run(ctx, io.dev<float>(i_o), io.dev<float>(i_d), n_rays, flags, O, ctx->stream)) != RXR_OK) return rc;
+    return io.download();
 }
 
 int rxr_intersect_to(rxr_ctx *ctx, const float *dev_origins, const float *dev_dirs, uint32_t n_rays, uint32_t flags, float *dev_t,
                      uint32_t *dev_mesh, uint32_t *dev_triangle, float *dev_hitpoint, float *dev_uv, float *dev_normal, void *hip_stream) {
     if (!ctx) return RXR_ERR_INVALID;
     if (!dev_origins || !dev_dirs || !dev_t || !dev_mesh || !dev_triangle)
-        return fail(ctx, RXR_ERR_INVALID, "rxr_intersect_to: NULL ray or output array");
-    if (flags & ~RXR_INTERSECT_FULL) return fail(ctx, RXR_ERR_INVALID, "rxr_intersect_to: unknown flags");
-    if (ctx->group) return fail(ctx, RXR_ERR_UNSUPPORTED, "rxr_intersect_to on a multi-device context: device pointers and streams belong to ONE device (use rxr_member)");
+        return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_intersect_to: NULL ray or output array");
+    if (flags & ~RXR_INTERSECT_FULL) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_intersect_to: unknown flags");
+    if (ctx->group) return rxr_fail(ctx, RXR_ERR_UNSUPPORTED, "rxr_intersect_to on a multi-device context: device pointers and streams belong to ONE device (use rxr_member)");
     if (!n_rays) return RXR_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     IsectOut O{};
@@ -514,12 +492,12 @@ int rxr_screen_rays_to(rxr_ctx *ctx, const float *inverse_view, const float *inv
                        uint32_t y0, uint32_t w, uint32_t h, float *dev_origins, float *dev_dirs, void *hip_stream) {
     if (!ctx) return RXR_ERR_INVALID;
     if (!inverse_view || !inverse_projection || !dev_origins || !dev_dirs)
-        return fail(ctx, RXR_ERR_INVALID, "rxr_screen_rays_to: NULL matrix or output array");
-    if (ctx->group) return fail(ctx, RXR_ERR_UNSUPPORTED, "rxr_screen_rays_to on a multi-device context: device pointers and streams belong to ONE device (use rxr_member)");
+        return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_screen_rays_to: NULL matrix or output array");
+    if (ctx->group) return rxr_fail(ctx, RXR_ERR_UNSUPPORTED, "rxr_screen_rays_to on a multi-device context: device pointers and streams belong to ONE device (use rxr_member)");
     const uint64_t n = (uint64_t)w * h;
     if (!n) return RXR_OK;
     if ((uint64_t)x0 + w > (1u << 24) || (uint64_t)y0 + h > (1u << 24))
-        return fail(ctx, RXR_ERR_INVALID, "rxr_screen_rays_to: pixel coordinates beyond 2^24 are not exact in f32");
+        return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_screen_rays_to: pixel coordinates beyond 2^24 are not exact in f32");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ScreenRayArgs S{};
     memcpy(S.iv, inverse_view, 64);

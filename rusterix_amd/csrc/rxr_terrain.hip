@@ -41,7 +41,7 @@
 #include <string>
 #include <vector>
 
-#include "rxr_ctx.h"
+#include "rxr_query.h"
 #include "rxr_exact_math.h"
 
 #define TERRAIN_BLOCK 8u            // a wave's texel block is TERRAIN_BLOCK x TERRAIN_BLOCK
@@ -266,8 +266,6 @@ extern "C" __global__ __launch_bounds__(64) void k_terrain_bake(TerrainArgs A) {
 
 namespace {
 
-int fail(rxr_ctx *ctx, int code, const std::string &msg) { return rxr_fail(ctx, code, msg); }
-
 struct TerrainShape {
     int32_t x0 = 0, y0 = 0;
     uint32_t gw = 0, gh = 0, max_steps = 0;
@@ -330,39 +328,27 @@ int check_terrain(const float *scale, int32_t chunk_size, const int32_t *cell_xy
     return RXR_OK;
 }
 
-// a range of device memory on the context's device?
-bool on_device(const rxr_ctx *ctx, const void *p, size_t bytes) {
-    hipPointerAttribute_t a0{}, a1{};
-    const hipError_t e0 = hipPointerGetAttributes(&a0, p), e1 = hipPointerGetAttributes(&a1, (const uint8_t *)p + bytes - 1);
-    if (e0 != hipSuccess || e1 != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a0.type == hipMemoryTypeDevice && a1.type == hipMemoryTypeDevice && a0.device == ctx->device && a1.device == ctx->device;
-}
-
 // the argument checks both bake entry points share; `who` starts the message
 int bake_check(rxr_ctx *ctx, const char *who, const int32_t *coords, uint32_t n, int32_t ppt) {
     const std::string w = who;
-    if (!ctx->terrain_set) return fail(ctx, RXR_ERR_INVALID, w + ": no terrain is resident (rxr_set_terrain)");
-    if (n && !coords) return fail(ctx, RXR_ERR_INVALID, w + ": NULL chunk_coords");
-    if (ppt < 1) return fail(ctx, RXR_ERR_INVALID, w + ": pixels_per_tile must be at least 1");
+    if (!ctx->terrain_set) return rxr_fail(ctx, RXR_ERR_INVALID, w + ": no terrain is resident (rxr_set_terrain)");
+    if (n && !coords) return rxr_fail(ctx, RXR_ERR_INVALID, w + ": NULL chunk_coords");
+    if (ppt < 1) return rxr_fail(ctx, RXR_ERR_INVALID, w + ": pixels_per_tile must be at least 1");
     const uint64_t side = (uint64_t)ctx->terrain_chunk_size * (uint64_t)ppt;
-    if (side > RXR_BAKE_MAX_DIM) return fail(ctx, RXR_ERR_INVALID, w + ": chunk_size * pixels_per_tile = " + std::to_string(side) + " exceeds RXR_BAKE_MAX_DIM");
-    if ((uint64_t)n * side * side > RXR_BAKE_MAX_TEXELS) return fail(ctx, RXR_ERR_INVALID, w + ": more than " + std::to_string(RXR_BAKE_MAX_TEXELS) + " texels in one call");
+    if (side > RXR_BAKE_MAX_DIM) return rxr_fail(ctx, RXR_ERR_INVALID, w + ": chunk_size * pixels_per_tile = " + std::to_string(side) + " exceeds RXR_BAKE_MAX_DIM");
+    if ((uint64_t)n * side * side > RXR_BAKE_MAX_TEXELS) return rxr_fail(ctx, RXR_ERR_INVALID, w + ": more than " + std::to_string(RXR_BAKE_MAX_TEXELS) + " texels in one call");
     for (uint32_t i = 0; i < n; ++i)
         for (int a = 0; a < 2; ++a) {
             const int64_t m = (int64_t)coords[2 * i + a] * ctx->terrain_chunk_size;
             // (+ chunk_size stays inside i32 too: the host's per-cell lookups below add cell indices to it)
             if (m < INT32_MIN || m + ctx->terrain_chunk_size > INT32_MAX)
-                return fail(ctx, RXR_ERR_INVALID, w + ": chunk_coords[" + std::to_string(i) + "] * chunk_size leaves i32 (the reference overflows)");
+                return rxr_fail(ctx, RXR_ERR_INVALID, w + ": chunk_coords[" + std::to_string(i) + "] * chunk_size leaves i32 (the reference overflows)");
         }
     return RXR_OK;
 }
 
 // the whole bake into device memory, queued on `s`
 int bake_run(rxr_ctx *ctx, const int32_t *coords, uint32_t n, int32_t ppt, uint8_t *dev_rgba, hipStream_t s) {
-    if (!ctx->ev_terrain) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_terrain, hipEventDisableTiming));
     uint64_t bound = TERRAIN_DEFAULT_LAUNCH_TAPS;
     if (const char *e = getenv("RXR_TERRAIN_LAUNCH_TAPS")) {
         const unsigned long long v = strtoull(e, nullptr, 10);
@@ -402,7 +388,8 @@ int bake_run(rxr_ctx *ctx, const int32_t *coords, uint32_t n, int32_t ppt, uint8
         const uint64_t nn = 2ull * (uint64_t)steps_of(ctx->terrain_scale, (b >> 8) & 255u) + 1ull;
         return nn * nn;
     };
-    if (ctx->terrain_pending) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_terrain, 0));
+    const int rc = rxr_query_begin(ctx, ctx->lane[Q_TERRAIN], s);
+    if (rc != RXR_OK) return rc;
     ctx->terrain_launches = 0;
     for (uint32_t c0 = 0; c0 < n; c0 += TERRAIN_LAUNCH_CHUNKS) {
         const uint32_t nc = std::min(n - c0, TERRAIN_LAUNCH_CHUNKS);
@@ -432,9 +419,7 @@ int bake_run(rxr_ctx *ctx, const int32_t *coords, uint32_t n, int32_t ppt, uint8
             ++ctx->terrain_launches;
         }
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev_terrain, s));
-    ctx->terrain_pending = true;
-    return RXR_OK;
+    return rxr_query_end(ctx, ctx->lane[Q_TERRAIN], s);
 }
 
 }  // namespace
@@ -447,26 +432,19 @@ int rxr_check_terrain(const float scale[2], int32_t chunk_size, const int32_t *c
     TerrainShape shape;
     std::string err;
     const int rc = check_terrain(scale, chunk_size, cell_xy, cell_texture, cell_blend, cell_offset, n_cells, textures, n_textures, shape, err);
-    if (message && message_capacity) {
-        const size_t n = std::min<size_t>(err.size(), message_capacity - 1);
-        memcpy(message, err.data(), n);
-        message[n] = 0;
-    }
+    rxr_copy_message(err, message, message_capacity);
     return rc;
 }
 
 int rxr_set_terrain(rxr_ctx *ctx, const float scale[2], int32_t chunk_size, const int32_t *cell_xy, const int32_t *cell_texture,
                     const uint32_t *cell_blend, const float *cell_offset, uint32_t n_cells, const rxr_texture *textures, uint32_t n_textures) {
     if (!ctx) return RXR_ERR_INVALID;
-    if (ctx->group) {
-        rxr_ctx *m0 = rxr_member(ctx, 0);
-        const int rc = rxr_set_terrain(m0, scale, chunk_size, cell_xy, cell_texture, cell_blend, cell_offset, n_cells, textures, n_textures);
-        return rc == RXR_OK ? rc : fail(ctx, rc, rxr_last_error(m0));
-    }
+    if (ctx->group)
+        return rxr_as_member0(ctx, [&](rxr_ctx *m) { return rxr_set_terrain(m, scale, chunk_size, cell_xy, cell_texture, cell_blend, cell_offset, n_cells, textures, n_textures); });
     TerrainShape shape;
     std::string err;
     int rc = check_terrain(scale, chunk_size, cell_xy, cell_texture, cell_blend, cell_offset, n_cells, textures, n_textures, shape, err);
-    if (rc != RXR_OK) return fail(ctx, rc, "rxr_set_terrain: " + err);
+    if (rc != RXR_OK) return rxr_fail(ctx, rc, "rxr_set_terrain: " + err);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if ((rc = rxr_quiesce(ctx)) != RXR_OK) return rc;   // queued bakes read what is replaced here
     ctx->terrain_set = false;
@@ -491,7 +469,7 @@ int rxr_set_terrain(rxr_ctx *ctx, const float scale[2], int32_t chunk_size, cons
     std::vector<TerrainTex> tex(n_textures);
     size_t n_texels = 0;
     for (uint32_t t = 0; t < n_textures; ++t) {
-        if (n_texels + (size_t)textures[t].width * textures[t].height > 0xFFFFFFFFull) return fail(ctx, RXR_ERR_INVALID, "rxr_set_terrain: more than 2^32 source texels");
+        if (n_texels + (size_t)textures[t].width * textures[t].height > 0xFFFFFFFFull) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_set_terrain: more than 2^32 source texels");
         tex[t] = TerrainTex{(uint32_t)n_texels, textures[t].width, textures[t].height, (float)textures[t].width - 1.0f, (float)textures[t].height - 1.0f, {0, 0, 0}};
         n_texels += (size_t)textures[t].width * textures[t].height;
     }
@@ -538,36 +516,30 @@ int rxr_set_terrain(rxr_ctx *ctx, const float scale[2], int32_t chunk_size, cons
 
 int rxr_bake_terrain(rxr_ctx *ctx, const int32_t *chunk_coords, uint32_t n, int32_t pixels_per_tile, uint8_t *rgba) {
     if (!ctx) return RXR_ERR_INVALID;
-    if (ctx->group) {
-        rxr_ctx *m0 = rxr_member(ctx, 0);
-        const int rc = rxr_bake_terrain(m0, chunk_coords, n, pixels_per_tile, rgba);
-        return rc == RXR_OK ? rc : fail(ctx, rc, rxr_last_error(m0));
-    }
+    if (ctx->group) return rxr_as_member0(ctx, [&](rxr_ctx *m) { return rxr_bake_terrain(m, chunk_coords, n, pixels_per_tile, rgba); });
     int rc = bake_check(ctx, "rxr_bake_terrain", chunk_coords, n, pixels_per_tile);
     if (rc != RXR_OK) return rc;
     if (!n) return RXR_OK;
-    if (!rgba) return fail(ctx, RXR_ERR_INVALID, "rxr_bake_terrain: NULL rgba");
+    if (!rgba) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_bake_terrain: NULL rgba");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t side = (size_t)ctx->terrain_chunk_size * (size_t)pixels_per_tile, bytes = (size_t)n * side * side * 4;
-    if ((rc = rxr_ensure(ctx, ctx->d_terrain_io, std::max<size_t>(bytes, 256))) != RXR_OK) return rc;
-    hipStream_t s = ctx->stream;
-    if ((rc = bake_run(ctx, chunk_coords, n, pixels_per_tile, (uint8_t *)ctx->d_terrain_io.p, s)) != RXR_OK) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(rgba, ctx->d_terrain_io.p, bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    ctx->terrain_pending = false;   // (ev_terrain lies behind on this very stream)
-    return RXR_OK;
+    const size_t side = (size_t)ctx->terrain_chunk_size * (size_t)pixels_per_tile;
+    QueryIO io{ctx, ctx->lane[Q_TERRAIN]};
+    const unsigned i_rgba = io.out(rgba, (size_t)n * side * side * 4);
+    if ((rc = io.upload()) != RXR_OK) return rc;
+    if ((rc = bake_run(ctx, chunk_coords, n, pixels_per_tile, io.dev<uint8_t>(i_rgba), ctx->stream)) != RXR_OK) return rc;
+    return io.download();
 }
 
 int rxr_bake_terrain_to(rxr_ctx *ctx, const int32_t *chunk_coords, uint32_t n, int32_t pixels_per_tile, uint8_t *dev_rgba, void *hip_stream) {
     if (!ctx) return RXR_ERR_INVALID;
-    if (ctx->group) return fail(ctx, RXR_ERR_UNSUPPORTED, "rxr_bake_terrain_to on a multi-device context: device pointers and streams belong to ONE device (use rxr_member)");
+    if (ctx->group) return rxr_fail(ctx, RXR_ERR_UNSUPPORTED, "rxr_bake_terrain_to on a multi-device context: device pointers and streams belong to ONE device (use rxr_member)");
     int rc = bake_check(ctx, "rxr_bake_terrain_to", chunk_coords, n, pixels_per_tile);
     if (rc != RXR_OK) return rc;
     if (!n) return RXR_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t side = (size_t)ctx->terrain_chunk_size * (size_t)pixels_per_tile, bytes = (size_t)n * side * side * 4;
-    if (!dev_rgba || ((uintptr_t)dev_rgba & 3u)) return fail(ctx, RXR_ERR_INVALID, "rxr_bake_terrain_to: dev_rgba must be 4-byte aligned device memory");
-    if (!on_device(ctx, dev_rgba, bytes)) return fail(ctx, RXR_ERR_INVALID, "rxr_bake_terrain_to: dev_rgba is not device memory of the context's device (or is too small)");
+    if (!dev_rgba || ((uintptr_t)dev_rgba & 3u)) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_bake_terrain_to: dev_rgba must be 4-byte aligned device memory");
+    if (!rxr_on_device(ctx, dev_rgba, bytes)) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_bake_terrain_to: dev_rgba is not device memory of the context's device (or is too small)");
     return bake_run(ctx, chunk_coords, n, pixels_per_tile, dev_rgba, hip_stream ? (hipStream_t)hip_stream : ctx->stream);
 }
 

@@ -32,7 +32,7 @@
 #include <string>
 #include <vector>
 
-#include "rxr_ctx.h"
+#include "rxr_query.h"
 #include "rxr_exact_math.h"
 
 #define HIT_WG 256u       // k_terrain_hit_lane's workgroup
@@ -197,8 +197,6 @@ extern "C" __global__ __launch_bounds__(64) void k_terrain_hit_wave(HitArgs A) {
 
 namespace {
 
-int fail(rxr_ctx *ctx, int code, const std::string &msg) { return rxr_fail(ctx, code, msg); }
-
 // t_k by the reference's additions
 const float *march_table() {
     static const std::vector<float> table = [] {
@@ -256,21 +254,9 @@ int check_heights(const float *scale, const int32_t *cell_xy, const float *cell_
     return RXR_OK;
 }
 
-// a range of device memory on the context's device?
-bool on_device(const rxr_ctx *ctx, const void *p, size_t bytes) {
-    hipPointerAttribute_t a0{}, a1{};
-    const hipError_t e0 = hipPointerGetAttributes(&a0, p), e1 = hipPointerGetAttributes(&a1, (const uint8_t *)p + bytes - 1);
-    if (e0 != hipSuccess || e1 != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a0.type == hipMemoryTypeDevice && a1.type == hipMemoryTypeDevice && a0.device == ctx->device && a1.device == ctx->device;
-}
-
 // every ray of a call on device arrays, queued on `s`
 int hits_run(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n, float max_distance, uint32_t *hit, float *t, float *world_pos,
              int32_t *grid_pos, hipStream_t s) {
-    if (!ctx->ev_heights) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_heights, hipEventDisableTiming));
     uint32_t bound = TERRAIN_HIT_DEFAULT_LAUNCH_RAYS;
     if (const char *e = getenv("RXR_TERRAIN_HIT_LAUNCH_RAYS")) {
         const unsigned long long v = strtoull(e, nullptr, 10);
@@ -280,7 +266,7 @@ int hits_run(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n, 
     if (const char *e = getenv("RXR_TERRAIN_HIT_ROUTE")) {
         if (!strcmp(e, "lane")) wave = false;
         else if (!strcmp(e, "wave")) wave = true;
-        else if (e[0]) return fail(ctx, RXR_ERR_INVALID, std::string("RXR_TERRAIN_HIT_ROUTE must be lane or wave, not ") + e);
+        else if (e[0]) return rxr_fail(ctx, RXR_ERR_INVALID, std::string("RXR_TERRAIN_HIT_ROUTE must be lane or wave, not ") + e);
     }
     HitArgs A{};
     A.heights = (const float *)ctx->d_heights.p;
@@ -298,7 +284,8 @@ int hits_run(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n, 
     A.t = t;
     A.world_pos = world_pos;
     A.grid_pos = grid_pos;
-    if (ctx->heights_pending) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_heights, 0));
+    const int rc = rxr_query_begin(ctx, ctx->lane[Q_HEIGHTS], s);
+    if (rc != RXR_OK) return rc;
     ctx->heights_launches = 0;
     ctx->heights_kernel = wave ? "k_terrain_hit_wave" : "k_terrain_hit_lane";
     for (uint32_t first = 0; first < n;) {
@@ -312,9 +299,7 @@ int hits_run(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n, 
         ++ctx->heights_launches;
         first += count;
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev_heights, s));
-    ctx->heights_pending = true;
-    return RXR_OK;
+    return rxr_query_end(ctx, ctx->lane[Q_HEIGHTS], s);
 }
 
 }  // namespace
@@ -326,25 +311,17 @@ int rxr_check_terrain_heights(const float scale[2], const int32_t *cell_xy, cons
     HeightShape shape;
     std::string err;
     const int rc = check_heights(scale, cell_xy, cell_height, n_cells, shape, err);
-    if (message && message_capacity) {
-        const size_t n = std::min<size_t>(err.size(), message_capacity - 1);
-        memcpy(message, err.data(), n);
-        message[n] = 0;
-    }
+    rxr_copy_message(err, message, message_capacity);
     return rc;
 }
 
 int rxr_set_terrain_heights(rxr_ctx *ctx, const float scale[2], const int32_t *cell_xy, const float *cell_height, uint32_t n_cells) {
     if (!ctx) return RXR_ERR_INVALID;
-    if (ctx->group) {
-        rxr_ctx *m0 = rxr_member(ctx, 0);
-        const int rc = rxr_set_terrain_heights(m0, scale, cell_xy, cell_height, n_cells);
-        return rc == RXR_OK ? rc : fail(ctx, rc, rxr_last_error(m0));
-    }
+    if (ctx->group) return rxr_as_member0(ctx, [&](rxr_ctx *m) { return rxr_set_terrain_heights(m, scale, cell_xy, cell_height, n_cells); });
     HeightShape shape;
     std::string err;
     int rc = check_heights(scale, cell_xy, cell_height, n_cells, shape, err);
-    if (rc != RXR_OK) return fail(ctx, rc, "rxr_set_terrain_heights: " + err);
+    if (rc != RXR_OK) return rxr_fail(ctx, rc, "rxr_set_terrain_heights: " + err);
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if ((rc = rxr_quiesce(ctx)) != RXR_OK) return rc;   // queued hit calls read what is replaced here
     ctx->heights_set = false;
@@ -373,44 +350,30 @@ int rxr_set_terrain_heights(rxr_ctx *ctx, const float scale[2], const int32_t *c
 int rxr_terrain_hits(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n_rays, float max_distance, uint32_t *hit, float *t,
                      float *world_pos, int32_t *grid_pos) {
     if (!ctx) return RXR_ERR_INVALID;
-    if (ctx->group) {
-        rxr_ctx *m0 = rxr_member(ctx, 0);
-        const int rc = rxr_terrain_hits(m0, origins, dirs, n_rays, max_distance, hit, t, world_pos, grid_pos);
-        return rc == RXR_OK ? rc : fail(ctx, rc, rxr_last_error(m0));
-    }
-    if (!ctx->heights_set) return fail(ctx, RXR_ERR_INVALID, "rxr_terrain_hits: no terrain heights are resident (rxr_set_terrain_heights)");
+    if (ctx->group) return rxr_as_member0(ctx, [&](rxr_ctx *m) { return rxr_terrain_hits(m, origins, dirs, n_rays, max_distance, hit, t, world_pos, grid_pos); });
+    if (!ctx->heights_set) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_terrain_hits: no terrain heights are resident (rxr_set_terrain_heights)");
     if (!n_rays) return RXR_OK;
-    if (!origins || !dirs || !hit) return fail(ctx, RXR_ERR_INVALID, "rxr_terrain_hits: NULL ray or hit array");
+    if (!origins || !dirs || !hit) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_terrain_hits: NULL ray or hit array");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    // device copies: origins, dirs, then hit, t, world_pos, grid_pos
     const size_t n = n_rays;
-    const size_t b_rays = n * 12, b_w = n * 4, b_t = t ? n * 4 : 0, b_wp = world_pos ? n * 12 : 0, b_gp = grid_pos ? n * 8 : 0;
-    const size_t off_d = b_rays, off_hit = 2 * b_rays, off_t = off_hit + b_w, off_wp = off_t + b_t, off_gp = off_wp + b_wp, total = off_gp + b_gp;
-    int rc = rxr_ensure(ctx, ctx->d_heights_io, std::max<size_t>(total, 256));
+    QueryIO io{ctx, ctx->lane[Q_HEIGHTS]};
+    const unsigned i_o = io.in(origins, n * 12), i_d = io.in(dirs, n * 12);
+    const unsigned i_hit = io.out(hit, n * 4), i_t = io.out(t, n * 4), i_wp = io.out(world_pos, n * 12), i_gp = io.out(grid_pos, n * 8);
+    int rc = io.upload();
     if (rc != RXR_OK) return rc;
-    uint8_t *io = (uint8_t *)ctx->d_heights_io.p;
-    hipStream_t s = ctx->stream;
-    HIPCHK(ctx, hipMemcpyAsync(io, origins, b_rays, hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipMemcpyAsync(io + off_d, dirs, b_rays, hipMemcpyHostToDevice, s));
-    if ((rc = hits_run(ctx, (const float *)io, (const float *)(io + off_d), n_rays, max_distance, (uint32_t *)(io + off_hit), b_t ? (float *)(io + off_t) : nullptr,
-                       b_wp ? (float *)(io + off_wp) : nullptr, b_gp ? (int32_t *)(io + off_gp) : nullptr, s)) != RXR_OK)
+    if ((rc = hits_run(ctx, io.dev<float>(i_o), io.dev<float>(i_d), n_rays, max_distance, io.dev<uint32_t>(i_hit), io.dev<float>(i_t), io.dev<float>(i_wp),
+                       io.dev<int32_t>(i_gp), ctx->stream)) != RXR_OK)
         return rc;
-    HIPCHK(ctx, hipMemcpyAsync(hit, io + off_hit, b_w, hipMemcpyDeviceToHost, s));
-    if (b_t) HIPCHK(ctx, hipMemcpyAsync(t, io + off_t, b_t, hipMemcpyDeviceToHost, s));
-    if (b_wp) HIPCHK(ctx, hipMemcpyAsync(world_pos, io + off_wp, b_wp, hipMemcpyDeviceToHost, s));
-    if (b_gp) HIPCHK(ctx, hipMemcpyAsync(grid_pos, io + off_gp, b_gp, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));
-    ctx->heights_pending = false;   // (ev_heights lies behind on this very stream)
-    return RXR_OK;
+    return io.download();
 }
 
 int rxr_terrain_hits_to(rxr_ctx *ctx, const float *dev_origins, const float *dev_dirs, uint32_t n_rays, float max_distance, uint32_t *dev_hit,
                         float *dev_t, float *dev_world_pos, int32_t *dev_grid_pos, void *hip_stream) {
     if (!ctx) return RXR_ERR_INVALID;
-    if (ctx->group) return fail(ctx, RXR_ERR_UNSUPPORTED, "rxr_terrain_hits_to on a multi-device context: device pointers and streams belong to ONE device (use rxr_member)");
-    if (!ctx->heights_set) return fail(ctx, RXR_ERR_INVALID, "rxr_terrain_hits_to: no terrain heights are resident (rxr_set_terrain_heights)");
+    if (ctx->group) return rxr_fail(ctx, RXR_ERR_UNSUPPORTED, "rxr_terrain_hits_to on a multi-device context: device pointers and streams belong to ONE device (use rxr_member)");
+    if (!ctx->heights_set) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_terrain_hits_to: no terrain heights are resident (rxr_set_terrain_heights)");
     if (!n_rays) return RXR_OK;
-    if (!dev_origins || !dev_dirs || !dev_hit) return fail(ctx, RXR_ERR_INVALID, "rxr_terrain_hits_to: NULL ray or hit array");
+    if (!dev_origins || !dev_dirs || !dev_hit) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_terrain_hits_to: NULL ray or hit array");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t n = n_rays;
     const struct {
@@ -421,9 +384,9 @@ int rxr_terrain_hits_to(rxr_ctx *ctx, const float *dev_origins, const float *dev
                   {dev_world_pos, n * 12, "dev_world_pos"}, {dev_grid_pos, n * 8, "dev_grid_pos"}};
     for (const auto &a : arrays) {
         if (!a.p) continue;
-        if ((uintptr_t)a.p & 3u) return fail(ctx, RXR_ERR_INVALID, std::string("rxr_terrain_hits_to: ") + a.name + " must be 4-byte aligned device memory");
-        if (!on_device(ctx, a.p, a.bytes))
-            return fail(ctx, RXR_ERR_INVALID, std::string("rxr_terrain_hits_to: ") + a.name + " is not device memory of the context's device (or is too small)");
+        if ((uintptr_t)a.p & 3u) return rxr_fail(ctx, RXR_ERR_INVALID, std::string("rxr_terrain_hits_to: ") + a.name + " must be 4-byte aligned device memory");
+        if (!rxr_on_device(ctx, a.p, a.bytes))
+            return rxr_fail(ctx, RXR_ERR_INVALID, std::string("rxr_terrain_hits_to: ") + a.name + " is not device memory of the context's device (or is too small)");
     }
     return hits_run(ctx, dev_origins, dev_dirs, n_rays, max_distance, dev_hit, dev_t, dev_world_pos, dev_grid_pos, hip_stream ? (hipStream_t)hip_stream : ctx->stream);
 }
