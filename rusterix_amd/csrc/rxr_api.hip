@@ -144,7 +144,7 @@ int rxr_create(rxr_ctx **out, int device_id) {
         if (v > 0) ctx->list_floor = (size_t)v;
     }
     if (const char *kl = getenv("RXR_MIN_KERNEL_LEVEL")) {  // A-B runs: render with k_raster_chunk (1) / k_raster_vm (2) regardless
-        if (kl[0] >= '0' && kl[0] <= '2') ctx->min_kernel_level = (uint32_t)(kl[0] - '0');
+        if (kl[0] >= '0' && kl[0] - '0' <= (int)KL_VM) ctx->min_kernel_level = (uint32_t)(kl[0] - '0');
     }
     if (hipHostGetDevicePointer((void **)&ctx->d_host_status, ctx->h_counters, 0) != hipSuccess) ctx->d_host_status = ctx->h_counters;
     *out = ctx;
@@ -724,7 +724,7 @@ static int render_impl(rxr_ctx *ctx, const RenderSpec &spec, void *dev_pixels, h
     // small scenes: one staging round of k_raster holds every triangle -> no set-up / binning launches at all
     const bool d3 = P.tiles_y && (P.flags & RXR_FLAG_D3_ACTIVE);
     P.fused_small = (d3 && P.n_tris3d <= RXR_STAGE_TRIS) ? ctx->small_mode : 0u;
-    if (P.kernel_level && P.fused_small == 1u) P.fused_small = 2u;  // k_raster_vm reads the records k_setup3d writes
+    if (P.kernel_level != KL_COMMON && P.fused_small == 1u) P.fused_small = 2u;  // k_raster_vm reads the records k_setup3d writes
     if (d3 && P.fused_small) {
         if (ctx->frame_uses_meshes) rxr_launch_project(&ctx->PP, s);
         if (P.fused_small == 2u) rxr_launch_setup(&P, s);  // records only; no counters, bins or lists are touched
@@ -2120,7 +2120,7 @@ extern "C" int rxr_debug_jit_generate(const rxr_shader_set *set, int compile, ch
         double seconds = 0.0;
         double total = 0.0;
         size_t bytes = 0;
-        for (int level : {2, 7, 8}) {  // (the three template levels rxr_jit_launch may ask for)
+        for (int level : jit_level_number) {  // (the three levels rxr_jit_launch may ask for)
             if (!rxr_jit_compile(gen, "gfx950", level, obj, seconds, err)) {
                 say(err);
                 return RXR_ERR_HIP;

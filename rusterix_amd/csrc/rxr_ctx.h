@@ -159,17 +159,17 @@ struct rxr_ctx {
     uint32_t parity = 0;             // counter set of the next launch
     bool scratch_dirty = false;      // a pre-pass was queued without its raster launch
     bool scratch2d_dirty = false;
-    uint32_t min_kernel_level = 0;   // RXR_MIN_KERNEL_LEVEL (tuning)
+    uint32_t min_kernel_level = KL_COMMON;   // RXR_MIN_KERNEL_LEVEL (tuning)
     // run-time compiled kernels of the current program set (rxr_jit.hip; opt-in RXR_SHADER_JIT=1), else null: the interpreter runs
-    // (one module per template level 2 / 7 / 8, compiled when the first frame that needs it is launched; jit_source: the generated
+    // (one module per JitSlot, compiled when the first frame that needs it is launched; jit_source: the generated
     // programs of the current set, empty when the set is not covered)
-    void *jit_module[3] = {nullptr, nullptr, nullptr}, *jit_fn[3] = {nullptr, nullptr, nullptr};
-    void *jit_fn_cut[3] = {nullptr, nullptr, nullptr};   // k_raster_jit_cut of the same module (levels 7 / 8), or null
-    bool jit_failed[3] = {false, false, false};
+    void *jit_module[N_JIT_SLOTS] = {nullptr, nullptr, nullptr}, *jit_fn[N_JIT_SLOTS] = {nullptr, nullptr, nullptr};
+    void *jit_fn_cut[N_JIT_SLOTS] = {nullptr, nullptr, nullptr};   // k_raster_jit_cut of the same module (JIT_NO_VIS / JIT_PLAIN), or null
+    bool jit_failed[N_JIT_SLOTS] = {false, false, false};
     bool jit_palette_miss = false;   // a compiled frame met a PaletteIndex without a colour: this set runs interpreted from now on (VMF_JIT_PALETTE_MISS)
     // background mode (the default): the compilation of a level runs in a child process (rxr_jitc); the interpreter renders until it is done
     bool jit_async = false;
-    std::string jit_wait_key[3];           // the background compilation (rxr_jit.hip registry) this context is attached to, per level
+    std::string jit_wait_key[N_JIT_SLOTS];           // the background compilation (rxr_jit.hip registry) this context is attached to, per level
     std::string jit_source, jit_arch;
     // mid-sized scenes: bin lists by k_blockscan (rxr_device.h RXR_BLOCKSCAN_*).  blockscan_off: the current frame overflowed a block or a
     // bin and goes through the general pipeline (reset by the next upload); RXR_BLOCKSCAN=0 turns the mode off, RXR_BLOCKSCAN_CAP sets
@@ -195,7 +195,7 @@ struct rxr_ctx {
     bool blockscan2d_off = false, last_used_blockscan2d = false;  // the same for the 2D bins (k_blockscan2d); RXR_BLOCKSCAN2D=0 turns it off
     uint32_t blockscan_cap = 0;           // RXR_BLOCKSCAN_CAP in effect
     bool relaxed_lights = true;           // rxr_set_light_math / RXR_LIGHT_MATH: the 3D light loop in relaxed arithmetic (RasterParams.relaxed_lights)
-    bool frame_needs_chunk_paths = true;  // the uploaded frame uses what feature level 1 adds (terrain / baked textures / staircase / editor paths)
+    bool frame_needs_chunk_paths = true;  // the uploaded frame uses the chunk paths (LevelFeatures.chunk: terrain / baked textures / staircase / editor paths)
     std::string jit_info;                // what happened to the last set ("compiled: ...", "not compiled: <why>", empty: not asked)
     bool programs_static = false;    // every program of the set has a stack depth that is a function of the pc (tag_static_depths)
     uint32_t small_mode = 2;         // RasterParams.fused_small for frames with <= RXR_STAGE_TRIS triangles;

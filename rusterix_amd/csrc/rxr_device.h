@@ -274,8 +274,80 @@ RXR_HD inline void rxr_ref_tile_span_quick(float lo, float extent, uint32_t size
     p1 = ((last + 1u) * ts < size) ? (last + 1u) * ts : size;
 }
 
-// kernel parameter block (passed by value; lives in the kernarg segment -> scalar loads)
-// Per-light constants of the relaxed point-light term (shade3d_lights<X, true>; RXR_LIGHT_MATH=relaxed).  Everything in the term that
+// ---- the raster code's feature levels -------------------------------------------------------------------------------------------
+// Every raster kernel is an instantiation of raster_tile / raster_tile_pair (rxr_kernels.hip) at one of these levels, so that the common
+// kernels carry none of the rarer paths.  Plain C++ like everything above RasterParams: tests/raster_level_walk.cpp prints the table.
+enum class Level {
+    Common,    // k_raster*, _fused, _rows*, _pair*
+    Chunk,     // k_raster_chunk*
+    Vm,        // k_raster_vm, and a compiled set's kernel when one of its programs may decide visibility
+    VmOol,     // (Vm's visibility loop: its alpha test with every interpreter site out of line)
+    VmS,       // k_raster_vm_s: all programs of the set have static stack depths (rxr_vm.h SSP)
+    VmSOol,    // (VmS's visibility loop)
+    VmSV,      // k_raster_vm_sv: VmS for frames in which no opaque-pass program decides visibility -- Chunk's visibility loop, no call in it
+    VmV,       // k_raster_vm_v: Vm for such frames, and a compiled set's kernel for them
+    JitPlain,  // compiled sets only: a frame that runs programs and uses none of the chunk paths gets Common's fragment code around them
+    VmP,       // k_raster_vm_p: VmSV for such frames
+};
+struct LevelFeatures {
+    bool chunk;         // the chunk paths: terrain texels, baked shader textures, the opacity staircase, grid background, brush
+    bool programs;      // batches may run Rusteria programs
+    bool ssp;           // ... with the wave-uniform stack pointer
+    bool inline_site;   // ... inlined where the winning fragment is shaded (false: every site is a call)
+    Level out_of_line;  // the level the visibility loop's out-of-line alpha test shades at: the same stack pointer, no inlined site
+                        // (asked where vis_programs holds; Chunk's test is inlined and shades at Chunk)
+    bool vis_programs;  // a program of the opaque pass may decide whether a fragment is written: that alpha test is a call in the loop
+    bool pixel_items;   // row mode's rounds work on pixel items (false: one item per row, rows_round PIX)
+};
+constexpr LevelFeatures level_features(Level l) {
+    switch (l) {  //                   chunk  programs ssp    inline out_of_line    vis    pixel_items
+        case Level::Common:   return {false, false, false, false, Level::Common, false, true};
+        case Level::Chunk:    return {true,  false, false, false, Level::Chunk,  false, true};
+        case Level::Vm:       return {true,  true,  false, true,  Level::VmOol,  true,  false};
+        case Level::VmOol:    return {true,  true,  false, false, Level::VmOol,  true,  false};
+        case Level::VmS:      return {true,  true,  true,  true,  Level::VmSOol, true,  false};
+        case Level::VmSOol:   return {true,  true,  true,  false, Level::VmSOol, true,  false};
+        case Level::VmSV:     return {true,  true,  true,  true,  Level::VmSOol, false, true};
+        case Level::VmV:      return {true,  true,  false, true,  Level::VmOol,  false, true};
+        case Level::JitPlain: return {false, true,  false, true,  Level::VmOol,  false, true};
+        case Level::VmP:      return {false, true,  true,  true,  Level::VmSOol, false, true};
+    }
+    return {};
+}
+
+// RasterParams.kernel_level: what the frame needs of the static kernels (rxr_upload_frame; RXR_MIN_KERNEL_LEVEL raises it as a number)
+enum KernelLevel : uint32_t {
+    KL_COMMON = 0,
+    KL_CHUNK = 1,  // a visible batch uses a terrain / baked texture, or an editor path
+    KL_VM = 2,     // a visible batch runs a program
+    KL_VM_S = 3,   // ... and all programs have static stack depths
+    KL_VM_SV = 4,  // KL_VM_S, and no opaque-pass program writes `opacity`
+    KL_VM_V = 5,   // KL_VM, likewise
+};
+// ... and the level of the static kernel such a frame gets (rxr_route.h picks among that level's kernels)
+constexpr Level static_level(uint32_t kernel_level, bool plain_programs) {
+    switch (kernel_level) {
+        case KL_COMMON: return Level::Common;
+        case KL_CHUNK: return Level::Chunk;
+        case KL_VM: return Level::Vm;
+        case KL_VM_S: return Level::VmS;
+        case KL_VM_SV: return plain_programs ? Level::VmP : Level::VmSV;
+        default: return Level::VmV;
+    }
+}
+
+// The run-time compile boundary (rxr_jit.hip): a program set's kernel is compiled per slot with -DRXR_JIT_LEVEL=<number>, and the number
+// stays in the disk-cache key and in the "compiled: template level" message -- the one place a level is a number.
+enum JitSlot { JIT_VIS, JIT_NO_VIS, JIT_PLAIN, N_JIT_SLOTS };
+constexpr int jit_level_number[N_JIT_SLOTS] = {2, 7, 8};
+constexpr Level jit_slot_level[N_JIT_SLOTS] = {Level::Vm, Level::VmV, Level::JitPlain};
+constexpr int jit_slot_of_number(int number) {
+    for (int slot = 0; slot < N_JIT_SLOTS; ++slot)
+        if (jit_level_number[slot] == number) return slot;
+    return -1;
+}
+
+// Per-light constants of the relaxed point-light term (shade3d_lights<LV, true>; RXR_LIGHT_MATH=relaxed).  Everything in the term that
 // depends on the light and the frame but not on the fragment -- colour x intensity x flicker, the smoothstep's reciprocal
 // 1 / (start - end) and its offset -end / (start - end) -- is a function of the inputs of rxr_upload_frame (the light records and
 // hash_anim), so the host evaluates it once per frame next to the light records instead of every wave once per light in VALU
@@ -295,6 +367,8 @@ struct LightFast {
 };
 static_assert(sizeof(LightFast) == 48, "LightFast: 32 bytes for the loop + 16 for the culling step");
 
+// kernel parameter block (passed by value; lives in the kernarg segment -> scalar loads)
+#if defined(__HIPCC__) || defined(RXR_JIT)  // (HIP's vector types: a plain C++ compiler gets everything above)
 struct RasterParams {
     uint32_t width, height;
     uint32_t row0, row1;           // band of rows this launch renders
@@ -361,9 +435,9 @@ struct RasterParams {
     uint32_t *chunk_tot;           // per k_scan workgroup: number of list entries of its chunk
     uint32_t *chunk_base;          // exclusive scan of chunk_tot (written by the last k_scan workgroup)
     uint32_t *counters_next;       // the other counter set, cleared for the next launch
-    uint32_t plain_programs;       // host only: the frame runs programs but needs none of level 1's chunk paths (k_raster_vm_p instead of k_raster_vm_sv)
-    uint32_t relaxed_lights;       // host only: RXR_LIGHT_MATH=relaxed -- feature levels 0 and 1 launch the kernels whose 3D light loop uses the
-                                   // relaxed arithmetic (k_raster_rl, k_raster_rows_rl, k_raster_chunk_rl; shade3d_lights<X, true>)
+    uint32_t plain_programs;       // host only: the frame runs programs but needs none of the chunk paths (k_raster_vm_p instead of k_raster_vm_sv)
+    uint32_t relaxed_lights;       // host only: RXR_LIGHT_MATH=relaxed -- Level::Common and Level::Chunk launch the kernels whose 3D light loop uses the
+                                   // relaxed arithmetic (k_raster_rl, k_raster_rows_rl, k_raster_chunk_rl; shade3d_lights<LV, true>)
     uint32_t blockscan_scatter;    // k_blockscan's phase 0 the other way round (many groups): every group has appended itself to the lists of the
                                    // blocks its range meets (k_setup3d, at most RXR_BLOCKSCAN_GROUP_BLOCKS of them) instead of every block
                                    // reading every group's range
@@ -382,7 +456,7 @@ struct RasterParams {
     uint32_t *counters;
 
     const rxr_light *lights;
-    const LightFast *lights_fast;      // one per light, made by the host with the frame (rxr_upload_frame): shade3d_lights<X, true>
+    const LightFast *lights_fast;      // one per light, made by the host with the frame (rxr_upload_frame): shade3d_lights<LV, true>
     const rxr_occluder *occluders;     // mapmini occluders first, then the chunks'
     const rxr_linedef *linedefs;
     const ChunkRange *chunks;
@@ -396,9 +470,7 @@ struct RasterParams {
     uint32_t *host_status2d;
 
     // Rusteria programs (rxr_set_shaders)
-    uint32_t kernel_level;             // 0: k_raster; 1: k_raster_chunk (a visible batch uses a terrain / baked texture);
-                                       // 2: k_raster_vm (a visible batch runs a program); 3: k_raster_vm_s (all programs have static
-                                       // stack depths); 4: k_raster_vm_sv (3, and no opaque-pass program writes `opacity`); 5: k_raster_vm_v (2, likewise)
+    uint32_t kernel_level;             // KernelLevel
     const uint32_t *vm_code;
     const DevProgram *programs;
     const DevPattern *patterns;        // n_patterns colour patterns, then n_normal_patterns normal patterns
@@ -409,7 +481,7 @@ struct RasterParams {
     uint32_t *staircase_overflow;      // pinned host word: set when a pixel's opacity staircase had to drop an entry (front_insert)
     float time;                        // Rasterizer.time
     float bg_grid[4];                  // RXR_BG_GRID: grid_size, subdivisions, offset.x, offset.y
-    uint32_t has_brush;                // Rasterizer.brush_preview (feature level >= 1)
+    uint32_t has_brush;                // Rasterizer.brush_preview (a chunk path)
     float brush_pos[3], brush_radius, brush_falloff;
 
     const DevTexDesc *tex;             // resident textures first, then this frame's chunk textures
@@ -432,3 +504,4 @@ struct RasterParams {
                                    // profile id: k_raster_rows_cut[_rl] (rxr_upload_frame)
     uint32_t pad_tail;
 };
+#endif

@@ -1052,7 +1052,7 @@ extern "C" int rxr_debug_jit_compile_file(const char *src_path, const char *arch
 
 void rxr_jit_drop(rxr_ctx *ctx) {
     ctx->jit_palette_miss = false;
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < N_JIT_SLOTS; ++k) {
         if (ctx->jit_module[k]) (void)hipModuleUnload((hipModule_t)ctx->jit_module[k]);
         ctx->jit_module[k] = ctx->jit_fn[k] = ctx->jit_fn_cut[k] = nullptr;
         ctx->jit_failed[k] = false;
@@ -1061,7 +1061,7 @@ void rxr_jit_drop(rxr_ctx *ctx) {
     ctx->jit_source.clear();
 }
 
-// generated header -> code object of the raster kernel at template level `level` (2 / 7 / 8) for `arch` ("gfx950"), through the
+// generated header -> code object of the raster kernel at template level `level` (one of jit_level_number) for `arch` ("gfx950"), through the
 // process-wide cache; needs no device
 bool rxr_jit_compile(const std::string &gen, const std::string &arch, int level, std::vector<char> &obj, double &seconds, std::string &err) {
     seconds = 0.0;
@@ -1151,31 +1151,30 @@ int rxr_jit_build(rxr_ctx *ctx, const std::vector<uint32_t> &code, const std::ve
 namespace {
 // the two kernels of a code object (rxr_kernels.hip under RXR_JIT): looked up and reported (rxr_ctx.last_raster_kernel) by these names
 const char *const k_jit_name = "k_raster_jit", *const k_jit_cut_name = "k_raster_jit_cut";
-// slot 0 / 1 / 2 = template level 2 / 7 / 8
-bool ensure_level(rxr_ctx *ctx, int slot) {
+bool ensure_level(rxr_ctx *ctx, JitSlot slot) {
     if (ctx->jit_fn[slot]) return true;
     if (ctx->jit_failed[slot]) return false;
-    static const int levels[3] = {2, 7, 8};
+    const int level = jit_level_number[slot];
     std::vector<char> obj;
     double seconds = 0.0;
     std::string err;
     if (ctx->jit_async) {
-        const int st = poll_background(ctx, slot, levels[slot], err);
+        const int st = poll_background(ctx, slot, level, err);
         if (st < 0) {
             ctx->jit_failed[slot] = true;
             ctx->jit_info = "not compiled: " + err;
             return false;
         }
         if (st == 0) {  // (this frame and the next ones: the interpreter)
-            ctx->jit_info = (ctx->jit_wait_key[slot].empty() ? "waiting for a compiler slot: template level " : "compiling in the background: template level ") + std::to_string(levels[slot]);
+            ctx->jit_info = (ctx->jit_wait_key[slot].empty() ? "waiting for a compiler slot: template level " : "compiling in the background: template level ") + std::to_string(level);
             return false;
         }
-        if (!rxr_jit_compile(ctx->jit_source, ctx->jit_arch, levels[slot], obj, seconds, err)) {  // (answers from the cache)
+        if (!rxr_jit_compile(ctx->jit_source, ctx->jit_arch, level, obj, seconds, err)) {  // (answers from the cache)
             ctx->jit_failed[slot] = true;
             ctx->jit_info = "not compiled: " + err;
             return false;
         }
-    } else if (!rxr_jit_compile(ctx->jit_source, ctx->jit_arch, levels[slot], obj, seconds, err)) {
+    } else if (!rxr_jit_compile(ctx->jit_source, ctx->jit_arch, level, obj, seconds, err)) {
         ctx->jit_failed[slot] = true;
         ctx->jit_info = "not compiled: " + err;
         return false;
@@ -1195,12 +1194,12 @@ bool ensure_level(rxr_ctx *ctx, int slot) {
     ctx->jit_fn[slot] = fn;
     hipFunction_t fn_cut = nullptr;
     ctx->jit_fn_cut[slot] = nullptr;
-    if (levels[slot] != 2) {  // (template level 2 has none)
+    if (!level_features(jit_slot_level[slot]).vis_programs) {  // (JIT_VIS has none)
         if (hipModuleGetFunction(&fn_cut, mod, k_jit_cut_name) == hipSuccess) ctx->jit_fn_cut[slot] = (void *)fn_cut;
         else (void)hipGetLastError();   // (a code object of an older build in the disk cache: the plain kernel serves; the error must not stay behind)
     }
     char msg[200];
-    snprintf(msg, sizeof msg, "compiled: template level %d, %zu bytes of code object, %.2f s%s", levels[slot], obj.size(), seconds, seconds == 0.0 ? " (cached)" : "");
+    snprintf(msg, sizeof msg, "compiled: template level %d, %zu bytes of code object, %.2f s%s", level, obj.size(), seconds, seconds == 0.0 ? " (cached)" : "");
     ctx->jit_info = msg;
     return true;
 }
@@ -1208,10 +1207,11 @@ bool ensure_level(rxr_ctx *ctx, int slot) {
 
 // the raster launch of a frame whose programs are compiled; false: no compiled kernel (the caller launches the interpreter kernels)
 bool rxr_jit_launch(rxr_ctx *ctx, const RasterParams *P, hipStream_t s) {
-    if (ctx->jit_source.empty() || P->kernel_level < 2u || ctx->jit_palette_miss) return false;
-    // RasterParams.kernel_level 4 / 5 (k_raster_vm_sv / _v, template levels 6 / 7): no program of the opaque pass decides
-    // visibility (rxr_upload_frame); 2 / 3: one may.  When the frame needs none of the chunk paths either: template level 8.
-    const int slot = P->kernel_level >= 4u ? (ctx->frame_needs_chunk_paths ? 1 : 2) : 0;
+    if (ctx->jit_source.empty() || P->kernel_level < KL_VM || ctx->jit_palette_miss) return false;
+    // does a program of the opaque pass decide visibility in the static kernel this frame would get (rxr_upload_frame)?  If none
+    // does and the frame needs none of the chunk paths either: JIT_PLAIN
+    const bool vis_programs = level_features(static_level(P->kernel_level, P->plain_programs != 0u)).vis_programs;
+    const JitSlot slot = vis_programs ? JIT_VIS : (ctx->frame_needs_chunk_paths ? JIT_NO_VIS : JIT_PLAIN);
     if (!ensure_level(ctx, slot)) return false;
     if (P->tiles_x * P->tiles_y == 0) return true;
     RasterParams params = *P;

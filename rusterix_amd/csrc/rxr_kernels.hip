@@ -517,17 +517,16 @@ __device__ __forceinline__ uint32_t brush_over_texel(const RasterParams &P, uint
     return out;
 }
 
-// feature level (template parameter X of the raster code, see below) -> does it carry the chunk paths of level 1 (terrain, baked shader
-// textures, opacity staircase, grid background, brush)?  Level 8 is "programs without them" (run-time compiled sets only)
-template <int X> inline constexpr bool lvl1 = X >= 1 && X != 8 && X != 9;  // (9: the interpreter's level 6 without them, k_raster_vm_p)
+// what the feature level LV of the raster code below carries (the table of rxr_device.h)
+template <Level LV> inline constexpr LevelFeatures feat = level_features(LV);
 
 // the texel switch of the raster loops (rasterizer.rs:1101-1222, :672-758); (wx, wy) is the position terrain batches sample at;
 // `world3`: the fragment's world position in the two 3D loops (terrain brush preview), nullptr in the 2D loop
 // UNIFORM: `B` is the same batch for every lane (the 2D pass walks one primitive at a time) -- its texture descriptor then
 // comes through the scalar cache like the batch header itself (uniform_record)
-template <int X, bool UNIFORM = false>
+template <Level LV, bool UNIFORM = false>
 __device__ __forceinline__ uint32_t batch_texel(const RasterParams &P, const DevBatch &B, float u, float v, float wx, float wy, const f3 *world3 = nullptr) {
-    if constexpr (!UNIFORM && !lvl1<X>) {
+    if constexpr (!UNIFORM && !feat<LV>.chunk) {
         // tex, pixel and repeat_mode are neighbours in the header: one 16-byte load instead of one word now and another, behind
         // the descriptor's round trip, when the sampler wants the repeat mode
         static_assert(__builtin_offsetof(DevBatch, tex) == 16 && __builtin_offsetof(DevBatch, pixel) == 20 && __builtin_offsetof(DevBatch, repeat_mode) == 24, "one 16-byte load");
@@ -542,7 +541,7 @@ __device__ __forceinline__ uint32_t batch_texel(const RasterParams &P, const Dev
         return sample_texture(d, texel_base(P, d), u, v, P.sample_mode, repeat);
     }
     if (B.tex < 0) return B.pixel;
-    if constexpr (lvl1<X>) {
+    if constexpr (feat<LV>.chunk) {
         if (B.flags & DB_TERRAIN) {
             uint32_t t = terrain_texel(P, B, wx, wy);
             if (P.has_brush && world3) t = brush_over_texel(P, t, *world3);
@@ -563,23 +562,13 @@ __device__ __forceinline__ uint32_t batch_texel(const RasterParams &P, const Dev
     }
 }
 
-// Feature levels (template parameter X of the raster code): 0 common, 1 chunk paths, 2 + programs with the interpreter inlined
-// in the opaque pass, 3 = 2 with every interpreter site out of line; 4 / 5 = 2 / 3 with the wave-uniform stack pointer
-// (all programs of the set have static stack depths, rxr_vm.h SSP)
-// 6 = 4 for frames in which no program decides whether an opaque fragment is written (none of the opaque pass's programs
-// writes `opacity`): the visibility loop's alpha test is level 1's, inlined, and the loop contains no call
-// 7 = 2 for such frames (programs with calls or PaletteIndex: per-lane stack pointer)
-// 8 = programs WITHOUT the chunk paths of level 1 (run-time compiled sets only, rxr_jit.hip: a frame whose batches run programs but
-// use no terrain / baked texture / staircase / editor background gets level 0's fragment code around its compiled programs)
-template <int X> struct vm_level { static constexpr bool ssp = (X >= 4 && X <= 6) || X == 9; static constexpr bool inline_site = X == 2 || X == 4 || X == 6 || X == 7 || X == 8 || X == 9; static constexpr int out_of_line = ssp ? 5 : 3; static constexpr bool vis_programs = X < 6; };
-
 // ---- the covered-fragment block of d3_rasterize after the depth test (rasterizer.rs:1062-1404) ----
 // Split in three so that the light loop runs in wave-uniform control flow (see shade3d_lights).
 struct Frag {
     f3 world, normal, view_dir, base, lit;
     float opacity;
     float rough, metal;  // mat_roughness / mat_metallic (:1321-1322): 0.5 / 0 unless a program ran
-    f3 emis;             // mat_emissive (:1323): what THIS fragment's program assigned (feature levels >= 2; frames in which a
+    f3 emis;             // mat_emissive (:1323): what THIS fragment's program assigned (levels with programs; frames in which a
                          // fragment could see another fragment's emissive are refused by rxr_upload_frame), else 0
 };
 
@@ -589,7 +578,7 @@ struct Frag {
 // the already-unit normal (:1320) is skipped.  The one DECISION they take part in -- flip the normal toward the camera when
 // n.v < 0 (:1096) -- is only taken from the relaxed values when every fragment of the wave has |n.v| >= 1e-4, a hundred times
 // their error; otherwise, and for magnitudes outside the window, the wave takes the exact sequences.
-template <int X, bool RL = false>
+template <Level LV, bool RL = false>
 __device__ __forceinline__ void shade3d_begin(const RasterParams &P, const TriShade &S, uint32_t batch_id, float alpha, float beta,
                                               float z, float fx, float fy, Frag &F, bool have_flags = false, uint32_t known_flags = 0u) {
     const DevBatch &B = P.batches3d[batch_id];
@@ -603,10 +592,10 @@ __device__ __forceinline__ void shade3d_begin(const RasterParams &P, const TriSh
     // fx, fy are pixel centres (0.5 .. 2^15) and the frame size is validated by rxr_upload_frame
     // (1 .. 32768): always inside the division window
     float x_ndc, y_ndc, vx, vy, vz, vw;
-    // relaxed mode, level 0, no occluder anywhere: the world position feeds only the light loop and the view direction -- continuous
+    // relaxed mode, neither chunk paths nor programs, no occluder anywhere: the world position feeds only the light loop and the view direction -- continuous
     // uses -- so its three divisions (pixel / frame size, the perspective divide) become reciprocal products (within 2 ulp).  With
     // an occluder in the frame its boxes are compared with the position (get_occlusion): the exact quotients then.
-    const bool relaxed_world = RL && X == 0 && !P.any_occluders;  // wave-uniform
+    const bool relaxed_world = RL && !feat<LV>.chunk && !feat<LV>.programs && !P.any_occluders;  // wave-uniform
     if (relaxed_world) {
         x_ndc = fmaf(fx, 2.0f * __builtin_amdgcn_rcpf(P.fwidth), -1.0f);
         y_ndc = fmaf(fy, -2.0f * __builtin_amdgcn_rcpf(P.fheight), 1.0f);
@@ -630,7 +619,7 @@ __device__ __forceinline__ void shade3d_begin(const RasterParams &P, const TriSh
     f3 cam = mk3(P.cam[0], P.cam[1], P.cam[2]);
     f3 view_dir, normal;
     bool relaxed_normals = false;  // wave-uniform
-    if constexpr (RL && X < 2) {
+    if constexpr (RL && !feat<LV>.programs) {
         const bool has_n = (b_flags & DB_HAS_NORMALS) != 0u;
         const f3 vd = sub3(cam, world);
         f3 ni = mk3(0.0f, 0.0f, 0.0f);
@@ -673,17 +662,17 @@ __device__ __forceinline__ void shade3d_begin(const RasterParams &P, const TriSh
 
     uint32_t texel;
     bool desc_in_record = false;  // wave-uniform
-    if constexpr (!lvl1<X> || X == 1) desc_in_record = rxm::wave_all((S.pad[1] & TS_DESC_VALID) != 0u);  // (terrain batches leave the words zero: make_setup)
+    if constexpr (!feat<LV>.chunk || !feat<LV>.programs) desc_in_record = rxm::wave_all((S.pad[1] & TS_DESC_VALID) != 0u);  // (terrain batches leave the words zero: make_setup)
     if (desc_in_record) {  // (make_setup: the descriptor as the record carries it -- the same sampler on the same words)
         const uint32_t p0 = S.pad[0], p1 = S.pad[1];
         const DevTexDesc d{p0, p1 & 0x1FFFu, (p1 >> 13) & 0x1FFFu, (p1 >> 28) & 3u};
         texel = sample_texture(d, texel_base(P, d), u, v, P.sample_mode, (p1 >> 26) & 3u);
-    } else texel = batch_texel<X>(P, B, u, v, world.x, world.z, &world);
+    } else texel = batch_texel<LV>(P, B, u, v, world.x, world.z, &world);
     const float INV_255 = 1.0f / 255.0f;  // lib.rs:52
     f3 base = mk3(srgb_to_linear_fast((float)(texel & 0xFFu) * INV_255), srgb_to_linear_fast((float)((texel >> 8) & 0xFFu) * INV_255),
                   srgb_to_linear_fast((float)((texel >> 16) & 0xFFu) * INV_255));
     F.opacity = rxm::div1_known((float)(texel >> 24), 255.0f, true);  // :1313; byte / 255 is inside the division window
-    if (lvl1<X> && B.baked_plus1) {  // chunk.shader_textures: the baked texel replaces colour and alpha, no program runs (:1239-1267)
+    if (feat<LV>.chunk && B.baked_plus1) {  // chunk.shader_textures: the baked texel replaces colour and alpha, no program runs (:1239-1267)
         const DevTexDesc &baked = P.tex[B.baked_plus1 - 1u];
         uint32_t bt = sample_texture(baked, texel_base(P, baked), u, v, P.sample_mode, B.repeat_mode);
         base = mk3(srgb_to_linear_fast((float)(bt & 0xFFu) * INV_255), srgb_to_linear_fast((float)((bt >> 8) & 0xFFu) * INV_255),
@@ -691,7 +680,7 @@ __device__ __forceinline__ void shade3d_begin(const RasterParams &P, const TriSh
         F.opacity = (float)(bt >> 24) * INV_255;  // execution.opacity.x = color.w of pixel_to_vec4 (:1262)
     }
     float rough = 0.5f, metal = 0.0f;  // :1315-1316 (no-shader branch)
-    if constexpr (X >= 2) {
+    if constexpr (feat<LV>.programs) {
         if (B.program_plus1) {  // :1283-1304
             rxvm::IO io;
             rxvm::io_defaults(io);
@@ -705,8 +694,8 @@ __device__ __forceinline__ void shade3d_begin(const RasterParams &P, const TriSh
             io.hitpoint = rxvm::mk(world.x, world.y, world.z);
             io.time = rxvm::splat(P.time);
             // (calling the out-of-line interpreter from the opaque pass too was slower: 304 vs 236 us on the probe)
-            if constexpr (vm_level<X>::inline_site) rxvm::shade_inline<vm_level<X>::ssp>(P, B.program_plus1 - 1u, io, rxvm::stack_block());
-            else rxvm::shade_call<vm_level<X>::ssp>(P, B.program_plus1 - 1u, io);  // X == 3 / 5: from the visibility loop's alpha test
+            if constexpr (feat<LV>.inline_site) rxvm::shade_inline<feat<LV>.ssp>(P, B.program_plus1 - 1u, io, rxvm::stack_block());
+            else rxvm::shade_call<feat<LV>.ssp>(P, B.program_plus1 - 1u, io);  // VmOol / VmSOol: from the visibility loop's alpha test
             base = mk3(io.color.x, io.color.y, io.color.z);  // :1319-1323
             normal = mk3(io.normal.x, io.normal.y, io.normal.z);
             rough = rclamp(io.roughness.x, 0.0f, 1.0f);
@@ -766,8 +755,8 @@ __device__ __forceinline__ void shade3d_begin(const RasterParams &P, const TriSh
 // few ulp moves a channel by at most one step); spot, area and daylight lights have hard cut-offs and stay exact in both modes.
 // Three A-B variants of the relaxed point-light term were tried against what stands below and are retired: the light's
 // constants read from its rxr_light record in the loop (now its LightFast record), the light direction formed and normalised
-// first (now folded into the dot products), and exp2(6 log2 x) below feature level 2 (now three multiplies).
-template <int X, bool RL = false>
+// first (now folded into the dot products), and exp2(6 log2 x) at levels without programs (now three multiplies).
+template <Level LV, bool RL = false>
 __device__ __forceinline__ void shade3d_lights(const RasterParams &P, bool hit, Frag &F) {
     const unsigned long long hitmask = __ballot(hit);
     if (hitmask == 0ull) return;
@@ -781,13 +770,13 @@ __device__ __forceinline__ void shade3d_lights(const RasterParams &P, bool hit, 
     // NaN / inf world positions are not bounded by the sphere: no culling for this wave then
     const bool can_cull = __ballot(hit && !(r < __builtin_huge_valf())) == 0ull;  // (INFINITY, without <cmath>: hiprtc)
     const float rmax = rxm::wave_max_nonneg(r);  // (a magnitude, +0 for the lanes without a fragment; meaningless and unused when !can_cull)
-    const float rough = (X >= 2) ? F.rough : 0.5f, metal = (X >= 2) ? F.metal : 0.0f;
+    const float rough = feat<LV>.programs ? F.rough : 0.5f, metal = feat<LV>.programs ? F.metal : 0.0f;
     // relaxed mode: the light-independent factors of shade_fast_brdf (:1875-1951) once per fragment -- diffuse weight kd, Fresnel
     // term f, shininess -- by the reference's own operations
     f3 rl_kd = mk3(0.0f, 0.0f, 0.0f), rl_f = rl_kd;
     float rl_shininess = 1.0f;
-    if constexpr (RL && X < 2) {
-        // no program below feature level 2: metal = 0 and the base colour is a texel's (finite), so f0 = lerp(0.04, base, 0) is 0.04
+    if constexpr (RL && !feat<LV>.programs) {
+        // levels without programs: metal = 0 and the base colour is a texel's (finite), so f0 = lerp(0.04, base, 0) is 0.04
         // in every channel -- the same floats as the general form below without its multiplications by zero
         rl_kd = scale3(F.base, 1.0f - 0.04f);
         rl_shininess = 6.0f;  // clamp(2 / 0.25 - 2, 1, 2048)
@@ -903,11 +892,11 @@ __device__ __forceinline__ void shade3d_lights(const RasterParams &P, bool hit, 
                         const f3 hu = mk3(fmaf(d.x, inv, F.view_dir.x), fmaf(d.y, inv, F.view_dir.y), fmaf(d.z, inv, F.view_dir.z));
                         const float hh = fmaf(hu.z, hu.z, fmaf(hu.y, hu.y, hu.x * hu.x));  // 0 (l = -v: n.h = NaN -> 0 below) or >= 1e-15
                         const float ndh = __builtin_amdgcn_fmed3f(fmaf(F.normal.z, hu.z, fmaf(F.normal.y, hu.y, F.normal.x * hu.x)) * __builtin_amdgcn_rsqf(hh), 0.0f, 1.0f);
-                        // Below feature level 2 no program sets roughness: rough = 0.5, shininess = 2 / 0.25 - 2 = 6 exactly, and the
+                        // At levels without programs nothing sets roughness: rough = 0.5, shininess = 2 / 0.25 - 2 = 6 exactly, and the
                         // reference's powf(n.h, 6) is three multiplies (each within half an ulp: closer to powf than exp2(6 log2 x),
                         // whose v_log_f32 error the exponent multiplies by six) instead of two quarter-rate transcendentals
                         float spec;
-                        if constexpr (X < 2) {
+                        if constexpr (!feat<LV>.programs) {
                             const float ndh2 = ndh * ndh;
                             spec = ndh2 * ndh2 * ndh2;
                         } else {
@@ -967,12 +956,12 @@ __device__ __forceinline__ void shade3d_lights(const RasterParams &P, bool hit, 
     }
 }
 
-// encode (:1394-1404).  `lit += mat_emissive` (:1394): below feature level 2 no program runs and emissive is 0 -- adding it cannot
+// encode (:1394-1404).  `lit += mat_emissive` (:1394): at levels without programs none runs and emissive is 0 -- adding it cannot
 // change the encoded byte (x + 0 == x except -0 + 0 == +0, and both encode to 0)
-template <int X, bool RL = false>
+template <Level LV, bool RL = false>
 __device__ __forceinline__ uint32_t shade3d_end(const Frag &F) {
     f3 lit = F.lit;
-    if constexpr (X >= 2) lit = add3(lit, F.emis);
+    if constexpr (feat<LV>.programs) lit = add3(lit, F.emis);
     if constexpr (RL) {  // linear_to_srgb_fast (:26-33) with v_sqrt_f32 (1 ulp) for the correctly rounded root
         const float sx = __builtin_amdgcn_sqrtf(lit.x), sy = __builtin_amdgcn_sqrtf(lit.y), sz = __builtin_amdgcn_sqrtf(lit.z);
         return pack4(f32_to_u8_saturated(1.055f * sx - 0.055f * sx * sx), f32_to_u8_saturated(1.055f * sy - 0.055f * sy * sy),
@@ -983,7 +972,7 @@ __device__ __forceinline__ uint32_t shade3d_end(const Frag &F) {
 }
 
 // the covered-fragment block of d3_rasterize_opacity (rasterizer.rs:1497-1682, no shader)
-template <int X>
+template <Level LV>
 __device__ __forceinline__ uint32_t shade3d_opacity(const RasterParams &P, const TriShade &S, uint32_t batch_id, float alpha, float beta,
                                                     float z, float fx, float fy) {
     const DevBatch &B = P.batches3d[batch_id];
@@ -992,7 +981,7 @@ __device__ __forceinline__ uint32_t shade3d_opacity(const RasterParams &P, const
     fragment_uv(S, alpha, beta, gamma, u, v);
     // screen_to_world (:1515, :1707-1727): needed by terrain texels and by programs
     float wx = 0.0f, wy = 0.0f, wz = 0.0f;
-    if ((lvl1<X> && (B.flags & DB_TERRAIN)) || (X >= 2 && B.program_plus1)) {
+    if ((feat<LV>.chunk && (B.flags & DB_TERRAIN)) || (feat<LV>.programs && B.program_plus1)) {
         float x_ndc = 2.0f * (fx / P.fwidth) - 1.0f;
         float y_ndc = 1.0f - 2.0f * (fy / P.fheight);
         float vx, vy, vz, vw, ww;
@@ -1004,13 +993,13 @@ __device__ __forceinline__ uint32_t shade3d_opacity(const RasterParams &P, const
         mat4_mul(P.inv_view, vx, vy, vz, vw, wx, wy, wz, ww);
     }
     const f3 world3 = mk3(wx, wy, wz);
-    uint32_t texel = batch_texel<X>(P, B, u, v, wx, wz, &world3);
+    uint32_t texel = batch_texel<LV>(P, B, u, v, wx, wz, &world3);
     const float INV_255 = 1.0f / 255.0f;
     float r = srgb_to_linear_fast((float)(texel & 0xFFu) * INV_255);
     float g = srgb_to_linear_fast((float)((texel >> 8) & 0xFFu) * INV_255);
     float b = srgb_to_linear_fast((float)((texel >> 16) & 0xFFu) * INV_255);
     float opacity = byte_over_255(texel >> 24);
-    if constexpr (X >= 2) {
+    if constexpr (feat<LV>.programs) {
         if (B.program_plus1) {  // :1642-1667
             rxvm::IO io;
             rxvm::io_defaults(io);
@@ -1022,7 +1011,7 @@ __device__ __forceinline__ uint32_t shade3d_opacity(const RasterParams &P, const
             io.time = rxvm::splat(P.time);
             io.roughness.x = 0.5f;
             io.metallic.x = 0.0f;
-            rxvm::shade_call<vm_level<X>::ssp>(P, B.program_plus1 - 1u, io);
+            rxvm::shade_call<feat<LV>.ssp>(P, B.program_plus1 - 1u, io);
             r = io.color.x;
             g = io.color.y;
             b = io.color.z;
@@ -1034,7 +1023,7 @@ __device__ __forceinline__ uint32_t shade3d_opacity(const RasterParams &P, const
 }
 
 // one 2D fragment (rasterizer.rs:656-895); returns the new pixel
-template <int X>
+template <Level LV>
 __device__ __forceinline__ uint32_t fragment2d(const RasterParams &P, const Prim2D &T, const DevBatch &B, uint32_t px, uint32_t py,
                                                float fx, float fy, uint32_t dst) {
     // barycentric_weights_2d (rasterizer.rs:1731-1750)
@@ -1055,8 +1044,8 @@ __device__ __forceinline__ uint32_t fragment2d(const RasterParams &P, const Prim
     float gy = ((float)py - P.fheight / 2.0f) - (P.translationd2[1] - P.fheight / 2.0f);
     float wx = gx / P.scaled2, wy = gy / P.scaled2;
 
-    uint32_t texel = batch_texel<X, true>(P, B, u, v, wx, wy);  // 2D terrain: chunk.sample_terrain_texture(world, ..), :749-751
-    if constexpr (X >= 2) {
+    uint32_t texel = batch_texel<LV, true>(P, B, u, v, wx, wy);  // 2D terrain: chunk.sample_terrain_texture(world, ..), :749-751
+    if constexpr (feat<LV>.programs) {
         if (B.program_plus1 && P.programs[B.program_plus1 - 1u].shade_entry != 0xFFFFFFFFu) {  // :760-797
             const float INV_255 = 1.0f / 255.0f;  // pixel_to_vec4, lib.rs:52-62
             rxvm::IO io;
@@ -1069,7 +1058,7 @@ __device__ __forceinline__ uint32_t fragment2d(const RasterParams &P, const Prim
             io.time = rxvm::splat(P.time);
             io.roughness.x = 0.5f;
             io.metallic.x = 0.0f;
-            rxvm::shade_call<vm_level<X>::ssp>(P, B.program_plus1 - 1u, io);
+            rxvm::shade_call<feat<LV>.ssp>(P, B.program_plus1 - 1u, io);
             texel = pack4(f32_to_u8_saturated(io.color.x), f32_to_u8_saturated(io.color.y), f32_to_u8_saturated(io.color.z), 255u);
         }
     }
@@ -2001,7 +1990,7 @@ struct Vis {
     float alpha, beta;
     uint32_t slot;   // staged slot of the winner (fused small-scene path: its TriShade lives in LDS)
     uint32_t batch;  // batch of the winner
-    // opacity pass, feature level >= 1 only: the "staircase" of prefix minima.  surface_id (rasterizer.rs:1682) is read by the
+    // opacity pass, levels with the chunk paths only: the "staircase" of prefix minima.  surface_id (rasterizer.rs:1682) is read by the
     // opaque batches of chunk k when only the opacity batches of chunks <= k have run (:314-357), so a candidate with
     // submission index t must see the opacity winner among fragments with index < t.  A fragment is a prefix minimum iff
     // no fragment with a smaller index has z <= its z; the set is kept here (index ascending = z descending).  Of one
@@ -2110,33 +2099,33 @@ __device__ __forceinline__ void bary_depth(float v0x, float v0y, float v1x, floa
 // the encoded alpha of an opaque-pass fragment whose alpha does not follow from (texture, uv) alone -- a program
 // that may write `opacity` (:1403-1408), a terrain texel, a baked shader texture: the whole front half of the
 // fragment block has to run to know whether the fragment is written at all
-template <int X>
+template <Level LV>
 __device__ __forceinline__ bool fragment_alpha_is_255_body(const RasterParams &P, const TriShade *shade, uint32_t batch, float alpha, float beta,
                                                            float z, float fx, float fy) {
     const TriShade H = *shade;
     Frag F;
-    shade3d_begin<(X >= 2 ? vm_level<X>::out_of_line : X)>(P, H, batch, alpha, beta, z, fx, fy, F);  // levels 3 / 5: the interpreter out of line
+    shade3d_begin<feat<LV>.out_of_line>(P, H, batch, alpha, beta, z, fx, fy, F);  // (programs: the interpreter out of line)
     return f32_to_u8_saturated(F.opacity) == 255u;
 }
-// Level 2 keeps it out of line (the interpreter's registers).  Level 1 inlines it: a real call anywhere in a kernel makes the
+// Vm and VmS keep it out of line (the interpreter's registers).  Chunk inlines it: a real call anywhere in a kernel makes the
 // compiler reserve the call ABI's registers and wait for all memory traffic around it -- k_raster_chunk ran the bench
 // frame at 329 us against k_raster's 197 us with the SAME instruction count until its only call went away.
-template <int X>
+template <Level LV>
 __device__ __noinline__ bool fragment_alpha_is_255_call(const RasterParams &P, const TriShade *shade, uint32_t batch, float alpha, float beta,
                                                         float z, float fx, float fy) {
-    return fragment_alpha_is_255_body<X>(P, shade, batch, alpha, beta, z, fx, fy);
+    return fragment_alpha_is_255_body<LV>(P, shade, batch, alpha, beta, z, fx, fy);
 }
-template <int X>
+template <Level LV>
 __device__ __forceinline__ bool fragment_alpha_is_255_full(const RasterParams &P, const TriShade *shade, uint32_t batch, float alpha, float beta,
                                                            float z, float fx, float fy) {
-    if constexpr (X == 1 || !vm_level<X>::vis_programs) return fragment_alpha_is_255_body<1>(P, shade, batch, alpha, beta, z, fx, fy);
-    else return fragment_alpha_is_255_call<X>(P, shade, batch, alpha, beta, z, fx, fy);
+    if constexpr (!feat<LV>.vis_programs) return fragment_alpha_is_255_body<Level::Chunk>(P, shade, batch, alpha, beta, z, fx, fy);
+    else return fragment_alpha_is_255_call<LV>(P, shade, batch, alpha, beta, z, fx, fy);
 }
 
 // ASC: the caller walks its candidates in ascending submission index from a fresh Vis, so a tie in z can never go to the candidate
 // (the reference's strict `z < z_buffer`, :1060, in submission order); LEAN: the caller recovers the winner's slot and batch from
 // vis.best after its walk (scan_implicit: slot == index, the record is still staged) -- two selects fewer per candidate
-template <bool OPACITY, int X, bool ASC = false, bool LEAN = false>
+template <bool OPACITY, Level LV, bool ASC = false, bool LEAN = false>
 __device__ __forceinline__ void visit(const RasterParams &P, const TriSetup &S, const TriShade *shade, uint32_t t, uint32_t slot,
                                       uint32_t px, uint32_t py, float fx, float fy, Vis &vis, int surf_profile, const Vis *opf) {
     uint32_t min_x = S.bx & 0xFFFFu, max_x = S.bx >> 16, min_y = S.by & 0xFFFFu, max_y = S.by >> 16;
@@ -2152,7 +2141,7 @@ __device__ __forceinline__ void visit(const RasterParams &P, const TriSetup &S, 
     if (is_opacity != OPACITY) return;
     if (!OPACITY) {
         // surface_id[idx].is_some() && surface_id[idx] == batch.profile_id  (:1044-1048)
-        if constexpr (lvl1<X>) {
+        if constexpr (feat<LV>.chunk) {
             if (S.bflags & DB_HAS_PROFILE) {
                 const int sp = front_lookup(*opf, (int)t);
                 if (sp >= 0 && (uint32_t)sp == S.profile_id) return;
@@ -2165,11 +2154,11 @@ __device__ __forceinline__ void visit(const RasterParams &P, const TriSetup &S, 
     float alpha, beta, z;
     bary_depth(S.v0x, S.v0y, S.v1x, S.v1y, S.v2x, S.v2y, S.area, S.iz0, S.iz1, S.iz2, fx, fy, alpha, beta, z);
     const float gamma = 1.0f - alpha - beta;
-    if constexpr (OPACITY && lvl1<X>) front_insert(vis, z, (int)t, (S.bflags & DB_HAS_PROFILE) ? (int)S.profile_id : -1, (int)(S.bflags >> DB_GROUP_SHIFT), P.staircase_overflow);
+    if constexpr (OPACITY && feat<LV>.chunk) front_insert(vis, z, (int)t, (S.bflags & DB_HAS_PROFILE) ? (int)S.profile_id : -1, (int)(S.bflags >> DB_GROUP_SHIFT), P.staircase_overflow);
     bool take = z < vis.zmin || (!ASC && z == vis.zmin && vis.best >= 0 && (int)t < vis.best);
     if (take) {
-        if (lvl1<X> && !OPACITY && (S.bflags & DB_FULL_ALPHA)) {  // frames with such batches run k_raster_chunk / k_raster_vm (RasterParams.kernel_level)
-            take = fragment_alpha_is_255_full<X>(P, shade, S.batch, alpha, beta, z, fx, fy);
+        if (feat<LV>.chunk && !OPACITY && (S.bflags & DB_FULL_ALPHA)) {  // frames with such batches run k_raster_chunk / k_raster_vm (KernelLevel)
+            take = fragment_alpha_is_255_full<LV>(P, shade, S.batch, alpha, beta, z, fx, fy);
         } else if (!OPACITY && (S.bflags & DB_ALPHA_TEST)) {
             // the fragment is only written when its encoded alpha is 255 (:1408): sample it now
             const TriShade H = *shade;
@@ -2183,7 +2172,7 @@ __device__ __forceinline__ void visit(const RasterParams &P, const TriSetup &S, 
                 texel = sample_texture(d, texel_base(P, d), u, v, P.sample_mode, (H.pad[1] >> 26) & 3u);
             } else {
                 const DevBatch &B = P.batches3d[S.batch];
-                texel = batch_texel<X>(P, B, u, v, 0.0f, 0.0f);  // never a terrain batch: those carry DB_FULL_ALPHA
+                texel = batch_texel<LV>(P, B, u, v, 0.0f, 0.0f);  // never a terrain batch: those carry DB_FULL_ALPHA
             }
             take = (texel >> 24) == 255u;
         }
@@ -2274,7 +2263,7 @@ struct StageShade {
     TriShade shade[RXR_STAGE_TRIS];
 };
 
-// ---- row-parallel visibility (kernel k_raster_rows: binned scenes, feature level 0) -------------------------
+// ---- row-parallel visibility (kernel k_raster_rows: binned scenes, Level::Common) -------------------------
 // In the walk above every wave tests every candidate against its 64 pixels; with many small triangles (a mesh, the
 // 1 M-triangle box grid: ~20 candidates per tile, each covering ~20 of 256 pixels) more than nine lanes in ten do
 // nothing useful.  Row mode turns the loop inside out for such rounds: the work items are the ROWS of the candidates'
@@ -2339,7 +2328,7 @@ static_assert(RXR_ROWS_RING * 4u * (RXR_TILE_THREADS / 64) <= RXR_SORT2D_MAX * 4
 // from there (runs of one candidate are ~20 items long).
 // INDIRECT: candidate k's record is st.tri[rl.slot[k] * 6] (scan_lists_rows) instead of st.tri[k * 6]
 // PIX: pixel items (above); false = one item per row with an x loop, which the interpreter kernels with programs in their visibility
-// loop keep (levels 2 - 5).  The others (6 / 7 / 9) take pixel items WITH the compaction since the end of round 4: pixel items alone had
+// loop keep (LevelFeatures.pixel_items).  The others take pixel items WITH the compaction since the end of round 4: pixel items alone had
 // cost k_raster_vm_sv 3-4 % on the 1 M-triangle grid in round 3 (its register budget is spent on the interpreter); as 4-pixel runs with
 // the per-wave rings they save k_raster_vm_p 7 % and k_raster_vm_sv 6 % (scan_lists_rows)
 // SPLIT: a round that holds candidates row mode cannot take -- cut-outs, whose fragments need a texel (:1408); candidates with a profile id
@@ -2497,7 +2486,7 @@ __device__ __forceinline__ uint32_t rows_round(const RasterParams &P, Stage &st,
                             const DevTexDesc d{H.pad[0], H.pad[1] & 0x1FFFu, (H.pad[1] >> 13) & 0x1FFFu, (H.pad[1] >> 28) & 3u};
                             texel = sample_texture(d, texel_base(P, d), u, v, P.sample_mode, (H.pad[1] >> 26) & 3u);
                         } else {
-                            texel = batch_texel<0>(P, P.batches3d[__float_as_uint(q4.w)], u, v, 0.0f, 0.0f);
+                            texel = batch_texel<Level::Common>(P, P.batches3d[__float_as_uint(q4.w)], u, v, 0.0f, 0.0f);
                         }
                         wins = (texel >> 24) == 255u;
                     }
@@ -2672,7 +2661,7 @@ __device__ __forceinline__ void rows_resolve(const RasterParams &P, const RowLds
 //   3. all 256 threads copy the survivors' 96-byte TriSetup records into LDS with coalesced 16-byte
 //      loads,
 //   4. every lane walks the staged records (uniform LDS addresses -> broadcast reads).
-template <bool OPACITY, int X>
+template <bool OPACITY, Level LV>
 __device__ __forceinline__ void scan_lists(const RasterParams &P, Stage &st, uint32_t b0, uint32_t b1, uint32_t tile_x0,
                                            uint32_t tile_y0px, uint32_t px, uint32_t py, float fx, float fy, Vis &vis,
                                            int surf_profile, const Vis *opf, RowLds *rl = nullptr) {
@@ -2729,19 +2718,19 @@ __device__ __forceinline__ void scan_lists(const RasterParams &P, Stage &st, uin
         }
         __syncthreads();
         // 4. walk (or, for rounds of small triangles, the rows of their boxes: rows_round)
-        if constexpr (!OPACITY && X == 0) {
+        if constexpr (!OPACITY && !feat<LV>.chunk && !feat<LV>.programs) {
             if (rl != nullptr && rows_round<false, true>(P, st, *rl, n, tile_x0, tile_y0px)) continue;
         }
         for (uint32_t k = 0; k < n; ++k) {
             const TriSetup &S = *reinterpret_cast<const TriSetup *>(&st.tri[k * 6u]);
             const uint32_t t = st.ids[k];
-            visit<OPACITY, X>(P, S, &P.tri_shade[t], t, k, px, py, fx, fy, vis, surf_profile, opf);
+            visit<OPACITY, LV>(P, S, &P.tri_shade[t], t, k, px, py, fx, fy, vis, surf_profile, opf);
         }
         __syncthreads();  // the stage is reused by the next round
     }
 }
 
-// scan_lists for k_raster_rows (opaque pass, feature level 0).  Binned scenes of small triangles are bound by the chain of
+// scan_lists for k_raster_rows (opaque pass, Level::Common).  Binned scenes of small triangles are bound by the chain of
 // dependent memory latencies per tile, not by arithmetic, so this variant stages FIRST and tests afterwards: the records
 // of all list entries of the round go to LDS as soon as their ids are known, the tile-level reject runs on the LDS copies
 // and compacts slot numbers instead of moving records -- one global round trip fewer than scan_lists (which reads the
@@ -2749,7 +2738,7 @@ __device__ __forceinline__ void scan_lists(const RasterParams &P, Stage &st, uin
 // SPLITR (k_raster_rows_cut*: frames with cut-out or profiled batches, RasterParams.split_rounds): rounds run in row mode around the
 // candidates row mode cannot take (rows_round SPLIT) instead of being walked as a whole.  A variant of its own, not a branch: compiled into
 // the plain kernels the few extra lines cost the 1 M-triangle grid 2-9 % through register allocation alone (profiles/r04/HISTORY).
-template <int X, bool SPLITR = false>
+template <Level LV, bool SPLITR = false>
 __device__ __forceinline__ void scan_lists_rows(const RasterParams &P, Stage &st, RowLds &rl, bool row_mode, uint32_t b0, uint32_t b1,
                                                 uint32_t tile_x0, uint32_t tile_y0px, uint32_t px, uint32_t py, float fx, float fy, Vis &vis,
                                                 int surf_profile, const Vis *opf, uint32_t *queue PHASE_PARAM) {
@@ -2799,8 +2788,7 @@ __device__ __forceinline__ void scan_lists_rows(const RasterParams &P, Stage &st
         __syncthreads();
         // 4. the rows of the candidates' boxes, or the walk
         PHASE_MARK(1);
-        // (levels 6 / 7 / 9 kept row items until the end of round 4; levels 2 - 5 still do: rows_round, PIX)
-        constexpr bool pixel_items = X < 2 || X == 8 || X == 9 || X == 6 || X == 7;
+        constexpr bool pixel_items = feat<LV>.pixel_items;  // (false: row items until the end of round 4, rows_round PIX)
         if constexpr (SPLITR) {
             // the candidates every pixel walks: all of the round when row mode refuses it (0), else the ones row mode left over (2: cut-outs;
             // profiled ones under an opacity pass -- rows_round SPLIT wrote their bits in front of its barriers; their records are untouched)
@@ -2823,7 +2811,7 @@ __device__ __forceinline__ void scan_lists_rows(const RasterParams &P, Stage &st
                         const uint32_t sl = rl.slot[k];
                         const TriSetup &S = *reinterpret_cast<const TriSetup *>(&st.tri[sl * 6u]);
                         const uint32_t t = st.ids[k];
-                        visit<false, X>(P, S, &P.tri_shade[t], t, sl, px, py, fx, fy, vis, surf_profile, opf);
+                        visit<false, LV>(P, S, &P.tri_shade[t], t, sl, px, py, fx, fy, vis, surf_profile, opf);
                     }
                 }
                 __syncthreads();  // the stage is reused by the next round
@@ -2840,7 +2828,7 @@ __device__ __forceinline__ void scan_lists_rows(const RasterParams &P, Stage &st
                 const uint32_t sl = rl.slot[k];
                 const TriSetup &S = *reinterpret_cast<const TriSetup *>(&st.tri[sl * 6u]);
                 const uint32_t t = st.ids[k];
-                visit<false, X>(P, S, &P.tri_shade[t], t, sl, px, py, fx, fy, vis, surf_profile, opf);
+                visit<false, LV>(P, S, &P.tri_shade[t], t, sl, px, py, fx, fy, vis, surf_profile, opf);
             }
             __syncthreads();  // the stage is reused by the next round
             PHASE_MARK(10);
@@ -2853,7 +2841,7 @@ __device__ __forceinline__ void scan_lists_rows(const RasterParams &P, Stage &st
 // written their records): no lists at all.  All records are copied to LDS with one round of coalesced
 // loads, THEN thread t tests record t against the tile from LDS and the survivors' indices are
 // ballot-compacted -- one global-memory latency per tile instead of three dependent ones.
-template <bool OPACITY, int X>
+template <bool OPACITY, Level LV>
 __device__ __forceinline__ void scan_implicit(const RasterParams &P, Stage &st, uint32_t tile_x0, uint32_t tile_y0px, uint32_t px, uint32_t py,
                                               float fx, float fy, Vis &vis, int surf_profile, const Vis *opf, uint32_t *win_flags = nullptr) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -2891,7 +2879,7 @@ __device__ __forceinline__ void scan_implicit(const RasterParams &P, Stage &st, 
         const uint32_t t = e & ~RXR_COVER_BIT;
         const TriSetup &S = *reinterpret_cast<const TriSetup *>(&st.tri[t * 6u]);
         if (e & RXR_COVER_BIT) visit_cover<true, true>(S, t, t, fx, fy, vis);
-        else visit<OPACITY, X, true, true>(P, S, &P.tri_shade[t], t, t, px, py, fx, fy, vis, surf_profile, opf);
+        else visit<OPACITY, LV, true, true>(P, S, &P.tri_shade[t], t, t, px, py, fx, fy, vis, surf_profile, opf);
     }
     // (LEAN: slot == index in this path, and the winner's record is still staged)
     vis.slot = (uint32_t)max(vis.best, 0);
@@ -2905,7 +2893,7 @@ __device__ __forceinline__ void scan_implicit(const RasterParams &P, Stage &st, 
 // staging round holds them all): no k_setup3d / k_scan / k_fill launches and no records in HBM --
 // thread t builds triangle t's TriSetup / TriShade itself (make_setup), tests its pixel box against
 // the tile, survivors are ballot-compacted straight into LDS, then every lane walks them.
-template <bool OPACITY, int X>
+template <bool OPACITY, Level LV>
 __device__ __forceinline__ void scan_fused(const RasterParams &P, Stage &st, StageShade &sh, uint32_t tile_x0, uint32_t tile_y0px, uint32_t px,
                                            uint32_t py, float fx, float fy, Vis &vis, int surf_profile, const Vis *opf) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -2939,7 +2927,7 @@ __device__ __forceinline__ void scan_fused(const RasterParams &P, Stage &st, Sta
     __syncthreads();
     for (uint32_t k = 0; k < n; ++k) {
         const TriSetup &SK = *reinterpret_cast<const TriSetup *>(&st.tri[k * 6u]);
-        visit<OPACITY, X>(P, SK, &sh.shade[k], st.ids[k], k, px, py, fx, fy, vis, surf_profile, opf);
+        visit<OPACITY, LV>(P, SK, &sh.shade[k], st.ids[k], k, px, py, fx, fy, vis, surf_profile, opf);
     }
     __syncthreads();  // a second pass (opacity, then opaque) rebuilds the stage
 }
@@ -2969,7 +2957,7 @@ __device__ __forceinline__ bool bresenham_hits(const Prim2D &Ln, int px, int py)
 }
 
 // one 2D primitive against this lane's pixel (rasterizer.rs:636-655 coverage, then fragment2d / the line colour)
-template <int X>
+template <Level LV>
 __device__ __forceinline__ uint32_t prim2d_pixel(const RasterParams &P, const Prim2D &T, uint32_t px, uint32_t py, float fx, float fy,
                                                  uint32_t color) {
     const uint32_t min_x = T.bx & 0xFFFFu, max_x = T.bx >> 16, min_y = T.by & 0xFFFFu, max_y = T.by >> 16;
@@ -2987,14 +2975,14 @@ __device__ __forceinline__ uint32_t prim2d_pixel(const RasterParams &P, const Pr
     if (in) {
         // (the primitive is the same for every lane: its batch header comes through the scalar cache, not as a vector load per wave)
         const DevBatch B = uniform_record(P.batches2d, T.batch_kind >> 2);
-        color = fragment2d<X>(P, T, B, px, py, fx, fy, color);
+        color = fragment2d<LV>(P, T, B, px, py, fx, fy, color);
     }
     return color;
 }
 
 // stages the Prim2D records of `n` primitive ids (st.ids-like array `ids`, already in submission order)
 // through LDS in rounds of RXR_STAGE_TRIS and applies them to this lane's pixel in order
-template <int X>
+template <Level LV>
 __device__ __forceinline__ uint32_t walk_prims2d(const RasterParams &P, Stage &st, const uint32_t *ids, uint32_t n, bool implicit_ids,
                                                  uint32_t px, uint32_t py, float fx, float fy, uint32_t color) {
     const uint32_t tid = threadIdx.x;
@@ -3009,7 +2997,7 @@ __device__ __forceinline__ uint32_t walk_prims2d(const RasterParams &P, Stage &s
         __syncthreads();
         for (uint32_t k = 0; k < m; ++k) {
             const Prim2D &T = *reinterpret_cast<const Prim2D *>(&st.tri[k * 6u]);
-            color = prim2d_pixel<X>(P, T, px, py, fx, fy, color);
+            color = prim2d_pixel<LV>(P, T, px, py, fx, fy, color);
         }
         __syncthreads();
     }
@@ -3038,7 +3026,7 @@ __device__ __forceinline__ bool d2_box_meets(const RasterParams &P, uint32_t til
 
 // The 2D pass of one tile (rasterizer.rs:501-553), strictly in submission order; the caller has checked that the union of the 2D
 // pixel boxes reaches the tile.  Uses the stage (and s_bin) of the workgroup: every thread of the workgroup must call it.
-template <int X>
+template <Level LV>
 __device__ __forceinline__ uint32_t pass2d(const RasterParams &P, Stage &stage, uint32_t *s_bin, uint32_t *s_sort, const uint32_t sort_cap, uint32_t bin,
                                            uint32_t tile_x0, uint32_t tile_y0px, uint32_t px, uint32_t py, float fx, float fy, uint32_t color) {
     const uint32_t tid = threadIdx.x;
@@ -3066,7 +3054,7 @@ __device__ __forceinline__ uint32_t pass2d(const RasterParams &P, Stage &stage, 
         }
         if (keep) stage.ids[off + before] = tid;
         __syncthreads();
-        if (n) color = walk_prims2d<X>(P, stage, stage.ids, n, false, px, py, fx, fy, color);
+        if (n) color = walk_prims2d<LV>(P, stage, stage.ids, n, false, px, py, fx, fy, color);
     } else {
         // candidates = [large 2D primitives whose box touches the tile] ++ [this tile's bin list], gathered
         // into LDS, sorted by primitive index (submission order), then staged and applied in order
@@ -3117,10 +3105,10 @@ __device__ __forceinline__ uint32_t pass2d(const RasterParams &P, Stage &stage, 
         const uint32_t n_cand = s_bin[2];
         if (n_cand > sort_cap) {
             // more candidates than the LDS sort holds: walk every primitive in order (correct, slow)
-            color = walk_prims2d<X>(P, stage, nullptr, P.n_prims2d, true, px, py, fx, fy, color);
+            color = walk_prims2d<LV>(P, stage, nullptr, P.n_prims2d, true, px, py, fx, fy, color);
         } else if (P.blockscan2d_cap) {
             // k_blockscan2d's lists are in submission order already, and the gather above keeps the order
-            color = walk_prims2d<X>(P, stage, s_sort, n_cand, false, px, py, fx, fy, color);
+            color = walk_prims2d<LV>(P, stage, s_sort, n_cand, false, px, py, fx, fy, color);
         } else {
             // bitonic sort of s_sort[0 .. n_cand) padded to the next power of two with 0xFFFFFFFF
             uint32_t n2 = 1;
@@ -3143,7 +3131,7 @@ __device__ __forceinline__ uint32_t pass2d(const RasterParams &P, Stage &stage, 
                     __syncthreads();
                 }
             }
-            color = walk_prims2d<X>(P, stage, s_sort, n_cand, false, px, py, fx, fy, color);
+            color = walk_prims2d<LV>(P, stage, s_sort, n_cand, false, px, py, fx, fy, color);
         }
     }
     return color;
@@ -3166,10 +3154,10 @@ struct RowStore {
 template <>
 struct RowStore<false> {};
 
-// SPANS: the kernel looks RasterParams.row_spans up (sparse frames).  The two common level-0 kernels of binned scenes exist in both forms
+// SPANS: the kernel looks RasterParams.row_spans up (sparse frames).  The two common Level::Common kernels of binned scenes exist in both forms
 // (k_raster_rows[_rl] / ..._sp): the look-up in front of every tile cost the dense bench frame 0.6 % when every kernel carried it
 // (profiles/r04/row_spans_lookup_cost_bench.txt); the small-scene kernels never take spans, the rarer levels always check.
-template <bool FUSED, int X, bool ROWS = false, bool RL = false, bool SPANS = (X != 0), bool SPLITR = false>
+template <bool FUSED, Level LV, bool ROWS = false, bool RL = false, bool SPANS = (feat<LV>.chunk || feat<LV>.programs), bool SPLITR = false>
 __device__ __forceinline__ void raster_tile(const RasterParams &P) {
     __shared__ Stage stage;
     __shared__ uint32_t s_bin[4];
@@ -3216,7 +3204,7 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
         if (P.background_kind == RXR_BG_VGRADIENT) {
             uint32_t i = sat_u8(rclamp(((float)py / P.fheight) * 128.0f, 0.0f, 128.0f));  // shader/vgradient.rs:11-15
             color = pack4(i, i, i, 255u);
-        } else if (lvl1<X> && P.background_kind == RXR_BG_GRID) {  // (editor-only: feature level >= 1, see rxr_upload_frame)
+        } else if (feat<LV>.chunk && P.background_kind == RXR_BG_GRID) {  // (editor-only: a chunk path, see rxr_upload_frame)
             color = grid_shade(P, px, py);
         } else if (P.background_kind == RXR_BG_HOST_PIXELS && in_frame) {
             color = P.bg_pixels[(size_t)py * P.width + px];
@@ -3257,16 +3245,16 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
         front_init(op);
         uint32_t op_color = 0u;  // the opacity winner is shaded at once: the opaque pass rebuilds the stage
         if (P.has_opacity) {
-            if constexpr (FUSED) scan_fused<true, X>(P, stage, shade_store.s, tile_x0, tile_y0px, px, py, fx, fy, op, -1, nullptr);
-            else if (P.fused_small == 2u) scan_implicit<true, X>(P, stage, tile_x0, tile_y0px, px, py, fx, fy, op, -1, nullptr);
-            else scan_lists<true, X>(P, stage, b0, b1, tile_x0, tile_y0px, px, py, fx, fy, op, -1, nullptr);
+            if constexpr (FUSED) scan_fused<true, LV>(P, stage, shade_store.s, tile_x0, tile_y0px, px, py, fx, fy, op, -1, nullptr);
+            else if (P.fused_small == 2u) scan_implicit<true, LV>(P, stage, tile_x0, tile_y0px, px, py, fx, fy, op, -1, nullptr);
+            else scan_lists<true, LV>(P, stage, b0, b1, tile_x0, tile_y0px, px, py, fx, fy, op, -1, nullptr);
             if (op.best >= 0) {
                 const DevBatch &OB = P.batches3d[op.batch];
                 surf_profile = (OB.flags & DB_HAS_PROFILE) ? (int)OB.profile_id : -1;
                 TriShade OS;
                 if constexpr (FUSED) OS = shade_store.s.shade[op.slot];
                 else OS = P.tri_shade[op.best];
-                op_color = shade3d_opacity<X>(P, OS, op.batch, op.alpha, op.beta, op.zmin, fx, fy);
+                op_color = shade3d_opacity<LV>(P, OS, op.batch, op.alpha, op.beta, op.zmin, fx, fy);
             }
             __syncthreads();  // everyone has copied its record before the stage is rebuilt
         }
@@ -3277,8 +3265,8 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
         uint32_t win_flags = 0u;  // the winner's batch flags, where the visibility pass had them at hand (scan_implicit)
         const bool have_flags = !FUSED && P.fused_small == 2u;  // (uniform)
         PHASE_MARK(0);
-        if constexpr (FUSED) scan_fused<false, X>(P, stage, shade_store.s, tile_x0, tile_y0px, px, py, fx, fy, vis, surf_profile, &op);
-        else if (P.fused_small == 2u) scan_implicit<false, X>(P, stage, tile_x0, tile_y0px, px, py, fx, fy, vis, surf_profile, &op, &win_flags);
+        if constexpr (FUSED) scan_fused<false, LV>(P, stage, shade_store.s, tile_x0, tile_y0px, px, py, fx, fy, vis, surf_profile, &op);
+        else if (P.fused_small == 2u) scan_implicit<false, LV>(P, stage, tile_x0, tile_y0px, px, py, fx, fy, vis, surf_profile, &op, &win_flags);
         else if (rows_binned) {
             // (the per-pixel surface_id of the opacity pass lives in the owning lane's registers: frames with opacity batches walk)
             if constexpr (ROWS) {
@@ -3287,23 +3275,23 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
                 // surface_id rule, :1044-1048): rounds with such a candidate walk, like rounds with cut-outs -- rows_round)
                 const bool row_mode = true;
                 if (row_mode) row_store.r.key[ly * RXR_TILE_W + lx] = RXR_ZKEY_INIT;  // own cell; published by the barriers of the first staging round
-                scan_lists_rows<X, SPLITR>(P, stage, row_store.r, row_mode, b0, b1, tile_x0, tile_y0px, px, py, fx, fy, vis, surf_profile, &op,
+                scan_lists_rows<LV, SPLITR>(P, stage, row_store.r, row_mode, b0, b1, tile_x0, tile_y0px, px, py, fx, fy, vis, surf_profile, &op,
                                    s_sort PHASE_ARG);
                 if (tid == 0 && my_bin_count) P.bin_count[bin] = 0u;  // (a non-empty list went through the barriers of a round)
                 PHASE_MARK(1);
                 if (row_mode) rows_resolve(P, row_store.r, lx, ly, fx, fy, vis, HS, hs_of);  // (the last round ended with a barrier)
                 PHASE_MARK(9);
             }
-        } else scan_lists<false, X>(P, stage, b0, b1, tile_x0, tile_y0px, px, py, fx, fy, vis, surf_profile, &op);
+        } else scan_lists<false, LV>(P, stage, b0, b1, tile_x0, tile_y0px, px, py, fx, fy, vis, surf_profile, &op);
 
         PHASE_MARK(1);
         // The opacity layer's colour and depth wait in LDS while the fragment is shaded (each thread its own two words of s_sort: the
         // 2D pass has not begun, and row mode -- whose fragment queue lives there -- does not run in frames with an opacity pass): the
         // shading code sits at the kernel's 64 registers, and values that are live across it without being used in it are what the
         // compiler sends to scratch memory (4 bytes per pixel and frame for the colour alone, in frames that have no opacity pass at all).
-        // (not in the level-1 kernels: k_raster_chunk[_rl] answered with MORE scratch -- 6 -> 20 spill instructions -- and ran 1.4 % slower)
+        // (not in the kernels of Level::Chunk: k_raster_chunk[_rl] answered with MORE scratch -- 6 -> 20 spill instructions -- and ran 1.4 % slower)
         static_assert(RXR_SORT2D_MAX >= 2 * RXR_TILE_THREADS, "two words per thread");
-        constexpr bool PARK_OPACITY = X != 1;
+        constexpr bool PARK_OPACITY = !feat<LV>.chunk || feat<LV>.programs;
         if (PARK_OPACITY && P.has_opacity) {  // (uniform)
             s_sort[tid] = op_color;
             s_sort[RXR_TILE_THREADS + tid] = __float_as_uint(op.best >= 0 ? op.zmin : 1.0f);
@@ -3318,13 +3306,13 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
         if (hit) {
             if constexpr (FUSED) HS = shade_store.s.shade[vis.slot];
             else if (!ROWS || hs_of != vis.best) HS = P.tri_shade[vis.best];
-            shade3d_begin<X, RL>(P, HS, vis.batch, vis.alpha, vis.beta, vis.zmin, fx, fy, F, have_flags, win_flags);
+            shade3d_begin<LV, RL>(P, HS, vis.batch, vis.alpha, vis.beta, vis.zmin, fx, fy, F, have_flags, win_flags);
         }
         PHASE_MARK(2);
-        if (P.n_lights) shade3d_lights<X, RL>(P, hit, F);  // wave-uniform call
+        if (P.n_lights) shade3d_lights<LV, RL>(P, hit, F);  // wave-uniform call
         PHASE_MARK(3);
-        color = hit ? shade3d_end<X, RL>(F) : pack4(0u, 0u, 0u, 255u);
-        if constexpr (lvl1<X>) {
+        color = hit ? shade3d_end<LV, RL>(F) : pack4(0u, 0u, 0u, 255u);
+        if constexpr (feat<LV>.chunk) {
             if (P.has_brush && !hit) color = miss_brush_preview(P, px, py);  // :435-458
         }
         PHASE_MARK(4);
@@ -3354,7 +3342,7 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
     // (a primitive only ever writes inside its box: :636-655, :1777-1821)
     const bool d2_here = (P.flags & RXR_FLAG_D2_ACTIVE) && P.n_prims2d && d2_box_meets(P, tile_x0, tile_y0px);
     if (d2_here) {
-        color = pass2d<X>(P, stage, s_bin, s_sort, RXR_SORT2D_MAX, bin, tile_x0, tile_y0px, px, py, fx, fy, color);
+        color = pass2d<LV>(P, stage, s_bin, s_sort, RXR_SORT2D_MAX, bin, tile_x0, tile_y0px, px, py, fx, fy, color);
     }
 
     PHASE_MARK(5);
@@ -3371,7 +3359,7 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
     PHASE_FLUSH;
 }
 
-// ---- pairs of tiles (binned scenes, feature level 0, no opacity pass) ---------------------------------------------------------------
+// ---- pairs of tiles (binned scenes, Level::Common, no opacity pass) ---------------------------------------------------------------
 // A tile of a scene of small triangles spends a quarter of its instructions on what does not depend on its pixels: list bounds, the
 // staging of its ~20 candidates, the tile-level reject, the scans and the owner search of a row-mode round.  A workgroup of the pair
 // kernels takes TWO vertically adjacent tiles -- the bins stay 16 x 16, the pre-pass and the stripes of a multi-GPU launch are untouched
@@ -3381,7 +3369,7 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
 // visibility goes through the z-buffer's (z, index) keys here: a round that is walked (large triangles, cut-outs) merges each lane's
 // winner into the lane's own two cells, so no per-pixel state lives in registers across the rounds.  Same fragments, same arg-min,
 // same shading code: byte-identical to the single-tile kernels (tests/test_gpu_rows.py, the full-size configurations).
-template <int X>
+template <Level LV>
 __device__ __forceinline__ void scan_lists_pair(const RasterParams &P, Stage &st, RowLdsT<32> &rl, uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1,
                                                 uint32_t tile_x0, uint32_t tile_y0px, uint32_t lx, uint32_t ly) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -3443,7 +3431,7 @@ __device__ __forceinline__ void scan_lists_pair(const RasterParams &P, Stage &st
                 const uint32_t sl = rl.slot[k];
                 const TriSetup &S = *reinterpret_cast<const TriSetup *>(&st.tri[sl * 6u]);
                 const uint32_t t = st.ids[k];
-                visit<false, X>(P, S, &P.tri_shade[t], t, sl, px, py, fx, fy, vis, -1, nullptr);
+                visit<false, LV>(P, S, &P.tri_shade[t], t, sl, px, py, fx, fy, vis, -1, nullptr);
             }
             if (vis.best >= 0) {  // (z < 1.0: visit starts from the cleared buffer's 1.0, :1060)
                 // this lane's own cell; the rounds are separated by barriers, so nobody else touches it now
@@ -3456,9 +3444,9 @@ __device__ __forceinline__ void scan_lists_pair(const RasterParams &P, Stage &st
     }
 }
 
-template <int X, bool RL>
+template <Level LV, bool RL>
 __device__ __forceinline__ void raster_tile_pair(const RasterParams &P) {
-    static_assert(X == 0, "the pair kernels serve feature level 0");
+    static_assert(!feat<LV>.chunk && !feat<LV>.programs, "the pair kernels serve Level::Common");
     __shared__ Stage stage;
     __shared__ uint32_t s_bin[4];
     __shared__ RowLdsT<32> rl;
@@ -3476,7 +3464,7 @@ __device__ __forceinline__ void raster_tile_pair(const RasterParams &P) {
     const uint32_t b0 = min(start_b, P.list_capacity), b1 = min(start_b + cnt_b, P.list_capacity);
     rl.key[tid] = RXR_ZKEY_INIT;  // own cells; published by the barriers of the first staging round
     rl.key[RXR_TILE_THREADS + tid] = RXR_ZKEY_INIT;
-    scan_lists_pair<X>(P, stage, rl, a0, a1, b0, b1, tile_x0, tile_y0px, lx, ly);
+    scan_lists_pair<LV>(P, stage, rl, a0, a1, b0, b1, tile_x0, tile_y0px, lx, ly);
     if (tid == 0) {  // (a non-empty list went through the barriers of a round: every thread has read the counts)
         if (cnt_a) P.bin_count[bin_a] = 0u;
         if (cnt_b) P.bin_count[bin_b] = 0u;
@@ -3512,12 +3500,12 @@ __device__ __forceinline__ void raster_tile_pair(const RasterParams &P) {
         F.opacity = 0.0f;
         F.rough = 0.5f;
         F.metal = 0.0f;
-        if (hit) shade3d_begin<X, RL>(P, HS, vis.batch, vis.alpha, vis.beta, vis.zmin, fx, fy, F);
-        if (P.n_lights) shade3d_lights<X, RL>(P, hit, F);  // wave-uniform call
-        uint32_t color = hit ? shade3d_end<X, RL>(F) : pack4(0u, 0u, 0u, 255u);
+        if (hit) shade3d_begin<LV, RL>(P, HS, vis.batch, vis.alpha, vis.beta, vis.zmin, fx, fy, F);
+        if (P.n_lights) shade3d_lights<LV, RL>(P, hit, F);  // wave-uniform call
+        uint32_t color = hit ? shade3d_end<LV, RL>(F) : pack4(0u, 0u, 0u, 255u);
         const uint32_t tile_yh = tile_y0px + h * RXR_TILE_H;
         const bool d2_here = (P.flags & RXR_FLAG_D2_ACTIVE) && P.n_prims2d && d2_box_meets(P, tile_x0, tile_yh);
-        if (d2_here) color = pass2d<X>(P, stage, s_bin, reinterpret_cast<uint32_t *>(rl.key), 512u, h ? bin_b : bin_a, tile_x0, tile_yh, px, py, fx, fy, color);
+        if (d2_here) color = pass2d<LV>(P, stage, s_bin, reinterpret_cast<uint32_t *>(rl.key), 512u, h ? bin_b : bin_a, tile_x0, tile_yh, px, py, fx, fy, color);
         if (in_frame) {
             const int64_t row = P.compact ? (int64_t)((ty0 + h) * RXR_TILE_H + ly) : (int64_t)py - P.out_base_row;
             P.out[(size_t)row * P.out_row_stride + px] = color;
@@ -3533,76 +3521,72 @@ __device__ __forceinline__ const RasterParams &kernarg_params_early() { return *
 // instruction); read in place they are scalar loads at the point of use (17 spill instructions).  Measured A-B-A-B on one
 // box: bench frame 208 -> 198 us, the 1-light frame 126 -> 117 us.
 #ifdef RXR_JIT
-// the kernel of a run-time compiled program set, one template level per compilation (rxr_jit.hip compiles a level when the first
-// frame that needs it is launched): 2 = a program may decide visibility, 7 = none does, 8 = 7 without the chunk paths of level 1.
-// (1 M triangles with the configuration-C5 program, raster kernel: level 7 at 8 waves per SIMD (64 VGPRs) 656 us, 7: 676, 6: 710;
-// level 2 at 8: 695 us, 7: 666, 6: 694, 5: 763; level 8 at 8: 566 us -- the interpreter kernels take 1180 us)
+// the kernel of a run-time compiled program set, one level per compilation (rxr_jit.hip compiles a level when the first frame that
+// needs it is launched): RXR_JIT_LEVEL is one of jit_level_number, JIT_LV its level (jit_slot_level: Vm, VmV or JitPlain)
+// (1 M triangles with the configuration-C5 program, raster kernel: VmV at 8 waves per SIMD (64 VGPRs) 656 us, 7: 676, 6: 710;
+// Vm at 8: 695 us, 7: 666, 6: 694, 5: 763; JitPlain at 8: 566 us -- the interpreter kernels take 1180 us)
 #ifndef RXR_JIT_LEVEL
 #define RXR_JIT_LEVEL 8
 #endif
+static_assert(jit_slot_of_number(RXR_JIT_LEVEL) >= 0, "RXR_JIT_LEVEL is none of jit_level_number");
+constexpr Level JIT_LV = jit_slot_level[jit_slot_of_number(RXR_JIT_LEVEL)];
 #ifndef RXR_JIT_WAVES_PER_SIMD
-#define RXR_JIT_WAVES_PER_SIMD (RXR_JIT_LEVEL == 2 ? 7 : 8)
+#define RXR_JIT_WAVES_PER_SIMD (feat<JIT_LV>.vis_programs ? 7 : 8)
 #endif
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_JIT_WAVES_PER_SIMD) k_raster_jit(RasterParams) { raster_tile<false, RXR_JIT_LEVEL, true>(kernarg_params_early()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_JIT_WAVES_PER_SIMD) k_raster_jit(RasterParams) { raster_tile<false, JIT_LV, true>(kernarg_params_early()); }
+static_assert((RXR_JIT_LEVEL != 2) == !feat<JIT_LV>.vis_programs, "k_raster_jit_cut: the levels at which no program decides visibility");
 #if RXR_JIT_LEVEL != 2
 // ... and for frames with cut-out or profiled batches (RasterParams.split_rounds), as k_raster_rows_cut: the same code object carries both
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_JIT_WAVES_PER_SIMD) k_raster_jit_cut(RasterParams) { raster_tile<false, RXR_JIT_LEVEL, true, false, true, true>(kernarg_params_early()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_JIT_WAVES_PER_SIMD) k_raster_jit_cut(RasterParams) { raster_tile<false, JIT_LV, true, false, true, true>(kernarg_params_early()); }
 #endif
 #else
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_RASTER_WAVES_PER_SIMD) k_raster(RasterParams) { raster_tile<false, 0>(kernarg_params_early()); }
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS) k_raster_fused(RasterParams) { raster_tile<true, 0>(kernarg_params_early()); }
-// RXR_LIGHT_MATH=relaxed (RasterParams.relaxed_lights): the same kernels with the relaxed light loop (shade3d_lights<X, true>)
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_RASTER_WAVES_PER_SIMD) k_raster_rl(RasterParams) { raster_tile<false, 0, false, true>(kernarg_params_early()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_RASTER_WAVES_PER_SIMD) k_raster(RasterParams) { raster_tile<false, Level::Common>(kernarg_params_early()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS) k_raster_fused(RasterParams) { raster_tile<true, Level::Common>(kernarg_params_early()); }
+// RXR_LIGHT_MATH=relaxed (RasterParams.relaxed_lights): the same kernels with the relaxed light loop (shade3d_lights<LV, true>)
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_RASTER_WAVES_PER_SIMD) k_raster_rl(RasterParams) { raster_tile<false, Level::Common, false, true>(kernarg_params_early()); }
 // binned scenes (more than RXR_STAGE_TRIS triangles): the walk may switch to row mode per round (rows_round)
 #ifndef RXR_ROWS_WAVES_PER_SIMD
 #define RXR_ROWS_WAVES_PER_SIMD 8  // C5: unbounded (87 VGPRs, 5 waves) 797 us, 6: 718, 7: 727; with the parameter block in place 6: 654, 8: 628
 #endif
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_ROWS_WAVES_PER_SIMD) k_raster_rows(RasterParams) { raster_tile<false, 0, true>(kernarg_params_early()); }
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_ROWS_WAVES_PER_SIMD) k_raster_rows_rl(RasterParams) { raster_tile<false, 0, true, true>(kernarg_params_early()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_ROWS_WAVES_PER_SIMD) k_raster_rows(RasterParams) { raster_tile<false, Level::Common, true>(kernarg_params_early()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_ROWS_WAVES_PER_SIMD) k_raster_rows_rl(RasterParams) { raster_tile<false, Level::Common, true, true>(kernarg_params_early()); }
 // ... and for sparse frames (RasterParams.row_spans)
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_ROWS_WAVES_PER_SIMD) k_raster_rows_sp(RasterParams) { raster_tile<false, 0, true, false, true>(kernarg_params_early()); }
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_ROWS_WAVES_PER_SIMD) k_raster_rows_rl_sp(RasterParams) { raster_tile<false, 0, true, true, true>(kernarg_params_early()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_ROWS_WAVES_PER_SIMD) k_raster_rows_sp(RasterParams) { raster_tile<false, Level::Common, true, false, true>(kernarg_params_early()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_ROWS_WAVES_PER_SIMD) k_raster_rows_rl_sp(RasterParams) { raster_tile<false, Level::Common, true, true, true>(kernarg_params_early()); }
 // ... and for frames with cut-out batches (texel alpha) or, under an opacity pass, batches with a profile id (RasterParams.split_rounds):
 // rounds in row mode AROUND such candidates (scan_lists_rows SPLITR) -- two batches with a fence texture among the 96 of the reduced box
 // grid: 98.5 -> 72 us, one in eight: 131 -> 79 us; kernels of their own so that the plain ones stay what they are
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_ROWS_WAVES_PER_SIMD) k_raster_rows_cut(RasterParams) { raster_tile<false, 0, true, false, true, true>(kernarg_params_early()); }
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_ROWS_WAVES_PER_SIMD) k_raster_rows_cut_rl(RasterParams) { raster_tile<false, 0, true, true, true, true>(kernarg_params_early()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_ROWS_WAVES_PER_SIMD) k_raster_rows_cut(RasterParams) { raster_tile<false, Level::Common, true, false, true, true>(kernarg_params_early()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_ROWS_WAVES_PER_SIMD) k_raster_rows_cut_rl(RasterParams) { raster_tile<false, Level::Common, true, true, true, true>(kernarg_params_early()); }
 // two tiles per workgroup (raster_tile_pair): binned scenes without an opacity pass, launches whose tile rows are adjacent
 #ifndef RXR_PAIR_WAVES_PER_SIMD
 #define RXR_PAIR_WAVES_PER_SIMD 8
 #endif
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_PAIR_WAVES_PER_SIMD) k_raster_pair(RasterParams) { raster_tile_pair<0, false>(kernarg_params_early()); }
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_PAIR_WAVES_PER_SIMD) k_raster_pair_rl(RasterParams) { raster_tile_pair<0, true>(kernarg_params_early()); }
-// feature levels (template parameter X) so that the common kernels above carry none of the rarer paths:
-//   1  k_raster_chunk: chunk textures -- terrain texels sampled by world position, baked shader textures, and the
-//      full-fragment alpha test they need
-//   2  k_raster_vm:    level 1 + Rusteria programs; the interpreter (rxr_vm.h) keeps its state in scratch memory
-// These two contain real (out-of-line) calls that take the parameter block by reference.  Handing them the by-value
-// kernel argument would make the compiler copy all of it to scratch and turn every P.field into a scratch load
-// (measured: 3.5x on the whole kernel); the kernarg segment itself is addressable, so they read it in place.
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_PAIR_WAVES_PER_SIMD) k_raster_pair(RasterParams) { raster_tile_pair<Level::Common, false>(kernarg_params_early()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_PAIR_WAVES_PER_SIMD) k_raster_pair_rl(RasterParams) { raster_tile_pair<Level::Common, true>(kernarg_params_early()); }
+// the rarer levels (rxr_device.h): k_raster_chunk -- chunk textures and the full-fragment alpha test they need -- and k_raster_vm, whose
+// interpreter (rxr_vm.h) keeps its state in scratch memory.  These two contain real (out-of-line) calls that take the parameter block
+// by reference.  Handing them the by-value kernel argument would make the compiler copy all of it to scratch and turn every P.field
+// into a scratch load (measured: 3.5x on the whole kernel); the kernarg segment itself is addressable, so they read it in place.
 __device__ __forceinline__ const RasterParams &kernarg_params() {
     return *(const RasterParams *)__builtin_amdgcn_kernarg_segment_ptr();
 }
-// Bench frame forced through this kernel (RXR_MIN_KERNEL_LEVEL=1): unbounded (97 VGPRs, 5 waves per SIMD) 297 us, 6: 230, 7: 219,
+// Bench frame forced through k_raster_chunk (RXR_MIN_KERNEL_LEVEL=1): unbounded (97 VGPRs, 5 waves per SIMD) 297 us, 6: 230, 7: 219,
 // 8: 209 (k_raster: 197).  Before the staircase left scratch memory (front_insert) and the last real call was inlined it
 // took 330 us with the same VALU instruction count: per-wave latency, not arithmetic.
 #ifndef RXR_CHUNK_WAVES_PER_SIMD
 #define RXR_CHUNK_WAVES_PER_SIMD 8
 #endif
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_CHUNK_WAVES_PER_SIMD) k_raster_chunk(RasterParams) { raster_tile<false, 1, true>(kernarg_params()); }
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_CHUNK_WAVES_PER_SIMD) k_raster_chunk_rl(RasterParams) { raster_tile<false, 1, true, true>(kernarg_params()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_CHUNK_WAVES_PER_SIMD) k_raster_chunk(RasterParams) { raster_tile<false, Level::Chunk, true>(kernarg_params()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_CHUNK_WAVES_PER_SIMD) k_raster_chunk_rl(RasterParams) { raster_tile<false, Level::Chunk, true, true>(kernarg_params()); }
 // ... and with rounds in row mode around cut-out / profiled candidates (RasterParams.split_rounds), as k_raster_rows_cut*
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_CHUNK_WAVES_PER_SIMD) k_raster_chunk_cut(RasterParams) { raster_tile<false, 1, true, false, true, true>(kernarg_params()); }
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_CHUNK_WAVES_PER_SIMD) k_raster_chunk_cut_rl(RasterParams) { raster_tile<false, 1, true, true, true, true>(kernarg_params()); }
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_VM_WAVES_PER_SIMD) k_raster_vm(RasterParams) { raster_tile<false, 2, true>(kernarg_params()); }
-// the same with the wave-uniform stack pointer, for sets whose programs all have static stack depths (kernel_level 3)
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_VM_WAVES_PER_SIMD) k_raster_vm_s(RasterParams) { raster_tile<false, 4, true>(kernarg_params()); }
-// ... and without interpreter calls in the visibility loop (kernel_level 4; vm_level<6>)
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_VM_WAVES_PER_SIMD) k_raster_vm_sv(RasterParams) { raster_tile<false, 6, true>(kernarg_params()); }
-// level 9 = 6 without the chunk paths of level 1, for frames that use none of them (RasterParams.plain_programs, rxr_upload_frame)
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_VM_WAVES_PER_SIMD) k_raster_vm_p(RasterParams) { raster_tile<false, 9, true>(kernarg_params()); }
-// the per-lane stack pointer without interpreter calls in the visibility loop (kernel_level 5; vm_level<7>)
-extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_VM_WAVES_PER_SIMD) k_raster_vm_v(RasterParams) { raster_tile<false, 7, true>(kernarg_params()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_CHUNK_WAVES_PER_SIMD) k_raster_chunk_cut(RasterParams) { raster_tile<false, Level::Chunk, true, false, true, true>(kernarg_params()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_CHUNK_WAVES_PER_SIMD) k_raster_chunk_cut_rl(RasterParams) { raster_tile<false, Level::Chunk, true, true, true, true>(kernarg_params()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_VM_WAVES_PER_SIMD) k_raster_vm(RasterParams) { raster_tile<false, Level::Vm, true>(kernarg_params()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_VM_WAVES_PER_SIMD) k_raster_vm_s(RasterParams) { raster_tile<false, Level::VmS, true>(kernarg_params()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_VM_WAVES_PER_SIMD) k_raster_vm_sv(RasterParams) { raster_tile<false, Level::VmSV, true>(kernarg_params()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_VM_WAVES_PER_SIMD) k_raster_vm_p(RasterParams) { raster_tile<false, Level::VmP, true>(kernarg_params()); }
+extern "C" __global__ void __launch_bounds__(RXR_TILE_THREADS, RXR_VM_WAVES_PER_SIMD) k_raster_vm_v(RasterParams) { raster_tile<false, Level::VmV, true>(kernarg_params()); }
 
 #if RXR_PHASE_TIMING
 extern "C" int rxr_debug_phase_read(unsigned long long *out16, int reset) {

@@ -1,6 +1,7 @@
 // rxr_route.h -- which raster kernel a launch gets.  Plain C++ (no HIP): the one decision behind rxr_launch_raster_grid and
 // rxr_raster_takes_spans (rxr_kernels.hip), compiled on its own by tests/test_raster_route_cpu.py.
 #pragma once
+#include "rxr_device.h"  // KernelLevel (the part of it that is plain C++)
 
 namespace rxr_route {
 
@@ -18,7 +19,7 @@ enum Route {
 // what a launch's RasterParams say (rxr_upload.hip, phase RasterParams; render_impl for fused_small) and the two environment
 // switches, which the caller reads per launch (the tests switch them)
 struct Facts {
-    unsigned kernel_level;  // 0 .. 5
+    unsigned kernel_level;  // KernelLevel
     bool plain_programs;
     unsigned fused_small;   // 0 binned, 1 fused (RXR_SMALL_MODE=1, at most RXR_STAGE_TRIS triangles), 2 implicit list
     bool d3_active;         // RXR_FLAG_D3_ACTIVE
@@ -42,8 +43,8 @@ struct Choice {
 inline bool rounds_cut(bool split_rounds, unsigned fused_small, bool d3_active) { return split_rounds && fused_small == 0u && d3_active; }
 
 //   fact                                                                                  kernel
-//   kernel_level 5 / 4 + plain_programs / 4 / 3 / 2                                       k_raster_vm_v / _p / _sv / _s / k_raster_vm
-//   kernel_level 1 (chunk textures, RXR_MIN_KERNEL_LEVEL=1)                               k_raster_chunk   [_cut: rounds_cut] [_rl]
+//   KL_VM_V / KL_VM_SV + plain_programs / KL_VM_SV / KL_VM_S / KL_VM                      k_raster_vm_v / _p / _sv / _s / k_raster_vm
+//   KL_CHUNK (chunk textures, RXR_MIN_KERNEL_LEVEL=1)                                     k_raster_chunk   [_cut: rounds_cut] [_rl]
 //   fused_small 1                                                                         k_raster_fused
 //   binned 3D frame (fused_small 0), RXR_PAIR_TILES=1, no opacity pass, tile_stride 1     k_raster_pair    [_rl]
 //   binned, split_rounds                                                                  k_raster_rows_cut [_rl]
@@ -51,15 +52,15 @@ inline bool rounds_cut(bool split_rounds, unsigned fused_small, bool d3_active) 
 //   binned                                                                                k_raster_rows    [_rl]
 //   small frame (fused_small 2), no 3D pass, RXR_NO_ROWS                                  k_raster         [_rl]
 //   _rl: Facts.rl with the 3D pass active (frames without a 3D light loop: one kernel for both modes)
-// Every level >= 1 looks the spans up, and so do k_raster_rows_cut* and the two _sp kernels; the small-scene kernels, the pair
+// Every level above KL_COMMON looks the spans up, and so do k_raster_rows_cut* and the two _sp kernels; the small-scene kernels, the pair
 // kernels and plain k_raster_rows* never do (raster_tile SPANS).
 inline Choice raster_route(const Facts &f) {
     const bool rl = f.rl && f.d3_active;
-    if (f.kernel_level >= 5u) return {VM_V, true, false};
-    if (f.kernel_level == 4u) return {f.plain_programs ? VM_P : VM_SV, true, false};
-    if (f.kernel_level == 3u) return {VM_S, true, false};
-    if (f.kernel_level == 2u) return {VM, true, false};
-    if (f.kernel_level == 1u) {
+    if (f.kernel_level >= KL_VM_V) return {VM_V, true, false};
+    if (f.kernel_level == KL_VM_SV) return {f.plain_programs ? VM_P : VM_SV, true, false};
+    if (f.kernel_level == KL_VM_S) return {VM_S, true, false};
+    if (f.kernel_level == KL_VM) return {VM, true, false};
+    if (f.kernel_level == KL_CHUNK) {
         if (rounds_cut(f.split_rounds, f.fused_small, f.d3_active)) return {rl ? CHUNK_CUT_RL : CHUNK_CUT, true, false};
         return {rl ? CHUNK_RL : CHUNK, true, false};
     }

@@ -572,7 +572,7 @@ struct FrameBuild {
     bool emissive_writer_3d = false;        // a visible 3D batch (either pass) runs a program that contains SetEmissive
     bool opaque_without_emissive = false;   // a visible opaque-pass 3D batch whose fragments do NOT assign emissive themselves
     uint32_t reads_2d = 0;  // PF_* read-before-written by the programs of visible 2D batches
-    int32_t first_opacity_chunk = -1;  // opacity batches in two or more chunks: surface_id needs the exact prefix order (level 1)
+    int32_t first_opacity_chunk = -1;  // opacity batches in two or more chunks: surface_id needs the exact prefix order (KL_CHUNK)
     bool seen_profiled_opaque = false; // ... and so does an opacity batch submitted AFTER an opaque batch that carries a profile id:
                                        // that opaque batch must not see it (rasterizer.rs:314-357; found by tools/fuzz_sweep.py)
     uint32_t opacity_group = 0;  // (header3d)
@@ -1290,16 +1290,16 @@ struct FrameBuild {
                         "reference that batch's fragments would add the emissive of whichever fragment ran before them in the tile");
         ctx->frame_uses_programs = uses_programs;
         P.vm_code = (const uint32_t *)ctx->d_vm_code.p;
-        // (the brush preview and the grid background are editor-only: they live in the feature levels >= 1 so that k_raster does not
+        // (the brush preview and the grid background are editor-only: they live in the levels with the chunk paths so that k_raster does not
         // carry them -- merely compiling the grid shader into it cost the bench frame 9 % more VALU instructions in SGPR spills)
         const bool editor_paths = (P.has_brush && (f->flags & RXR_FLAG_D3_ACTIVE)) || f->background_kind == RXR_BG_GRID;
-        P.kernel_level = std::max(ctx->min_kernel_level, uses_programs ? 2u : ((uses_chunk_tex || editor_paths) ? 1u : 0u));
-        ctx->frame_needs_chunk_paths = uses_chunk_tex || editor_paths || ctx->min_kernel_level >= 1u;  // (rxr_jit_launch: level 8 otherwise)
+        P.kernel_level = std::max<uint32_t>(ctx->min_kernel_level, uses_programs ? KL_VM : ((uses_chunk_tex || editor_paths) ? KL_CHUNK : KL_COMMON));
+        ctx->frame_needs_chunk_paths = uses_chunk_tex || editor_paths || ctx->min_kernel_level >= KL_CHUNK;  // (rxr_jit_launch: JIT_PLAIN otherwise)
         P.plain_programs = (!ctx->frame_needs_chunk_paths && !getenv("RXR_NO_PLAIN_PROGRAMS")) ? 1u : 0u;
         {
             // RXR_LIGHT_MATH (read per frame; rxr_set_light_math sets the context's own default): "exact" -- the light loop in the
             // reference's correctly rounded operations; "relaxed" -- point lights through rsq / rcp products, within the 1-per-channel
-            // tolerance of lit 3D fragments (shade3d_lights<X, true>; feature levels 0 and 1)
+            // tolerance of lit 3D fragments (shade3d_lights<LV, true>; Level::Common and Level::Chunk)
             const char *lm = getenv("RXR_LIGHT_MATH");
             P.relaxed_lights = lm ? (lm[0] == 'r' ? 1u : 0u) : (ctx->relaxed_lights ? 1u : 0u);
             // the fused point-light term multiplies where the reference branches (a light out of range contributes intensity * 0): with an
@@ -1319,11 +1319,11 @@ struct FrameBuild {
                 if (v >= 1e-4f) P.rl_flip_guard = v;
             }
         }
-        if (P.kernel_level == 2u && uses_programs && ctx->programs_static) P.kernel_level = 3u;  // k_raster_vm_s: wave-uniform stack pointer
+        if (P.kernel_level == KL_VM && uses_programs && ctx->programs_static) P.kernel_level = KL_VM_S;  // k_raster_vm_s: wave-uniform stack pointer
         // k_raster_vm_sv: ... and no program decides whether an opaque fragment is written, so the visibility loop is the one of
         // k_raster_chunk, without a call of the interpreter in it
-        if (P.kernel_level == 3u && !vis_programs && !getenv("RXR_VM_VIS_CALLS")) P.kernel_level = 4u;
-        else if (P.kernel_level == 2u && uses_programs && !vis_programs && !getenv("RXR_VM_VIS_CALLS")) P.kernel_level = 5u;  // k_raster_vm_v
+        if (P.kernel_level == KL_VM_S && !vis_programs && !getenv("RXR_VM_VIS_CALLS")) P.kernel_level = KL_VM_SV;
+        else if (P.kernel_level == KL_VM && uses_programs && !vis_programs && !getenv("RXR_VM_VIS_CALLS")) P.kernel_level = KL_VM_V;  // k_raster_vm_v
         P.programs = (const DevProgram *)ctx->d_programs.p;
         P.patterns = (const DevPattern *)ctx->d_patterns.p;
         P.pattern_data = (const float *)ctx->d_pattern_data.p;

@@ -1,4 +1,4 @@
-"""The two arithmetic modes of the 3D direct-light loop (rxr_set_light_math, include/rxr.h; shade3d_lights<X, RL> in
+"""The two arithmetic modes of the 3D direct-light loop (rxr_set_light_math, include/rxr.h; shade3d_lights<LV, RL> in
 rusterix_amd/csrc/rxr_kernels.hip) against the CPU oracle.
 
 Reference path: src/rasterizer.rs:1373-1391 (the light loop), src/map/light.rs:491-552 (CompiledLight::radiance_at /

@@ -5,14 +5,18 @@ block; per out-of-line device function its whole body.  Normalised: comments, bl
 
     tools/kernel_text_sha.py rxr_kernels.s               # name, sha of the text, sha of the descriptor
     tools/kernel_text_sha.py before.s after.s            # the same side by side; exit status 1 when a column differs
+    tools/kernel_text_sha.py --rename NEW=OLD before.s after.s   # a symbol whose mangled name had to change: NEW reads as OLD everywhere
 """
 import hashlib
 import re
 import sys
 
 
-def functions(path):
-    lines = open(path).read().split("\n")
+def functions(path, renames=()):
+    text = open(path).read()
+    for new, old in renames:
+        text = text.replace(new, old)
+    lines = text.split("\n")
     out, desc = {}, {}
     i = 0
     while i < len(lines):
@@ -44,8 +48,15 @@ def sha(lines):
     return hashlib.sha256("\n".join(lines).encode()).hexdigest()[:16] if lines is not None else "-" * 16
 
 
-def main(paths):
-    tables = [functions(p) for p in paths]
+def main(args):
+    renames, paths = [], []
+    while args:
+        a = args.pop(0)
+        if a == "--rename":
+            renames.append(tuple(args.pop(0).split("=", 1)))
+        else:
+            paths.append(a)
+    tables = [functions(p, renames) for p in paths]
     names = sorted(set().union(*(t[0] for t in tables)), key=lambda n: (n not in tables[0][1], n))
     differ = 0
     for n in names:
