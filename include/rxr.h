@@ -768,7 +768,9 @@ int rxr_check_terrain_heights(const float scale[2], const int32_t *cell_xy, cons
 /* makes a terrain's heights resident (they stay until the next call; n_cells == 0 registers the empty terrain, a plane at 0).
  * cell_height[i] is what Terrain::get_height returns for cell_xy[i] (the caller flattens chunk.processed_heights where a chunk has
  * them, else chunk.heights, src/terrain/chunk.rs:81-95); any f32 bit pattern is legal.  A coordinate given twice: the later entry wins.  The library keeps a dense f32 grid over the cells' bounding
- * rectangle; cells outside it and cells not listed are 0.0, the reference's answer.  Independent of rxr_set_terrain: buffers and
+ * rectangle; cells outside it and cells not listed are 0.0, the reference's answer -- and, over the same rectangle, which cells
+ * were listed (rxr_terrain_meshes: they are the cells of the chunk meshes).  Re-registration waits for queued picks and mesh
+ * builds.  Independent of rxr_set_terrain: buffers and
  * scale of its own; either may be registered without the other.  Arrays are read before the call returns.  A refused call leaves
  * the resident heights as they were.  Multi-device handles: member 0.
  * Replaces: Terrain::get_height, src/terrain/mod.rs:82-89. */
@@ -792,6 +794,38 @@ int rxr_terrain_hits(rxr_ctx *ctx, const float *origins, const float *dirs, uint
  * Multi-device handles: RXR_ERR_UNSUPPORTED (use rxr_member). */
 int rxr_terrain_hits_to(rxr_ctx *ctx, const float *dev_origins, const float *dev_dirs, uint32_t n_rays, float max_distance,
                         uint32_t *dev_hit, float *dev_t, float *dev_world_pos, int32_t *dev_grid_pos, void *hip_stream);
+
+/* ---- terrain chunk meshes: TerrainChunk::build_mesh (rusterix_amd/csrc/rxr_terrain_mesh.hip) --------------------------------------
+ * The Batch3D a chunk's terrain texture is drawn on (src/terrain/chunk.rs:253-297) with its vertex normals
+ * (Batch3D::compute_vertex_normals, src/batch/batch3d.rs:771-809), from the resident heights, exact to the bit.  A cell of chunk
+ * (cx, cy) -- world cells cx * chunk_size .. + chunk_size - 1, likewise in y -- is PRESENT iff rxr_set_terrain_heights listed it
+ * (twice is present; a listed 0.0 is present, an unlisted cell is not): the caller lists the keys of processed_heights.  The
+ * reference walks a hash map, so its numbering is whatever the hash gives; this is THE MESH IT BUILDS WHEN THE CELLS ARE VISITED IN
+ * ASCENDING (ly, lx), row by row:
+ *   per present cell, its corners (0,0), (1,0), (0,1), (1,1) that no earlier cell made get the next vertex indices; a vertex is
+ *   [X as f32 * scale.x, get_height(X, Y), Y as f32 * scale.y, 1.0], (X, Y) the corner in world cells; the cell's triangles are
+ *   (i0, i2, i1) and (i1, i2, i3).  Normals start at +0.0; per triangle in index order normalized(cross(p1 - p0, p2 - p0)) is added
+ *   to its three vertices; each sum is divided by its count and normalised again.
+ * Kept as it is: the last row and column of corners read the neighbouring chunks' heights, or 0.0 where no cell is listed; uvs are
+ * all [0, 0] and do not cross this boundary; a NaN height gives NaN normals (a NaN is a NaN: sign and payload are the device's); a
+ * sum of length zero divides by zero.  build_mesh_d2 and process_batch_modifiers are host work and not part of this. */
+#define RXR_TERRAIN_MESH_MAX_CHUNK_SIZE 64
+/* n chunks in one call, with the fixed strides VS = (chunk_size + 1)^2 vertices and TS = 2 * chunk_size^2 triangles a chunk:
+ * counts [n][2] = vertices, triangles of chunk i; vertices [n][VS][4]; indices [n][TS][3], chunk-local (they index chunk i's own
+ * vertices); normals [n][VS][3].  Slots past a chunk's counts are NOT written; a chunk without a present cell has counts 0, 0 (the
+ * reference returns an empty batch for a chunk without processed_heights: do not ask for such a chunk, or ignore its answer).  The
+ * scale is rxr_set_terrain_heights'.  RXR_ERR_INVALID: no rxr_set_terrain_heights yet, chunk_size < 1, a chunk whose cells leave
+ * +-2^30, a NULL pointer (all four outputs are required), output sizes that overflow; RXR_ERR_UNSUPPORTED: chunk_size above
+ * RXR_TERRAIN_MESH_MAX_CHUNK_SIZE.  n == 0 does nothing.  Host memory, blocking.  The call is split into launches of 256 chunks.
+ * Changes no frame, scratch, bake or picking state.  Multi-device handles: member 0.
+ * Replaces: TerrainChunk::build_mesh, src/terrain/chunk.rs:253-297, and Batch3D::compute_vertex_normals, src/batch/batch3d.rs:771-809. */
+int rxr_terrain_meshes(rxr_ctx *ctx, const int32_t *chunk_coords /* [n][2] */, uint32_t n, int32_t chunk_size,
+                       uint32_t *counts, float *vertices, uint32_t *indices, float *normals);
+/* the same into DEVICE arrays (each one's first and last byte are checked to be memory of the context's device; 4-byte aligned),
+ * queued on hip_stream (NULL = the context's stream); chunk_coords is host memory and is read before the call returns.
+ * Asynchronous.  Multi-device handles: RXR_ERR_UNSUPPORTED (use rxr_member). */
+int rxr_terrain_meshes_to(rxr_ctx *ctx, const int32_t *chunk_coords, uint32_t n, int32_t chunk_size, uint32_t *dev_counts,
+                          float *dev_vertices, uint32_t *dev_indices, float *dev_normals, void *hip_stream);
 
 #ifdef __cplusplus
 }

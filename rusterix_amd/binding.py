@@ -496,6 +496,12 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         L.terrain_ray_hits_cpu = fn("terrain_ray_hits_cpu", None, vp, pf, pf, u32, f32, pu, pf, pf, pi)
         L.terrain_ray_hits = fn("terrain_ray_hits", i32, vp, pf, pf, u32, f32, pu, pf, pf, pi)
 
+    # terrain chunk meshes (product host library only)
+    has_terrain_mesh = hasattr(lib, prefix + "terrain_build_meshes")
+    if has_terrain_mesh:
+        L.terrain_build_mesh = fn("terrain_build_mesh", vp, vp, i32, i32)
+        L.terrain_build_meshes = fn("terrain_build_meshes", i32, vp, C.POINTER(C.c_int32), u32, i32, C.POINTER(vp))
+
     def last_error():
         if not hasattr(lib, prefix + "last_error"):
             return ""
@@ -1022,6 +1028,33 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         def ray_terrain_hits_cpu(self, origins, dirs, max_distance):
             """the same arrays from the CPU ray_terrain_hit over the host's worker pool"""
             return self._hits(origins, dirs, max_distance, False)
+
+        # ---- the chunk mesh (reference src/terrain/chunk.rs:253-297) ----
+        def build_mesh(self, coord):
+            """TerrainChunk::build_mesh for chunk `coord` on the CPU, cells visited row by row: a Batch3D with source Terrain, zero
+            uvs and computed normals, which chunk.terrain_batch3d(..) accepts; a cell is present iff set_height named it"""
+            if not has_terrain_mesh:
+                raise NotImplementedError(f"{name}: no terrain mesh in this library")
+            return Batch3D(L.terrain_build_mesh(self._h, coord[0], coord[1]))
+
+        def _meshes(self, coords, device):
+            if not has_terrain_mesh:
+                raise NotImplementedError(f"{name}: no terrain mesh in this library")
+            cc = np.ascontiguousarray(np.asarray(coords, np.int32).reshape(-1, 2))
+            n = cc.shape[0]
+            out = (vp * max(n, 1))()
+            rc = L.terrain_build_meshes(self._h, cc.ctypes.data_as(C.POINTER(C.c_int32)), n, 1 if device else 0, out)
+            if rc != 0:
+                raise RasterizeError(rc, last_error())
+            return [Batch3D(out[i]) for i in range(n)]
+
+        def build_meshes(self, coords):
+            """build_mesh for every chunk of `coords` in one device call (rxr_terrain_meshes, include/rxr.h): a list of Batch3D"""
+            return self._meshes(coords, True)
+
+        def build_meshes_cpu(self, coords):
+            """the same list from the CPU build_mesh over the host's worker pool"""
+            return self._meshes(coords, False)
 
     class Assets:
         """reference src/server/assets.rs (`tile_list`, `.textures(..)` builder)."""

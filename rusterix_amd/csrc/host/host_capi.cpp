@@ -199,6 +199,21 @@ int rxh_terrain_ray_hits(void *t, const float *origins, const float *dirs, uint3
                          int32_t *grid_pos) {
     return ((Terrain *)t)->ray_terrain_hits(origins, dirs, n, max_distance, hit, t_hit, world_pos, grid_pos);
 }
+// TerrainChunk::build_mesh on the CPU: a new Batch3D (rxh_batch3d_free)
+void *rxh_terrain_build_mesh(void *t, int32_t cx, int32_t cy) { return new Batch3D(((Terrain *)t)->build_mesh(cx, cy)); }
+// the same for n chunks on the device (rxr_terrain_meshes) or, device == 0, on the CPU over the host's worker pool: out[i] is a new
+// Batch3D; RXR_OK or a negative rxr_status (nothing is allocated then)
+int rxh_terrain_build_meshes(void *t, const int32_t *coords, uint32_t n, int device, void **out) {
+    std::vector<Batch3D> meshes;
+    if (device) {
+        const int rc = ((Terrain *)t)->build_meshes(coords, n, meshes);
+        if (rc != RXR_OK) return rc;
+    } else {
+        ((Terrain *)t)->build_meshes_cpu(coords, n, meshes);
+    }
+    for (uint32_t i = 0; i < n; ++i) out[i] = new Batch3D(std::move(meshes[i]));
+    return RXR_OK;
+}
 // Terrain::bake_chunk on the CPU: side * side * 4 bytes; RXR_OK or a negative rxr_status
 int rxh_terrain_bake_chunk(void *t, int32_t cx, int32_t cy, int32_t ppt, uint8_t *rgba) {
     std::vector<uint8_t> out;

@@ -1182,20 +1182,99 @@ int Terrain::ray_terrain_hits(const float *origins, const float *dirs, uint32_t 
     std::string err;
     rxr_ctx *ctx = context(&err);
     if (!ctx) return RXR_ERR_NO_DEVICE;
-    if (g_heights_gen != heights_generation) {
-        std::vector<int32_t> xy;
-        std::vector<float> height;
-        flatten_heights(xy, height);
-        const int rc = rxr_set_terrain_heights(ctx, scale, xy.data(), height.data(), (uint32_t)height.size());
-        if (rc != RXR_OK) {
-            g_error = rxr_last_error(ctx);
-            return rc;
-        }
-        g_heights_gen = heights_generation;
-    }
-    const int rc = rxr_terrain_hits(ctx, origins, dirs, n, max_distance, hit, t, world_pos, grid_pos);
+    int rc = register_heights(ctx);
+    if (rc != RXR_OK) return rc;
+    rc = rxr_terrain_hits(ctx, origins, dirs, n, max_distance, hit, t, world_pos, grid_pos);
     if (rc != RXR_OK) g_error = rxr_last_error(ctx);
     return rc;
+}
+
+int Terrain::register_heights(rxr_ctx *ctx) const {
+    if (g_heights_gen == heights_generation) return RXR_OK;
+    std::vector<int32_t> xy;
+    std::vector<float> height;
+    flatten_heights(xy, height);
+    const int rc = rxr_set_terrain_heights(ctx, scale, xy.data(), height.data(), (uint32_t)height.size());
+    if (rc != RXR_OK) {
+        g_error = rxr_last_error(ctx);
+        return rc;
+    }
+    g_heights_gen = heights_generation;
+    return RXR_OK;
+}
+
+// ---- the chunk mesh ----
+Batch3D Terrain::build_mesh(int32_t cx, int32_t cy) const {
+    std::vector<float> vertices, uvs;
+    std::vector<uint32_t> indices;
+    std::map<std::pair<int32_t, int32_t>, uint32_t> vertex_map;
+    const int64_t ox = (int64_t)cx * chunk_size, oy = (int64_t)cy * chunk_size;
+    for (int64_t ly = 0; ly < chunk_size; ++ly)
+        for (int64_t lx = 0; lx < chunk_size; ++lx) {
+            const int64_t wx = ox + lx, wy = oy + ly;
+            if (wx < INT32_MIN || wx >= INT32_MAX || wy < INT32_MIN || wy >= INT32_MAX) continue;   // (no such key)
+            if (!heights.count({(int32_t)wx, (int32_t)wy})) continue;
+            uint32_t i[4];
+            const int d[4][2] = {{0, 0}, {1, 0}, {0, 1}, {1, 1}};
+            for (int k = 0; k < 4; ++k) {
+                const int32_t px = (int32_t)wx + d[k][0], py = (int32_t)wy + d[k][1];
+                auto it = vertex_map.find({px, py});
+                if (it == vertex_map.end()) {
+                    it = vertex_map.emplace(std::make_pair(px, py), (uint32_t)(vertices.size() / 4)).first;
+                    const float v[4] = {(float)px * scale[0], get_height(px, py), (float)py * scale[1], 1.0f};
+                    vertices.insert(vertices.end(), v, v + 4);
+                    uvs.push_back(0.0f);
+                    uvs.push_back(0.0f);
+                }
+                i[k] = it->second;
+            }
+            const uint32_t t[6] = {i[0], i[2], i[1], i[1], i[2], i[3]};
+            indices.insert(indices.end(), t, t + 6);
+        }
+    Batch3D b = Batch3D::make(vertices.data(), vertices.size() / 4, indices.data(), indices.size() / 3, uvs.data());
+    b.source_ = PixelSource::Terrain();
+    b.compute_vertex_normals();
+    return b;
+}
+
+void Terrain::build_meshes_cpu(const int32_t *coords, uint32_t n, std::vector<Batch3D> &out) const {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);   // (the worker pool runs one job at a time)
+    (void)height_grid();                              // (built once, before the workers read it)
+    out.assign(n, Batch3D());
+    rxr_parallel::run(n, (size_t)n * chunk_size * chunk_size * 64, [&](size_t i) { out[i] = build_mesh(coords[2 * i], coords[2 * i + 1]); });
+}
+
+int Terrain::build_meshes(const int32_t *coords, uint32_t n, std::vector<Batch3D> &out) const {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::string err;
+    rxr_ctx *ctx = context(&err);
+    if (!ctx) return RXR_ERR_NO_DEVICE;
+    int rc = register_heights(ctx);
+    if (rc != RXR_OK) return rc;
+    out.clear();
+    if (chunk_size < 1 || chunk_size > RXR_TERRAIN_MESH_MAX_CHUNK_SIZE) {   // (the strides below need a size the library takes: its own answer)
+        rc = rxr_terrain_meshes(ctx, coords, n, chunk_size, nullptr, nullptr, nullptr, nullptr);
+        if (rc != RXR_OK) g_error = rxr_last_error(ctx);
+        return rc;
+    }
+    const size_t VS = (size_t)(chunk_size + 1) * (chunk_size + 1), TS = 2 * (size_t)chunk_size * chunk_size;
+    std::vector<uint32_t> counts(2 * (size_t)n), indices((size_t)n * TS * 3);
+    std::vector<float> vertices((size_t)n * VS * 4), normals((size_t)n * VS * 3);
+    rc = rxr_terrain_meshes(ctx, coords, n, chunk_size, counts.data(), vertices.data(), indices.data(), normals.data());
+    if (rc != RXR_OK) {
+        g_error = rxr_last_error(ctx);
+        return rc;
+    }
+    out.reserve(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const size_t nv = counts[2 * (size_t)i], nt = counts[2 * (size_t)i + 1];
+        const std::vector<float> uvs(nv * 2, 0.0f);   // all [0, 0] in the reference: they do not cross the ABI
+        Batch3D b = Batch3D::make(vertices.data() + i * VS * 4, nv, indices.data() + i * TS * 3, nt, uvs.data());
+        b.source_ = PixelSource::Terrain();
+        b.normals.assign(normals.begin() + i * VS * 3, normals.begin() + i * VS * 3 + nv * 3);
+        out.push_back(std::move(b));
+    }
+    return RXR_OK;
 }
 
 void Rasterizer::screen_ray(float x, float y, float origin[3], float dir[3]) const {

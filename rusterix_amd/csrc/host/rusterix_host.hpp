@@ -85,6 +85,7 @@ struct PixelSource {
     static PixelSource Off() { return {}; }
     static PixelSource StaticTileIndex(uint16_t i) { PixelSource s; s.kind = RXR_SOURCE_STATIC_TILE; s.index = i; return s; }
     static PixelSource DynamicTileIndex(uint16_t i) { PixelSource s; s.kind = RXR_SOURCE_DYNAMIC_TILE; s.index = i; return s; }
+    static PixelSource Terrain() { PixelSource s; s.kind = RXR_SOURCE_TERRAIN; return s; }
     static PixelSource FromPixel(const uint8_t p[4]) { PixelSource s; s.kind = RXR_SOURCE_PIXEL; for (int i = 0; i < 4; ++i) s.pixel[i] = p[i]; return s; }
 };
 
@@ -329,6 +330,18 @@ public:
     // the cell list of rxr_set_terrain_heights
     void flatten_heights(std::vector<int32_t> &xy, std::vector<float> &height) const;
 
+    // ---- the chunk mesh (src/terrain/chunk.rs:253-297) ----
+    // TerrainChunk::build_mesh for chunk (cx, cy) on the CPU, the plain dictionary transcription with the cells visited in ascending
+    // (ly, lx) (the reference's hash order is not an order: DESIGN.md section 13): a cell is present iff it is a key of `heights`;
+    // source Terrain, uvs zero, normals from compute_vertex_normals.  An empty batch for a chunk without a present cell.
+    Batch3D build_mesh(int32_t cx, int32_t cy) const;
+    // the same for n chunks on the device (rxr_set_terrain_heights when the heights changed since they were registered, then
+    // rxr_terrain_meshes, include/rxr.h): out[i] is the batch of coords[i].  RXR_OK or a negative rxr_status; there is no fall-back
+    // to the CPU.
+    int build_meshes(const int32_t *coords, uint32_t n, std::vector<Batch3D> &out) const;
+    // build_mesh for n chunks over the host's worker pool (what tools/terrain_mesh_bench.py measures the device against)
+    void build_meshes_cpu(const int32_t *coords, uint32_t n, std::vector<Batch3D> &out) const;
+
 private:
     // get_height's answers as a dense grid over the cells' bounding rectangle, rebuilt when heights_generation moved (the CPU march
     // looks a cell up 1500 times a ray)
@@ -339,6 +352,7 @@ private:
     };
     mutable HeightGrid height_grid_;
     const HeightGrid &height_grid() const;
+    int register_heights(rxr_ctx *ctx) const;   // rxr_set_terrain_heights unless the context holds this generation
 };
 
 // src/rasterizer.rs:35-193

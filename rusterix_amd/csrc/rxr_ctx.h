@@ -34,6 +34,7 @@ enum : uint32_t {
     Q_BAKE,      // rxr_bake_shaders_to: the programs and its job list
     Q_TERRAIN,   // rxr_bake_terrain_to: the resident terrain
     Q_HEIGHTS,   // rxr_terrain_hits_to: the resident heights
+    Q_MESH,      // rxr_terrain_meshes_to: the resident heights and their presence mask
     Q_LANES
 };
 #define RXR_MAX_TILE_ROWS 2048u   // frames of at most 32768 rows
@@ -231,7 +232,7 @@ struct rxr_ctx {
     uint32_t n_patterns = 0, n_normal_patterns = 0, n_palette = 0;
     bool frame_uses_programs = false;
 
-    QueryLane lane[Q_LANES];         // the four device queries below: stream ordering and staging (rxr_query.h)
+    QueryLane lane[Q_LANES];         // the device queries below: stream ordering and staging (rxr_query.h)
 
     // ray picking (rxr_intersect.hip): buffers of its own -- an intersect never touches the frame state (has_frame, the bins, the
     // counters).  d_isect_tris: (p0, edge1, edge2) per registered triangle; d_isect_misc: the segments and per-mesh profile ids
@@ -266,14 +267,17 @@ struct rxr_ctx {
     uint32_t terrain_launches = 0;    // k_terrain_bake launches of the last bake call (rxr_debug_terrain_launches)
 
     // terrain picks (rxr_terrain_hit.hip): the resident heights of rxr_set_terrain_heights, independent of the resident terrain above.
-    // d_heights: the dense f32 grid over the cells' bounding rectangle; d_heights_tk: the 1500 values t_k of the march.
-    DevBuf d_heights, d_heights_tk;
+    // d_heights: the dense f32 grid over the cells' bounding rectangle; d_heights_tk: the 1500 values t_k of the march;
+    // d_heights_mask: one byte per cell of the same grid, 1 where the caller listed the cell (rxr_terrain_mesh.hip: a listed 0.0 is a
+    // cell of the mesh, an unlisted one is not).
+    DevBuf d_heights, d_heights_tk, d_heights_mask;
     bool heights_set = false;
     float heights_scale[2] = {1.0f, 1.0f};
     int32_t heights_x0 = 0, heights_y0 = 0;
     uint32_t heights_gw = 0, heights_gh = 0;
     uint32_t heights_launches = 0;    // march launches of the last hit call (rxr_debug_terrain_hit_kernel)
     const char *heights_kernel = "";  // ... and their kernel's symbol name; a static string
+    uint32_t mesh_launches = 0;       // k_terrain_mesh launches of the last mesh call (rxr_debug_terrain_mesh_launches)
 
     FrameStream fstream;    // rxr_stream_begin .. rxr_upload_frame
     int last_upload_streamed = 0;  // 0 plain, 1 streamed (copied), 2 streamed out of page-locked arrays

@@ -1,5 +1,5 @@
 // rxr_query.h -- the host scaffold the device queries next to the renderer share (rxr_intersect.hip, rxr_bake.hip, rxr_terrain.hip,
-// rxr_terrain_hit.hip): the cross-stream ordering of a query's lane (rxr_ctx.h: QueryLane), the staging of a blocking form's host
+// rxr_terrain_hit.hip, rxr_terrain_mesh.hip): the cross-stream ordering of a query's lane (rxr_ctx.h: QueryLane), the staging of a blocking form's host
 // arrays, and the small helpers of their entry points.  A query's `_run` queues its launches between rxr_query_begin and
 // rxr_query_end on whichever stream it is given; its blocking form stages through QueryIO on ctx->stream.
 #pragma once
@@ -39,6 +39,10 @@ struct QueryIO {
     unsigned out(void *host, size_t bytes) {   // host == NULL: an output the caller does not ask for
         dst[L.n] = host;
         return L.add(host ? bytes : 0);
+    }
+    unsigned inout(void *host, size_t bytes) {   // an output the kernel writes only parts of: the rest comes back as it went up
+        dst[L.n] = host;
+        return in(host, bytes);
     }
     template <class T>
     T *dev(unsigned i) const {   // (null for an absent output)

@@ -323,20 +323,27 @@ int rxr_set_terrain_heights(rxr_ctx *ctx, const float scale[2], const int32_t *c
     int rc = check_heights(scale, cell_xy, cell_height, n_cells, shape, err);
     if (rc != RXR_OK) return rxr_fail(ctx, rc, "rxr_set_terrain_heights: " + err);
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if ((rc = rxr_quiesce(ctx)) != RXR_OK) return rc;   // queued hit calls read what is replaced here
+    if ((rc = rxr_quiesce(ctx)) != RXR_OK) return rc;   // queued hit and mesh calls read what is replaced here
     ctx->heights_set = false;
     // the dense grid; a coordinate given twice: the later entry wins
     const size_t n_grid = (size_t)shape.gw * shape.gh;
+    // ... and the presence mask over the same rectangle (rxr_terrain_mesh.hip): 1 where the caller listed the cell, whatever its height
     std::vector<float> grid(n_grid, 0.0f);
-    for (uint32_t i = 0; i < n_cells; ++i)
-        grid[(size_t)((int64_t)cell_xy[2 * (size_t)i + 1] - shape.y0) * shape.gw + (size_t)((int64_t)cell_xy[2 * (size_t)i] - shape.x0)] = cell_height[i];
+    std::vector<uint8_t> mask(n_grid, 0);
+    for (uint32_t i = 0; i < n_cells; ++i) {
+        const size_t at = (size_t)((int64_t)cell_xy[2 * (size_t)i + 1] - shape.y0) * shape.gw + (size_t)((int64_t)cell_xy[2 * (size_t)i] - shape.x0);
+        grid[at] = cell_height[i];
+        mask[at] = 1;
+    }
     hipStream_t s = ctx->stream;
     if ((rc = rxr_ensure(ctx, ctx->d_heights, std::max<size_t>(n_grid * sizeof(float), 256))) != RXR_OK) return rc;
+    if ((rc = rxr_ensure(ctx, ctx->d_heights_mask, std::max<size_t>(n_grid, 256))) != RXR_OK) return rc;
     const bool table_new = !ctx->d_heights_tk.p;
     if ((rc = rxr_ensure(ctx, ctx->d_heights_tk, RXR_TERRAIN_MARCH_STEPS * sizeof(float))) != RXR_OK) return rc;
     if (n_grid) HIPCHK(ctx, hipMemcpyAsync(ctx->d_heights.p, grid.data(), n_grid * sizeof(float), hipMemcpyHostToDevice, s));
+    if (n_grid) HIPCHK(ctx, hipMemcpyAsync(ctx->d_heights_mask.p, mask.data(), n_grid, hipMemcpyHostToDevice, s));
     if (table_new) HIPCHK(ctx, hipMemcpyAsync(ctx->d_heights_tk.p, march_table(), RXR_TERRAIN_MARCH_STEPS * sizeof(float), hipMemcpyHostToDevice, s));
-    HIPCHK(ctx, hipStreamSynchronize(s));   // (the host vector above is read until here)
+    HIPCHK(ctx, hipStreamSynchronize(s));   // (the host vectors above are read until here)
     ctx->heights_scale[0] = scale[0];
     ctx->heights_scale[1] = scale[1];
     ctx->heights_x0 = shape.x0;

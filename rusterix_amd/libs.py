@@ -88,6 +88,9 @@ def rxr_abi():
         "rxr_terrain_hits_to": (i32, [vp, vp, vp, u32, C.c_float, vp, vp, vp, vp, vp]),
         "rxr_debug_terrain_hit_kernel": (C.c_char_p, [vp, C.POINTER(u32)]),
         "rxr_debug_terrain_hit_few_rays": (u32, []),
+        "rxr_terrain_meshes": (i32, [vp, vp, u32, i32, vp, vp, vp, vp]),
+        "rxr_terrain_meshes_to": (i32, [vp, vp, u32, i32, vp, vp, vp, vp, vp]),
+        "rxr_debug_terrain_mesh_launches": (u32, [vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
