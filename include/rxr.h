@@ -445,6 +445,42 @@ int rxr_set_textures(rxr_ctx *ctx, const rxr_tile *static_tiles, uint32_t n_stat
  * from `self` (src/batch/batch3d.rs:482-740).  Call again only when geometry or materials change. */
 int rxr_set_meshes(rxr_ctx *ctx, const rxr_mesh3d *meshes, uint32_t n_meshes);
 
+/* Replaces the geometry of n ALREADY REGISTERED meshes in place, from host memory, when their counts are unchanged (a height stroke on a
+ * terrain chunk moves vertices and normals, not which cells exist).  The layout is exactly what rxr_terrain_meshes[_to] writes, so its
+ * output feeds this call with no repacking: counts [n][2] = vertices, triangles of mesh_indices[i]; vertices [n][vertex_stride][4];
+ * indices [n][triangle_stride][3], mesh-local; normals [n][vertex_stride][3].  Slots past a mesh's counts are never read.
+ * mesh_indices indexes the meshes in rxr_set_meshes order.  uvs, transform, cull mode, source, shader, list and chunk stay as
+ * registered; so do every other mesh and every prefix array.
+ * Accepted only if, for every i, counts[i] equals the registered (n_vertices, n_triangles) of mesh_indices[i] and every index is below
+ * that vertex count; anything else is RXR_ERR_INVALID, the message names the first offending mesh and why, and NOTHING HAS BEEN
+ * CHANGED -- not the pools, not the boxes, not a previously uploaded frame: the caller then falls back to rxr_set_meshes.  Also
+ * RXR_ERR_INVALID: no valid registration, a mesh index out of range or named twice, a NULL pointer with n > 0 (an array of 0 bytes
+ * -- a stride of 0 -- is not looked at), a stride below a named mesh's registered count, byte sizes that overflow.  n == 0 does nothing.
+ * After success the object-space pools and the static originals of clipped_indices / clipped_normals hold the new values, the
+ * context's object-space box of each named mesh is the new one (f32::min / f32::max over the vertices, a NaN coordinate ignored;
+ * equal to the host loop's under ==, the sign of a zero bound is not specified), the pick records are rebuilt by the next
+ * rxr_intersect, and THE RESIDENT FRAME IS DROPPED: upload it again, as after rxr_set_meshes.
+ * Blocking: the call first waits for everything the context has queued (renders and picks read the pools) and returns once the pools
+ * are updated, so work queued later on any stream sees the new geometry.  All arrays are read before it returns.  The checks run on
+ * the device (k_mesh_check: counts, indices, box; one 32-byte record per mesh comes back), then k_mesh_commit writes.
+ * Multi-device handles: every member.
+ * Replaces, for the named meshes: the object-space box of batch3d.rs:494-507 (rxr_set_meshes' host loop) and the static copies of
+ * batch3d.rs:566-574 (k_proj_static). */
+int rxr_update_meshes(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t n, const uint32_t *counts, const float *vertices,
+                      const uint32_t *indices, const float *normals, uint32_t vertex_stride, uint32_t triangle_stride);
+/* the same from DEVICE arrays (each one's first and last byte are checked to be memory of the context's device; 4-byte aligned: else
+ * RXR_ERR_INVALID); mesh_indices is host memory and is read before the call returns.  The kernels are queued on hip_stream (NULL = the
+ * context's stream), so the call is ordered behind the rxr_terrain_meshes_to on that stream that produced its inputs, and no geometry
+ * crosses PCIe.  BLOCKING like the host form: it waits for the context's queued work, synchronises hip_stream for the read-back of
+ * the n 32-byte check records, and again behind the writes.  Multi-device handles: RXR_ERR_UNSUPPORTED (use rxr_member).
+ * Replaces: as rxr_update_meshes (batch3d.rs:494-507, :566-574). */
+int rxr_update_meshes_to(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t n, const uint32_t *dev_counts, const float *dev_vertices,
+                         const uint32_t *dev_indices, const float *dev_normals, uint32_t vertex_stride, uint32_t triangle_stride,
+                         void *hip_stream);
+/* debugging / tests: the object-space box the context currently holds for mesh `mesh_index` (batch3d.rs:494-507), whether it came from
+ * rxr_set_meshes or from an update; (+inf, -inf) for a mesh without vertices.  Multi-device handles: member 0. */
+int rxr_mesh_bounds(rxr_ctx *ctx, uint32_t mesh_index, float lo[3], float hi[3]);
+
 /* The 2D half of the same: registers the object-space 2D batches of a scene (submission order, src/rasterizer.rs:503-552) for
  * device-side projection; what Batch2D::project reads from `self` (src/batch/batch2d.rs:373-425).  Call again only when geometry
  * or materials change.  A batch whose texture tile does not exist is refused HERE (the reference panics only when the batch is on

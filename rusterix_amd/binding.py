@@ -502,6 +502,11 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         L.terrain_build_mesh = fn("terrain_build_mesh", vp, vp, i32, i32)
         L.terrain_build_meshes = fn("terrain_build_meshes", i32, vp, C.POINTER(C.c_int32), u32, i32, C.POINTER(vp))
 
+    # registered meshes updated in place (product host library only)
+    has_mesh_update = hasattr(lib, prefix + "scene_rebuild_terrain_meshes")
+    if has_mesh_update:
+        L.scene_rebuild_terrain_meshes = fn("scene_rebuild_terrain_meshes", i32, vp, vp, C.POINTER(C.c_int32), u32, pu)
+
     def last_error():
         if not hasattr(lib, prefix + "last_error"):
             return ""
@@ -893,6 +898,24 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
                 raise RasterizeError(rc, last_error())
             return out
 
+        def rebuild_terrain_meshes(self, terrain, coords, chunks):
+            """A height stroke without PCIe traffic: the meshes of `terrain`'s chunks `coords` ([n][2]) are built on the device and
+            written over the registered geometry of the single terrain_batch3d of scene chunk chunks[i], in place
+            (rxr_terrain_meshes_to + rxr_update_meshes_to, include/rxr.h).  Needs device projection.  Returns 0 for that fast path --
+            the host batches keep their old arrays and their stamp, so the next rasterize sends matrices only -- or 1 for the
+            fallback (a cell was added or removed, or the context holds no registration of this geometry yet): the batches were
+            rebuilt on the host and the next rasterize registers the scene again."""
+            if not has_mesh_update:
+                raise NotImplementedError(f"{name}: no in-place mesh update in this library")
+            cc = np.ascontiguousarray(np.asarray(coords, np.int32).reshape(-1, 2))
+            ch = np.ascontiguousarray(np.asarray(chunks, np.uint32).reshape(-1))
+            if len(cc) != len(ch):
+                raise ValueError("coords and chunks must have the same length")
+            rc = L.scene_rebuild_terrain_meshes(self._h, terrain._h, cc.ctypes.data_as(C.POINTER(C.c_int32)), len(cc), _up(ch))
+            if rc < 0:
+                raise RasterizeError(rc, last_error())
+            return rc
+
         def projected_batch3d(self, list_kind, index, chunk=-1):
             """Outputs of clip_and_project for one batch (after rasterize): dict of numpy arrays."""
             nv, nt, hn = C.c_uint32(), C.c_uint32(), C.c_uint32()
@@ -1268,8 +1291,29 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         def projection_matrix(self, width, height):
             return self.matrices(width, height)[1]
 
+    def update_meshes(mesh_indices, counts, vertices, indices, normals):
+        """rxr_update_meshes (include/rxr.h) on the process-wide context, over host arrays in the layout of rxr_terrain_meshes: counts
+        [n][2], vertices [n][VS][4], indices [n][TS][3], normals [n][VS][3]; the strides are the arrays' second extents.  Raises
+        RasterizeError with the library's message when the call is refused."""
+        if not has_mesh_update:
+            raise NotImplementedError(f"{name}: no in-place mesh update in this library")
+        from .libs import rxr_abi
+
+        m = np.ascontiguousarray(np.asarray(mesh_indices, np.uint32).reshape(-1))
+        n = len(m)
+        c = _u32(counts, (n, 2))
+        v, i = np.ascontiguousarray(vertices, np.float32), np.ascontiguousarray(indices, np.uint32)
+        if v.ndim != 3 or i.ndim != 3 or v.shape[0] != n or i.shape[0] != n or v.shape[2] != 4 or i.shape[2] != 3:
+            raise ValueError("vertices must be [n][VS][4] and indices [n][TS][3]")
+        nr = _f32(normals, (n, v.shape[1], 3))
+        rxr = rxr_abi()
+        ctx = lib.rxh_context()
+        rc = rxr.rxr_update_meshes(ctx, m.ctypes.data, n, c.ctypes.data, v.ctypes.data, i.ctypes.data, nr.ctypes.data, v.shape[1], i.shape[1])
+        if rc != 0:
+            raise RasterizeError(rc, (rxr.rxr_last_error(ctx) or b"").decode())
+
     return types.SimpleNamespace(
-        name=name, lib=lib, prefix=prefix, raw=L,
+        name=name, lib=lib, prefix=prefix, raw=L, update_meshes=update_meshes,
         Scene=Scene, Batch3D=Batch3D, Batch2D=Batch2D, Chunk=Chunk, Assets=Assets, Rasterizer=Rasterizer, Terrain=Terrain,
         D3OrbitCamera=D3OrbitCamera, D3FirstPCamera=D3FirstPCamera,
         # shared value types

@@ -214,6 +214,10 @@ int rxh_terrain_build_meshes(void *t, const int32_t *coords, uint32_t n, int dev
     for (uint32_t i = 0; i < n; ++i) out[i] = new Batch3D(std::move(meshes[i]));
     return RXR_OK;
 }
+// Scene::rebuild_terrain_meshes: 0 (updated in place on the device), 1 (fallback: the batches were replaced on the host) or a negative rxr_status
+int rxh_scene_rebuild_terrain_meshes(void *s, void *t, const int32_t *coords, uint32_t n, const uint32_t *chunks) {
+    return ((Scene *)s)->rebuild_terrain_meshes(*(const Terrain *)t, coords, n, chunks);
+}
 // Terrain::bake_chunk on the CPU: side * side * 4 bytes; RXR_OK or a negative rxr_status
 int rxh_terrain_bake_chunk(void *t, int32_t cx, int32_t cy, int32_t ppt, uint8_t *rgba) {
     std::vector<uint8_t> out;

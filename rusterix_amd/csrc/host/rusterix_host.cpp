@@ -1277,6 +1277,79 @@ int Terrain::build_meshes(const int32_t *coords, uint32_t n, std::vector<Batch3D
     return RXR_OK;
 }
 
+// (rxr_api.hip; not part of include/rxr.h: this mirror links no HIP runtime, so its device scratch comes from the device library -- a
+// host with an allocator of its own hands rxr_terrain_meshes_to / rxr_update_meshes_to its own memory)
+extern "C" void *rxr_mirror_scratch(rxr_ctx *ctx, size_t bytes);
+
+int Scene::rebuild_terrain_meshes(const Terrain &terrain, const int32_t *coords, uint32_t n, const uint32_t *chunks_) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::string err;
+    rxr_ctx *ctx = context(&err);
+    if (!ctx) return RXR_ERR_NO_DEVICE;
+    if (!g_device_projection) {
+        g_error = "Scene::rebuild_terrain_meshes: device projection is off (set_device_projection): there are no registered meshes to update";
+        return RXR_ERR_UNSUPPORTED;
+    }
+    if (!n) return 0;
+    if (!coords || !chunks_) {
+        g_error = "Scene::rebuild_terrain_meshes: NULL array";
+        return RXR_ERR_INVALID;
+    }
+    // each batch's position in batches3d_in_order(): per chunk opacity, batches, terrain
+    std::vector<uint32_t> first_of_chunk(chunks.size() + 1, 0);
+    for (size_t c = 0; c < chunks.size(); ++c)
+        first_of_chunk[c + 1] = first_of_chunk[c] + (uint32_t)(chunks[c].batches3d_opacity.size() + chunks[c].batches3d.size() + chunks[c].terrain_batch3d.size());
+    std::vector<uint32_t> mesh_index(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t c = chunks_[i];
+        if (c >= chunks.size() || chunks[c].terrain_batch3d.size() != 1) {
+            g_error = "Scene::rebuild_terrain_meshes: chunks[" + std::to_string(i) + "] = " + std::to_string(c) + " is not a chunk with one terrain_batch3d";
+            return RXR_ERR_INVALID;
+        }
+        mesh_index[i] = first_of_chunk[c + 1] - 1u;
+    }
+    const int32_t cs = terrain.chunk_size;
+    std::vector<rxr_mesh3d> meshes;
+    uint64_t full = 0, geometry = 0;
+    // the fast path needs a registration made by a device-projected upload (sources resolved) of exactly this geometry; one made by
+    // Scene::intersect alone is registered again by the next upload, from the host arrays
+    const bool held = scene_meshes(*this, nullptr, meshes, nullptr, full, geometry) && g_mesh_fingerprint != 0 && geometry == g_mesh_geometry_fingerprint;
+    if (held && rxr_member_count(ctx) == 1 && cs >= 1 && cs <= RXR_TERRAIN_MESH_MAX_CHUNK_SIZE) {
+        int rc = terrain.register_heights(ctx);
+        if (rc != RXR_OK) return rc;
+        const size_t VS = (size_t)(cs + 1) * (cs + 1), TS = 2 * (size_t)cs * cs;
+        auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+        const size_t o_v = up((size_t)n * 8), o_i = o_v + up((size_t)n * VS * 16), o_n = o_i + up((size_t)n * TS * 12), total = o_n + up((size_t)n * VS * 12);
+        uint8_t *d = (uint8_t *)rxr_mirror_scratch(ctx, total);
+        if (!d) {
+            g_error = rxr_last_error(ctx);
+            return RXR_ERR_OOM;
+        }
+        uint32_t *dc = (uint32_t *)d, *di = (uint32_t *)(d + o_i);
+        float *dv = (float *)(d + o_v), *dn = (float *)(d + o_n);
+        rc = rxr_terrain_meshes_to(ctx, coords, n, cs, dc, dv, di, dn, nullptr);
+        if (rc == RXR_OK) rc = rxr_update_meshes_to(ctx, mesh_index.data(), n, dc, dv, di, dn, (uint32_t)VS, (uint32_t)TS, nullptr);   // (the same stream: the context's)
+        if (rc == RXR_OK) return 0;
+        if (rc != RXR_ERR_INVALID) {
+            g_error = rxr_last_error(ctx);
+            return rc;
+        }
+        // refused (counts changed): nothing was changed on the device
+    }
+    std::vector<Batch3D> built;
+    const int rc = terrain.build_meshes(coords, n, built);
+    if (rc != RXR_OK) return rc;
+    for (uint32_t i = 0; i < n; ++i) {
+        Batch3D &b = chunks[chunks_[i]].terrain_batch3d[0];   // (material, transform and cull mode stay the batch's own)
+        b.vertices = std::move(built[i].vertices);
+        b.indices = std::move(built[i].indices);
+        b.uvs = std::move(built[i].uvs);
+        b.normals = std::move(built[i].normals);
+        b.touch();
+    }
+    return 1;
+}
+
 void Rasterizer::screen_ray(float x, float y, float origin[3], float dir[3]) const {
     const float ndc_x = 2.0f * (x / width) - 1.0f;
     const float ndc_y = 1.0f - 2.0f * (y / height);  // flip y

@@ -267,6 +267,20 @@ public:
     // baked from it on the device onto shader_textures (None for a program without `shade`, which is not baked); the bytes are host memory.
     // Returns the shader's index in the chunk or a negative rxr_status (a program the device cannot bake is not added).
     int chunk_add_shader(size_t chunk, Program program, const Assets &assets);
+    // A height stroke's way to the frame without crossing PCIe: the meshes of the terrain's chunks coords[i] = (cx, cy) are built on the
+    // device (rxr_terrain_meshes_to, into device scratch) and written over the registered geometry of chunks[chunks_[i]]'s single
+    // terrain_batch3d in place (rxr_update_meshes_to on the same stream, include/rxr.h).  Needs device projection (else
+    // RXR_ERR_UNSUPPORTED).  Returns
+    //   0  the fast path: the context's meshes are the new ones.  THE HOST Batch3D ARRAYS OF THOSE BATCHES ARE LEFT AS THEY WERE: their
+    //      geometry_stamp, and with it the registration's fingerprints, are unchanged, so the next upload sends matrices only and does
+    //      not overwrite the device's newer geometry with the stale host copy.  (Anything else that re-registers the scene -- another
+    //      batch touched, a material changed -- does send the stale copy: refresh these batches from Terrain::build_meshes first.)
+    //   1  the fallback: the update was refused (RXR_ERR_INVALID: a cell was added or removed, so the counts changed), or the context
+    //      does not hold a device-projection registration of this scene's geometry yet (the next upload registers from the host arrays,
+    //      which must then be the new ones), or the context is a multi-device one.  Terrain::build_meshes to the host, the batches'
+    //      geometry replaced and touch()ed: the next upload registers again.
+    //   a negative rxr_status otherwise.
+    int rebuild_terrain_meshes(const class Terrain &terrain, const int32_t *coords, uint32_t n, const uint32_t *chunks_);
 };
 
 // src/terrain/mod.rs, src/terrain/chunk.rs: what Terrain::bake_chunk reads -- `sources` and `blend_modes` per cell, behind the asset
@@ -343,6 +357,7 @@ public:
     void build_meshes_cpu(const int32_t *coords, uint32_t n, std::vector<Batch3D> &out) const;
 
 private:
+    friend class Scene;   // (rebuild_terrain_meshes registers the heights)
     // get_height's answers as a dense grid over the cells' bounding rectangle, rebuilt when heights_generation moved (the CPU march
     // looks a cell up 1500 times a ray)
     struct HeightGrid {

@@ -23,6 +23,8 @@
 
 thread_local LaunchTimes *rxr_launch_times = nullptr;  // rxr_launch.h: the profiling slot of the render this thread is queueing
 extern "C" void rxr_launch_proj_static(const ProjectParams *P, hipStream_t s);
+extern "C" void rxr_launch_mesh_check(const MeshUpdateArgs *A, uint32_t n, hipStream_t s);
+extern "C" void rxr_launch_mesh_commit(const MeshUpdateArgs *A, uint32_t n, hipStream_t s);
 extern "C" void rxr_launch_project(const ProjectParams *P, hipStream_t s);
 extern "C" void rxr_launch_proj_edges(const ProjectParams *P, hipStream_t s);
 extern "C" void rxr_launch_setup(const RasterParams *P, hipStream_t s);
@@ -174,7 +176,7 @@ void rxr_destroy(rxr_ctx *ctx) {
     }
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)rxr_quiesce(ctx);
-    DevBuf *bufs[] = {&ctx->d_stripes, &ctx->d_obj, &ctx->d_proj_out, &ctx->d_proj_misc, &ctx->d_tex, &ctx->d_texels, &ctx->d_frame, &ctx->d_tri_setup, &ctx->d_tri_shade, &ctx->d_tri_box, &ctx->d_bin_count, &ctx->d_bins, &ctx->d_bin2d_count, &ctx->d_bins2d,
+    DevBuf *bufs[] = {&ctx->d_stripes, &ctx->d_obj, &ctx->d_mesh_check, &ctx->d_mirror_scratch, &ctx->d_proj_out, &ctx->d_proj_misc, &ctx->d_tex, &ctx->d_texels, &ctx->d_frame, &ctx->d_tri_setup, &ctx->d_tri_shade, &ctx->d_tri_box, &ctx->d_bin_count, &ctx->d_bins, &ctx->d_bin2d_count, &ctx->d_bins2d,
                       &ctx->d_list2d, &ctx->d_large2d,
                       &ctx->d_list, &ctx->d_large, &ctx->d_counters, &ctx->d_fb,
                       &ctx->d_vm_code, &ctx->d_programs, &ctx->d_patterns, &ctx->d_pattern_data, &ctx->d_palette,
@@ -395,6 +397,7 @@ int rxr_set_meshes(rxr_ctx *ctx, const rxr_mesh3d *meshes, uint32_t n_meshes) {
     if ((rc = rxr_ensure(ctx, ctx->d_proj_misc, take.o)) != RXR_OK) return rc;
     HIPCHK(ctx, hipMemsetAsync(ctx->d_proj_misc.p, 0, take.o, ctx->stream));
     ctx->pp_off_meshes = m_dm;
+    ctx->obj_off_meshes = off_dm;
 
     ProjectParams &PP = ctx->PP;
     memset(&PP, 0, sizeof(PP));
@@ -429,6 +432,160 @@ int rxr_set_meshes(rxr_ctx *ctx, const rxr_mesh3d *meshes, uint32_t n_meshes) {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ctx->meshes_valid = true;
     return RXR_OK;
+}
+
+// ---- rxr_update_meshes: registered meshes' geometry replaced in place (kernels: rxr_project.hip) ------------------------------
+// what both forms refuse before anything is queued, but for their pointers; bytes[4]: the arrays' sizes
+static int update_check(rxr_ctx *ctx, const char *who, const uint32_t *mesh_indices, uint32_t n, uint32_t vstride, uint32_t tstride, size_t bytes[4]) {
+    const std::string w = who;
+    if (!ctx->meshes_valid) return rxr_fail(ctx, RXR_ERR_INVALID, w + ": no valid registration (the last rxr_set_meshes failed)");
+    if (!mesh_indices) return rxr_fail(ctx, RXR_ERR_INVALID, w + ": NULL mesh_indices");
+    // (the sizes depend on n and the strides alone: refused before anything is read)
+    const size_t per[4] = {8, (size_t)vstride * 16, (size_t)tstride * 12, (size_t)vstride * 12};
+    for (int i = 0; i < 4; ++i)
+        if (__builtin_mul_overflow((size_t)n, per[i], &bytes[i])) return rxr_fail(ctx, RXR_ERR_INVALID, w + ": the arrays' sizes overflow");
+    if (n > ctx->meshes.size())
+        return rxr_fail(ctx, RXR_ERR_INVALID, w + ": " + std::to_string(n) + " meshes named, " + std::to_string(ctx->meshes.size()) + " are registered (no such mesh, or one named twice)");
+    std::vector<uint8_t> named(ctx->meshes.size(), 0);
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t m = mesh_indices[i];
+        const std::string at = w + ": mesh_indices[" + std::to_string(i) + "] = " + std::to_string(m);
+        if (m >= ctx->meshes.size()) return rxr_fail(ctx, RXR_ERR_INVALID, at + ": no such mesh (" + std::to_string(ctx->meshes.size()) + " are registered)");
+        if (named[m]) return rxr_fail(ctx, RXR_ERR_INVALID, at + ": named twice");
+        named[m] = 1;
+        const DevMesh &M = ctx->meshes[m].dev;
+        if (M.n_verts > vstride) return rxr_fail(ctx, RXR_ERR_INVALID, at + ": vertex_stride " + std::to_string(vstride) + " is below its " + std::to_string(M.n_verts) + " vertices");
+        if (M.n_tris > tstride) return rxr_fail(ctx, RXR_ERR_INVALID, at + ": triangle_stride " + std::to_string(tstride) + " is below its " + std::to_string(M.n_tris) + " triangles");
+    }
+    return RXR_OK;
+}
+
+// both phases on `s` over DEVICE arrays; the streams are idle (rxr_quiesce) and stay so until this returns
+static int update_run(rxr_ctx *ctx, const char *who, const uint32_t *mesh_indices, uint32_t n, const uint32_t *counts, const float *vertices,
+                      const uint32_t *indices, const float *normals, uint32_t vstride, uint32_t tstride, hipStream_t s) {
+    int rc = rxr_ensure(ctx, ctx->d_mesh_check, (size_t)n * sizeof(MeshCheckRec));
+    if (rc != RXR_OK) return rc;
+    const ProjectParams &PP = ctx->PP;
+    MeshUpdateArgs A{};
+    A.meshes = (const DevMesh *)((const uint8_t *)ctx->d_obj.p + ctx->obj_off_meshes);
+    A.vstride = vstride;
+    A.tstride = tstride;
+    A.obj_verts = const_cast<float4 *>(PP.obj_verts);
+    A.obj_idx = const_cast<uint32_t *>(PP.obj_idx);
+    A.obj_normals = const_cast<float *>(PP.obj_normals);
+    A.nrm = PP.nrm;
+    A.idx = PP.idx;
+    auto each_launch = [&](void (*launch)(const MeshUpdateArgs *, uint32_t, hipStream_t)) -> int {
+        for (uint32_t c0 = 0; c0 < n; c0 += RXR_MESH_UPDATE_LAUNCH) {
+            const uint32_t nc = std::min(n - c0, RXR_MESH_UPDATE_LAUNCH);
+            memcpy(A.mesh, mesh_indices + c0, (size_t)nc * sizeof(uint32_t));
+            A.counts = counts + 2 * (size_t)c0;
+            A.vertices = vertices + (size_t)c0 * vstride * 4;
+            A.indices = indices + (size_t)c0 * tstride * 3;
+            A.normals = normals + (size_t)c0 * vstride * 3;
+            A.rec = (MeshCheckRec *)ctx->d_mesh_check.p + c0;
+            launch(&A, nc, s);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        return RXR_OK;
+    };
+    // phase 1: nothing is written but the records
+    if ((rc = each_launch(rxr_launch_mesh_check)) != RXR_OK) return rc;
+    std::vector<MeshCheckRec> rec(n);
+    HIPCHK(ctx, hipMemcpyAsync(rec.data(), ctx->d_mesh_check.p, (size_t)n * sizeof(MeshCheckRec), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!rec[i].status) continue;
+        const DevMesh &M = ctx->meshes[mesh_indices[i]].dev;
+        std::string why;
+        if (rec[i].status & MESH_UPD_BAD_VERTS) why = "its vertex count differs from the registered " + std::to_string(M.n_verts);
+        else if (rec[i].status & MESH_UPD_BAD_TRIS) why = "its triangle count differs from the registered " + std::to_string(M.n_tris);
+        else why = "triangle " + std::to_string(rec[i].bad_triangle) + " has a vertex index that is not below its " + std::to_string(M.n_verts) + " vertices";
+        return rxr_fail(ctx, RXR_ERR_INVALID, std::string(who) + ": mesh_indices[" + std::to_string(i) + "] = " + std::to_string(mesh_indices[i]) + ": " + why +
+                                                  " (nothing was changed; register again with rxr_set_meshes)");
+    }
+    // phase 2
+    if ((rc = each_launch(rxr_launch_mesh_commit)) != RXR_OK) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    for (uint32_t i = 0; i < n; ++i) {
+        HostMesh &h = ctx->meshes[mesh_indices[i]];
+        memcpy(h.aabb_lo, rec[i].lo, 12);
+        memcpy(h.aabb_hi, rec[i].hi, 12);
+    }
+    ctx->isect_ready = false;  // (the next pick builds its records again, as after rxr_set_meshes)
+    ctx->has_frame = false;    // (the resident frame's cull decisions and row spans came from the old boxes)
+    return RXR_OK;
+}
+
+int rxr_update_meshes(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t n, const uint32_t *counts, const float *vertices, const uint32_t *indices,
+                      const float *normals, uint32_t vertex_stride, uint32_t triangle_stride) {
+    if (!ctx) return RXR_ERR_INVALID;
+    if (ctx->group) return rxr_group_update_meshes(ctx, mesh_indices, n, counts, vertices, indices, normals, vertex_stride, triangle_stride);
+    if (!n) return RXR_OK;
+    size_t bytes[4];
+    int rc = update_check(ctx, "rxr_update_meshes", mesh_indices, n, vertex_stride, triangle_stride, bytes);
+    if (rc != RXR_OK) return rc;
+    const void *arrays[4] = {counts, vertices, indices, normals};
+    for (int i = 0; i < 4; ++i)
+        if (bytes[i] && !arrays[i]) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_update_meshes: NULL array");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if ((rc = rxr_quiesce(ctx)) != RXR_OK) return rc;   // renders and picks read the pools
+    QueryLane &lane = ctx->lane[Q_MESH_UPDATE];
+    QueryIO io{ctx, lane};
+    // (an array of 0 bytes -- a stride of 0, every named mesh empty -- is not staged; the kernels never read it)
+    const unsigned i_c = io.in(counts, bytes[0]), i_v = io.in(bytes[1] ? vertices : nullptr, bytes[1]), i_i = io.in(bytes[2] ? indices : nullptr, bytes[2]),
+                   i_n = io.in(bytes[3] ? normals : nullptr, bytes[3]);
+    if ((rc = io.upload()) != RXR_OK) return rc;
+    rc = update_run(ctx, "rxr_update_meshes", mesh_indices, n, io.dev<uint32_t>(i_c), io.dev<float>(i_v), io.dev<uint32_t>(i_i), io.dev<float>(i_n), vertex_stride,
+                    triangle_stride, ctx->stream);
+    if (rc != RXR_OK) (void)hipStreamSynchronize(ctx->stream);   // (the caller's arrays have been read before the call returns)
+    return rc;
+}
+
+int rxr_update_meshes_to(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t n, const uint32_t *dev_counts, const float *dev_vertices,
+                         const uint32_t *dev_indices, const float *dev_normals, uint32_t vertex_stride, uint32_t triangle_stride, void *hip_stream) {
+    if (!ctx) return RXR_ERR_INVALID;
+    if (ctx->group) return rxr_fail(ctx, RXR_ERR_UNSUPPORTED, "rxr_update_meshes_to on a multi-device context: device pointers and streams belong to ONE device (use rxr_member)");
+    if (!n) return RXR_OK;
+    size_t bytes[4];
+    int rc = update_check(ctx, "rxr_update_meshes_to", mesh_indices, n, vertex_stride, triangle_stride, bytes);
+    if (rc != RXR_OK) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const struct {
+        const void *p;
+        const char *name;
+    } arrays[4] = {{dev_counts, "dev_counts"}, {dev_vertices, "dev_vertices"}, {dev_indices, "dev_indices"}, {dev_normals, "dev_normals"}};
+    for (int i = 0; i < 4; ++i) {
+        if (!bytes[i]) continue;   // (strides of 0: every named mesh is empty, the array is not looked at)
+        if (!arrays[i].p || ((uintptr_t)arrays[i].p & 3u))
+            return rxr_fail(ctx, RXR_ERR_INVALID, std::string("rxr_update_meshes_to: ") + arrays[i].name + " must be 4-byte aligned device memory");
+        if (!rxr_on_device(ctx, arrays[i].p, bytes[i]))
+            return rxr_fail(ctx, RXR_ERR_INVALID, std::string("rxr_update_meshes_to: ") + arrays[i].name + " is not device memory of the context's device (or is too small)");
+    }
+    if ((rc = rxr_quiesce(ctx)) != RXR_OK) return rc;   // renders and picks read the pools
+    return update_run(ctx, "rxr_update_meshes_to", mesh_indices, n, dev_counts, dev_vertices, dev_indices, dev_normals, vertex_stride, triangle_stride,
+                      hip_stream ? (hipStream_t)hip_stream : ctx->stream);
+}
+
+int rxr_mesh_bounds(rxr_ctx *ctx, uint32_t mesh_index, float lo[3], float hi[3]) {
+    if (!ctx) return RXR_ERR_INVALID;
+    if (ctx->group) return rxr_as_member0(ctx, [&](rxr_ctx *m) { return rxr_mesh_bounds(m, mesh_index, lo, hi); });
+    if (!lo || !hi) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_mesh_bounds: NULL output");
+    if (!ctx->meshes_valid || mesh_index >= ctx->meshes.size()) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_mesh_bounds: no such mesh");
+    memcpy(lo, ctx->meshes[mesh_index].aabb_lo, 12);
+    memcpy(hi, ctx->meshes[mesh_index].aabb_hi, 12);
+    return RXR_OK;
+}
+
+// Not part of include/rxr.h: device memory of the context for a host layer that links no HIP runtime of its own (the C++ mirror's
+// Scene::rebuild_terrain_meshes builds chunk meshes into it and hands them to rxr_update_meshes_to).  At least `bytes`, 256-byte
+// aligned, owned by the context and valid until the next call asks for more (which waits for queued work first) or rxr_destroy; NULL
+// on failure or on a multi-device handle.
+void *rxr_mirror_scratch(rxr_ctx *ctx, size_t bytes) {
+    if (!ctx || ctx->group) return nullptr;
+    if (hipSetDevice(ctx->device) != hipSuccess) return nullptr;
+    if (rxr_ensure(ctx, ctx->d_mirror_scratch, bytes ? bytes : 16) != RXR_OK) return nullptr;
+    return ctx->d_mirror_scratch.p;
 }
 
 // ---- the 2D half of the device-side projection (row N1): Batch2D::project's inputs, registered once ---------------------------

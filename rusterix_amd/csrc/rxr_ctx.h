@@ -35,6 +35,7 @@ enum : uint32_t {
     Q_TERRAIN,   // rxr_bake_terrain_to: the resident terrain
     Q_HEIGHTS,   // rxr_terrain_hits_to: the resident heights
     Q_MESH,      // rxr_terrain_meshes_to: the resident heights and their presence mask
+    Q_MESH_UPDATE,   // rxr_update_meshes: the staged copies of the caller's host arrays (both forms block; the lane orders nothing else)
     Q_LANES
 };
 #define RXR_MAX_TILE_ROWS 2048u   // frames of at most 32768 rows
@@ -208,6 +209,9 @@ struct rxr_ctx {
     ProjectParams PP{};
     size_t mesh_verts_out = 0, mesh_tris_out = 0;
     size_t pp_off_meshes = 0;  // byte offset of the per-frame DevMesh array inside d_proj_misc
+    size_t obj_off_meshes = 0; // byte offset of the registration's static DevMesh array inside d_obj (PP.meshes moves to the per-frame one)
+    DevBuf d_mesh_check;       // rxr_update_meshes: one MeshCheckRec per named mesh
+    DevBuf d_mirror_scratch;   // rxr_mirror_scratch (rxr_api.hip): a host layer's device scratch
     bool frame_uses_meshes = false;
     // ... and its 2D half (rxr_set_meshes2d / rxr_set_projection2d)
     struct HostMesh2D {
@@ -384,6 +388,8 @@ struct BlobCursor {
 void rxr_group_destroy(rxr_ctx *ctx);
 int rxr_group_set_textures(rxr_ctx *ctx, const rxr_tile *static_tiles, uint32_t n_static, const rxr_tile *dynamic_tiles, uint32_t n_dynamic);
 int rxr_group_set_meshes(rxr_ctx *ctx, const rxr_mesh3d *meshes, uint32_t n_meshes);
+int rxr_group_update_meshes(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t n, const uint32_t *counts, const float *vertices, const uint32_t *indices,
+                            const float *normals, uint32_t vertex_stride, uint32_t triangle_stride);
 int rxr_group_set_meshes2d(rxr_ctx *ctx, const rxr_mesh2d *meshes, uint32_t n_meshes);
 int rxr_group_set_projection2d(rxr_ctx *ctx, const float *mat3);
 int rxr_group_set_shaders(rxr_ctx *ctx, const rxr_shader_set *set);

@@ -357,6 +357,14 @@ int rxr_group_set_meshes(rxr_ctx *ctx, const rxr_mesh3d *meshes, uint32_t n_mesh
     return run_all(ctx, [&](uint32_t i) { return rxr_set_meshes(ctx->group->members[i], meshes, n_meshes); });
 }
 
+int rxr_group_update_meshes(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t n, const uint32_t *counts, const float *vertices, const uint32_t *indices,
+                            const float *normals, uint32_t vertex_stride, uint32_t triangle_stride) {
+    // (every member holds the same registration, so all accept or all refuse)
+    return run_all(ctx, [&](uint32_t i) {
+        return rxr_update_meshes(ctx->group->members[i], mesh_indices, n, counts, vertices, indices, normals, vertex_stride, triangle_stride);
+    });
+}
+
 int rxr_group_set_meshes2d(rxr_ctx *ctx, const rxr_mesh2d *meshes, uint32_t n_meshes) {
     return run_all(ctx, [&](uint32_t i) { return rxr_set_meshes2d(ctx->group->members[i], meshes, n_meshes); });
 }

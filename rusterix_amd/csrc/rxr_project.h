@@ -132,3 +132,30 @@ struct Project2DParams {
     uint32_t *d2_box;               // min_x, max_x, min_y, max_y of the non-empty pixel boxes (RasterParams.d2_box_dev)
     uint32_t *bad_line;             // pinned status word: a segment end point beyond +-2^30 (the host builder refuses the frame)
 };
+
+// ---- rxr_update_meshes (include/rxr.h): some registered meshes' geometry replaced in place, counts unchanged ---------------------------
+#define RXR_MESH_UPDATE_LAUNCH 256u   // named meshes per launch (1 KiB of kernel arguments)
+// what k_mesh_check finds out about one named mesh; the host reads the records back and refuses the call if any status is set
+enum : uint32_t { MESH_UPD_BAD_VERTS = 1u, MESH_UPD_BAD_TRIS = 2u, MESH_UPD_BAD_INDEX = 4u };
+struct MeshCheckRec {
+    uint32_t status;         // MESH_UPD_* (0: accepted)
+    uint32_t bad_triangle;   // MESH_UPD_BAD_INDEX: the first triangle with a vertex index >= the vertex count
+    float lo[3], hi[3];      // the object-space box of the new vertices (batch3d.rs:494-507): +-inf without a non-NaN coordinate
+};  // 32 B
+struct MeshUpdateArgs {
+    const DevMesh *meshes;       // the registration's static array (bases and counts)
+    // the caller's arrays in the layout of rxr_terrain_meshes, from this launch's first named mesh on
+    const uint32_t *counts;      // [n][2]
+    const float *vertices;       // [n][vstride][4]
+    const uint32_t *indices;     // [n][tstride][3], mesh-local
+    const float *normals;        // [n][vstride][3]
+    uint32_t vstride, tstride;
+    MeshCheckRec *rec;           // [n]
+    // the pools (ProjectParams): object space at vin_base / tin_base, the static originals of the output pools at vout_base / tout_base
+    float4 *obj_verts;
+    uint32_t *obj_idx;
+    float *obj_normals;
+    float *nrm;
+    uint32_t *idx;
+    uint32_t mesh[RXR_MESH_UPDATE_LAUNCH];   // the named meshes, rxr_set_meshes order
+};

@@ -235,6 +235,145 @@ extern "C" __global__ void __launch_bounds__(256) k_proj_static(ProjectParams P)
     }
 }
 
+// ---- rxr_update_meshes (include/rxr.h): the geometry of some registered meshes replaced in place, counts unchanged -------------------
+// Two phases, because a refused call changes nothing: k_mesh_check reads the caller's arrays only and leaves one record per named
+// mesh; the host reads the records and, if every status is 0, launches k_mesh_commit, which redoes for those meshes what
+// rxr_set_meshes' upload and k_proj_static did (the object pools; the static originals of clipped_indices / clipped_normals,
+// batch3d.rs:566-574).  One workgroup per named mesh in both; the mesh numbers travel as kernel arguments.
+namespace {
+// A reduction over the 64 lanes of a wave with DPP operands (EVERY lane active), the ladder of rxm::wave_max_nonneg: inside each quad,
+// across the quads of a row of 16, rows 0 -> 1 and 2 -> 3 (row_bcast:15), rows 0..1 -> 2..3 (row_bcast:31) -- lane 63 holds the
+// result, which comes back in a scalar register.  Lanes a pattern does not write read `identity`.
+template <class Op> __device__ __forceinline__ uint32_t wave_reduce_bits(uint32_t v, const uint32_t identity, Op op) {
+    int x = (int)v;
+#define RXR_DPP_STEP(ctrl, row_mask) x = (int)op((uint32_t)x, (uint32_t)__builtin_amdgcn_update_dpp((int)identity, x, ctrl, row_mask, 0xf, false))
+    RXR_DPP_STEP(0xB1, 0xf);   // quad_perm:[1,0,3,2]
+    RXR_DPP_STEP(0x4E, 0xf);   // quad_perm:[2,3,0,1]
+    RXR_DPP_STEP(0x141, 0xf);  // row_half_mirror
+    RXR_DPP_STEP(0x140, 0xf);  // row_mirror: every lane of a row holds the row's result
+    RXR_DPP_STEP(0x142, 0xa);  // row_bcast:15 into rows 1 and 3
+    RXR_DPP_STEP(0x143, 0xc);  // row_bcast:31 into rows 2 and 3
+#undef RXR_DPP_STEP
+    return (uint32_t)__builtin_amdgcn_readlane(x, 63);
+}
+// (operands are never NaN here: the per-lane running values start at +-inf and fminf / fmaxf drop a NaN coordinate)
+__device__ __forceinline__ float wave_min_f32(float v) {
+    return __uint_as_float(wave_reduce_bits(__float_as_uint(v), __float_as_uint(INFINITY),
+                                            [](uint32_t a, uint32_t b) { return __float_as_uint(fminf(__uint_as_float(a), __uint_as_float(b))); }));
+}
+__device__ __forceinline__ float wave_max_f32(float v) {
+    return __uint_as_float(wave_reduce_bits(__float_as_uint(v), __float_as_uint(-INFINITY),
+                                            [](uint32_t a, uint32_t b) { return __float_as_uint(fmaxf(__uint_as_float(a), __uint_as_float(b))); }));
+}
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+    return wave_reduce_bits(v, 0xFFFFFFFFu, [](uint32_t a, uint32_t b) { return min(a, b); });
+}
+// the caller's arrays are 4-byte aligned, no more
+struct alignas(4) Words4 {
+    uint32_t x, y, z, w;
+};
+}  // namespace
+
+// phase 1: counts against the registration, every index against the vertex count, the object-space box (batch3d.rs:494-507).  Reads
+// no slot past the mesh's counts and writes nothing but its record.
+extern "C" __global__ void __launch_bounds__(256) k_mesh_check(MeshUpdateArgs A) {
+    __shared__ uint32_t s_part[4][8];   // per wave: first bad triangle, lo[3], hi[3]
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, b = blockIdx.x;
+    const uint32_t m = A.mesh[b];
+    const uint32_t nv = A.counts[2 * (size_t)b], nt = A.counts[2 * (size_t)b + 1];
+    const uint32_t status = (nv != A.meshes[m].n_verts ? MESH_UPD_BAD_VERTS : 0u) | (nt != A.meshes[m].n_tris ? MESH_UPD_BAD_TRIS : 0u);
+    // (workgroup-uniform: a mesh whose counts differ is not looked at any further -- the strides were checked against the registered counts)
+    const uint32_t n_words = status ? 0u : 3u * nt, n_box = status ? 0u : nv;   // (3 * n_tris < 2^31: rxr_set_meshes)
+
+    const uint32_t *ix = A.indices + (size_t)b * A.tstride * 3;
+    uint32_t bad = 0xFFFFFFFFu;
+    for (uint32_t w = tid; w < n_words; w += 256u)   // (consecutive lanes, consecutive words)
+        if (ix[w] >= nv) bad = min(bad, w / 3u);
+
+    const float *vx = A.vertices + (size_t)b * A.vstride * 4;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (uint32_t v = tid; v < n_box; v += 256u) {
+        Words4 p;
+        __builtin_memcpy(&p, vx + 4 * (size_t)v, sizeof(p));
+        const float c[3] = {__uint_as_float(p.x), __uint_as_float(p.y), __uint_as_float(p.z)};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {   // f32::min / f32::max: a NaN operand is ignored
+            lo[k] = fminf(lo[k], c[k]);
+            hi[k] = fmaxf(hi[k], c[k]);
+        }
+    }
+    // (every lane is back here: the loops above are the only divergence)
+    const uint32_t wbad = wave_min_u32(bad);
+    float wlo[3], whi[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        wlo[k] = wave_min_f32(lo[k]);
+        whi[k] = wave_max_f32(hi[k]);
+    }
+    if (lane == 0u) {
+        s_part[wave][0] = wbad;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            s_part[wave][1 + k] = __float_as_uint(wlo[k]);
+            s_part[wave][4 + k] = __float_as_uint(whi[k]);
+        }
+    }
+    __syncthreads();
+    if (tid == 0u) {
+        MeshCheckRec r;
+        uint32_t first = 0xFFFFFFFFu;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            r.lo[k] = INFINITY;
+            r.hi[k] = -INFINITY;
+        }
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            first = min(first, s_part[w][0]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                r.lo[k] = fminf(r.lo[k], __uint_as_float(s_part[w][1 + k]));
+                r.hi[k] = fmaxf(r.hi[k], __uint_as_float(s_part[w][4 + k]));
+            }
+        }
+        r.status = status | (first != 0xFFFFFFFFu ? MESH_UPD_BAD_INDEX : 0u);
+        r.bad_triangle = first != 0xFFFFFFFFu ? first : 0u;
+        A.rec[b] = r;
+    }
+}
+
+// phase 2 (every record accepted): the mesh's own slots of the object pools and of the output pools' originals; no uvs, no slot of
+// another mesh, no appended slot (those past vout_base + n_verts / tout_base + n_tris belong to the frame's clipping)
+extern "C" __global__ void __launch_bounds__(256) k_mesh_commit(MeshUpdateArgs A) {
+    const uint32_t tid = threadIdx.x, b = blockIdx.x;
+    const uint32_t m = A.mesh[b];
+    const uint32_t nv = A.meshes[m].n_verts, nt = A.meshes[m].n_tris;
+    const uint32_t vin = A.meshes[m].vin_base, tin = A.meshes[m].tin_base, vout = A.meshes[m].vout_base, tout = A.meshes[m].tout_base;
+
+    const float *vx = A.vertices + (size_t)b * A.vstride * 4;
+    uint4 *dv = reinterpret_cast<uint4 *>(A.obj_verts + vin);
+    for (uint32_t v = tid; v < nv; v += 256u) {
+        Words4 p;
+        __builtin_memcpy(&p, vx + 4 * (size_t)v, sizeof(p));
+        dv[v] = make_uint4(p.x, p.y, p.z, p.w);
+    }
+    // (words, not floats: a NaN keeps its payload)
+    const uint32_t *ns = reinterpret_cast<const uint32_t *>(A.normals + (size_t)b * A.vstride * 3);
+    uint32_t *dn = reinterpret_cast<uint32_t *>(A.obj_normals + 3 * (size_t)vin), *on = reinterpret_cast<uint32_t *>(A.nrm + 3 * (size_t)vout);
+    for (size_t w = tid; w < 3 * (size_t)nv; w += 256u) {
+        const uint32_t f = ns[w];
+        dn[w] = f;
+        on[w] = f;
+    }
+    const uint32_t *ix = A.indices + (size_t)b * A.tstride * 3;
+    uint32_t *di = A.obj_idx + 3 * (size_t)tin, *oi = A.idx + 3 * (size_t)tout;
+    for (uint32_t w = tid; w < 3u * nt; w += 256u) {
+        const uint32_t i = ix[w];
+        di[w] = i;
+        oi[w] = i;
+    }
+}
+
 // per frame: reset the per-mesh boxes to (+inf, +inf, -inf, -inf), batch3d.rs:750-753
 namespace {
 // P.ticket[1]: does ANY triangle of the frame append vertices / fan triangles (near-plane clip)?  Cleared here, raised by k_clip_count.
@@ -570,6 +709,13 @@ extern "C" void rxr_launch_proj_static(const ProjectParams *P, hipStream_t s) {
     uint32_t n = P->n_verts_in > P->n_tris_in ? P->n_verts_in : P->n_tris_in;
     if (n == 0) return;
     RXR_LAUNCH(k_proj_static, dim3((n + 255u) / 256u), dim3(256), s, *P);
+}
+// rxr_update_meshes: n <= RXR_MESH_UPDATE_LAUNCH named meshes, phase 1 / phase 2
+extern "C" void rxr_launch_mesh_check(const MeshUpdateArgs *A, uint32_t n, hipStream_t s) {
+    if (n) RXR_LAUNCH(k_mesh_check, dim3(n), dim3(256), s, *A);
+}
+extern "C" void rxr_launch_mesh_commit(const MeshUpdateArgs *A, uint32_t n, hipStream_t s) {
+    if (n) RXR_LAUNCH(k_mesh_commit, dim3(n), dim3(256), s, *A);
 }
 extern "C" void rxr_launch_project(const ProjectParams *P, hipStream_t s) {
     if (P->n_meshes == 0) return;

@@ -91,6 +91,9 @@ def rxr_abi():
         "rxr_terrain_meshes": (i32, [vp, vp, u32, i32, vp, vp, vp, vp]),
         "rxr_terrain_meshes_to": (i32, [vp, vp, u32, i32, vp, vp, vp, vp, vp]),
         "rxr_debug_terrain_mesh_launches": (u32, [vp]),
+        "rxr_update_meshes": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, u32]),
+        "rxr_update_meshes_to": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, u32, vp]),
+        "rxr_mesh_bounds": (i32, [vp, u32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -172,6 +172,34 @@ pub fn terrain_ray_hits(rays: &[Ray], max_distance: f32) -> Option<Vec<Option<Te
     })).collect())
 }
 
+// ---- registered meshes updated in place (include/rxr.h rxr_update_meshes) ----------------------------------------
+/// Replaces the geometry of already registered meshes (`mesh_indices`, in the order the shim registered the scene's batches) when
+/// their counts are unchanged -- a height stroke on a terrain chunk -- instead of registering the whole scene again.  The slices are
+/// in the layout `rxr_terrain_meshes` writes: `counts` [n][2], `vertices` [n][vertex_stride][4], `indices` [n][triangle_stride][3],
+/// `normals` [n][vertex_stride][3].  True: the device holds the new geometry (the next frame is uploaded as usual; the shim's mesh
+/// fingerprint is left alone, so keep the host batches' sampled bytes as they were or call `invalidate_device_caches()`).  False:
+/// no device context, slices too short, or the library refused (counts changed, an index out of range): nothing was changed on the
+/// device and the caller registers the scene again.
+pub fn update_meshes(mesh_indices: &[u32], counts: &[u32], vertices: &[f32], indices: &[u32], normals: &[f32], vertex_stride: u32, triangle_stride: u32) -> bool {
+    let guard = STATE.lock().unwrap();
+    let Some(ctx) = guard.as_ref().and_then(|st| st.ctx.as_ref()) else { return false };
+    let (n, vs, ts) = (mesh_indices.len(), vertex_stride as usize, triangle_stride as usize);
+    if counts.len() < 2 * n || vertices.len() < n * vs * 4 || indices.len() < n * ts * 3 || normals.len() < n * vs * 3 {
+        return false;
+    }
+    unsafe {
+        rxr_update_meshes(ctx.0, mesh_indices.as_ptr(), n as u32, counts.as_ptr(), vertices.as_ptr(), indices.as_ptr(), normals.as_ptr(), vertex_stride, triangle_stride) == RXR_OK
+    }
+}
+
+/// The object-space box (lo, hi) the device context holds for registered mesh `mesh_index` (`rxr_mesh_bounds`): debugging.
+pub fn mesh_bounds(mesh_index: u32) -> Option<([f32; 3], [f32; 3])> {
+    let guard = STATE.lock().unwrap();
+    let ctx = guard.as_ref()?.ctx.as_ref()?;
+    let (mut lo, mut hi) = ([0f32; 3], [0f32; 3]);
+    (unsafe { rxr_mesh_bounds(ctx.0, mesh_index, lo.as_mut_ptr(), hi.as_mut_ptr()) } == RXR_OK).then_some((lo, hi))
+}
+
 // ---- NodeOp tree -> the word stream of include/rxr.h ------------------------------------------------------------
 /// Depth-first serialisation of `Program.user_functions[i]` (rusteria/src/node/nodeop.rs:12-103): opcode = the variant's
 /// position in the enum, payloads as documented in include/rxr.h.  Block lengths are in words.
