@@ -863,6 +863,77 @@ int rxr_terrain_meshes(rxr_ctx *ctx, const int32_t *chunk_coords /* [n][2] */, u
 int rxr_terrain_meshes_to(rxr_ctx *ctx, const int32_t *chunk_coords, uint32_t n, int32_t chunk_size, uint32_t *dev_counts,
                           float *dev_vertices, uint32_t *dev_indices, float *dev_normals, void *hip_stream);
 
+/* ---- generated terrain heights: TerrainGenerator::sample_height_at (rusterix_amd/csrc/rxr_terrain_gen.hip) ------------------------
+ * The height field the 3D chunk builder and the region server evaluate (src/chunkbuilder/terrain_generator.rs:57-163, :488-509):
+ * per point the maximum of a smoothstep cone per control vertex times the map-edge falloff (interpolate_height_at, :650-714,
+ * calculate_map_edge_falloff, :718-743), plus the ridge sectors' heights by the distance to their polygon edges
+ * (calculate_ridge_height_at, :513-550), pulled towards the road and river linedefs in list order (apply_linedef_smoothing,
+ * :555-623).  Every f32 operation once, in the reference's order, divisions and square roots correctly rounded: the bits are the
+ * reference's, except behind a powf (the ridge and linedef falloffs), which is the device's libm call.  Kept as it is: the
+ * exact-match scan (magnitude < 1e-6) runs over ALL control points before the cones, the first in list order wins and returns
+ * height * edge_factor without the cones (ridges and linedefs still apply); with no control point the base is 0.0 without the edge
+ * factor; the maximum starts at +0.0 and takes a contribution only under `>` (negative and NaN contributions never count);
+ * f32::min skips a NaN, so a ridge without edges is at distance +inf and contributes 0.0; clamp(0.0, 1.0) keeps a NaN and -0.0;
+ * ridge contributions are added and linedefs folded in list order, a linedef only when its influence > 0.0, the over-influence
+ * correction last.  TerrainConfig's idw_power and max_influence_distance are read by nothing in the reference and do not cross this
+ * boundary; apply_exclusions, partition_by_tiles and the blend batches stay host work, fed by these heights. */
+#define RXR_TERRAIN_GEN_CONTROL_POINT_FLOATS 4u /* x, y, height, smoothness (the caller has applied config.smoothness's default)   */
+#define RXR_TERRAIN_GEN_RIDGE_FLOATS 4u         /* height, plateau_width, falloff_distance, falloff_steepness                      */
+#define RXR_TERRAIN_GEN_RIDGE_EDGE_FLOATS 4u    /* x0, y0, x1, y1, in the sector's linedef order                                    */
+#define RXR_TERRAIN_GEN_LINEDEF_FLOATS 9u       /* the reference's tuple of seven: start (x, y), end (x, y), start_height,
+                                                   end_height, width, falloff_distance, falloff_steepness                          */
+#define RXR_TERRAIN_GEN_MAX_CONTROL_POINTS (1u << 16)
+#define RXR_TERRAIN_GEN_MAX_RIDGES (1u << 12)
+#define RXR_TERRAIN_GEN_MAX_RIDGE_EDGES (1u << 16)
+#define RXR_TERRAIN_GEN_MAX_LINEDEFS (1u << 14)
+/* validation only, no context: the status rxr_set_terrain_generator would return and, in `message`, the reason.
+ * RXR_ERR_UNSUPPORTED: a count above its RXR_TERRAIN_GEN_MAX_*.  RXR_ERR_INVALID: a NULL array with a non-zero count, a NULL
+ * map_box, ridge_edge_offsets that do not start at 0, decrease or do not end at n_ridge_edges, edges without a ridge. */
+int rxr_check_terrain_generator(const float *control_points, uint32_t n_control_points, const float *ridges, uint32_t n_ridges,
+                                const uint32_t *ridge_edge_offsets, const float *ridge_edges, uint32_t n_ridge_edges,
+                                const float *linedefs, uint32_t n_linedefs, const float map_box[4], char *message,
+                                uint32_t message_capacity);
+/* makes the lists TerrainGenerator::generate collects (:255-294) resident, flattened by the caller (they stay until the next call).
+ * The caller skips a sector or an edge the reference would skip for a missing id.  map_box: (min.x, min.y, max.x, max.y) after the
+ * reference's flip of y, or its +-100 fallback.  Every count may be 0 and any f32 bit pattern is legal in a record.  What does not
+ * depend on the point (a segment's direction, squared length and degenerate test, a control point's doubled radius, a linedef's
+ * height difference) is computed here, once, in the reference's f32 operations.  Re-registration waits for queued evaluations.
+ * Independent of rxr_set_terrain and rxr_set_terrain_heights.  Arrays are read before the call returns.  A refused call leaves
+ * the resident records as they were.  Multi-device handles: member 0.
+ * Replaces: collect_control_points / collect_ridge_sectors / collect_terrain_linedefs per call, :57-154, :325-435. */
+int rxr_set_terrain_generator(rxr_ctx *ctx, const float *control_points /* [n_control_points][4] */, uint32_t n_control_points,
+                              const float *ridges /* [n_ridges][4] */, uint32_t n_ridges,
+                              const uint32_t *ridge_edge_offsets /* [n_ridges + 1]: ridge r owns edges [r] .. [r + 1] */,
+                              const float *ridge_edges /* [n_ridge_edges][4] */, uint32_t n_ridge_edges,
+                              const float *linedefs /* [n_linedefs][9] */, uint32_t n_linedefs, const float map_box[4]);
+/* n points [n][2] against the resident records: heights [n] = sample_height_at; normals [n][3] (may be NULL) = sample_normal_at
+ * (:166-181): the heights at p, p + (0.1, 0.0) and p + (0.0, 0.1) in the same launch, the tangents' cross product, normalised as
+ * vek does it.  A NaN where the reference has one; its sign and payload are the device's.  RXR_ERR_INVALID: no
+ * rxr_set_terrain_generator yet, or a NULL required pointer; n == 0 does nothing.  Host memory, blocking.  The call is split into
+ * launches of bounded work, points x records (RXR_TERRAIN_GEN_LAUNCH_POINTS in the environment, read at each call, overrides the
+ * points a launch).  Changes no frame, scratch, bake, picking or mesh state.  Multi-device handles: member 0.
+ * Replaces: TerrainGenerator::sample_height_at / sample_normal_at, :57-181; src/server/region.rs:2059-2066. */
+int rxr_generated_heights(rxr_ctx *ctx, const float *points, uint32_t n, float *heights, float *normals);
+/* the same on DEVICE arrays (each given array's first and last byte are checked to be memory of the context's device; 4-byte
+ * aligned), queued on hip_stream (NULL = the context's stream).  Asynchronous.  Multi-device handles: RXR_ERR_UNSUPPORTED. */
+int rxr_generated_heights_to(rxr_ctx *ctx, const float *dev_points, uint32_t n, float *dev_heights, float *dev_normals,
+                             void *hip_stream);
+/* the grids of generate_grid (:460-485) for n chunk boxes [n][4] = (min.x, min.y, max.x, max.y) in one call: with cell_size =
+ * 1.0 / subdivisions as f32 and the floor of min / the ceil of max, steps = ceil((max - min) / cell_size) as i32 + 1 per axis and
+ * the point (ix, iy) is (min_x + ix as f32 * cell_size, min_y + iy as f32 * cell_size), made on the device.  counts [n][2] =
+ * (steps_x, steps_y) of box i, a negative one as 0 (the grid is then empty; an extent whose `as i32` saturates wraps to a negative
+ * step with the `+ 1`, as a release build of the reference does: an infinite box is an empty grid, not an error); heights of box i start at heights + i * stride, in
+ * the reference's iy-major order; slots past steps_x * steps_y are NOT written.  RXR_ERR_INVALID: no rxr_set_terrain_generator
+ * yet, subdivisions == 0, a NULL pointer, a box whose grid exceeds `stride` points (nothing is queued then), sizes that overflow.
+ * n == 0 does nothing.  Host memory, blocking.  Launches and state as rxr_generated_heights.  Multi-device handles: member 0.
+ * Replaces: generate_grid and interpolate_heights, :460-509. */
+int rxr_generated_grids(rxr_ctx *ctx, const float *boxes, uint32_t n, uint32_t subdivisions, uint32_t stride, uint32_t *counts,
+                        float *heights);
+/* the same into DEVICE arrays, queued on hip_stream (NULL = the context's stream); boxes is host memory and is read before the
+ * call returns.  Asynchronous.  Multi-device handles: RXR_ERR_UNSUPPORTED (use rxr_member). */
+int rxr_generated_grids_to(rxr_ctx *ctx, const float *boxes, uint32_t n, uint32_t subdivisions, uint32_t stride,
+                           uint32_t *dev_counts, float *dev_heights, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -502,6 +502,21 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         L.terrain_build_mesh = fn("terrain_build_mesh", vp, vp, i32, i32)
         L.terrain_build_meshes = fn("terrain_build_meshes", i32, vp, C.POINTER(C.c_int32), u32, i32, C.POINTER(vp))
 
+    # the generated terrain's height field (product host library only)
+    has_terrain_gen = hasattr(lib, prefix + "terrain_generator_new")
+    if has_terrain_gen:
+        pi_ = C.POINTER(C.c_int32)
+        L.terrain_generator_new = fn("terrain_generator_new", vp, u32)
+        L.terrain_generator_free = fn("terrain_generator_free", None, vp)
+        L.terrain_generator_set = fn("terrain_generator_set", i32, vp, pf, u32, pf, u32, pu, pf, u32, pf, u32, pf)
+        L.terrain_generator_sample_cpu = fn("terrain_generator_sample_cpu", None, vp, pf, u32, pf, pf)
+        L.terrain_generator_sample = fn("terrain_generator_sample", i32, vp, pf, u32, pf, pf)
+        L.terrain_generator_tile_normal = fn("terrain_generator_tile_normal", None, vp, i32, i32, pf)
+        L.terrain_generator_tile_outline = fn("terrain_generator_tile_outline", None, vp, i32, i32, pf)
+        L.terrain_generator_grid = fn("terrain_generator_grid", None, vp, pf, pi_, pf, u32)
+        L.terrain_generator_triangulate = fn("terrain_generator_triangulate", None, i32, i32, pu)
+        L.terrain_generator_grids = fn("terrain_generator_grids", i32, vp, pf, u32, u32, i32, pu, pf)
+
     # registered meshes updated in place (product host library only)
     has_mesh_update = hasattr(lib, prefix + "scene_rebuild_terrain_meshes")
     if has_mesh_update:
@@ -1079,6 +1094,121 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
             """the same list from the CPU build_mesh over the host's worker pool"""
             return self._meshes(coords, False)
 
+    class TerrainGenerator:
+        """reference src/chunkbuilder/terrain_generator.rs: the height field of the generated 3D terrain over the lists
+        TerrainGenerator::generate collects from the Map (:255-294), which the caller flattens: control_points [C][4] (x, y, height,
+        smoothness), ridges [R][4] (height, plateau_width, falloff_distance, falloff_steepness) with their edges [E][4] (x0, y0, x1,
+        y1) and ridge_edge_offsets [R + 1], linedefs [L][9] (start, end, start_height, end_height, width, falloff_distance,
+        falloff_steepness), map_box (min.x, min.y, max.x, max.y).  `*_cpu` run the host mirror's transcription, the others the device
+        (rxr_generated_heights / rxr_generated_grids, include/rxr.h)"""
+
+        def __init__(self, control_points=(), ridges=(), ridge_edge_offsets=None, ridge_edges=(), linedefs=(), map_box=(-100.0, -100.0, 100.0, 100.0),
+                     subdivisions=1):
+            if not has_terrain_gen:
+                raise NotImplementedError(f"{name}: no terrain generator in this library")
+            self.subdivisions = int(subdivisions)
+            self._h = L.terrain_generator_new(self.subdivisions)
+            self.set(control_points, ridges, ridge_edge_offsets, ridge_edges, linedefs, map_box)
+
+        def __del__(self):
+            if getattr(self, "_h", None):
+                L.terrain_generator_free(self._h)
+                self._h = None
+
+        def set(self, control_points=(), ridges=(), ridge_edge_offsets=None, ridge_edges=(), linedefs=(), map_box=(-100.0, -100.0, 100.0, 100.0)):
+            def records(a, k):   # (an empty list has no shape to infer)
+                a = _f32(a)
+                if a.size % k:
+                    raise ValueError(f"records of {k} floats expected")
+                return a.reshape(a.size // k, k)
+
+            cp, rd, ed, ln, mb = records(control_points, 4), records(ridges, 4), records(ridge_edges, 4), records(linedefs, 9), _f32(map_box, (4,))
+            off = np.ascontiguousarray(np.zeros(1, np.uint32) if ridge_edge_offsets is None else np.asarray(ridge_edge_offsets, np.uint32).reshape(-1))
+            if len(off) != len(rd) + 1:
+                raise ValueError("ridge_edge_offsets must have one entry more than ridges")
+            rc = L.terrain_generator_set(self._h, _fp(cp) if len(cp) else None, len(cp), _fp(rd) if len(rd) else None, len(rd), _up(off),
+                                         _fp(ed) if len(ed) else None, len(ed), _fp(ln) if len(ln) else None, len(ln), _fp(mb))
+            if rc != 0:
+                raise ValueError("ridge_edge_offsets do not describe ridge_edges")
+            return self
+
+        def _sample(self, points, normals, device):
+            p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 2))
+            n = p.shape[0]
+            h, nr = np.zeros(max(n, 1), np.float32), np.zeros((max(n, 1), 3), np.float32)
+            args = (self._h, _fp(p) if n else None, n, _fp(h), _fp(nr) if normals else None)
+            if device:
+                rc = L.terrain_generator_sample(*args)
+                if rc != 0:
+                    raise RasterizeError(rc, last_error())
+            else:
+                L.terrain_generator_sample_cpu(*args)
+            return (h[:n], nr[:n]) if normals else h[:n]
+
+        def sample_heights(self, points):
+            """sample_height_at (:57-163) for [n][2] points in one device call: [n] float32"""
+            return self._sample(points, False, True)
+
+        def sample_normals(self, points):
+            """sample_height_at and sample_normal_at (:166-181) for [n][2] points in one device call: ([n], [n][3]) float32"""
+            return self._sample(points, True, True)
+
+        def sample_heights_cpu(self, points):
+            return self._sample(points, False, False)
+
+        def sample_normals_cpu(self, points):
+            return self._sample(points, True, False)
+
+        def tile_normal(self, tile):
+            """tile_normal (:184-189) on the CPU"""
+            out = np.zeros(3, np.float32)
+            L.terrain_generator_tile_normal(self._h, tile[0], tile[1], _fp(out))
+            return out
+
+        def tile_outline_world(self, tile):
+            """tile_outline_world (:194-242) on the CPU: [4 * max(subdivisions, 1)][3]"""
+            out = np.zeros((4 * max(self.subdivisions, 1), 3), np.float32)
+            L.terrain_generator_tile_outline(self._h, tile[0], tile[1], _fp(out))
+            return out
+
+        def generate_grid(self, box, capacity=1 << 20):
+            """generate_grid (:460-485) on the CPU: (steps_x, steps_y) as the reference's i32 and the points [steps_y][steps_x][2]
+            (None when a step is not positive or the grid exceeds `capacity` points)"""
+            b, steps = _f32(box, (4,)), np.zeros(2, np.int32)
+            L.terrain_generator_grid(self._h, _fp(b), steps.ctypes.data_as(C.POINTER(C.c_int32)), None, 0)
+            sx, sy = int(steps[0]), int(steps[1])
+            if sx <= 0 or sy <= 0 or sx * sy > capacity:
+                return (sx, sy), None
+            pts = np.zeros((sy, sx, 2), np.float32)
+            L.terrain_generator_grid(self._h, _fp(b), steps.ctypes.data_as(C.POINTER(C.c_int32)), _fp(pts), sx * sy)
+            return (sx, sy), pts
+
+        @staticmethod
+        def triangulate(steps_x, steps_y):
+            """triangulate (:829-879) without exclusions, from the counts alone: [2 * (steps_x - 1) * (steps_y - 1)][3] uint32"""
+            n = max(steps_x - 1, 0) * max(steps_y - 1, 0)
+            out = np.zeros((max(2 * n, 1), 3), np.uint32)
+            L.terrain_generator_triangulate(steps_x, steps_y, _up(out))
+            return out[:2 * n]
+
+        def _grids(self, boxes, stride, device, fill):
+            b = np.ascontiguousarray(np.asarray(boxes, np.float32).reshape(-1, 4))
+            n = b.shape[0]
+            counts = np.zeros((max(n, 1), 2), np.uint32)
+            heights = np.full((max(n, 1), max(int(stride), 1)), fill, np.float32)
+            rc = L.terrain_generator_grids(self._h, _fp(b) if n else None, n, int(stride), 1 if device else 0, _up(counts), _fp(heights))
+            if rc != 0:
+                raise RasterizeError(rc, last_error())
+            return counts[:n], heights[:n, :int(stride)]
+
+        def grid_heights(self, boxes, stride, fill=0.0):
+            """the grids of generate_grid for [n][4] chunk boxes in one device call (rxr_generated_grids): counts [n][2] = (steps_x,
+            steps_y) and heights [n][stride], iy-major; slots past a box's count keep `fill`"""
+            return self._grids(boxes, stride, True, fill)
+
+        def grid_heights_cpu(self, boxes, stride, fill=0.0):
+            return self._grids(boxes, stride, False, fill)
+
     class Assets:
         """reference src/server/assets.rs (`tile_list`, `.textures(..)` builder)."""
 
@@ -1314,7 +1444,7 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
 
     return types.SimpleNamespace(
         name=name, lib=lib, prefix=prefix, raw=L, update_meshes=update_meshes,
-        Scene=Scene, Batch3D=Batch3D, Batch2D=Batch2D, Chunk=Chunk, Assets=Assets, Rasterizer=Rasterizer, Terrain=Terrain,
+        Scene=Scene, Batch3D=Batch3D, Batch2D=Batch2D, Chunk=Chunk, Assets=Assets, Rasterizer=Rasterizer, Terrain=Terrain, TerrainGenerator=TerrainGenerator,
         D3OrbitCamera=D3OrbitCamera, D3FirstPCamera=D3FirstPCamera,
         # shared value types
         Texture=Texture, Tile=Tile, Light=Light, PixelSource=PixelSource, RenderMode=RenderMode,

@@ -214,6 +214,60 @@ int rxh_terrain_build_meshes(void *t, const int32_t *coords, uint32_t n, int dev
     for (uint32_t i = 0; i < n; ++i) out[i] = new Batch3D(std::move(meshes[i]));
     return RXR_OK;
 }
+// ---- the generated terrain's height field (rusterix::TerrainGenerator) ----------------------------
+void *rxh_terrain_generator_new(uint32_t subdivisions) {
+    TerrainGenerator *g = new TerrainGenerator();
+    g->subdivisions = subdivisions;
+    return g;
+}
+void rxh_terrain_generator_free(void *g) { delete (TerrainGenerator *)g; }
+// the lists of rxr_set_terrain_generator (include/rxr.h); 0, or RXR_ERR_INVALID for offsets the lists do not fit (nothing changes then)
+int rxh_terrain_generator_set(void *g_, const float *cps, uint32_t C, const float *ridges, uint32_t R, const uint32_t *off, const float *edges, uint32_t E,
+                              const float *lines, uint32_t L, const float *map_box) {
+    TerrainGenerator *g = (TerrainGenerator *)g_;
+    if (rxr_check_terrain_generator(cps, C, ridges, R, off, edges, E, lines, L, map_box, nullptr, 0) == RXR_ERR_INVALID) return RXR_ERR_INVALID;
+    g->control_points.assign(cps, cps + 4 * (size_t)C);
+    g->ridges.assign(ridges, ridges + 4 * (size_t)R);
+    g->ridge_edge_offsets.assign(1, 0u);
+    if (R) g->ridge_edge_offsets.assign(off, off + R + 1);
+    g->ridge_edges.assign(edges, edges + 4 * (size_t)E);
+    g->linedefs.assign(lines, lines + 9 * (size_t)L);
+    memcpy(g->map_box, map_box, sizeof g->map_box);
+    g->touch();
+    return RXR_OK;
+}
+// interpolate_heights / sample_normal_at for n points on the CPU over the host's worker pool (normals may be NULL)
+void rxh_terrain_generator_sample_cpu(void *g, const float *points, uint32_t n, float *heights, float *normals) {
+    ((TerrainGenerator *)g)->interpolate_heights(points, n, heights, normals);
+}
+// ... and on the device (rxr_generated_heights); RXR_OK or a negative rxr_status
+int rxh_terrain_generator_sample(void *g, const float *points, uint32_t n, float *heights, float *normals) {
+    return ((TerrainGenerator *)g)->sample_heights(points, n, heights, normals);
+}
+void rxh_terrain_generator_tile_normal(void *g, int32_t tx, int32_t tz, float *normal) { ((TerrainGenerator *)g)->tile_normal(tx, tz, normal); }
+// tile_outline_world: out receives [4 * max(subdivisions, 1)][3]
+void rxh_terrain_generator_tile_outline(void *g, int32_t tx, int32_t tz, float *out) {
+    const std::vector<float> o = ((TerrainGenerator *)g)->tile_outline_world(tx, tz);
+    memcpy(out, o.data(), o.size() * sizeof(float));
+}
+// generate_grid's steps; points (may be NULL) receives [steps_y][steps_x][2] when both are positive and their product is at most capacity
+void rxh_terrain_generator_grid(void *g, const float *box, int32_t *steps, float *points, uint32_t capacity) {
+    ((TerrainGenerator *)g)->grid_steps(box, steps[0], steps[1]);
+    if (!points || steps[0] <= 0 || steps[1] <= 0 || (uint64_t)steps[0] * (uint64_t)steps[1] > capacity) return;   // (no points are made then)
+    const std::vector<float> grid = ((TerrainGenerator *)g)->generate_grid(box, steps[0], steps[1]);
+    memcpy(points, grid.data(), grid.size() * sizeof(float));
+}
+// triangulate: 6 * (steps_x - 1) * (steps_y - 1) indices
+void rxh_terrain_generator_triangulate(int32_t steps_x, int32_t steps_y, uint32_t *indices) {
+    const std::vector<uint32_t> t = TerrainGenerator::triangulate(steps_x, steps_y);
+    memcpy(indices, t.data(), t.size() * sizeof(uint32_t));
+}
+// n boxes in the layout of rxr_generated_grids: on the device, or (device == 0) on the CPU
+int rxh_terrain_generator_grids(void *g, const float *boxes, uint32_t n, uint32_t stride, int device, uint32_t *counts, float *heights) {
+    if (device) return ((TerrainGenerator *)g)->grid_heights(boxes, n, stride, counts, heights);
+    ((TerrainGenerator *)g)->grid_heights_cpu(boxes, n, stride, counts, heights);
+    return RXR_OK;
+}
 // Scene::rebuild_terrain_meshes: 0 (updated in place on the device), 1 (fallback: the batches were replaced on the host) or a negative rxr_status
 int rxh_scene_rebuild_terrain_meshes(void *s, void *t, const int32_t *coords, uint32_t n, const uint32_t *chunks) {
     return ((Scene *)s)->rebuild_terrain_meshes(*(const Terrain *)t, coords, n, chunks);

@@ -491,6 +491,7 @@ uint64_t g_tex_static_gen = 0, g_tex_dynamic_gen = 0;
 uint64_t g_shaders_gen = 0, g_shader_env_gen = 0;
 uint64_t g_terrain_gen = 0;   // the Terrain::generation the context's resident terrain was registered from (0: none)
 uint64_t g_heights_gen = 0;   // the Terrain::heights_generation the context's resident heights were registered from (0: none)
+uint64_t g_generator_gen = 0; // the TerrainGenerator::generation the context's resident generator records were registered from (0: none)
 // (RXR_DEVICE_PROJECTION=1 in the environment makes device projection the initial choice, as in the Rust shim: shim/.../lib.rs)
 bool g_device_projection = [] { const char *e = getenv("RXR_DEVICE_PROJECTION"); return e && e[0] == '1'; }();
 bool g_device_edges = !(getenv("RXR_HOST_EDGES") && atoi(getenv("RXR_HOST_EDGES")) != 0);
@@ -526,6 +527,7 @@ void drop_context_locked() {
     g_shaders_gen = g_shader_env_gen = 0;
     g_terrain_gen = 0;
     g_heights_gen = 0;
+    g_generator_gen = 0;
 }
 }  // namespace
 
@@ -1668,6 +1670,241 @@ int Rasterizer::rasterize(Scene &scene, uint8_t *pixels, size_t w, size_t h, siz
     if (timing) fprintf(stderr, "rxr_e2e_timing project_and_handover_ms=%.3f\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     rxr_ctx *ctx = context();
     rc = rxr_render_download(ctx, pixels);
+    if (rc != RXR_OK) g_error = rxr_last_error(ctx);
+    return rc;
+}
+
+// ---- the generated terrain's height field (src/chunkbuilder/terrain_generator.rs) -----------------
+namespace {
+// distance_point_to_segment (:1037-1055) and the same lines of apply_linedef_smoothing (:575-586)
+float gen_segment_distance(Vec2 point, Vec2 seg_start, Vec2 seg_end, float &t_param) {
+    const Vec2 seg = seg_end - seg_start;
+    const float len_sq = rvek::dot(seg, seg);
+    if (len_sq < 1e-8f) {
+        t_param = 0.0f;
+        return rvek::magnitude(point - seg_start);
+    }
+    const float t = rvek::rclamp(rvek::dot(point - seg_start, seg) / len_sq, 0.0f, 1.0f);
+    const Vec2 projection = seg_start + seg * t;
+    t_param = t;
+    return rvek::magnitude(point - projection);
+}
+}  // namespace
+
+float TerrainGenerator::sample_height_at(float x, float y) const {
+    const Vec2 point{x, y};
+    // calculate_map_edge_falloff (:718-743)
+    auto edge_falloff = [&]() {
+        const float min_edge_dist = std::fmin(std::fmin(std::fmin(point.x - map_box[0], map_box[2] - point.x), point.y - map_box[1]), map_box[3] - point.y);
+        if (min_edge_dist <= 0.0f) return 0.0f;
+        if (min_edge_dist >= 10.0f) return 1.0f;
+        const float t = min_edge_dist / 10.0f;
+        return t * t * (3.0f - 2.0f * t);
+    };
+    // interpolate_height_at (:650-714)
+    const size_t C = control_points.size() / 4;
+    float base_height = 0.0f;
+    if (C) {
+        bool exact = false;
+        for (size_t i = 0; i < C && !exact; ++i) {
+            const float *cp = &control_points[4 * i];
+            if (rvek::magnitude(point - Vec2{cp[0], cp[1]}) < 1e-6f) {
+                base_height = cp[2] * edge_falloff();
+                exact = true;
+            }
+        }
+        if (!exact) {
+            float max_height = 0.0f;
+            for (size_t i = 0; i < C; ++i) {
+                const float *cp = &control_points[4 * i];
+                const float distance = rvek::magnitude(point - Vec2{cp[0], cp[1]});
+                const float smoothness = cp[3] * 2.0f;
+                const float effective_radius = smoothness, smoothing = effective_radius;
+                const float sdf_dist = distance - effective_radius;
+                float falloff;
+                if (sdf_dist < -smoothing) falloff = 1.0f;
+                else if (sdf_dist > smoothing) falloff = 0.0f;
+                else {
+                    const float t = (smoothing - sdf_dist) / (2.0f * smoothing);
+                    falloff = t * t * (3.0f - 2.0f * t);
+                }
+                const float height_contribution = cp[2] * falloff;
+                if (height_contribution > max_height) max_height = height_contribution;
+            }
+            base_height = max_height * edge_falloff();
+        }
+    }
+    // calculate_ridge_height_at (:513-550)
+    float ridge_height = 0.0f;
+    for (size_t r = 0; r < ridges.size() / 4; ++r) {
+        const float *rr = &ridges[4 * r];
+        float min_dist = INFINITY;
+        for (uint32_t e = ridge_edge_offsets[r]; e < ridge_edge_offsets[r + 1]; ++e) {
+            const float *s = &ridge_edges[4 * (size_t)e];
+            float t_unused;
+            min_dist = std::fmin(min_dist, gen_segment_distance(point, Vec2{s[0], s[1]}, Vec2{s[2], s[3]}, t_unused));
+        }
+        float contribution;
+        if (min_dist <= rr[1]) contribution = rr[0];
+        else {
+            const float falloff_dist = min_dist - rr[1];
+            if (falloff_dist >= rr[2]) contribution = 0.0f;
+            else {
+                const float t = 1.0f - (falloff_dist / rr[2]);
+                contribution = rr[0] * std::pow(t, rr[3]);
+            }
+        }
+        ridge_height += contribution;
+    }
+    // apply_linedef_smoothing (:555-623)
+    const float current_height = base_height + ridge_height;
+    float final_height = current_height, total_influence = 0.0f;
+    for (size_t l = 0; l < linedefs.size() / 9; ++l) {
+        const float *s = &linedefs[9 * l];
+        float t_param;
+        const float dist_to_line = gen_segment_distance(point, Vec2{s[0], s[1]}, Vec2{s[2], s[3]}, t_param);
+        const float target_height = s[4] + (s[5] - s[4]) * t_param;
+        float influence;
+        if (dist_to_line <= s[6]) influence = 1.0f;
+        else {
+            const float falloff_dist = dist_to_line - s[6];
+            if (falloff_dist >= s[7]) influence = 0.0f;
+            else {
+                const float t = 1.0f - (falloff_dist / s[7]);
+                influence = std::pow(t, s[8]);
+            }
+        }
+        if (influence > 0.0f) {
+            total_influence += influence;
+            final_height = final_height * (1.0f - influence) + target_height * influence;
+        }
+    }
+    if (total_influence > 1.0f) {
+        const float excess = total_influence - 1.0f;
+        final_height = final_height * (1.0f - excess * 0.5f) + current_height * (excess * 0.5f);
+    }
+    return final_height;
+}
+
+void TerrainGenerator::sample_normal_at(float x, float y, float normal[3]) const {
+    const float delta = 0.1f;
+    const float h_center = sample_height_at(x, y);
+    const float h_right = sample_height_at(x + delta, y + 0.0f);
+    const float h_up = sample_height_at(x + 0.0f, y + delta);
+    const Vec3 tangent_x{delta, h_right - h_center, 0.0f}, tangent_z{0.0f, h_up - h_center, delta};
+    const Vec3 n = rvek::normalized(rvek::cross(tangent_x, tangent_z));
+    normal[0] = n.x, normal[1] = n.y, normal[2] = n.z;
+}
+
+void TerrainGenerator::tile_normal(int32_t tx, int32_t tz, float normal[3]) const { sample_normal_at((float)tx + 0.5f, (float)tz + 0.5f, normal); }
+
+std::vector<float> TerrainGenerator::tile_outline_world(int32_t tx, int32_t tz) const {
+    const uint32_t sub = std::max(subdivisions, 1u);
+    const float step = 1.0f / (float)sub;
+    std::vector<float> outline;
+    auto push = [&](float x, float z) {
+        const float v[3] = {x, sample_height_at(x, z), z};
+        outline.insert(outline.end(), v, v + 3);
+    };
+    for (uint32_t i = 0; i < sub; ++i) push((float)tx + (float)i * step, (float)tz);                 // bottom edge, left to right
+    for (uint32_t i = 0; i < sub; ++i) push((float)tx + 1.0f, (float)tz + (float)i * step);          // right edge, bottom to top
+    for (uint32_t i = 0; i < sub; ++i) push((float)tx + 1.0f - (float)i * step, (float)tz + 1.0f);   // top edge, right to left
+    for (uint32_t i = 0; i < sub; ++i) push((float)tx, (float)tz + 1.0f - (float)i * step);          // left edge, top to bottom
+    return outline;
+}
+
+void TerrainGenerator::grid_steps(const float box[4], int32_t &steps_x, int32_t &steps_y) const {
+    const float cell_size = 1.0f / (float)subdivisions;
+    const float min_x = std::floor(box[0]), min_y = std::floor(box[1]), max_x = std::ceil(box[2]), max_y = std::ceil(box[3]);
+    // (`as i32 + 1` wraps in a release build where the cast saturated)
+    steps_x = (int32_t)((uint32_t)as_i32(std::ceil((max_x - min_x) / cell_size)) + 1u);
+    steps_y = (int32_t)((uint32_t)as_i32(std::ceil((max_y - min_y) / cell_size)) + 1u);
+}
+
+std::vector<float> TerrainGenerator::generate_grid(const float box[4], int32_t &steps_x, int32_t &steps_y) const {
+    const float cell_size = 1.0f / (float)subdivisions;
+    const float min_x = std::floor(box[0]), min_y = std::floor(box[1]);
+    grid_steps(box, steps_x, steps_y);
+    std::vector<float> grid;
+    for (int32_t iy = 0; iy < steps_y; ++iy)
+        for (int32_t ix = 0; ix < steps_x; ++ix) {
+            grid.push_back(min_x + (float)ix * cell_size);
+            grid.push_back(min_y + (float)iy * cell_size);
+        }
+    return grid;
+}
+
+void TerrainGenerator::interpolate_heights(const float *points, size_t n, float *heights, float *normals) const {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);   // (the worker pool runs one job at a time)
+    const size_t per = 64, items = (n + per - 1) / per;
+    const size_t records = control_points.size() / 4 + ridge_edges.size() / 4 + linedefs.size() / 9 + 1;
+    rxr_parallel::run(items, n * records * (normals ? 3 : 1), [&](size_t item) {
+        for (size_t i = item * per; i < std::min(n, (item + 1) * per); ++i) {
+            heights[i] = sample_height_at(points[2 * i], points[2 * i + 1]);
+            if (normals) sample_normal_at(points[2 * i], points[2 * i + 1], normals + 3 * i);
+        }
+    });
+}
+
+std::vector<uint32_t> TerrainGenerator::triangulate(int32_t steps_x, int32_t steps_y) {
+    std::vector<uint32_t> indices;
+    if (steps_x < 2 || steps_y < 2) return indices;
+    const uint32_t cols = (uint32_t)steps_x;
+    indices.reserve((size_t)(steps_x - 1) * (steps_y - 1) * 6);
+    for (uint32_t iy = 0; iy + 1 < (uint32_t)steps_y; ++iy)
+        for (uint32_t ix = 0; ix + 1 < cols; ++ix) {
+            const uint32_t i0 = iy * cols + ix, i1 = i0 + 1, i2 = i0 + cols, i3 = i2 + 1;
+            const uint32_t t[6] = {i0, i2, i1, i1, i2, i3};
+            indices.insert(indices.end(), t, t + 6);
+        }
+    return indices;
+}
+
+void TerrainGenerator::grid_heights_cpu(const float *boxes, uint32_t n, uint32_t stride, uint32_t *counts, float *heights) const {
+    for (uint32_t b = 0; b < n; ++b) {
+        int32_t sx, sy;
+        grid_steps(boxes + 4 * (size_t)b, sx, sy);
+        counts[2 * (size_t)b] = (uint32_t)std::max(sx, 0);
+        counts[2 * (size_t)b + 1] = (uint32_t)std::max(sy, 0);
+        if ((uint64_t)std::max(sx, 0) * (uint64_t)std::max(sy, 0) > stride) continue;   // (the points are made only where they fit)
+        const std::vector<float> grid = generate_grid(boxes + 4 * (size_t)b, sx, sy);
+        interpolate_heights(grid.data(), grid.size() / 2, heights + (size_t)b * stride);
+    }
+}
+
+int TerrainGenerator::register_records(rxr_ctx *ctx) const {
+    if (g_generator_gen == generation) return RXR_OK;
+    const int rc = rxr_set_terrain_generator(ctx, control_points.data(), (uint32_t)(control_points.size() / 4), ridges.data(), (uint32_t)(ridges.size() / 4),
+                                             ridge_edge_offsets.data(), ridge_edges.data(), (uint32_t)(ridge_edges.size() / 4), linedefs.data(),
+                                             (uint32_t)(linedefs.size() / 9), map_box);
+    if (rc != RXR_OK) {
+        g_error = rxr_last_error(ctx);
+        return rc;
+    }
+    g_generator_gen = generation;
+    return RXR_OK;
+}
+
+int TerrainGenerator::sample_heights(const float *points, uint32_t n, float *heights, float *normals) const {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::string err;
+    rxr_ctx *ctx = context(&err);
+    if (!ctx) return RXR_ERR_NO_DEVICE;
+    int rc = register_records(ctx);
+    if (rc != RXR_OK) return rc;
+    rc = rxr_generated_heights(ctx, points, n, heights, normals);
+    if (rc != RXR_OK) g_error = rxr_last_error(ctx);
+    return rc;
+}
+
+int TerrainGenerator::grid_heights(const float *boxes, uint32_t n, uint32_t stride, uint32_t *counts, float *heights) const {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::string err;
+    rxr_ctx *ctx = context(&err);
+    if (!ctx) return RXR_ERR_NO_DEVICE;
+    int rc = register_records(ctx);
+    if (rc != RXR_OK) return rc;
+    rc = rxr_generated_grids(ctx, boxes, n, subdivisions, stride, counts, heights);
     if (rc != RXR_OK) g_error = rxr_last_error(ctx);
     return rc;
 }

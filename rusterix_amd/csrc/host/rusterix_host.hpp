@@ -370,6 +370,45 @@ private:
     int register_heights(rxr_ctx *ctx) const;   // rxr_set_terrain_heights unless the context holds this generation
 };
 
+// src/chunkbuilder/terrain_generator.rs: the height field of the generated 3D terrain, over the lists TerrainGenerator::generate
+// collects from the Map (:255-294), flattened as rxr_set_terrain_generator takes them (include/rxr.h).  The CPU functions are plain
+// transcriptions (nothing hoisted); the device forms register the lists when they changed.  apply_exclusions with excluded sectors,
+// partition_by_tiles, mesh_fix_winding and the blend batches are the caller's, fed by these heights.
+class TerrainGenerator {
+public:
+    uint32_t subdivisions = 1;                        // TerrainConfig.subdivisions (:24)
+    std::vector<float> control_points;                // [C][4]: x, y, height, smoothness (config.smoothness's default applied)
+    std::vector<float> ridges;                        // [R][4]: height, plateau_width, falloff_distance, falloff_steepness
+    std::vector<uint32_t> ridge_edge_offsets{0u};     // [R + 1]
+    std::vector<float> ridge_edges;                   // [E][4]: x0, y0, x1, y1
+    std::vector<float> linedefs;                      // [L][9]: start, end, start_height, end_height, width, falloff_distance, falloff_steepness
+    float map_box[4] = {-100.0f, -100.0f, 100.0f, 100.0f};   // (:273-284)
+    uint64_t generation = next_generation();          // code that edits the fields calls touch()
+    void touch() { generation = next_generation(); }
+
+    float sample_height_at(float x, float y) const;                     // :57-163
+    void sample_normal_at(float x, float y, float normal[3]) const;     // :166-181
+    void tile_normal(int32_t tx, int32_t tz, float normal[3]) const;    // :184-189
+    std::vector<float> tile_outline_world(int32_t tx, int32_t tz) const;   // :194-242: [4 * max(subdivisions, 1)][3]
+    // generate_grid (:460-485): the points [steps_y][steps_x][2]; the steps as the reference's i32 (a negative one: no points)
+    std::vector<float> generate_grid(const float box[4], int32_t &steps_x, int32_t &steps_y) const;
+    void grid_steps(const float box[4], int32_t &steps_x, int32_t &steps_y) const;   // ... the steps alone: nothing is allocated
+    // interpolate_heights (:488-509) for n points [n][2] over the host's worker pool; normals ([n][3]) may be null
+    void interpolate_heights(const float *points, size_t n, float *heights, float *normals = nullptr) const;
+    // triangulate (:829-879) without exclusions: the indices are a closed form of the counts -- per cell (ix, iy), row by row,
+    // (i, i + steps_x, i + 1) and (i + 1, i + steps_x, i + steps_x + 1) with i = iy * steps_x + ix
+    static std::vector<uint32_t> triangulate(int32_t steps_x, int32_t steps_y);
+    // n boxes [n][4] on the CPU, in the layout of rxr_generated_grids
+    void grid_heights_cpu(const float *boxes, uint32_t n, uint32_t stride, uint32_t *counts, float *heights) const;
+    // the device forms (rxr_set_terrain_generator when the lists changed since they were registered, then rxr_generated_heights /
+    // rxr_generated_grids, include/rxr.h).  RXR_OK or a negative rxr_status; there is no fall-back to the CPU.
+    int sample_heights(const float *points, uint32_t n, float *heights, float *normals) const;
+    int grid_heights(const float *boxes, uint32_t n, uint32_t stride, uint32_t *counts, float *heights) const;
+
+private:
+    int register_records(rxr_ctx *ctx) const;
+};
+
 // src/rasterizer.rs:35-193
 class Rasterizer {
 public:

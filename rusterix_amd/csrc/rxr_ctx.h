@@ -35,6 +35,7 @@ enum : uint32_t {
     Q_TERRAIN,   // rxr_bake_terrain_to: the resident terrain
     Q_HEIGHTS,   // rxr_terrain_hits_to: the resident heights
     Q_MESH,      // rxr_terrain_meshes_to: the resident heights and their presence mask
+    Q_GEN,       // rxr_generated_heights_to / rxr_generated_grids_to: the resident generator records
     Q_MESH_UPDATE,   // rxr_update_meshes: the staged copies of the caller's host arrays (both forms block; the lane orders nothing else)
     Q_LANES
 };
@@ -282,6 +283,16 @@ struct rxr_ctx {
     uint32_t heights_launches = 0;    // march launches of the last hit call (rxr_debug_terrain_hit_kernel)
     const char *heights_kernel = "";  // ... and their kernel's symbol name; a static string
     uint32_t mesh_launches = 0;       // k_terrain_mesh launches of the last mesh call (rxr_debug_terrain_mesh_launches)
+
+    // generated terrain heights (rxr_terrain_gen.hip): the resident records of rxr_set_terrain_generator, independent of both terrains
+    // above.  d_gen: one blob of control points, ridges, ridge edge offsets, ridge edges and linedefs, in the kernel's record layout
+    // (gen_off: their byte offsets; gen_n: control points, ridges, ridge edges, linedefs).
+    DevBuf d_gen;
+    bool gen_set = false;
+    size_t gen_off[5] = {};
+    uint32_t gen_n[4] = {};
+    float gen_box[4] = {};
+    uint32_t gen_launches = 0;        // launches of the last evaluation call (rxr_debug_terrain_gen_launches)
 
     FrameStream fstream;    // rxr_stream_begin .. rxr_upload_frame
     int last_upload_streamed = 0;  // 0 plain, 1 streamed (copied), 2 streamed out of page-locked arrays
