@@ -379,6 +379,8 @@ struct RasterParams {
     uint32_t flags;                // RXR_FLAG_*
     float fwidth, fheight;
     float inv_view[16], inv_proj[16];
+    float ndc_sx, ndc_sy;          // relaxed light mode: 2 / width and -2 / height, each rounded once by the host (rxr_upload_frame) -- a reciprocal
+                                   // of a wave-uniform operand is a VALU instruction every wave pays (shade3d_begin)
     float cam[3];
     float translationd2[2];
     float scaled2;

@@ -567,10 +567,25 @@ __device__ __forceinline__ uint32_t batch_texel(const RasterParams &P, const Dev
 struct Frag {
     f3 world, normal, view_dir, base, lit;
     float opacity;
+    uint32_t alpha_bits;  // the texel's alpha byte where it stands (bits 24..31): at levels without chunk paths and programs it IS the encoded
+                          // alpha -- trunc(fma(clamp(RN(a / 255), 0, 1), 255, 0.5)) = a for every byte a -- and `opacity` is never formed
     float rough, metal;  // mat_roughness / mat_metallic (:1321-1322): 0.5 / 0 unless a program ran
     f3 emis;             // mat_emissive (:1323): what THIS fragment's program assigned (levels with programs; frames in which a
                          // fragment could see another fragment's emissive are refused by rxr_upload_frame), else 0
 };
+
+// screen_to_world (rasterizer.rs:1707-1727) in the reference's own sequence: two quotients, the inverse projection, the perspective
+// divide, the inverse view.  fx, fy are pixel centres (0.5 .. 2^15) and the frame size is validated by rxr_upload_frame
+// (1 .. 32768): always inside the division window
+__device__ __forceinline__ f3 screen_to_world_exact(const RasterParams &P, float fx, float fy, float z) {
+    float vx, vy, vz, vw, wx, wy, wz, ww;
+    const float x_ndc = 2.0f * rxm::div1_known(fx, P.fwidth, true) - 1.0f;
+    const float y_ndc = 1.0f - 2.0f * rxm::div1_known(fy, P.fheight, true);
+    mat4_mul(P.inv_proj, x_ndc, y_ndc, z, 1.0f, vx, vy, vz, vw);
+    rxm::div3_self(vx, vy, vz, vw, vx, vy, vz, vw);
+    mat4_mul(P.inv_view, vx, vy, vz, vw, wx, wy, wz, ww);
+    return mk3(wx, wy, wz);
+}
 
 // everything before the light loop: uv, world position, normal, texel, ambient terms (:1062-1370)
 // RL (relaxed light mode, frames with a 3D light loop only): the view direction and the surface normal feed nothing but the lit
@@ -588,34 +603,26 @@ __device__ __forceinline__ void shade3d_begin(const RasterParams &P, const TriSh
     float u, v;
     fragment_uv(S, alpha, beta, gamma, u, v);
 
-    // screen_to_world (rasterizer.rs:1707-1727)
-    // fx, fy are pixel centres (0.5 .. 2^15) and the frame size is validated by rxr_upload_frame
-    // (1 .. 32768): always inside the division window
-    float x_ndc, y_ndc, vx, vy, vz, vw;
-    // relaxed mode, neither chunk paths nor programs, no occluder anywhere: the world position feeds only the light loop and the view direction -- continuous
-    // uses -- so its three divisions (pixel / frame size, the perspective divide) become reciprocal products (within 2 ulp).  With
-    // an occluder in the frame its boxes are compared with the position (get_occlusion): the exact quotients then.
-    const bool relaxed_world = RL && !feat<LV>.chunk && !feat<LV>.programs && !P.any_occluders;  // wave-uniform
+    // screen_to_world (rasterizer.rs:1707-1727).  Relaxed mode, neither chunk paths nor programs, no occluder anywhere: the world position feeds only
+    // the light loop and the view direction -- continuous uses -- so its three divisions (pixel / frame size, the perspective divide) become
+    // products: with 2 / width and -2 / height as the host rounded them (no reciprocal of a wave-uniform operand here) and with v_rcp_f32 of
+    // w (within 2 ulp).  The two matrix products keep the reference's own operation order: w is a difference of two nearly equal
+    // terms, and only the same roundings in the same order land on the reference's value (one product with a combined matrix, its
+    // constant column innermost, left 21 831 pixels of the 4K bench frame a step off where this leaves about a hundred).  With an occluder
+    // in the frame its boxes are compared with the position (get_occlusion): the exact quotients then, as for a w outside the window.
+    bool relaxed_world = RL && !feat<LV>.chunk && !feat<LV>.programs && !P.any_occluders;  // wave-uniform
+    f3 world;
     if (relaxed_world) {
-        x_ndc = fmaf(fx, 2.0f * __builtin_amdgcn_rcpf(P.fwidth), -1.0f);
-        y_ndc = fmaf(fy, -2.0f * __builtin_amdgcn_rcpf(P.fheight), 1.0f);
-        mat4_mul(P.inv_proj, x_ndc, y_ndc, z, 1.0f, vx, vy, vz, vw);
-        if (rxm::wave_all(rxm::in_window(vw))) {
+        float vx, vy, vz, vw, wx, wy, wz, ww;
+        mat4_mul(P.inv_proj, fmaf(fx, P.ndc_sx, -1.0f), fmaf(fy, P.ndc_sy, 1.0f), z, 1.0f, vx, vy, vz, vw);
+        relaxed_world = rxm::wave_all(rxm::in_window(vw));
+        if (relaxed_world) {
             const float rw = __builtin_amdgcn_rcpf(vw);
-            vx *= rw;
-            vy *= rw;
-            vz *= rw;
-            vw = 1.0f;
-        } else rxm::div3_self(vx, vy, vz, vw, vx, vy, vz, vw);
-    } else {
-        x_ndc = 2.0f * rxm::div1_known(fx, P.fwidth, true) - 1.0f;
-        y_ndc = 1.0f - 2.0f * rxm::div1_known(fy, P.fheight, true);
-        mat4_mul(P.inv_proj, x_ndc, y_ndc, z, 1.0f, vx, vy, vz, vw);
-        rxm::div3_self(vx, vy, vz, vw, vx, vy, vz, vw);
+            mat4_mul(P.inv_view, vx * rw, vy * rw, vz * rw, 1.0f, wx, wy, wz, ww);
+            world = mk3(wx, wy, wz);
+        }
     }
-    float wx, wy, wz, ww;
-    mat4_mul(P.inv_view, vx, vy, vz, vw, wx, wy, wz, ww);
-    f3 world = mk3(wx, wy, wz);
+    if (!relaxed_world) world = screen_to_world_exact(P, fx, fy, z);
     f3 cam = mk3(P.cam[0], P.cam[1], P.cam[2]);
     f3 view_dir, normal;
     bool relaxed_normals = false;  // wave-uniform
@@ -642,14 +649,7 @@ __device__ __forceinline__ void shade3d_begin(const RasterParams &P, const TriSh
         }
     }
     if (!relaxed_normals) {
-        if (relaxed_world) {  // (rare: the exact sequences want the reference's world position -- its quotients again)
-            x_ndc = 2.0f * rxm::div1_known(fx, P.fwidth, true) - 1.0f;
-            y_ndc = 1.0f - 2.0f * rxm::div1_known(fy, P.fheight, true);
-            mat4_mul(P.inv_proj, x_ndc, y_ndc, z, 1.0f, vx, vy, vz, vw);
-            rxm::div3_self(vx, vy, vz, vw, vx, vy, vz, vw);
-            mat4_mul(P.inv_view, vx, vy, vz, vw, wx, wy, wz, ww);
-            world = mk3(wx, wy, wz);
-        }
+        if (relaxed_world) world = screen_to_world_exact(P, fx, fy, z);  // (rare: the exact sequences want the reference's world position)
         view_dir = norm3_fast(sub3(cam, world));
         if (b_flags & DB_HAS_NORMALS) {  // :1083-1099
             f3 n0 = mk3(S.n0[0], S.n0[1], S.n0[2]), n1 = mk3(S.n1[0], S.n1[1], S.n1[2]), n2 = mk3(S.n2[0], S.n2[1], S.n2[2]);
@@ -672,6 +672,7 @@ __device__ __forceinline__ void shade3d_begin(const RasterParams &P, const TriSh
     f3 base = mk3(srgb_to_linear_fast((float)(texel & 0xFFu) * INV_255), srgb_to_linear_fast((float)((texel >> 8) & 0xFFu) * INV_255),
                   srgb_to_linear_fast((float)((texel >> 16) & 0xFFu) * INV_255));
     F.opacity = rxm::div1_known((float)(texel >> 24), 255.0f, true);  // :1313; byte / 255 is inside the division window
+    F.alpha_bits = texel & 0xFF000000u;  // (shade3d_end, levels without chunk paths and programs: nothing else reads or writes the opacity there)
     if (feat<LV>.chunk && B.baked_plus1) {  // chunk.shader_textures: the baked texel replaces colour and alpha, no program runs (:1239-1267)
         const DevTexDesc &baked = P.tex[B.baked_plus1 - 1u];
         uint32_t bt = sample_texture(baked, texel_base(P, baked), u, v, P.sample_mode, B.repeat_mode);
@@ -962,13 +963,17 @@ template <Level LV, bool RL = false>
 __device__ __forceinline__ uint32_t shade3d_end(const Frag &F) {
     f3 lit = F.lit;
     if constexpr (feat<LV>.programs) lit = add3(lit, F.emis);
+    // (a baked texture or a program may replace the opacity: encoded from the float there; else the texel's own byte, see Frag)
+    uint32_t alpha;
+    if constexpr (feat<LV>.chunk || feat<LV>.programs) alpha = f32_to_u8_saturated(F.opacity) << 24;
+    else alpha = F.alpha_bits;
     if constexpr (RL) {  // linear_to_srgb_fast (:26-33) with v_sqrt_f32 (1 ulp) for the correctly rounded root
         const float sx = __builtin_amdgcn_sqrtf(lit.x), sy = __builtin_amdgcn_sqrtf(lit.y), sz = __builtin_amdgcn_sqrtf(lit.z);
         return pack4(f32_to_u8_saturated(1.055f * sx - 0.055f * sx * sx), f32_to_u8_saturated(1.055f * sy - 0.055f * sy * sy),
-                     f32_to_u8_saturated(1.055f * sz - 0.055f * sz * sz), f32_to_u8_saturated(F.opacity));
+                     f32_to_u8_saturated(1.055f * sz - 0.055f * sz * sz), 0u) | alpha;
     }
     return pack4(f32_to_u8_saturated(linear_to_srgb_fast(lit.x)), f32_to_u8_saturated(linear_to_srgb_fast(lit.y)),
-                 f32_to_u8_saturated(linear_to_srgb_fast(lit.z)), f32_to_u8_saturated(F.opacity));
+                 f32_to_u8_saturated(linear_to_srgb_fast(lit.z)), 0u) | alpha;
 }
 
 // the covered-fragment block of d3_rasterize_opacity (rasterizer.rs:1497-1682, no shader)
@@ -3301,6 +3306,7 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
         Frag F;
         F.world = F.normal = F.view_dir = F.base = F.lit = F.emis = mk3(0.0f, 0.0f, 0.0f);
         F.opacity = 0.0f;
+        F.alpha_bits = 0u;
         F.rough = 0.5f;
         F.metal = 0.0f;
         if (hit) {
@@ -3498,6 +3504,7 @@ __device__ __forceinline__ void raster_tile_pair(const RasterParams &P) {
         Frag F;
         F.world = F.normal = F.view_dir = F.base = F.lit = F.emis = mk3(0.0f, 0.0f, 0.0f);
         F.opacity = 0.0f;
+        F.alpha_bits = 0u;
         F.rough = 0.5f;
         F.metal = 0.0f;
         if (hit) shade3d_begin<LV, RL>(P, HS, vis.batch, vis.alpha, vis.beta, vis.zmin, fx, fy, F);

@@ -1250,6 +1250,8 @@ struct FrameBuild {
         P.fheight = H;
         memcpy(P.inv_view, f->inverse_view, 64);
         memcpy(P.inv_proj, f->inverse_projection, 64);
+        P.ndc_sx = (float)(2.0 / (double)W);  // (the frame size is validated: 1 .. 32768)
+        P.ndc_sy = (float)(-2.0 / (double)H);
         memcpy(P.cam, f->camera_pos, 12);
         memcpy(P.translationd2, f->translationd2, 8);
         P.scaled2 = f->scaled2;
