@@ -167,6 +167,7 @@ int bake_run(rxr_ctx *ctx, const uint32_t *programs, uint32_t n, uint32_t width,
     A.fault = (uint32_t *)ctx->d_bake_fault.p;
     const dim3 grid(n * A.groups_per_job);   // (at most RXR_BAKE_MAX_TEXELS / 256 + n workgroups)
     hipLaunchKernelGGL(ctx->programs_static ? k_bake_s : k_bake, grid, dim3(RXR_TILE_THREADS), 0, s, A);
+    ctx->last_bake_kernel = ctx->programs_static ? 2u : 1u;
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_bake_fault, ctx->d_bake_fault.p, BAKE_FAULT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     return rxr_query_end(ctx, ctx->lane[Q_BAKE], s);
@@ -224,6 +225,13 @@ int rxr_bake_shaders_to(rxr_ctx *ctx, const uint32_t *programs, uint32_t n, uint
     if ((dev_pixels && !rxr_on_device(ctx, dev_pixels, texels * 16)) || (dev_rgba && !rxr_on_device(ctx, dev_rgba, texels * 4)))
         return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_bake_shaders_to: an output array is not device memory of the context's device (or is too small)");
     return bake_run(ctx, programs, n, width, height, dev_pixels, dev_rgba, hip_stream ? (hipStream_t)hip_stream : ctx->stream);
+}
+
+// tests: the kernel of the context's most recent bake launch -- 1 k_bake (per-lane stack depths), 2 k_bake_s (static depths), 0 when
+// the context has launched no bake; a multi-device handle answers for member 0
+uint32_t rxr_debug_last_bake_kernel(rxr_ctx *ctx) {
+    if (ctx && ctx->group) ctx = rxr_member(ctx, 0);
+    return ctx ? ctx->last_bake_kernel : 0u;
 }
 
 }  // extern "C"

@@ -258,6 +258,7 @@ struct rxr_ctx {
     uint32_t *h_bake_fault = nullptr, *h_bake_jobs = nullptr;
     size_t bake_jobs_cap = 0;        // words
     size_t bake_jobs_used = 0;       // ... of which launches since the last rxr_quiesce may still read this many
+    uint32_t last_bake_kernel = 0;   // the last bake launch's kernel: 0 none yet, 1 k_bake, 2 k_bake_s (rxr_debug_last_bake_kernel: tests)
 
     // terrain chunk textures (rxr_terrain.hip): the resident terrain of rxr_set_terrain and the bake's buffers, all its own.
     // d_terrain_cells: the dense grid (TerrainCell per cell of the bounding rectangle); d_terrain_tex / _texels: the source textures'

@@ -77,6 +77,7 @@ def rxr_abi():
         "rxr_check_bake": (i32, [vp, u32, C.c_char_p, u32]),
         "rxr_bake_shaders": (i32, [vp, vp, u32, u32, u32, vp, vp]),
         "rxr_bake_shaders_to": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
+        "rxr_debug_last_bake_kernel": (u32, [vp]),
         "rxr_check_terrain": (i32, [vp, i32, vp, vp, vp, vp, u32, vp, u32, C.c_char_p, u32]),
         "rxr_set_terrain": (i32, [vp, vp, i32, vp, vp, vp, vp, u32, vp, u32]),
         "rxr_bake_terrain": (i32, [vp, vp, u32, i32, vp]),
