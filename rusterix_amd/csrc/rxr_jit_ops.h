@@ -3,9 +3,13 @@
 //
 // Every expression below is the expression of the interpreter's handler for that opcode, copied character for character (the
 // handler is named by its `case`): a compiled program performs the same float operations in the same order as the interpreter,
-// and both are checked against the CPU oracle and against each other (tests/test_gpu_shader_jit.py: every exact opcode, random
-// programs, the configuration-C5 program).  The libm-backed opcodes call the interpreter's own out-of-line functions
-// (slow_unary / slow_binary).  Included by rxr_vm.h in RXR_JIT mode only.
+// and both are checked against the CPU oracle and against each other -- byte for byte in ordinary frames
+// (tests/test_gpu_shader_jit.py: every exact opcode, random programs, the configuration-C5 program;
+// tests/test_gpu_shader_edge_values.py: special operands) and FLOAT FOR FLOAT through windows of the value
+// (tests/test_gpu_jit_floats.py: every function below on 4 096 operand pairs, 96 random programs, control flow; a last-ulp
+// difference from the interpreter's handler, a contracted multiply-add or a lost -ffp-contract=off in rxr_jit.hip's option
+// list fails there).  The libm-backed opcodes call the interpreter's own out-of-line functions (slow_unary / slow_binary;
+// tests/test_gpu_libm_ulp.py).  Included by rxr_vm.h in RXR_JIT mode only.
 #pragma once
 
 namespace rxvm {
