@@ -787,6 +787,48 @@ int rxr_bake_terrain(rxr_ctx *ctx, const int32_t *chunk_coords, uint32_t n, int3
 int rxr_bake_terrain_to(rxr_ctx *ctx, const int32_t *chunk_coords, uint32_t n, int32_t pixels_per_tile, uint8_t *dev_rgba,
                         void *hip_stream);
 
+/* ---- resident chunk textures (rusterix_amd/csrc/rxr_chunk_tex.hip) ---------------------------------------------------------------
+ * chunk.terrain_texture and chunk.shader_textures (src/chunk.rs:36, :53) registered ONCE and rewritten in place, instead of crossing
+ * the ABI in every rxr_upload_frame (which scans every texel for its alpha and copies it into the frame blob): what rxr_set_meshes and
+ * rxr_update_meshes_to are for chunk geometry.  Both bakes write device memory (rxr_bake_terrain_to, rxr_bake_shaders_to); with a
+ * registration their bytes reach the renderer without visiting the host.
+ *
+ * Registration.  textures[i] is SLOT i; its size is fixed until the next registration.  rgba == NULL reserves a slot of that size filled
+ * with zero bytes (not opaque), to be written by an update.  chunk_terrain[c] is the slot of chunk c's terrain_texture or -1 for None;
+ * chunk_shader_slots[chunk_shader_first[c] .. chunk_shader_first[c + 1]) are the slots of its shader_textures, -1 for None (a program
+ * without `shade`).  A slot may be named by several chunks, or by none.  RXR_ERR_INVALID, with the previous registration left as it
+ * was: a side of 0 or above 32768, 2^31 texels or more in all (the limits of a frame's own chunk textures), a slot index that is
+ * neither -1 nor below n_textures, chunk_shader_first that does not start at 0 or decreases, a NULL array with a non-zero count.
+ * n_chunks == 0 removes the registration.  Blocking; all arrays are read before it returns.  Multi-device handles: every member.
+ *
+ * Frames.  While a registration is held, rxr_upload_frame wants frame.n_chunks == the registered n_chunks and, in every rxr_chunk,
+ * terrain_texture == NULL and n_shader_textures == 0; anything else is RXR_ERR_INVALID and the message says so.  origin, size, the
+ * occluders and the program range still come from the frame's rxr_chunk (size == 0 with a terrain slot is refused as before);
+ * pixels_per_tile is the slot's width / size.  Such a frame is drawn by the same kernels with the same bytes as the frame that carries
+ * the textures: only where the texels live differs.  Registering, removing and updating DROP THE RESIDENT FRAME: upload it again (it
+ * then costs no texels).
+ *
+ * Updates.  slots[i] names the slot source i goes to; source i is its w * h * 4 bytes, the sources lie back to back in the order of
+ * `slots` -- the layout rxr_bake_terrain_to writes for n chunks, and rxr_bake_shaders_to's dev_rgba -- so they are 4-byte aligned and
+ * no more.  Refused on the host before anything is queued, changing nothing: no registration, a slot out of range, a slot named twice,
+ * and for _to a dev_rgba that is not memory of the context's device (first and last byte are checked) or not 4-byte aligned.  n == 0
+ * does nothing.  BLOCKING, both forms: they wait for everything the context has queued (renders read the pool), queue
+ * k_chunk_tex_commit on hip_stream (NULL = the context's stream) behind the bake that produced dev_rgba, copy n flag words back and
+ * synchronise that stream.  The kernel copies and computes each slot's flag "every texel has alpha 255", which decides what
+ * add_local's scan decided for a frame's own textures.  Multi-device handles: the host form runs on every member, the _to form is
+ * RXR_ERR_UNSUPPORTED (use rxr_member). */
+/* validation only, no context: the status rxr_set_chunk_textures would return and, in `message`, the reason */
+int rxr_check_chunk_textures(const rxr_texture *textures, uint32_t n_textures, const int32_t *chunk_terrain,
+                             const uint32_t *chunk_shader_first, const int32_t *chunk_shader_slots, uint32_t n_chunks, char *message,
+                             uint32_t message_capacity);
+int rxr_set_chunk_textures(rxr_ctx *ctx, const rxr_texture *textures, uint32_t n_textures, const int32_t *chunk_terrain,
+                           const uint32_t *chunk_shader_first, const int32_t *chunk_shader_slots, uint32_t n_chunks);
+int rxr_update_chunk_textures(rxr_ctx *ctx, const uint32_t *slots, uint32_t n, const uint8_t *rgba);
+int rxr_update_chunk_textures_to(rxr_ctx *ctx, const uint32_t *slots, uint32_t n, const uint8_t *dev_rgba, void *hip_stream);
+/* debugging / tests, and a host mirror whose copy went stale: slot's size, its flag and (rgba != NULL) its w * h * 4 bytes.  Any
+ * output may be NULL.  Multi-device handles: member 0. */
+int rxr_read_chunk_texture(rxr_ctx *ctx, uint32_t slot, uint32_t size[2], uint32_t *all_opaque, uint8_t *rgba);
+
 /* ---- terrain picks: Terrain::ray_terrain_hit (rusterix_amd/csrc/rxr_terrain_hit.hip) ---------------------------------------------
  * "Ray / terrain hit used for editing" (src/terrain/mod.rs:427-479), exact to the bit.  The reference does not intersect the terrain
  * mesh: it marches the height field in up to RXR_TERRAIN_MARCH_STEPS steps of 0.1 along the caller's UN-NORMALISED dir with nearest

@@ -522,6 +522,17 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
     if has_mesh_update:
         L.scene_rebuild_terrain_meshes = fn("scene_rebuild_terrain_meshes", i32, vp, vp, C.POINTER(C.c_int32), u32, pu)
 
+    # resident chunk textures (product host library only)
+    has_chunk_textures = hasattr(lib, prefix + "terrain_rebuild_chunk_textures")
+    if has_chunk_textures:
+        L.scene_set_resident_chunk_textures = fn("scene_set_resident_chunk_textures", None, vp, i32)
+        L.scene_resident_chunk_textures = fn("scene_resident_chunk_textures", i32, vp)
+        L.chunk_textures_generation = fn("chunk_textures_generation", C.c_uint64, vp, i32)
+        L.chunk_touch_textures = fn("chunk_touch_textures", None, vp, i32)
+        L.chunk_terrain_texture_stale = fn("chunk_terrain_texture_stale", i32, vp, i32)
+        L.chunk_texture_registrations = fn("chunk_texture_registrations", C.c_uint64)
+        L.terrain_rebuild_chunk_textures = fn("terrain_rebuild_chunk_textures", i32, vp, vp, C.POINTER(C.c_int32), u32, pu, i32)
+
     def last_error():
         if not hasattr(lib, prefix + "last_error"):
             return ""
@@ -765,8 +776,33 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
             if rc <= 0:
                 return None
             data = np.zeros(w.value * h.value * 4, np.uint8)
-            L.chunk_terrain_texture(self._scene._h, self.index, C.byref(w), C.byref(h), _bp(data))
+            # (a texture Terrain.rebuild_chunk_textures left stale on the host is read back from the device's slot here)
+            rc = L.chunk_terrain_texture(self._scene._h, self.index, C.byref(w), C.byref(h), _bp(data))
+            if rc < 0:
+                raise RasterizeError(rc, last_error())
             return Texture(data, w.value, h.value)
+
+        @staticmethod
+        def _need_chunk_textures():
+            if not has_chunk_textures:
+                raise NotImplementedError(f"{name}: no resident chunk textures in this library")
+
+        def textures_generation(self):
+            """Chunk::textures_generation: re-stamped by everything that assigns the chunk's terrain or shader textures; what decides
+            whether a resident registration (Scene.resident_chunk_textures) is still current"""
+            self._need_chunk_textures()
+            return int(L.chunk_textures_generation(self._scene._h, self.index))
+
+        def touch_textures(self):
+            """Chunk::touch_textures, for code that writes the textures' bytes behind the mirror's back"""
+            self._need_chunk_textures()
+            L.chunk_touch_textures(self._scene._h, self.index)
+            return self
+
+        def terrain_texture_stale(self):
+            """True while the device's slot holds newer bytes than the host copy (terrain_texture() reads them back)"""
+            self._need_chunk_textures()
+            return bool(L.chunk_terrain_texture_stale(self._scene._h, self.index))
 
         def add_occluder(self, mn, mx, occlusion):
             L.chunk_add_occluder(self._scene._h, self.index, mn[0], mn[1], mx[0], mx[1], occlusion)
@@ -931,6 +967,19 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
                 raise RasterizeError(rc, last_error())
             return rc
 
+        @property
+        def resident_chunk_textures(self):
+            """Scene::resident_chunk_textures (opt-in, off by default): the chunks' terrain and shader textures are registered once
+            (rxr_set_chunk_textures, include/rxr.h) and frames go without them; registered again when a chunk's textures_generation
+            moved or chunks were added or removed"""
+            return bool(L.scene_resident_chunk_textures(self._h)) if has_chunk_textures else False
+
+        @resident_chunk_textures.setter
+        def resident_chunk_textures(self, on):
+            if not has_chunk_textures:
+                raise NotImplementedError(f"{name}: no resident chunk textures in this library")
+            L.scene_set_resident_chunk_textures(self._h, 1 if on else 0)
+
         def projected_batch3d(self, list_kind, index, chunk=-1):
             """Outputs of clip_and_project for one batch (after rasterize): dict of numpy arrays."""
             nv, nt, hn = C.c_uint32(), C.c_uint32(), C.c_uint32()
@@ -1004,6 +1053,24 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
             if rc != 0:
                 raise RasterizeError(rc, last_error())
             return chunk
+
+        def rebuild_chunk_textures(self, scene, coords, chunks, pixels_per_tile):
+            """A texture stroke without PCIe traffic: the textures of this terrain's chunks `coords` ([n][2]) are baked on the device
+            and written over the resident slots of scene chunk chunks[i]'s terrain texture (rxr_bake_terrain_to +
+            rxr_update_chunk_textures_to, include/rxr.h).  Returns 0 for that fast path -- the host textures are left stale and
+            chunk.terrain_texture() reads them back -- or 1 for the fallback, build_chunk_at per chunk (scene.resident_chunk_textures off,
+            no registration of this scene held yet, a chunk without a terrain texture or with another side): the next rasterize
+            registers again."""
+            if not has_chunk_textures:
+                raise NotImplementedError(f"{name}: no resident chunk textures in this library")
+            cc = np.ascontiguousarray(np.asarray(coords, np.int32).reshape(-1, 2))
+            ch = np.ascontiguousarray(np.asarray(chunks, np.uint32).reshape(-1))
+            if len(cc) != len(ch):
+                raise ValueError("coords and chunks must have the same length")
+            rc = L.terrain_rebuild_chunk_textures(self._h, scene._h, cc.ctypes.data_as(C.POINTER(C.c_int32)), len(cc), _up(ch), pixels_per_tile)
+            if rc < 0:
+                raise RasterizeError(rc, last_error())
+            return rc
 
         # ---- heights and the editor's pick (:82-95, :148-173, :427-479) ----
         @staticmethod
@@ -1442,8 +1509,14 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         if rc != 0:
             raise RasterizeError(rc, (rxr.rxr_last_error(ctx) or b"").decode())
 
+    def chunk_texture_registrations():
+        """how many times an upload has registered a scene's chunk textures (Scene.resident_chunk_textures): an unchanged scene adds none"""
+        if not has_chunk_textures:
+            raise NotImplementedError(f"{name}: no resident chunk textures in this library")
+        return int(L.chunk_texture_registrations())
+
     return types.SimpleNamespace(
-        name=name, lib=lib, prefix=prefix, raw=L, update_meshes=update_meshes,
+        name=name, lib=lib, prefix=prefix, raw=L, update_meshes=update_meshes, chunk_texture_registrations=chunk_texture_registrations,
         Scene=Scene, Batch3D=Batch3D, Batch2D=Batch2D, Chunk=Chunk, Assets=Assets, Rasterizer=Rasterizer, Terrain=Terrain, TerrainGenerator=TerrainGenerator,
         D3OrbitCamera=D3OrbitCamera, D3FirstPCamera=D3FirstPCamera,
         # shared value types

@@ -104,6 +104,8 @@ void rxh_chunk_set_terrain(void *s, int chunk, const uint8_t *rgba, uint32_t w, 
     c.origin[1] = oy;
     c.size = size;
     c.has_terrain_texture = rgba != nullptr;
+    c.terrain_texture_stale = false;
+    c.touch_textures();
     if (rgba) {
         c.terrain_texture.width = w;
         c.terrain_texture.height = h;
@@ -126,6 +128,30 @@ void rxh_chunk_add_shader_texture(void *s, int chunk, const uint8_t *rgba, uint3
     }
     c.shader_textures.push_back(std::move(t));
     c.shader_texture_present.push_back(rgba ? 1 : 0);
+    c.touch_textures();
+}
+// ---- resident chunk textures (Scene::resident_chunk_textures) ----------------------------------------
+void rxh_scene_set_resident_chunk_textures(void *s, int on) { ((Scene *)s)->resident_chunk_textures = on != 0; }
+int rxh_scene_resident_chunk_textures(void *s) { return ((Scene *)s)->resident_chunk_textures ? 1 : 0; }
+// Chunk::textures_generation (0 for a bad index) and Chunk::touch_textures
+uint64_t rxh_chunk_textures_generation(void *s, int chunk) {
+    Scene *sc = (Scene *)s;
+    return chunk >= 0 && (size_t)chunk < sc->chunks.size() ? sc->chunks[chunk].textures_generation : 0;
+}
+void rxh_chunk_touch_textures(void *s, int chunk) {
+    Scene *sc = (Scene *)s;
+    if (chunk >= 0 && (size_t)chunk < sc->chunks.size()) sc->chunks[chunk].touch_textures();
+}
+// 1: the device holds newer bytes of chunks[chunk].terrain_texture than the host copy (rxh_chunk_terrain_texture reads them back)
+int rxh_chunk_terrain_texture_stale(void *s, int chunk) {
+    Scene *sc = (Scene *)s;
+    return chunk >= 0 && (size_t)chunk < sc->chunks.size() && sc->chunks[chunk].terrain_texture_stale ? 1 : 0;
+}
+// how many registrations Rasterizer::upload has made (tests: an unchanged scene registers nothing)
+uint64_t rxh_chunk_texture_registrations(void) { return chunk_texture_registrations(); }
+// Terrain::rebuild_chunk_textures: 0 (baked and updated in place on the device), 1 (fallback: build_chunk_at per chunk) or a negative rxr_status
+int rxh_terrain_rebuild_chunk_textures(void *t, void *s, const int32_t *coords, uint32_t n, const uint32_t *chunks, int32_t ppt) {
+    return ((Terrain *)t)->rebuild_chunk_textures(*(Scene *)s, coords, n, chunks, ppt);
 }
 // Chunk::add_shader with the bake (Scene::chunk_add_shader): the shader index in the chunk, or a negative rxr_status
 int rxh_chunk_add_shader_baked(void *s, int chunk, void *assets, uint32_t n_globals, int32_t shade_index, uint32_t shade_locals,
@@ -295,6 +321,10 @@ int rxh_chunk_terrain_texture(void *s, int chunk, uint32_t *w, uint32_t *h, uint
     if (chunk < 0 || (size_t)chunk >= sc->chunks.size()) return -1;
     const Chunk &c = sc->chunks[chunk];
     if (!c.has_terrain_texture) return 0;
+    if (rgba && c.terrain_texture_stale) {   // the device's slot holds the bytes (Terrain::rebuild_chunk_textures): read them back
+        const int rc = sc->refresh_chunk_textures();
+        if (rc != RXR_OK) return rc;
+    }
     *w = c.terrain_texture.width;
     *h = c.terrain_texture.height;
     if (rgba) memcpy(rgba, c.terrain_texture.data.data(), c.terrain_texture.data.size());

@@ -502,7 +502,13 @@ int g_light_math = RXR_LIGHT_MATH_RELAXED;  // the library's default
 uint64_t g_mesh_fingerprint = 0;
 uint64_t g_mesh_geometry_fingerprint = 0;  // what rxr_intersect reads of the registered meshes (Scene::intersect)
 uint64_t g_mesh2d_fingerprint = 0;
+// resident chunk textures: the Chunk::textures_generation of every chunk the context's registration was made from (g_ctex_held: there is one)
+bool g_ctex_held = false;
+std::vector<uint64_t> g_ctex_gens;
+uint64_t g_ctex_registrations = 0;
 }  // namespace
+
+uint64_t chunk_texture_registrations() { return g_ctex_registrations; }
 
 void set_device_projection(bool on) { g_device_projection = on; }
 bool device_projection() { return g_device_projection; }
@@ -528,6 +534,8 @@ void drop_context_locked() {
     g_terrain_gen = 0;
     g_heights_gen = 0;
     g_generator_gen = 0;
+    g_ctex_held = false;
+    g_ctex_gens.clear();
 }
 }  // namespace
 
@@ -838,6 +846,7 @@ int Scene::chunk_add_shader(size_t chunk, Program program, const Assets &assets)
     }
     chunks[chunk].shader_textures.push_back(std::move(tex));
     chunks[chunk].shader_texture_present.push_back(has_shade ? 1 : 0);
+    chunks[chunk].touch_textures();
     return (int)chunks[chunk].shaders.size() - 1;
 }
 
@@ -1014,26 +1023,33 @@ int Terrain::bake_chunk(int32_t cx, int32_t cy, int32_t ppt, std::vector<uint8_t
     return RXR_OK;
 }
 
+namespace {
+// rxr_set_terrain unless the context holds this generation of the terrain
+int register_terrain(rxr_ctx *ctx, const Terrain &T) {
+    if (g_terrain_gen == T.generation) return RXR_OK;
+    std::vector<int32_t> xy, texture;
+    std::vector<uint32_t> blend;
+    std::vector<float> offset;
+    T.flatten(xy, texture, blend, offset);
+    std::vector<rxr_texture> tex;
+    for (const Texture &t : T.textures) tex.push_back(rxr_texture{t.data.data(), t.width, t.height});
+    const int rc = rxr_set_terrain(ctx, T.scale, T.chunk_size, xy.data(), texture.data(), blend.data(), offset.data(), (uint32_t)texture.size(), tex.data(),
+                                   (uint32_t)tex.size());
+    if (rc != RXR_OK) {
+        g_error = rxr_last_error(ctx);
+        return rc;
+    }
+    g_terrain_gen = T.generation;
+    return RXR_OK;
+}
+}  // namespace
+
 int Terrain::bake_chunks(const int32_t *coords, uint32_t n, int32_t ppt, uint8_t *rgba) const {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     std::string err;
     rxr_ctx *ctx = context(&err);
     if (!ctx) return RXR_ERR_NO_DEVICE;
-    if (g_terrain_gen != generation) {
-        std::vector<int32_t> xy, texture;
-        std::vector<uint32_t> blend;
-        std::vector<float> offset;
-        flatten(xy, texture, blend, offset);
-        std::vector<rxr_texture> tex;
-        for (const Texture &t : textures) tex.push_back(rxr_texture{t.data.data(), t.width, t.height});
-        const int rc = rxr_set_terrain(ctx, scale, chunk_size, xy.data(), texture.data(), blend.data(), offset.data(), (uint32_t)texture.size(), tex.data(),
-                                       (uint32_t)tex.size());
-        if (rc != RXR_OK) {
-            g_error = rxr_last_error(ctx);
-            return rc;
-        }
-        g_terrain_gen = generation;
-    }
+    if (const int rc = register_terrain(ctx, *this); rc != RXR_OK) return rc;
     const int rc = rxr_bake_terrain(ctx, coords, n, ppt, rgba);
     if (rc != RXR_OK) g_error = rxr_last_error(ctx);
     return rc;
@@ -1045,6 +1061,8 @@ int Terrain::build_chunk_at(int32_t cx, int32_t cy, int32_t ppt, Chunk &chunk) c
         return RXR_ERR_INVALID;
     }
     const uint32_t side = (uint32_t)(chunk_size * ppt);
+    // (re-stamped on entry: where the call ends without assigning, a registration made again is the safe side)
+    chunk.touch_textures();
     Texture baked;
     baked.width = baked.height = side;
     baked.data.resize((size_t)side * side * 4);
@@ -1054,7 +1072,105 @@ int Terrain::build_chunk_at(int32_t cx, int32_t cy, int32_t ppt, Chunk &chunk) c
     if (!chunks.count({cx, cy})) return RXR_OK;   // :383-391: baked, but the terrain has no chunk there: nothing is set
     chunk.terrain_texture = std::move(baked);
     chunk.has_terrain_texture = true;
+    chunk.terrain_texture_stale = false;
     return RXR_OK;
+}
+
+// (rxr_api.hip; see Scene::rebuild_terrain_meshes)
+extern "C" void *rxr_mirror_scratch(rxr_ctx *ctx, size_t bytes);
+
+namespace {
+// does the context hold the registration made from exactly these chunks' textures?
+bool chunk_textures_current(const Scene &scene) {
+    if (!g_ctex_held || g_ctex_gens.size() != scene.chunks.size()) return false;
+    for (size_t c = 0; c < scene.chunks.size(); ++c)
+        if (g_ctex_gens[c] != scene.chunks[c].textures_generation) return false;
+    return true;
+}
+}  // namespace
+
+int Scene::refresh_chunk_textures() {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    bool any = false;
+    for (const Chunk &c : chunks) any = any || c.terrain_texture_stale;
+    if (!any) return RXR_OK;
+    std::string err;
+    rxr_ctx *ctx = context(&err);
+    if (!ctx) return RXR_ERR_NO_DEVICE;
+    for (Chunk &c : chunks) {
+        if (!c.terrain_texture_stale) continue;
+        if (!g_ctex_held || c.slot_registration != g_ctex_registrations) {
+            g_error = "Scene::refresh_chunk_textures: the context no longer holds this scene's chunk textures (another scene was uploaded): build the chunks again";
+            return RXR_ERR_INVALID;
+        }
+        const int rc = rxr_read_chunk_texture(ctx, (uint32_t)c.terrain_slot, nullptr, nullptr, c.terrain_texture.data.data());
+        if (rc != RXR_OK) {
+            g_error = rxr_last_error(ctx);
+            return rc;
+        }
+        c.terrain_texture_stale = false;
+    }
+    return RXR_OK;
+}
+
+int Terrain::rebuild_chunk_textures(Scene &scene, const int32_t *coords, uint32_t n, const uint32_t *chunks_, int32_t ppt) const {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::string err;
+    rxr_ctx *ctx = context(&err);
+    if (!ctx) return RXR_ERR_NO_DEVICE;
+    if (!n) return 0;
+    if (!coords || !chunks_) {
+        g_error = "Terrain::rebuild_chunk_textures: NULL array";
+        return RXR_ERR_INVALID;
+    }
+    if (chunk_size < 1 || ppt < 1 || (int64_t)chunk_size * ppt > RXR_BAKE_MAX_DIM) {
+        g_error = "Terrain::rebuild_chunk_textures: chunk_size and pixels_per_tile must be at least 1 and their product at most RXR_BAKE_MAX_DIM";
+        return RXR_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < n; ++i)
+        if (chunks_[i] >= scene.chunks.size()) {
+            g_error = "Terrain::rebuild_chunk_textures: chunks[" + std::to_string(i) + "] = " + std::to_string(chunks_[i]) + ": no such chunk";
+            return RXR_ERR_INVALID;
+        }
+    const uint32_t side = (uint32_t)(chunk_size * ppt);
+    bool fast = scene.resident_chunk_textures && rxr_member_count(ctx) == 1 && chunk_textures_current(scene);
+    std::vector<uint32_t> slots(n);
+    for (uint32_t i = 0; i < n && fast; ++i) {
+        const Chunk &c = scene.chunks[chunks_[i]];
+        fast = c.has_terrain_texture && c.terrain_slot >= 0 && c.terrain_texture.width == side && c.terrain_texture.height == side && this->chunks.count({coords[2 * i], coords[2 * i + 1]}) != 0;
+        slots[i] = (uint32_t)c.terrain_slot;
+    }
+    if (fast) {
+        int rc = register_terrain(ctx, *this);
+        if (rc != RXR_OK) return rc;
+        uint8_t *d = (uint8_t *)rxr_mirror_scratch(ctx, (size_t)n * side * side * 4);
+        if (!d) {
+            g_error = rxr_last_error(ctx);
+            return RXR_ERR_OOM;
+        }
+        rc = rxr_bake_terrain_to(ctx, coords, n, ppt, d, nullptr);
+        if (rc == RXR_OK) rc = rxr_update_chunk_textures_to(ctx, slots.data(), n, d, nullptr);   // (the same stream: the context's)
+        if (rc == RXR_OK) {
+            for (uint32_t i = 0; i < n; ++i) {   // the registration holds the new version: it stays current
+                Chunk &c = scene.chunks[chunks_[i]];
+                c.touch_textures();
+                c.terrain_texture_stale = true;
+                g_ctex_gens[chunks_[i]] = c.textures_generation;
+            }
+            return 0;
+        }
+        if (rc != RXR_ERR_INVALID) {
+            g_error = rxr_last_error(ctx);
+            return rc;
+        }
+        // refused (a chunk named twice): nothing was changed on the device
+    }
+    // the host copies that are rebuilt are not read back first; the others are, by the next upload's registration
+    for (uint32_t i = 0; i < n; ++i) {
+        const int rc = build_chunk_at(coords[2 * i], coords[2 * i + 1], ppt, scene.chunks[chunks_[i]]);
+        if (rc != RXR_OK) return rc;
+    }
+    return 1;
 }
 
 // ---- heights and the editor's pick ----
@@ -1529,6 +1645,49 @@ int Rasterizer::upload(Scene &scene, size_t w, size_t h, size_t tile_size, const
         rc.origin[1] = ch.origin[1];
         rc.size = ch.size;
         chunks.push_back(rc);
+    }
+    if (scene.resident_chunk_textures && !scene.chunks.empty()) {
+        // the chunks' textures are registered once (rxr_set_chunk_textures) and the frames go without them
+        if (!chunk_textures_current(scene)) {
+            int rc = scene.refresh_chunk_textures();   // (host copies the held registration has newer bytes of)
+            if (rc != RXR_OK) return rc;
+            std::vector<rxr_texture> tex;
+            std::vector<int32_t> terrain_slot, shader_slots;
+            std::vector<uint32_t> shader_first{0u};
+            for (Chunk &ch : scene.chunks) {
+                ch.terrain_slot = ch.has_terrain_texture ? (int32_t)tex.size() : -1;
+                terrain_slot.push_back(ch.terrain_slot);
+                if (ch.has_terrain_texture) tex.push_back(rxr_texture{ch.terrain_texture.data.data(), (uint32_t)ch.terrain_texture.width, (uint32_t)ch.terrain_texture.height});
+                for (size_t k = 0; k < ch.shader_textures.size(); ++k) {
+                    shader_slots.push_back(ch.shader_texture_present[k] ? (int32_t)tex.size() : -1);
+                    if (ch.shader_texture_present[k]) tex.push_back(rxr_texture{ch.shader_textures[k].data.data(), (uint32_t)ch.shader_textures[k].width, (uint32_t)ch.shader_textures[k].height});
+                }
+                shader_first.push_back((uint32_t)shader_slots.size());
+            }
+            g_ctex_held = false;
+            rc = rxr_set_chunk_textures(ctx, tex.data(), (uint32_t)tex.size(), terrain_slot.data(), shader_first.data(), shader_slots.data(), (uint32_t)scene.chunks.size());
+            if (rc != RXR_OK) {
+                g_error = rxr_last_error(ctx);
+                (void)rxr_set_chunk_textures(ctx, nullptr, 0, nullptr, nullptr, nullptr, 0);   // (the frames below would not match what was held before)
+                return rc;
+            }
+            ++g_ctex_registrations;
+            g_ctex_held = true;
+            g_ctex_gens.clear();
+            for (Chunk &ch : scene.chunks) {
+                g_ctex_gens.push_back(ch.textures_generation);
+                ch.slot_registration = g_ctex_registrations;
+            }
+        }
+        for (rxr_chunk &rc : chunks) {
+            rc.terrain_texture = nullptr;
+            rc.shader_textures = nullptr;
+            rc.n_shader_textures = 0;
+        }
+    } else if (g_ctex_held) {
+        (void)rxr_set_chunk_textures(ctx, nullptr, 0, nullptr, nullptr, nullptr, 0);
+        g_ctex_held = false;
+        g_ctex_gens.clear();
     }
     for (const Batch3D &b : scene.d3_static) b3.push_back(view3d(b, RXR_LIST_STATIC, -1, slots));
     for (const Batch3D &b : scene.d3_dynamic) b3.push_back(view3d(b, RXR_LIST_DYNAMIC, -1, slots));

@@ -226,6 +226,16 @@ struct Chunk {
     int32_t size = 1;                               // :26
     std::vector<Texture> shader_textures;           // :53, Vec<Option<Texture>>
     std::vector<uint8_t> shader_texture_present;
+    // Resident chunk textures (Scene::resident_chunk_textures): whether the context's registration still holds this chunk's textures is
+    // decided by this stamp, not by their bytes.  Every mirror method that assigns terrain_texture or shader_textures re-stamps it; code
+    // that writes the fields directly calls touch_textures().
+    uint64_t textures_generation = next_generation();
+    void touch_textures() { textures_generation = next_generation(); }
+    // Terrain::rebuild_chunk_textures' fast path wrote the device's slot and left terrain_texture.data as it was: Scene::refresh_chunk_textures
+    // (which the C API's reader calls) brings the bytes back
+    bool terrain_texture_stale = false;
+    int32_t terrain_slot = -1;                      // the texture's slot in the registration (Rasterizer::upload)
+    uint64_t slot_registration = 0;                 // ... and which registration that was (chunk_texture_registrations() when it was made)
 };
 
 // src/scene.rs:8-50
@@ -281,7 +291,18 @@ public:
     //      geometry replaced and touch()ed: the next upload registers again.
     //   a negative rxr_status otherwise.
     int rebuild_terrain_meshes(const class Terrain &terrain, const int32_t *coords, uint32_t n, const uint32_t *chunks_);
+    // Opt-in, off by default: Rasterizer::upload registers the chunks' terrain and shader textures once (rxr_set_chunk_textures,
+    // include/rxr.h) and sends frames without them, instead of handing every texel over with every frame.  The registration is made again
+    // when a chunk's textures_generation differs from the one registered, when chunks were added or removed, or when another scene's
+    // registration is held; a scene with the option off removes a registration it finds.
+    bool resident_chunk_textures = false;
+    // the host copies of the textures the device holds newer bytes of (Chunk::terrain_texture_stale), read back through
+    // rxr_read_chunk_texture.  RXR_OK, or RXR_ERR_INVALID when the context no longer holds this scene's registration (another scene was
+    // uploaded in between: the bytes are gone, build the chunk again).
+    int refresh_chunk_textures();
 };
+// how many times Rasterizer::upload has called rxr_set_chunk_textures with textures (tests: an unchanged scene registers nothing)
+uint64_t chunk_texture_registrations();
 
 // src/terrain/mod.rs, src/terrain/chunk.rs: what Terrain::bake_chunk reads -- `sources` and `blend_modes` per cell, behind the asset
 // lookup: a cell's source is the texture sample_source would sample (tile.textures.first()), or a source without one (a PixelSource
@@ -314,6 +335,16 @@ public:
     // Terrain::build_chunk_at (:372-399) with modifiers == false: bakes on the device and sets chunk.terrain_texture -- unless the
     // terrain has no chunk at `coord`, as in the reference.  RXR_OK or a negative rxr_status.
     int build_chunk_at(int32_t cx, int32_t cy, int32_t pixels_per_tile, Chunk &chunk) const;
+    // A texture stroke's way to the frame without crossing PCIe: the textures of the terrain's chunks coords[i] = (cx, cy) are baked on the
+    // device (rxr_bake_terrain_to, into device scratch) and written over the slots of scene.chunks[chunks_[i]]'s terrain textures on the
+    // same stream (rxr_update_chunk_textures_to, include/rxr.h).  Returns
+    //   0  the fast path.  The chunks' host terrain_texture bytes are left as they were and marked stale (Chunk::terrain_texture_stale);
+    //      the registration counts as current, so the next upload sends no texel.
+    //   1  the fallback, build_chunk_at per chunk (the next upload registers again): scene.resident_chunk_textures is off, the context
+    //      does not hold this scene's registration, it is a multi-device one, a chunk has no terrain texture yet, its side is not
+    //      chunk_size * pixels_per_tile, the terrain has no chunk at a coordinate, or a chunk is named twice.
+    //   a negative rxr_status otherwise.
+    int rebuild_chunk_textures(Scene &scene, const int32_t *coords, uint32_t n, const uint32_t *chunks_, int32_t pixels_per_tile) const;
     // the cell list of rxr_set_terrain
     void flatten(std::vector<int32_t> &xy, std::vector<int32_t> &texture, std::vector<uint32_t> &blend, std::vector<float> &offset) const;
 

@@ -8,6 +8,7 @@
 
 #include <atomic>
 #include <cstdlib>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -37,6 +38,7 @@ enum : uint32_t {
     Q_MESH,      // rxr_terrain_meshes_to: the resident heights and their presence mask
     Q_GEN,       // rxr_generated_heights_to / rxr_generated_grids_to: the resident generator records
     Q_MESH_UPDATE,   // rxr_update_meshes: the staged copies of the caller's host arrays (both forms block; the lane orders nothing else)
+    Q_CHUNK_TEX,     // rxr_set_chunk_textures / rxr_update_chunk_textures: the staged copies of the caller's host texels (all forms block)
     Q_LANES
 };
 #define RXR_MAX_TILE_ROWS 2048u   // frames of at most 32768 rows
@@ -84,6 +86,21 @@ enum : uint32_t {
 #define HS_MAX_ENTRIES CNT_LARGE
 
 struct rxr_group;
+
+// Resident chunk textures (rxr_set_chunk_textures, rxr_chunk_tex.hip): what chunk.terrain_texture / chunk.shader_textures are while a
+// registration is held.  slots[i]: size, place in the pool (texels from its start, a multiple of four: 16 bytes) and the flag "every
+// texel has alpha 255" as k_chunk_tex_commit last computed it; terrain / shader_first / shader_slots: the caller's maps, copied.
+struct ChunkTextures {
+    struct Slot { uint32_t w, h, offset, opaque; };
+    bool set = false;
+    std::vector<Slot> slots;
+    std::vector<int32_t> terrain;          // [n_chunks] slot or -1
+    std::vector<uint32_t> shader_first;    // [n_chunks + 1]
+    std::vector<int32_t> shader_slots;     // slot or -1
+    DevBuf pool;                           // the texels
+    DevBuf flags;                          // one word per source of the call in flight (k_chunk_tex_commit)
+    uint32_t launches = 0;                 // k_chunk_tex_commit launches of the last call (rxr_debug_chunk_tex_launches)
+};
 
 // Streaming hand-over of a large frame's projected 3D batches (rxr_stream_begin / rxr_stream_batch3d, include/rxr.h): the host
 // hands batch i over from whatever thread projected it; batches are RETIRED in index order (which fixes their dense offsets in
@@ -145,6 +162,7 @@ struct rxr_ctx {
     DevBuf d_tex, d_texels;
     std::vector<DevTexDesc> h_tex;
     std::vector<TileRange> tiles_static, tiles_dynamic;
+    ChunkTextures ctex;              // rxr_set_chunk_textures
 
     // frame blob
     void *h_stage = nullptr;
@@ -402,6 +420,7 @@ int rxr_group_set_textures(rxr_ctx *ctx, const rxr_tile *static_tiles, uint32_t 
 int rxr_group_set_meshes(rxr_ctx *ctx, const rxr_mesh3d *meshes, uint32_t n_meshes);
 int rxr_group_update_meshes(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t n, const uint32_t *counts, const float *vertices, const uint32_t *indices,
                             const float *normals, uint32_t vertex_stride, uint32_t triangle_stride);
+int rxr_group_each(rxr_ctx *ctx, const std::function<int(rxr_ctx *)> &fn);   // fn(member) for every member, on the members' worker threads
 int rxr_group_set_meshes2d(rxr_ctx *ctx, const rxr_mesh2d *meshes, uint32_t n_meshes);
 int rxr_group_set_projection2d(rxr_ctx *ctx, const float *mat3);
 int rxr_group_set_shaders(rxr_ctx *ctx, const rxr_shader_set *set);

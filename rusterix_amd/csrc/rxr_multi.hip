@@ -365,6 +365,11 @@ int rxr_group_update_meshes(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t
     });
 }
 
+// fn(member) for every member, each on its own worker thread: for entry points that live in other files (rxr_chunk_tex.hip)
+int rxr_group_each(rxr_ctx *ctx, const std::function<int(rxr_ctx *)> &fn) {
+    return run_all(ctx, [&](uint32_t i) { return fn(ctx->group->members[i]); });
+}
+
 int rxr_group_set_meshes2d(rxr_ctx *ctx, const rxr_mesh2d *meshes, uint32_t n_meshes) {
     return run_all(ctx, [&](uint32_t i) { return rxr_set_meshes2d(ctx->group->members[i], meshes, n_meshes); });
 }

@@ -559,6 +559,7 @@ struct FrameBuild {
     const bool use_meshes2d = (f->use_meshes & 2u) != 0;   // the 2D batches are the meshes of rxr_set_meshes2d
     const uint32_t n_b3 = use_meshes ? (uint32_t)ctx->meshes.size() : f->n_batches3d, n_b2 = use_meshes2d ? (uint32_t)ctx->meshes2d.size() : f->n_batches2d;
     const uint32_t n_res_tex = (uint32_t)ctx->h_tex.size();
+    const bool resident_ctex = ctx->ctex.set;  // the chunk textures are the slots of rxr_set_chunk_textures (rxr_chunk_tex.hip), not the frame's
     const float W = (float)f->width, H = (float)f->height;
     const std::chrono::steady_clock::time_point ut0 = std::chrono::steady_clock::now();  // RXR_E2E_TIMING diagnostics (tools/e2e_probe.py)
     double ut_validated = 0, ut_quiesced = 0, ut_headers = 0, ut_arrays = 0;
@@ -816,7 +817,31 @@ struct FrameBuild {
         }
         chunk_terrain.assign(f->n_chunks, -1);
         chunk_baked.resize(f->n_chunks);
-        for (uint32_t c = 0; c < f->n_chunks; ++c) {
+        if (resident_ctex) {
+            // the chunk textures are those of rxr_set_chunk_textures: one DevTexDesc per slot behind the resident ones, no texels in the frame
+            const ChunkTextures &T = ctx->ctex;
+            if (f->n_chunks != T.terrain.size())
+                return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_upload_frame: " + std::to_string(f->n_chunks) + " chunks, but rxr_set_chunk_textures registered the textures of " +
+                                                          std::to_string(T.terrain.size()) + " (register again, or remove the registration with n_chunks == 0)");
+            for (const ChunkTextures::Slot &s : T.slots) local_tex.push_back(LocalTex{nullptr, s.opaque != 0});
+        }
+        for (uint32_t c = 0; c < f->n_chunks && resident_ctex; ++c) {
+            const rxr_chunk &ck = f->chunks[c];
+            const ChunkTextures &T = ctx->ctex;
+            if (ck.terrain_texture || ck.n_shader_textures)
+                return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_upload_frame: chunk " + std::to_string(c) + " carries its own terrain_texture / shader_textures while rxr_set_chunk_textures holds a registration (they must be NULL / 0)");
+            if (ck.n_occluders && !ck.occluders) return rxr_fail(ctx, RXR_ERR_INVALID, "chunk: NULL occluders");
+            n_occ_total += ck.n_occluders;
+            if ((uint64_t)ck.program_base + ck.n_programs > ctx->programs.size())
+                return rxr_fail(ctx, RXR_ERR_INVALID, "chunk: program range exceeds the programs set with rxr_set_shaders");
+            if (T.terrain[c] >= 0) {
+                if (ck.size == 0) return rxr_fail(ctx, RXR_ERR_INVALID, "chunk: size 0 with a terrain texture (the reference divides by it, chunk.rs:138)");
+                chunk_terrain[c] = (int32_t)(n_res_tex + (uint32_t)T.terrain[c]);
+            }
+            for (uint32_t k = T.shader_first[c]; k < T.shader_first[c + 1]; ++k)
+                chunk_baked[c].push_back(T.shader_slots[k] >= 0 ? (int32_t)(n_res_tex + (uint32_t)T.shader_slots[k]) : -1);
+        }
+        for (uint32_t c = 0; c < f->n_chunks && !resident_ctex; ++c) {
             const rxr_chunk &ck = f->chunks[c];
             if (ck.n_occluders && !ck.occluders) return rxr_fail(ctx, RXR_ERR_INVALID, "chunk: NULL occluders");
             n_occ_total += ck.n_occluders;
@@ -1092,7 +1117,7 @@ struct FrameBuild {
                 cr[c].origin_x = f->chunks[c].origin[0];
                 cr[c].origin_y = f->chunks[c].origin[1];
                 if (chunk_terrain[c] >= 0) {
-                    const int64_t wdt = (int32_t)f->chunks[c].terrain_texture->width;
+                    const int64_t wdt = (int32_t)(resident_ctex ? ctx->ctex.slots[(uint32_t)chunk_terrain[c] - n_res_tex].w : f->chunks[c].terrain_texture->width);
                     cr[c].pixels_per_tile = (int32_t)(wdt / f->chunks[c].size);  // `texture.width as i32 / self.size`, chunk.rs:138
                 }
                 if (f->chunks[c].n_occluders) memcpy(oc + cur, f->chunks[c].occluders, f->chunks[c].n_occluders * sizeof(rxr_occluder));
@@ -1104,7 +1129,15 @@ struct FrameBuild {
         DevTexDesc *td = (DevTexDesc *)(st + L.off_tdesc);
         if (n_res_tex) memcpy(td, ctx->h_tex.data(), n_res_tex * sizeof(DevTexDesc));
         size_t texel = 0;
-        for (size_t k = 0; k < local_tex.size(); ++k) {
+        for (size_t k = 0; k < local_tex.size() && resident_ctex; ++k) {  // (texels: the resident pool, RasterParams.frame_texels)
+            const ChunkTextures::Slot &s = ctx->ctex.slots[k];
+            td[n_res_tex + k] = DevTexDesc{};
+            td[n_res_tex + k].offset = s.offset;
+            td[n_res_tex + k].w = s.w;
+            td[n_res_tex + k].h = s.h;
+            td[n_res_tex + k].all_opaque = (s.opaque ? 1u : 0u) | 2u;
+        }
+        for (size_t k = 0; k < local_tex.size() && !resident_ctex; ++k) {
             const rxr_texture &t = *local_tex[k].t;
             DevTexDesc &e = td[n_res_tex + k];
             e.offset = (uint32_t)texel;
@@ -1411,7 +1444,7 @@ struct FrameBuild {
         }
         P.texels = (const uint32_t *)ctx->d_texels.p;
         P.tex = (const DevTexDesc *)(d + L.off_tdesc);
-        P.frame_texels = (const uint32_t *)(d + L.off_ltex);
+        P.frame_texels = resident_ctex ? (const uint32_t *)ctx->ctex.pool.p : (const uint32_t *)(d + L.off_ltex);
         P.bg_pixels = (const uint32_t *)(d + L.off_bg);
         ctx->frame_uses_meshes2d = use_meshes2d;
         if (use_meshes2d) {

@@ -102,6 +102,13 @@ def rxr_abi():
         "rxr_update_meshes": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, u32]),
         "rxr_update_meshes_to": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, u32, vp]),
         "rxr_mesh_bounds": (i32, [vp, u32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+        "rxr_check_chunk_textures": (i32, [vp, u32, vp, vp, vp, u32, C.c_char_p, u32]),
+        "rxr_set_chunk_textures": (i32, [vp, vp, u32, vp, vp, vp, u32]),
+        "rxr_update_chunk_textures": (i32, [vp, vp, u32, vp]),
+        "rxr_update_chunk_textures_to": (i32, [vp, vp, u32, vp, vp]),
+        "rxr_read_chunk_texture": (i32, [vp, u32, C.POINTER(u32), C.POINTER(u32), vp]),
+        "rxr_debug_chunk_tex_constants": (None, [C.POINTER(u32)]),
+        "rxr_debug_chunk_tex_launches": (u32, [vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
