@@ -918,7 +918,8 @@ int rxr_terrain_meshes_to(rxr_ctx *ctx, const int32_t *chunk_coords, uint32_t n,
  * f32::min skips a NaN, so a ridge without edges is at distance +inf and contributes 0.0; clamp(0.0, 1.0) keeps a NaN and -0.0;
  * ridge contributions are added and linedefs folded in list order, a linedef only when its influence > 0.0, the over-influence
  * correction last.  TerrainConfig's idw_power and max_influence_distance are read by nothing in the reference and do not cross this
- * boundary; apply_exclusions, partition_by_tiles and the blend batches stay host work, fed by these heights. */
+ * boundary; apply_exclusions is rxr_generated_meshes below; partition_by_tiles, mesh_fix_winding and the blend batches stay host
+ * work, fed by those meshes. */
 #define RXR_TERRAIN_GEN_CONTROL_POINT_FLOATS 4u /* x, y, height, smoothness (the caller has applied config.smoothness's default)   */
 #define RXR_TERRAIN_GEN_RIDGE_FLOATS 4u         /* height, plateau_width, falloff_distance, falloff_steepness                      */
 #define RXR_TERRAIN_GEN_RIDGE_EDGE_FLOATS 4u    /* x0, y0, x1, y1, in the sector's linedef order                                    */
@@ -975,6 +976,57 @@ int rxr_generated_grids(rxr_ctx *ctx, const float *boxes, uint32_t n, uint32_t s
  * call returns.  Asynchronous.  Multi-device handles: RXR_ERR_UNSUPPORTED (use rxr_member). */
 int rxr_generated_grids_to(rxr_ctx *ctx, const float *boxes, uint32_t n, uint32_t subdivisions, uint32_t stride,
                            uint32_t *dev_counts, float *dev_heights, void *hip_stream);
+
+/* ---- generated terrain meshes: TerrainGenerator::apply_exclusions (rusterix_amd/csrc/rxr_terrain_excl.hip) ----------------------------
+ * The vertices of a generated chunk (src/chunkbuilder/terrain_generator.rs:747-825) with the sectors of terrain_mode == 1 cut out.
+ * A sector is ACTIVE for a chunk box iff its bounding box intersects the box as given (collect_excluded_sectors, :438-457;
+ * BBox::intersects, src/map/bbox.rs:43-48: four <= / >= comparisons, touching counts, a NaN makes it inactive).  A sector with
+ * fewer than three vertices is active like any other and holds no point.
+ *   no active sector   the SHARED layout: vertex i is grid point i, [x, h, y, 1.0], in grid order; its triangles are the closed form
+ *                      triangulate (per cell, row by row, (i0, i2, i1) and (i1, i2, i3))
+ *   otherwise          the UNSHARED layout: the triangles of that closed form in its order, but for those whose three corners lie
+ *                      inside ONE active sector (corners inside different sectors do not drop a triangle); a kept triangle is its
+ *                      three vertices one after the other, its indices base, base + 1, base + 2
+ * point_in_sector (:891-950) over the polygon of the sector's vertices in order: inside iff the point lies within 0.01 of an edge
+ * of squared length > 0.0 (t clamped as f32::clamp does), or else by the parity of the ray cast, whose crossing abscissa is
+ * multiplied, divided, added as written.  Every keep / drop decision, count, x and z are the reference's to the bit; h is the word
+ * rxr_generated_grids gives for that grid point (the same device function).  uvs are [x, z] and do not cross this boundary. */
+#define RXR_TERRAIN_GEN_MAX_EXCLUDED_SECTORS (1u << 12)
+#define RXR_TERRAIN_GEN_MAX_EXCLUSION_VERTICES (1u << 16)
+/* validation only, no context: the status rxr_set_terrain_exclusions would return and, in `message`, the reason.
+ * RXR_ERR_UNSUPPORTED: a count above its RXR_TERRAIN_GEN_MAX_*.  RXR_ERR_INVALID: a NULL array with a non-zero count,
+ * vertex_offsets that do not start at 0, decrease or do not end at n_vertices, vertices without a sector. */
+int rxr_check_terrain_exclusions(const float *sector_boxes, const uint32_t *vertex_offsets, const float *vertices,
+                                 uint32_t n_sectors, uint32_t n_vertices, char *message, uint32_t message_capacity);
+/* makes the map's sectors of terrain_mode == 1 resident, flattened by the caller (they stay until the next call; n_sectors == 0 is
+ * legal and clears them).  sector_boxes: (min.x, min.y, max.x, max.y) as the reference's sector.bounding_box computes it; a sector's
+ * vertices: its linedefs' start vertices in linedef order, missing linedefs and vertices skipped, possibly none.  Any f32 bit
+ * pattern is legal.  What does not depend on the point (an edge's vj - vi, its squared length and the > 0.0 test) is computed here,
+ * once, in the reference's f32 operations.  Re-registration waits for queued mesh calls.  Independent of
+ * rxr_set_terrain_generator.  Arrays are read before the call returns.  A refused call leaves the resident sectors as they were.
+ * Multi-device handles: member 0.
+ * Replaces: collect_excluded_sectors per chunk, :438-457, and the vertex walk of point_in_sector per call, :893-900. */
+int rxr_set_terrain_exclusions(rxr_ctx *ctx, const float *sector_boxes /* [n_sectors][4] */,
+                               const uint32_t *vertex_offsets /* [n_sectors + 1]: sector s owns vertices [s] .. [s + 1] */,
+                               const float *vertices /* [n_vertices][2] */, uint32_t n_sectors, uint32_t n_vertices);
+/* the meshes of n chunk boxes [n][4] = (min.x, min.y, max.x, max.y) in one call, grids as in rxr_generated_grids.  counts [n][4] =
+ * (steps_x, steps_y, active_sectors, n_vertices) of box i; its vertices start at vertices + i * stride * 4, [x, h, y, 1.0] each (the
+ * layout rxr_terrain_meshes writes).  active_sectors == 0: the shared layout, n_vertices = steps_x * steps_y; otherwise the unshared
+ * one, n_vertices = 3 * kept triangles.  Slots past n_vertices are NOT written.  A grid with a negative or zero step is empty.
+ * RXR_ERR_INVALID, before anything is queued: no rxr_set_terrain_generator yet, subdivisions == 0, a NULL pointer, sizes that
+ * overflow, a box whose layout can exceed `stride` vertices (6 * (steps_x - 1) * (steps_y - 1) where a sector is active, else
+ * steps_x * steps_y).  No rxr_set_terrain_exclusions yet is n_sectors == 0.  n == 0 does nothing.  Host memory, blocking.  The call
+ * is cut into rounds of two launches (classification, emission) over a bounded number of points
+ * (RXR_TERRAIN_EXCL_LAUNCH_POINTS in the environment, read at each call, overrides it).  Changes no frame, scratch, bake, picking
+ * or mesh state.  Multi-device handles: member 0.
+ * Replaces: generate_grid, interpolate_heights and apply_exclusions, :460-509, :747-825. */
+int rxr_generated_meshes(rxr_ctx *ctx, const float *boxes, uint32_t n, uint32_t subdivisions, uint32_t stride, uint32_t *counts,
+                         float *vertices);
+/* the same into DEVICE arrays (each one's first and last byte are checked to be memory of the context's device; 4-byte aligned),
+ * queued on hip_stream (NULL = the context's stream); boxes is host memory and is read before the call returns.  Asynchronous.
+ * Multi-device handles: RXR_ERR_UNSUPPORTED (use rxr_member). */
+int rxr_generated_meshes_to(rxr_ctx *ctx, const float *boxes, uint32_t n, uint32_t subdivisions, uint32_t stride,
+                            uint32_t *dev_counts, float *dev_vertices, void *hip_stream);
 
 #ifdef __cplusplus
 }

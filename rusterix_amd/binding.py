@@ -516,6 +516,9 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         L.terrain_generator_grid = fn("terrain_generator_grid", None, vp, pf, pi_, pf, u32)
         L.terrain_generator_triangulate = fn("terrain_generator_triangulate", None, i32, i32, pu)
         L.terrain_generator_grids = fn("terrain_generator_grids", i32, vp, pf, u32, u32, i32, pu, pf)
+        L.terrain_generator_set_exclusions = fn("terrain_generator_set_exclusions", i32, vp, pf, pu, pf, u32, u32)
+        L.terrain_generator_meshes = fn("terrain_generator_meshes", i32, vp, pf, u32, u32, i32, pu, pf)
+        L.terrain_generator_points_in_sector = fn("terrain_generator_points_in_sector", None, vp, pf, u32, u32, C.POINTER(C.c_uint8))
 
     # registered meshes updated in place (product host library only)
     has_mesh_update = hasattr(lib, prefix + "scene_rebuild_terrain_meshes")
@@ -1275,6 +1278,48 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
 
         def grid_heights_cpu(self, boxes, stride, fill=0.0):
             return self._grids(boxes, stride, False, fill)
+
+        def set_exclusions(self, sector_boxes=(), vertex_offsets=None, vertices=()):
+            """the map's sectors of terrain_mode == 1 (collect_excluded_sectors, :438-457), flattened: sector_boxes [S][4] (min.x,
+            min.y, max.x, max.y), vertices [V][2] (the linedefs' start vertices in linedef order) and vertex_offsets [S + 1]"""
+            sb = _f32(sector_boxes)
+            sb = sb.reshape(sb.size // 4, 4)
+            vt = _f32(vertices)
+            vt = vt.reshape(vt.size // 2, 2)
+            off = np.ascontiguousarray(np.zeros(1, np.uint32) if vertex_offsets is None else np.asarray(vertex_offsets, np.uint32).reshape(-1))
+            if len(off) != len(sb) + 1:
+                raise ValueError("vertex_offsets must have one entry more than sector_boxes")
+            rc = L.terrain_generator_set_exclusions(self._h, _fp(sb) if len(sb) else None, _up(off), _fp(vt) if len(vt) else None, len(sb), len(vt))
+            if rc != 0:
+                raise ValueError("vertex_offsets do not describe vertices")
+            return self
+
+        def points_in_sector_cpu(self, points, sector):
+            """point_in_sector (:891-950) on the CPU for [n][2] points against excluded sector `sector`: [n] bool"""
+            p = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 2))
+            out = np.zeros(max(len(p), 1), np.uint8)
+            L.terrain_generator_points_in_sector(self._h, _fp(p) if len(p) else None, len(p), int(sector), out.ctypes.data_as(C.POINTER(C.c_uint8)))
+            return out[:len(p)].astype(bool)
+
+        def _meshes(self, boxes, stride, device, fill):
+            b = np.ascontiguousarray(np.asarray(boxes, np.float32).reshape(-1, 4))
+            n = b.shape[0]
+            counts = np.zeros((max(n, 1), 4), np.uint32)
+            vertices = np.full((max(n, 1), max(int(stride), 1), 4), fill, np.float32)
+            rc = L.terrain_generator_meshes(self._h, _fp(b) if n else None, n, int(stride), 1 if device else 0, _up(counts), _fp(vertices))
+            if rc != 0:
+                raise RasterizeError(rc, last_error())
+            return counts[:n], vertices[:n, :int(stride)]
+
+        def generate_meshes(self, boxes, stride, fill=0.0):
+            """apply_exclusions (:747-825) behind generate_grid and interpolate_heights for [n][4] chunk boxes in one device call
+            (rxr_generated_meshes): counts [n][4] = (steps_x, steps_y, active_sectors, n_vertices) and vertices [n][stride][4] =
+            [x, h, y, 1]; no active sector: the grid in grid order, else three vertices per kept triangle; slots past n_vertices
+            keep `fill`"""
+            return self._meshes(boxes, stride, True, fill)
+
+        def generate_meshes_cpu(self, boxes, stride, fill=0.0):
+            return self._meshes(boxes, stride, False, fill)
 
     class Assets:
         """reference src/server/assets.rs (`tile_list`, `.textures(..)` builder)."""

@@ -294,6 +294,27 @@ int rxh_terrain_generator_grids(void *g, const float *boxes, uint32_t n, uint32_
     ((TerrainGenerator *)g)->grid_heights_cpu(boxes, n, stride, counts, heights);
     return RXR_OK;
 }
+// the lists of rxr_set_terrain_exclusions (include/rxr.h); 0, or RXR_ERR_INVALID for offsets the lists do not fit (nothing changes then)
+int rxh_terrain_generator_set_exclusions(void *g_, const float *boxes, const uint32_t *off, const float *verts, uint32_t S, uint32_t V) {
+    TerrainGenerator *g = (TerrainGenerator *)g_;
+    if (rxr_check_terrain_exclusions(boxes, off, verts, S, V, nullptr, 0) == RXR_ERR_INVALID) return RXR_ERR_INVALID;
+    g->excluded_boxes.assign(boxes, boxes + 4 * (size_t)S);
+    g->excluded_vertex_offsets.assign(1, 0u);
+    if (S) g->excluded_vertex_offsets.assign(off, off + S + 1);
+    g->excluded_vertices.assign(verts, verts + 2 * (size_t)V);
+    g->touch();
+    return RXR_OK;
+}
+// n boxes in the layout of rxr_generated_meshes: on the device, or (device == 0) the CPU apply_exclusions
+int rxh_terrain_generator_meshes(void *g, const float *boxes, uint32_t n, uint32_t stride, int device, uint32_t *counts, float *vertices) {
+    if (device) return ((TerrainGenerator *)g)->generate_meshes(boxes, n, stride, counts, vertices);
+    ((TerrainGenerator *)g)->generate_meshes_cpu(boxes, n, stride, counts, vertices);
+    return RXR_OK;
+}
+// point_in_sector for n points [n][2] against sector s on the CPU: inside [n] (1 / 0)
+void rxh_terrain_generator_points_in_sector(void *g, const float *points, uint32_t n, uint32_t s, uint8_t *inside) {
+    for (uint32_t i = 0; i < n; ++i) inside[i] = ((TerrainGenerator *)g)->point_in_sector(points[2 * (size_t)i], points[2 * (size_t)i + 1], s) ? 1 : 0;
+}
 // Scene::rebuild_terrain_meshes: 0 (updated in place on the device), 1 (fallback: the batches were replaced on the host) or a negative rxr_status
 int rxh_scene_rebuild_terrain_meshes(void *s, void *t, const int32_t *coords, uint32_t n, const uint32_t *chunks) {
     return ((Scene *)s)->rebuild_terrain_meshes(*(const Terrain *)t, coords, n, chunks);

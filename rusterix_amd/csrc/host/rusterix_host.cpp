@@ -492,6 +492,7 @@ uint64_t g_shaders_gen = 0, g_shader_env_gen = 0;
 uint64_t g_terrain_gen = 0;   // the Terrain::generation the context's resident terrain was registered from (0: none)
 uint64_t g_heights_gen = 0;   // the Terrain::heights_generation the context's resident heights were registered from (0: none)
 uint64_t g_generator_gen = 0; // the TerrainGenerator::generation the context's resident generator records were registered from (0: none)
+uint64_t g_exclusion_gen = 0; // ... and the one its resident excluded sectors were registered from (0: none)
 // (RXR_DEVICE_PROJECTION=1 in the environment makes device projection the initial choice, as in the Rust shim: shim/.../lib.rs)
 bool g_device_projection = [] { const char *e = getenv("RXR_DEVICE_PROJECTION"); return e && e[0] == '1'; }();
 bool g_device_edges = !(getenv("RXR_HOST_EDGES") && atoi(getenv("RXR_HOST_EDGES")) != 0);
@@ -534,6 +535,7 @@ void drop_context_locked() {
     g_terrain_gen = 0;
     g_heights_gen = 0;
     g_generator_gen = 0;
+    g_exclusion_gen = 0;
     g_ctex_held = false;
     g_ctex_gens.clear();
 }
@@ -2064,6 +2066,125 @@ int TerrainGenerator::grid_heights(const float *boxes, uint32_t n, uint32_t stri
     int rc = register_records(ctx);
     if (rc != RXR_OK) return rc;
     rc = rxr_generated_grids(ctx, boxes, n, subdivisions, stride, counts, heights);
+    if (rc != RXR_OK) g_error = rxr_last_error(ctx);
+    return rc;
+}
+
+// ---- the generated terrain's excluded sectors (:438-457, :747-825, :891-950) ------------------------
+bool TerrainGenerator::sector_active(uint32_t s, const float box[4]) const {
+    // sector_bbox.intersects(bbox), src/map/bbox.rs:43-48
+    const float *sb = &excluded_boxes[4 * (size_t)s];
+    return sb[0] <= box[2] && sb[2] >= box[0] && sb[1] <= box[3] && sb[3] >= box[1];
+}
+
+bool TerrainGenerator::point_in_sector(float x, float y, uint32_t s) const {
+    const Vec2 point{x, y};
+    const float *verts = excluded_vertices.data() + 2 * (size_t)excluded_vertex_offsets[s];
+    const size_t len = excluded_vertex_offsets[s + 1] - excluded_vertex_offsets[s];
+    if (len < 3) return false;
+    const float epsilon = 0.01f;
+    size_t j = len - 1;
+    for (size_t i = 0; i < len; ++i) {
+        const Vec2 vi{verts[2 * i], verts[2 * i + 1]}, vj{verts[2 * j], verts[2 * j + 1]};
+        const Vec2 edge = vj - vi;
+        const float edge_length_sq = rvek::dot(edge, edge);
+        if (edge_length_sq > 0.0f) {
+            const float t = rvek::rclamp(rvek::dot(point - vi, edge) / edge_length_sq, 0.0f, 1.0f);
+            const Vec2 projection = vi + edge * t;
+            const float dist = rvek::magnitude(point - projection);
+            if (dist < epsilon) return true;
+        }
+        j = i;
+    }
+    bool inside = false;
+    j = len - 1;
+    for (size_t i = 0; i < len; ++i) {
+        const Vec2 vi{verts[2 * i], verts[2 * i + 1]}, vj{verts[2 * j], verts[2 * j + 1]};
+        if (((vi.y > point.y) != (vj.y > point.y)) && (point.x < (vj.x - vi.x) * (point.y - vi.y) / (vj.y - vi.y) + vi.x)) inside = !inside;
+        j = i;
+    }
+    return inside;
+}
+
+std::vector<float> TerrainGenerator::apply_exclusions(const float *grid, const float *heights, int32_t steps_x, int32_t steps_y, const std::vector<uint32_t> &active) const {
+    std::vector<float> out;
+    const size_t P = (steps_x > 0 && steps_y > 0) ? (size_t)steps_x * (size_t)steps_y : 0;
+    auto push = [&](size_t i) {
+        const float v[3] = {grid[2 * i], heights[i], grid[2 * i + 1]};
+        out.insert(out.end(), v, v + 3);
+    };
+    if (active.empty()) {
+        for (size_t i = 0; i < P; ++i) push(i);
+        return out;
+    }
+    const std::vector<uint32_t> indices = triangulate(steps_x, steps_y);
+    const size_t T = indices.size() / 3;
+    std::vector<uint8_t> exclude(T, 0);
+    {
+        std::lock_guard<std::recursive_mutex> lk(g_mu);   // (the worker pool runs one job at a time)
+        const size_t per = 64, items = (T + per - 1) / per;
+        rxr_parallel::run(items, T * 3 * (excluded_vertices.size() / 2 + 1), [&](size_t item) {
+            for (size_t t = item * per; t < std::min(T, (item + 1) * per); ++t) {
+                const uint32_t *ix = &indices[3 * t];
+                for (const uint32_t s : active)
+                    if (point_in_sector(grid[2 * ix[0]], grid[2 * ix[0] + 1], s) && point_in_sector(grid[2 * ix[1]], grid[2 * ix[1] + 1], s) &&
+                        point_in_sector(grid[2 * ix[2]], grid[2 * ix[2] + 1], s)) {
+                        exclude[t] = 1;
+                        break;
+                    }
+            }
+        });
+    }
+    for (size_t t = 0; t < T; ++t)
+        if (!exclude[t])
+            for (int k = 0; k < 3; ++k) push(indices[3 * t + k]);
+    return out;
+}
+
+void TerrainGenerator::generate_meshes_cpu(const float *boxes, uint32_t n, uint32_t stride, uint32_t *counts, float *vertices) const {
+    const uint32_t S = (uint32_t)(excluded_boxes.size() / 4);
+    for (uint32_t b = 0; b < n; ++b) {
+        const float *box = boxes + 4 * (size_t)b;
+        int32_t sx, sy;
+        grid_steps(box, sx, sy);
+        std::vector<uint32_t> active;
+        for (uint32_t s = 0; s < S; ++s)
+            if (sector_active(s, box)) active.push_back(s);
+        uint32_t *c = counts + 4 * (size_t)b;
+        c[0] = (uint32_t)std::max(sx, 0), c[1] = (uint32_t)std::max(sy, 0), c[2] = (uint32_t)active.size(), c[3] = 0;
+        const uint64_t points = (uint64_t)c[0] * c[1], cells = (c[0] > 1 && c[1] > 1) ? (uint64_t)(c[0] - 1) * (c[1] - 1) : 0;
+        if ((active.empty() ? points : 6 * cells) > stride) continue;   // (the points are made only where the layout fits)
+        if (!active.empty() && !cells) continue;
+        const std::vector<float> grid = generate_grid(box, sx, sy);
+        std::vector<float> heights(grid.size() / 2);
+        interpolate_heights(grid.data(), heights.size(), heights.data());
+        const std::vector<float> v = apply_exclusions(grid.data(), heights.data(), sx, sy, active);
+        c[3] = (uint32_t)(v.size() / 3);
+        float *o = vertices + (size_t)b * stride * 4;
+        for (size_t i = 0; i < v.size() / 3; ++i) o[4 * i] = v[3 * i], o[4 * i + 1] = v[3 * i + 1], o[4 * i + 2] = v[3 * i + 2], o[4 * i + 3] = 1.0f;
+    }
+}
+
+int TerrainGenerator::register_exclusions(rxr_ctx *ctx) const {
+    if (g_exclusion_gen == generation) return RXR_OK;
+    const int rc = rxr_set_terrain_exclusions(ctx, excluded_boxes.data(), excluded_vertex_offsets.data(), excluded_vertices.data(), (uint32_t)(excluded_boxes.size() / 4),
+                                              (uint32_t)(excluded_vertices.size() / 2));
+    if (rc != RXR_OK) {
+        g_error = rxr_last_error(ctx);
+        return rc;
+    }
+    g_exclusion_gen = generation;
+    return RXR_OK;
+}
+
+int TerrainGenerator::generate_meshes(const float *boxes, uint32_t n, uint32_t stride, uint32_t *counts, float *vertices) const {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::string err;
+    rxr_ctx *ctx = context(&err);
+    if (!ctx) return RXR_ERR_NO_DEVICE;
+    int rc = register_records(ctx);
+    if (rc != RXR_OK || (rc = register_exclusions(ctx)) != RXR_OK) return rc;
+    rc = rxr_generated_meshes(ctx, boxes, n, subdivisions, stride, counts, vertices);
     if (rc != RXR_OK) g_error = rxr_last_error(ctx);
     return rc;
 }

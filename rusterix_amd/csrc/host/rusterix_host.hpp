@@ -403,11 +403,16 @@ private:
 
 // src/chunkbuilder/terrain_generator.rs: the height field of the generated 3D terrain, over the lists TerrainGenerator::generate
 // collects from the Map (:255-294), flattened as rxr_set_terrain_generator takes them (include/rxr.h).  The CPU functions are plain
-// transcriptions (nothing hoisted); the device forms register the lists when they changed.  apply_exclusions with excluded sectors,
-// partition_by_tiles, mesh_fix_winding and the blend batches are the caller's, fed by these heights.
+// transcriptions (nothing hoisted); the device forms register the lists when they changed.  apply_exclusions is generate_meshes;
+// partition_by_tiles, mesh_fix_winding and the blend batches are the caller's, fed by those meshes.
 class TerrainGenerator {
 public:
     uint32_t subdivisions = 1;                        // TerrainConfig.subdivisions (:24)
+    // the map's sectors of terrain_mode == 1, flattened as rxr_set_terrain_exclusions takes them: a sector's bounding box as the
+    // reference computes it and its linedefs' start vertices in linedef order (missing ones skipped, possibly none)
+    std::vector<float> excluded_boxes;                // [S][4]: min.x, min.y, max.x, max.y
+    std::vector<uint32_t> excluded_vertex_offsets{0u};   // [S + 1]
+    std::vector<float> excluded_vertices;             // [V][2]
     std::vector<float> control_points;                // [C][4]: x, y, height, smoothness (config.smoothness's default applied)
     std::vector<float> ridges;                        // [R][4]: height, plateau_width, falloff_distance, falloff_steepness
     std::vector<uint32_t> ridge_edge_offsets{0u};     // [R + 1]
@@ -435,9 +440,23 @@ public:
     // rxr_generated_grids, include/rxr.h).  RXR_OK or a negative rxr_status; there is no fall-back to the CPU.
     int sample_heights(const float *points, uint32_t n, float *heights, float *normals) const;
     int grid_heights(const float *boxes, uint32_t n, uint32_t stride, uint32_t *counts, float *heights) const;
+    // collect_excluded_sectors' test (:438-457): does sector s's box intersect the chunk box as given?
+    bool sector_active(uint32_t s, const float box[4]) const;
+    bool point_in_sector(float x, float y, uint32_t s) const;   // :891-950
+    // apply_exclusions (:747-825) over the grid points [P][2] and their heights, for the sectors `active` in list order: the
+    // vertices [..][3] = (x, h, y); shared layout (grid order) when `active` is empty, else three per kept triangle.  The keep
+    // flags are computed over the host's worker pool.
+    std::vector<float> apply_exclusions(const float *grid, const float *heights, int32_t steps_x, int32_t steps_y, const std::vector<uint32_t> &active) const;
+    // n boxes [n][4] on the CPU, in the layout of rxr_generated_meshes: counts [n][4], vertices [n][stride][4] (a box whose layout
+    // does not fit the stride gets its counts and no vertices)
+    void generate_meshes_cpu(const float *boxes, uint32_t n, uint32_t stride, uint32_t *counts, float *vertices) const;
+    // ... and on the device (rxr_set_terrain_generator / rxr_set_terrain_exclusions when the lists changed, then
+    // rxr_generated_meshes).  RXR_OK or a negative rxr_status; there is no fall-back to the CPU.
+    int generate_meshes(const float *boxes, uint32_t n, uint32_t stride, uint32_t *counts, float *vertices) const;
 
 private:
     int register_records(rxr_ctx *ctx) const;
+    int register_exclusions(rxr_ctx *ctx) const;
 };
 
 // src/rasterizer.rs:35-193

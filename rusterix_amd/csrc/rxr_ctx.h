@@ -39,6 +39,7 @@ enum : uint32_t {
     Q_GEN,       // rxr_generated_heights_to / rxr_generated_grids_to: the resident generator records
     Q_MESH_UPDATE,   // rxr_update_meshes: the staged copies of the caller's host arrays (both forms block; the lane orders nothing else)
     Q_CHUNK_TEX,     // rxr_set_chunk_textures / rxr_update_chunk_textures: the staged copies of the caller's host texels (all forms block)
+    Q_EXCL,          // rxr_generated_meshes_to: the resident generator records, the resident excluded sectors and the call scratch
     Q_LANES
 };
 #define RXR_MAX_TILE_ROWS 2048u   // frames of at most 32768 rows
@@ -312,6 +313,17 @@ struct rxr_ctx {
     uint32_t gen_n[4] = {};
     float gen_box[4] = {};
     uint32_t gen_launches = 0;        // launches of the last evaluation call (rxr_debug_terrain_gen_launches)
+
+    // excluded sectors of the generated terrain's chunk meshes (rxr_terrain_excl.hip): the resident records of rxr_set_terrain_exclusions,
+    // independent of the generator's.  d_excl: one blob of sector boxes [S][4], vertex offsets [S + 1] and one edge record per polygon
+    // vertex (excl_off: their byte offsets); excl_boxes: the boxes' host copy (which sectors are active for a chunk box decides its
+    // layout, and with it what the call refuses); d_excl_scratch: a call's heights and inside-bits, reused launch after launch.
+    DevBuf d_excl, d_excl_scratch;
+    size_t excl_off[3] = {};
+    uint32_t excl_S = 0, excl_V = 0;
+    std::vector<float> excl_boxes;
+    std::vector<uint32_t> excl_voff{0u};   // ... and of the vertex offsets (a round's work counts the vertices of a box's active sectors)
+    uint32_t excl_launches = 0;       // classification launches of the last mesh call (rxr_debug_terrain_excl_launches)
 
     FrameStream fstream;    // rxr_stream_begin .. rxr_upload_frame
     int last_upload_streamed = 0;  // 0 plain, 1 streamed (copied), 2 streamed out of page-locked arrays

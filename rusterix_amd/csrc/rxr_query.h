@@ -1,5 +1,5 @@
 // rxr_query.h -- the host scaffold the device queries next to the renderer share (rxr_intersect.hip, rxr_bake.hip, rxr_terrain.hip,
-// rxr_terrain_hit.hip, rxr_terrain_mesh.hip, rxr_terrain_gen.hip): the cross-stream ordering of a query's lane (rxr_ctx.h: QueryLane), the staging of a blocking form's host
+// rxr_terrain_hit.hip, rxr_terrain_mesh.hip, rxr_terrain_gen.hip, rxr_terrain_excl.hip): the cross-stream ordering of a query's lane (rxr_ctx.h: QueryLane), the staging of a blocking form's host
 // arrays, and the small helpers of their entry points.  A query's `_run` queues its launches between rxr_query_begin and
 // rxr_query_end on whichever stream it is given; its blocking form stages through QueryIO on ctx->stream.
 #pragma once

@@ -99,6 +99,11 @@ def rxr_abi():
         "rxr_generated_grids": (i32, [vp, vp, u32, u32, u32, vp, vp]),
         "rxr_generated_grids_to": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
         "rxr_debug_terrain_gen_launches": (u32, [vp]),
+        "rxr_check_terrain_exclusions": (i32, [vp, vp, vp, u32, u32, C.c_char_p, u32]),
+        "rxr_set_terrain_exclusions": (i32, [vp, vp, vp, vp, u32, u32]),
+        "rxr_generated_meshes": (i32, [vp, vp, u32, u32, u32, vp, vp]),
+        "rxr_generated_meshes_to": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
+        "rxr_debug_terrain_excl_launches": (u32, [vp]),
         "rxr_update_meshes": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, u32]),
         "rxr_update_meshes_to": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, u32, vp]),
         "rxr_mesh_bounds": (i32, [vp, u32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
