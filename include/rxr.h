@@ -1028,6 +1028,95 @@ int rxr_generated_meshes(rxr_ctx *ctx, const float *boxes, uint32_t n, uint32_t 
 int rxr_generated_meshes_to(rxr_ctx *ctx, const float *boxes, uint32_t n, uint32_t subdivisions, uint32_t stride,
                             uint32_t *dev_counts, float *dev_vertices, void *hip_stream);
 
+/* ---- path tracing the resident scene: Tracer::trace (rusterix_amd/csrc/rxr_trace.hip) ----------------------------------------------
+ * The reference's second renderer (src/tracer/trace.rs:105-475 into an AccumBuffer, src/tracer/buffer.rs) over the meshes of
+ * rxr_set_meshes and the tiles of rxr_set_textures, as it stands (DESIGN.md section 18 has the derivation):
+ *   camera   per pixel (x, y): screen_uv = (x / width, 1 - y / height), jitter = (rand, rand), then the per-pixel part of the camera's
+ *            create_ray (src/camera/d3firstp.rs:112-138, d3orbit.rs:117-153, d3iso.rs:159-182) from 14 host-computed floats: position,
+ *            forward, right, up (3 each), half_width, half_height -- what create_ray computes before it looks at uv (their tan,
+ *            normalized and cross run on the host; half_width includes the aspect; iso: position = the camera's position(), forward =
+ *            (center - position).normalized(), right and up = basis()'s, half_height = scale, half_width = scale *
+ *            max(width / height, 1e-6)).
+ *   hit      Batch3D::intersect(ray, false) per mesh, folded by `hit.t < best.t` in rxr_set_meshes order over the lists RXR_LIST_CHUNK,
+ *            _CHUNK_TERRAIN, _STATIC and _DYNAMIC: rxr_intersect's RXR_INTERSECT_FULL under its plain rule, profile ids ignored.  The
+ *            opacity and overlay lists are not looked at.  (The reference walks scene.chunks in hash-map order; the mesh order is
+ *            this library's definition.  Its intersects_aabb pre-tests only cull and are left out.)
+ *   texel    evaluate_hit (:377-475): RXR_SOURCE_PIXEL; a static / dynamic tile at animation_frame % n_textures sampled at the hit's uv
+ *            with sample_mode and the mesh's repeat mode; RXR_SOURCE_TERRAIN in a chunk: chunk.sample_terrain_texture at (w.x, w.z) of
+ *            ray.at(t) from the chunk's resident terrain texture (rxr_set_chunk_textures; no texture: zero); anything else is zero.  tex_lin = srgb_to_linear(texel) through a table of
+ *            256 floats built on the host (rxr_trace_srgb_table); albedo = tex_lin.xyz.
+ *   material per mesh (role, modifier, value), role RXR_TRACE_NO_MATERIAL for None: value' = modifier.modify(texel, value)
+ *            (src/shapestack/material.rs:80-110; modifiers 0 None, 1 Luminance, 2 Saturation, 3 InvLuminance, 4 InvSaturation); roles
+ *            0 Matte: specular_weight = 1 - value', 1 Glossy and 2 Metallic: = value', 3 Transparent: nothing, 4 Emissive: emissive =
+ *            tex_lin.xyz * value * 10 (the unmodified value).
+ *   bounce   (:272-331) emissive != 0: ret += emissive * throughput, the path ends.  Else ret += (sum of radiance_at(world, normal,
+ *            hash_u32(animation_frame)) * 10 over `lights`) * (throughput * (albedo / PI)); p_spec = specular_weight.clamp(0, 1);
+ *            rand < p_spec: dir = reflect(dir, normal), throughput *= specular_weight / p_spec; else dir = sample_cosine(normal),
+ *            throughput *= (albedo * p_diff) / (p_diff * PI); origin = origin + dir * t + normal * 0.01 WITH THE NEW dir (the reference
+ *            assigns ray.dir first); p = max(throughput).clamp(0.001, 1), the path ends when rand > p, else throughput *= 1 / p.  A
+ *            miss ends the path and adds nothing (no render graph: the sky of render_miss_d3 is out of scope).
+ *   average  per call frame f = first_frame + k: t = 1 / (f + 1), accum = accum * (1 - t) + (ret.x, ret.y, ret.z, 1) * t, unfused.
+ * Random numbers: the reference draws from an OS-seeded generator whose stream is unspecified; this one is counter-based, a sample
+ * depends on (seed, frame, pixel index y * width + x, slot) alone:
+ *   pcg(v): s = v * 747796405 + 2891336453; w = ((s >> ((s >> 28) + 4)) ^ s) * 277803737; return (w >> 22) ^ w      (all u32, wrapping)
+ *   u32 = pcg(pcg(pcg(seed + frame) + pixel) + slot);   f32 = (u32 >> 8) as f32 * 2^-24, in [0, 1)                (rand's f32)
+ * Slots 0, 1: the jitter; bounce b: 2 + 4 b + (0 specular choice, 1 r1, 2 r2, 3 roulette), spent whether or not the branch runs.
+ * No libm function runs on the device before a path's first diffuse bounce (the cos and sin of sample_cosine); up to there every
+ * float is the reference's.  acos (spot lights) is the device's as in the rasterizer's exact light loop. */
+#define RXR_TRACE_CAMERA_FIRSTP 0
+#define RXR_TRACE_CAMERA_ORBIT 1
+#define RXR_TRACE_CAMERA_ISO 2
+#define RXR_TRACE_CAMERA_FLOATS 14    /* position, forward, right, up (3 each), half_width, half_height */
+#define RXR_TRACE_NO_MATERIAL 4294967295u
+#define RXR_TRACE_MAX_BOUNCES 8       /* the reference's constant; the generator's slots are laid out for it */
+#define RXR_TRACE_MAX_LIGHTS 4096     /* the light list is walked per hit by every path: a bound on a record the kernel takes whole */
+/* validation only, no context: what rxr_set_trace_scene checks without looking at the registered meshes.  RXR_ERR_INVALID: lights
+ * NULL with n_lights > 0, a light type, material role (0..4 or RXR_TRACE_NO_MATERIAL) or modifier (0..4) out of range, an unknown
+ * sample mode, material_kinds given without material_values or the reverse.  RXR_ERR_UNSUPPORTED: n_lights above
+ * RXR_TRACE_MAX_LIGHTS. */
+int rxr_check_trace_scene(const uint32_t *material_kinds, const float *material_values, uint32_t n_meshes, const rxr_light *lights,
+                          uint32_t n_lights, uint32_t sample_mode, char *message, uint32_t message_capacity);
+/* what the tracer reads besides meshes and textures (stays until the next call, or the next rxr_set_meshes / rxr_set_textures, which
+ * drop it): material_kinds [n_meshes][2] = (role, modifier) and material_values [n_meshes], both NULL for no materials; the lights
+ * the reference chains (scene.lights, then scene.dynamic_lights; chunk lights are NOT part of it); the tracer's sample mode;
+ * scene.animation_frame; chunk_origin_size [n_chunks][3] = chunk.origin.x, chunk.origin.y, chunk.size of every chunk a terrain-sourced
+ * mesh lies in (NULL with n_chunks 0 when there is none; the textures themselves are those of rxr_set_chunk_textures, which drops the
+ * trace scene as well).  n_meshes must equal the count of the last rxr_set_meshes (RXR_ERR_INVALID).  RXR_ERR_INVALID as well: a
+ * participating mesh whose tile does not exist or has no texture, or whose chunk's size is below 1 (the reference panics), or whose
+ * chunk chunk_origin_size does not reach.  RXR_ERR_UNSUPPORTED: a participating mesh of source RXR_SOURCE_TERRAIN while no resident
+ * chunk texture is registered for its chunk.  A refused call leaves the previous trace scene as it was.  Blocking.  Multi-device
+ * handles: member 0. */
+int rxr_set_trace_scene(rxr_ctx *ctx, const uint32_t *material_kinds, const float *material_values, uint32_t n_meshes,
+                        const rxr_light *lights, uint32_t n_lights, uint32_t sample_mode, uint64_t animation_frame,
+                        const int32_t *chunk_origin_size, uint32_t n_chunks);
+/* the 256 floats srgb_to_linear(byte * (1 / 255)) every context uses (trace.rs:14-20; the host's powf, built once per process: ctx
+ * may be NULL) */
+int rxr_trace_srgb_table(rxr_ctx *ctx, float out[256]);
+/* the generator above as the kernels run it, evaluated on the host (no context, no device): a host's CPU path of the same loop and
+ * the tests draw from it */
+float rxr_trace_rand(uint32_t seed, uint32_t frame, uint32_t pixel, uint32_t slot);
+/* n_frames samples of every pixel, averaged into accum (host memory, [height][width][4], in/out) as frames first_frame ..
+ * first_frame + n_frames - 1, without going back to the host in between.  camera: RXR_TRACE_CAMERA_FLOATS floats.  RXR_ERR_INVALID:
+ * a NULL pointer, width, height or n_frames of 0, more than 2^24 pixels a side or 2^28 in all, an unknown camera kind, no
+ * rxr_set_trace_scene for the current meshes.  RXR_ERR_UNSUPPORTED: bounces above RXR_TRACE_MAX_BOUNCES.  A refused call leaves accum
+ * untouched.  bounces == 0 averages black.  A trace changes no frame state: a frame uploaded before it renders as it would have.
+ * Blocking.  Multi-device handles: member 0.
+ * Replaces: Tracer::trace, src/tracer/trace.rs:105-375, once per frame. */
+int rxr_trace(rxr_ctx *ctx, uint32_t camera_kind, const float *camera, uint32_t width, uint32_t height, uint32_t first_frame,
+              uint32_t n_frames, uint32_t seed, uint32_t bounces, float *accum);
+/* the same on DEVICE memory (first and last byte are checked to be memory of the context's device; 16-byte aligned), queued on
+ * hip_stream (NULL = the context's stream); camera is host memory and is read before the call returns.  Asynchronous.  Multi-device
+ * handles: RXR_ERR_UNSUPPORTED (use rxr_member). */
+int rxr_trace_to(rxr_ctx *ctx, uint32_t camera_kind, const float *camera, uint32_t width, uint32_t height, uint32_t first_frame,
+                 uint32_t n_frames, uint32_t seed, uint32_t bounces, float *dev_accum, void *hip_stream);
+/* AccumBuffer::to_u8_vec (src/tracer/buffer.rs:68-91): per colour channel x <= 0.0031308 ? x * 12.92 : 1.055 * x.powf(1 / 2.4) -
+ * 0.055, then (srgb.clamp(0, 1) * 255 + 0.5) as u8; alpha (a.clamp(0, 1) * 255 + 0.5) as u8.  powf is the device's: a channel whose
+ * exact value lies within its error of an integer may differ from a host's by one.  accum and rgba ([height][width][4] bytes) are
+ * host memory; blocking.  Multi-device handles: member 0. */
+int rxr_accum_to_rgba(rxr_ctx *ctx, const float *accum, uint32_t width, uint32_t height, uint8_t *rgba);
+/* the same on DEVICE memory, queued on hip_stream (NULL = the context's stream).  Multi-device handles: RXR_ERR_UNSUPPORTED. */
+int rxr_accum_to_rgba_to(rxr_ctx *ctx, const float *dev_accum, uint32_t width, uint32_t height, uint8_t *dev_rgba, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

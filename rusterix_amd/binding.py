@@ -466,6 +466,18 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         L.scene_intersect = fn("scene_intersect", i32, vp, pf, pf, u32, u32, pf, pu, pu, pf, pf, pf)
         L.rasterizer_screen_ray = fn("rasterizer_screen_ray", None, vp, f32, f32, pf, pf)
 
+    # the path tracer (product host library only): Scene.trace, AccumBuffer, Batch3D.material
+    has_trace = hasattr(lib, prefix + "scene_trace")
+    if has_trace:
+        L.scene_trace = fn("scene_trace", i32, vp, vp, vp, u32, pf, u32, u32, u32, u32, i32, u32)
+        L.accum_new = fn("accum_new", vp, u32, u32)
+        L.accum_free = fn("accum_free", None, vp)
+        L.accum_pixels = fn("accum_pixels", pf, vp)
+        L.accum_frame = fn("accum_frame", C.c_uint64, vp)
+        L.accum_set_frame = fn("accum_set_frame", None, vp, C.c_uint64)
+        L.accum_to_u8 = fn("accum_to_u8", None, vp, pb)
+        L.batch3d_set_material = fn("batch3d_set_material", None, vp, i32, u32, u32, f32)
+
     # the shader-texture bake (product host library only, like ray picking)
     has_bake = hasattr(lib, prefix + "scene_bake_shaders")
     if has_bake:
@@ -612,6 +624,14 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
 
         def repeat_mode(self, m):
             L.batch3d_set_repeat_mode(self._h, m)
+            return self
+
+        def material(self, role=None, modifier=0, value=1.0):
+            """batch.material (reference src/shapestack/material.rs): role 0 Matte, 1 Glossy, 2 Metallic, 3 Transparent, 4 Emissive;
+            modifier 0 None, 1 Luminance, 2 Saturation, 3 InvLuminance, 4 InvSaturation; role None: no material.  Read by Scene.trace."""
+            if not has_trace:
+                raise NotImplementedError(f"{name}: no path tracer in this library")
+            L.batch3d_set_material(self._h, 0 if role is None else 1, 0 if role is None else role, modifier, value)
             return self
 
         def cull_mode(self, m):
@@ -900,6 +920,23 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
 
         def num_dynamic_lights(self):
             return L.scene_num_dynamic_lights(self._h)
+
+        def trace(self, camera, accum, assets, width=None, height=None, n_frames=1, seed=0, bounces=8, sample_mode=SAMPLE_NEAREST, cpu=False,
+                  threads=0):
+            """Tracer::trace (reference src/tracer/trace.rs:105-375) n_frames times into `accum` (an AccumBuffer), on the device
+            (rxr_set_trace_scene + rxr_trace, include/rxr.h) or, with cpu=True, by the mirror's host loop of the same operations.
+            `camera`: a D3FirstPCamera / D3OrbitCamera (their trace_constants) or (kind, the 14 floats) as rusterix_amd.trace's
+            camera_firstp / camera_orbit / camera_iso return them.  accum.frame advances by n_frames."""
+            if not has_trace:
+                raise NotImplementedError(f"{name}: no path tracer in this library")
+            kind, consts = camera.trace_constants(accum.width, accum.height) if hasattr(camera, "trace_constants") else camera
+            consts = _f32(consts, (14,))
+            rc = L.scene_trace(self._h, assets._h, accum._h, kind, _fp(consts), sample_mode, n_frames, seed, bounces, 1 if cpu else 0, threads)
+            if rc != 0:
+                f = getattr(lib, prefix + "last_error")
+                f.restype = C.c_char_p
+                raise RasterizeError(rc, (f() or b"").decode())
+            return accum
 
         def intersect(self, origins, dirs, full=False):
             """Scene::intersect (reference src/scene.rs:216-276) for every ray of origins / dirs ([n][3]), on the device
@@ -1477,6 +1514,39 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
                 raise RasterizeError(rc, msg)
             return self
 
+    class AccumBuffer:
+        """reference src/tracer/buffer.rs: linear RGBA f32 [height][width][4] (`pixels`, a view of the mirror's buffer) and `frame`"""
+
+        def __init__(self, width, height):
+            if not has_trace:
+                raise NotImplementedError(f"{name}: no path tracer in this library")
+            self.width, self.height = int(width), int(height)
+            self._h = L.accum_new(self.width, self.height)
+            self.pixels = np.ctypeslib.as_array(L.accum_pixels(self._h), shape=(self.height, self.width, 4))
+
+        def __del__(self):
+            if getattr(self, "_h", None):
+                self.pixels = None
+                L.accum_free(self._h)
+                self._h = None
+
+        @property
+        def frame(self):
+            return int(L.accum_frame(self._h))
+
+        @frame.setter
+        def frame(self, f):
+            L.accum_set_frame(self._h, int(f))
+
+        def reset(self):
+            self.frame = 0
+
+        def to_u8_vec(self):
+            """AccumBuffer::to_u8_vec (:78-91) on the host: [height][width][4] bytes"""
+            out = np.zeros((self.height, self.width, 4), np.uint8)
+            L.accum_to_u8(self._h, _bp(out))
+            return out
+
     class D3OrbitCamera:
         """reference src/camera/d3orbit.rs:23-56,186-195."""
 
@@ -1508,6 +1578,11 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         def projection_matrix(self, width, height):
             return self.matrices(width, height)[1]
 
+        def trace_constants(self, width, height):
+            """(RXR_TRACE_CAMERA_ORBIT, what create_ray computes before it looks at the pixel): Scene.trace's camera"""
+            from .trace import camera_orbit
+            return camera_orbit(self.center, self.distance, self.azimuth, self.elevation, self.fov, width, height)
+
     class D3FirstPCamera:
         """reference src/camera/d3firstp.rs:17-42."""
 
@@ -1526,6 +1601,11 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
             c = _f32(self.center, (3,))
             L.camera_firstp(_fp(pos), _fp(c), self.fov, self.near, self.far, width, height, _fp(v), _fp(p))
             return v, p
+
+        def trace_constants(self, width, height):
+            """(RXR_TRACE_CAMERA_FIRSTP, what create_ray computes before it looks at the pixel): Scene.trace's camera"""
+            from .trace import camera_firstp
+            return camera_firstp(self.position, self.center, self.fov, width, height)
 
         def view_matrix(self):
             return self.matrices(1.0, 1.0)[0]
@@ -1563,7 +1643,7 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
     return types.SimpleNamespace(
         name=name, lib=lib, prefix=prefix, raw=L, update_meshes=update_meshes, chunk_texture_registrations=chunk_texture_registrations,
         Scene=Scene, Batch3D=Batch3D, Batch2D=Batch2D, Chunk=Chunk, Assets=Assets, Rasterizer=Rasterizer, Terrain=Terrain, TerrainGenerator=TerrainGenerator,
-        D3OrbitCamera=D3OrbitCamera, D3FirstPCamera=D3FirstPCamera,
+        D3OrbitCamera=D3OrbitCamera, D3FirstPCamera=D3FirstPCamera, AccumBuffer=AccumBuffer,
         # shared value types
         Texture=Texture, Tile=Tile, Light=Light, PixelSource=PixelSource, RenderMode=RenderMode,
         VGrayGradientShader=VGrayGradientShader, GridShader=GridShader, Mat4=Mat4, Mat3=Mat3, Program=Program,

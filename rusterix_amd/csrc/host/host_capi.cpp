@@ -71,6 +71,22 @@ int rxh_scene_intersect(void *s, const float *origins, const float *dirs, uint32
                         uint32_t *triangle, float *hitpoint, float *uv, float *normal) {
     return ((Scene *)s)->intersect(origins, dirs, n, flags, t, mesh, triangle, hitpoint, uv, normal);
 }
+// Tracer::trace into an AccumBuffer handle (rusterix_host.hpp): camera_kind + the 14 floats of include/rxr.h; cpu != 0: the host loop
+int rxh_scene_trace(void *s, void *assets, void *accum, uint32_t camera_kind, const float *camera, uint32_t sample_mode, uint32_t n_frames,
+                    uint32_t seed, uint32_t bounces, int cpu, uint32_t threads) {
+    Tracer t;
+    t.sample_mode = sample_mode;
+    return t.trace(camera_kind, camera, *(Scene *)s, *(AccumBuffer *)accum, *(Assets *)assets, n_frames, seed, bounces, cpu != 0, threads);
+}
+void *rxh_accum_new(uint32_t width, uint32_t height) { return new AccumBuffer(width, height); }
+void rxh_accum_free(void *a) { delete (AccumBuffer *)a; }
+float *rxh_accum_pixels(void *a) { return ((AccumBuffer *)a)->pixels.data(); }
+uint64_t rxh_accum_frame(void *a) { return ((AccumBuffer *)a)->frame; }
+void rxh_accum_set_frame(void *a, uint64_t frame) { ((AccumBuffer *)a)->frame = (size_t)frame; }
+void rxh_accum_to_u8(void *a, uint8_t *out) {
+    const std::vector<uint8_t> v = ((AccumBuffer *)a)->to_u8_vec();
+    memcpy(out, v.data(), v.size());
+}
 void rxh_scene_free(void *s) { delete (Scene *)s; }
 void rxh_scene_set_animation_frame(void *s, uint64_t f) { ((Scene *)s)->animation_frame = (size_t)f; }
 void rxh_scene_set_background(void *s, int kind) { ((Scene *)s)->background = (uint32_t)kind; }
@@ -392,6 +408,14 @@ void rxh_batch3d_set_source_seq(void *b, int is_item, uint32_t id, uint32_t seq)
     ((Batch3D *)b)->source_ = is_item ? PixelSource::ItemTile(id, seq) : PixelSource::EntityTile(id, seq);
 }
 void rxh_batch3d_set_repeat_mode(void *b, int m) { ((Batch3D *)b)->repeat_mode_ = (uint32_t)m; }
+// batch.material (src/shapestack/material.rs): role and modifier as their to_u8 / from_u8 numbers; has == 0: None
+void rxh_batch3d_set_material(void *b, int has, uint32_t role, uint32_t modifier, float value) {
+    Batch3D *B = (Batch3D *)b;
+    B->has_material = has != 0;
+    B->material_role = role;
+    B->material_modifier = modifier;
+    B->material_value = value;
+}
 void rxh_batch3d_set_cull_mode(void *b, int m) { ((Batch3D *)b)->cull_mode_ = (CullMode)m; }
 void rxh_batch3d_set_ambient_color(void *b, float r, float g, float bl) { ((Batch3D *)b)->ambient_color_ = Vec3{r, g, bl}; }
 void rxh_batch3d_set_transform(void *b, const float *m16) { ((Batch3D *)b)->transform_3d = mat4_from(m16); }

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <thread>
 
 namespace rusterix {
 
@@ -872,6 +873,421 @@ int Scene::intersect(const float *origins, const float *dirs, uint32_t n, uint32
     const int rc = rxr_intersect(ctx, origins, dirs, n, flags, t, mesh, triangle, hitpoint, uv, normal);
     if (rc != RXR_OK) g_error = rxr_last_error(ctx);
     return rc;
+}
+
+// ---- Tracer (src/tracer/trace.rs, src/tracer/buffer.rs) ------------------------------------------------------------------------
+// The CPU path is the loop of rxr_trace.hip (include/rxr.h states it) a pixel at a time: the same operations in the same order on the
+// scene's own arrays, the library's generator and sRGB table.  tests/test_trace_cpu.py holds it to tests/trace_ref.py bit for bit.
+namespace {
+struct T3 {
+    float x, y, z;
+};
+inline T3 t_add(T3 a, T3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+inline T3 t_sub(T3 a, T3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+inline T3 t_mul(T3 a, T3 b) { return {a.x * b.x, a.y * b.y, a.z * b.z}; }
+inline T3 t_scale(T3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
+inline T3 t_div(T3 a, float s) { return {a.x / s, a.y / s, a.z / s}; }
+inline float t_dot(T3 a, T3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+inline T3 t_cross(T3 a, T3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+inline T3 t_normalized(T3 a) { return t_div(a, std::sqrt(t_dot(a, a))); }
+inline T3 t_arr(const float *p) { return {p[0], p[1], p[2]}; }
+inline float t_clamp(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }   // f32::clamp: a NaN stays
+inline uint32_t t_as_u32(float x) {   // Rust's `as u32`
+    if (!(x > 0.0f)) return 0u;
+    return x >= 4294967296.0f ? 0xFFFFFFFFu : (uint32_t)x;
+}
+constexpr float T_PI = 3.14159265358979323846f;
+
+// Texture::sample (texture.rs:203-232, :307-323, :414-460), colour channels
+void t_sample(const Texture &tex, float u, float v, uint32_t sample_mode, uint32_t repeat_mode, uint32_t rgb[3]) {
+    auto frac = [](float x) { return x - std::floor(x); };
+    switch (repeat_mode) {
+        case RXR_REPEAT_CLAMP_XY: u = t_clamp(u, 0.0f, 1.0f), v = t_clamp(v, 0.0f, 1.0f); break;
+        case RXR_REPEAT_REPEAT_XY: u = frac(u), v = frac(v); break;
+        case RXR_REPEAT_REPEAT_X: u = frac(u), v = t_clamp(v, 0.0f, 1.0f); break;
+        default: u = t_clamp(u, 0.0f, 1.0f), v = frac(v); break;
+    }
+    const uint32_t w = tex.width, h = tex.height;
+    auto at = [&](uint32_t x, uint32_t y, int c) { return (float)tex.data[((size_t)y * w + x) * 4 + c]; };
+    if (sample_mode == RXR_SAMPLE_NEAREST) {
+        const uint32_t tx = std::min(t_as_u32(std::round(u * ((float)w - 1.0f))), w - 1u);
+        const uint32_t ty = std::min(t_as_u32(std::round(v * ((float)h - 1.0f))), h - 1u);
+        for (int c = 0; c < 3; ++c) rgb[c] = (uint32_t)at(tx, ty, c);
+        return;
+    }
+    const float x = u * ((float)w - 1.0f), y = v * ((float)h - 1.0f);
+    const float fx = std::floor(x), fy = std::floor(y);
+    const uint32_t x0 = std::min(t_as_u32(fx), w - 1u), y0 = std::min(t_as_u32(fy), h - 1u);
+    const uint32_t x1 = std::min(x0 + 1u, w - 1u), y1 = std::min(y0 + 1u, h - 1u);
+    const float dx = x - fx, dy = y - fy;
+    for (int c = 0; c < 3; ++c) {
+        const float a = at(x0, y0, c) + dx * (at(x1, y0, c) - at(x0, y0, c));
+        const float b = at(x0, y1, c) + dx * (at(x1, y1, c) - at(x0, y1, c));
+        rgb[c] = std::min(t_as_u32(std::round(a + dy * (b - a))), 255u);
+    }
+}
+
+float t_smoothstep(float e0, float e1, float x) {
+    const float t = t_clamp((x - e0) / (e1 - e0), 0.0f, 1.0f);
+    return t * t * (3.0f - 2.0f * t);
+}
+T3 t_flicker(const rxr_light &l, float intensity, uint32_t hash) {
+    float ff = 1.0f;
+    if (l.flicker > 0.0f) {
+        const uint32_t combined = hash + (t_as_u32(l.position[0]) + t_as_u32(l.position[1]) + t_as_u32(l.position[2])) * 100u;
+        ff = 1.0f - t_clamp((float)combined / 4294967296.0f, 0.0f, 1.0f) * l.flicker;
+    }
+    return {l.color[0] * intensity * ff, l.color[1] * intensity * ff, l.color[2] * intensity * ff};
+}
+// CompiledLight::radiance_at(point, Some(normal), hash) over color_at(point, hash, false) (map/light.rs:491-677)
+bool t_radiance(const rxr_light &l, T3 point, T3 n, uint32_t hash, T3 &out) {
+    if (!l.emitting) return false;
+    const T3 lp = t_arr(l.position), tp = t_sub(point, lp);
+    const float distance = std::sqrt(t_dot(tp, tp));
+    bool lambert = true;
+    switch (l.light_type) {
+        case RXR_LIGHT_POINT:
+            if (distance >= l.end_distance) return false;
+            out = distance <= l.start_distance ? t_flicker(l, l.intensity, hash)
+                                               : t_flicker(l, l.intensity * t_smoothstep(l.end_distance, l.start_distance, distance), hash);
+            break;
+        case RXR_LIGHT_AMBIENT:
+        case RXR_LIGHT_AMBIENT_DAYLIGHT:
+            out = t_flicker(l, l.intensity, hash);
+            lambert = false;
+            break;
+        case RXR_LIGHT_SPOT: {
+            if (distance >= l.end_distance) return false;
+            const float att = distance <= l.start_distance ? 1.0f : 1.0f - ((distance - l.start_distance) / (l.end_distance - l.start_distance));
+            if (std::acos(t_dot(t_arr(l.direction), t_normalized(tp))) > l.cone_angle) return false;
+            out = t_flicker(l, l.intensity * att, hash);
+            break;
+        }
+        case RXR_LIGHT_AREA: {
+            if (distance >= l.end_distance) return false;
+            if (distance < 0.1f) {
+                out = t_arr(l.color);
+                break;
+            }
+            const float datt = distance <= l.start_distance ? 1.0f : t_smoothstep(l.end_distance, l.start_distance, distance);
+            const float area = l.width * l.height;
+            const T3 direction = t_normalized(tp);
+            const float att = l.from_linedef ? datt * area * l.intensity : std::fmax(t_dot(t_arr(l.normal), direction), 0.0f) * datt * area * l.intensity;
+            out = {l.color[0] * att, l.color[1] * att, l.color[2] * att};
+            break;
+        }
+        default: {   // Daylight
+            if (distance >= l.end_distance) return false;
+            const float aa = std::fmax(t_dot(t_arr(l.normal), t_normalized(tp)), 0.0f);
+            const float datt = distance <= l.start_distance ? 1.0f : t_smoothstep(l.end_distance, l.start_distance, distance);
+            const float att = aa * datt * l.intensity;
+            out = {l.color[0] * att, l.color[1] * att, l.color[2] * att};
+            lambert = false;
+            break;
+        }
+    }
+    if (lambert) out = t_scale(out, std::fmax(t_dot(n, t_normalized(t_sub(lp, point))), 0.0f));
+    return true;
+}
+
+float t_modify(uint32_t modifier, T3 c, float strength) {   // MaterialModifier::modify, shapestack/material.rs:80-110
+    if (modifier == 1 || modifier == 3) {
+        const float lum = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
+        return modifier == 1 ? lum * strength : (1.0f - lum) * strength;
+    }
+    if (modifier == 2 || modifier == 4) {
+        const float mx = std::fmax(c.x, std::fmax(c.y, c.z)), mn = std::fmin(c.x, std::fmin(c.y, c.z));
+        const float sat = mx > 0.0f ? (mx - mn) / mx : 0.0f;
+        return modifier == 2 ? sat * strength : (1.0f - sat) * strength;
+    }
+    return strength;
+}
+
+struct TracedBatch {
+    const Batch3D *b;
+    const Chunk *chunk;
+};
+
+struct CpuTrace {
+    uint32_t kind, width, height, seed, bounces, sample_mode, hash_anim;
+    T3 pos, fwd, right, up;
+    float half_w, half_h;
+    const Scene *scene;
+    const Assets *assets;
+    std::vector<TracedBatch> batches;
+    std::vector<rxr_light> lights;
+    float srgb[256];
+
+    // one sample of pixel i of frame `frame` (trace.rs:169-351)
+    T3 sample(uint32_t i, uint32_t frame) const {
+        const float sx = (float)width, sy = (float)height;
+        const float uvx = (float)(i % width) / sx;
+        float uvy = 1.0f - (float)(i / width) / sy;
+        const float jx = rxr_trace_rand(seed, frame, i, 0u), jy = rxr_trace_rand(seed, frame, i, 1u);
+        T3 o = pos, d;
+        if (kind == RXR_TRACE_CAMERA_FIRSTP) {
+            const float psx = 1.0f / sx, psy = 1.0f / sy;
+            const T3 lower_left = t_sub(t_sub(t_add(pos, fwd), t_scale(right, half_w)), t_scale(up, half_h));
+            const T3 horizontal = t_scale(right, 2.0f * half_w), vertical = t_scale(up, 2.0f * half_h);
+            d = t_normalized(t_sub(t_add(t_add(lower_left, t_scale(horizontal, psx * jx + uvx)), t_scale(vertical, psy * jy + uvy)), pos));
+        } else if (kind == RXR_TRACE_CAMERA_ORBIT) {
+            const float psx = 1.0f / sx, psy = 1.0f / sy;
+            uvy = 1.0f - uvy;
+            const float nx = (psx * jx + uvx) * 2.0f - 1.0f, ny = (psy * jy + uvy) * 2.0f - 1.0f;
+            d = t_normalized(t_sub(t_add(fwd, t_scale(t_scale(right, nx), half_w)), t_scale(t_scale(up, ny), half_h)));
+        } else {
+            const T3 horizontal = t_scale({-right.x, -right.y, -right.z}, 2.0f * half_w), vertical = t_scale(up, 2.0f * half_h);
+            const float psx = 1.0f / std::fmax(sx, 1.0f), psy = 1.0f / std::fmax(sy, 1.0f);
+            o = t_add(t_add(pos, t_scale(horizontal, (psx * jx + uvx) - 0.5f)), t_scale(vertical, (psy * jy + uvy) - 0.5f));
+            d = fwd;
+        }
+        T3 ret{0.0f, 0.0f, 0.0f}, thr{1.0f, 1.0f, 1.0f};
+        for (uint32_t bounce = 0; bounce < bounces; ++bounce) {
+            // the closest hit: Batch3D::intersect per batch (batch3d.rs:844-948), folded by a strict `<`
+            const T3 ld = t_normalized(d);
+            float best_t = FLT_MAX, bu = 0.0f, bv = 0.0f;
+            const TracedBatch *hit = nullptr;
+            size_t htri = 0;
+            for (const TracedBatch &tb : batches) {
+                const Batch3D &B = *tb.b;
+                for (size_t k = 0; k < B.triangle_count(); ++k) {
+                    const T3 p0 = t_arr(&B.vertices[4 * (size_t)B.indices[3 * k]]);
+                    const T3 e1 = t_sub(t_arr(&B.vertices[4 * (size_t)B.indices[3 * k + 1]]), p0), e2 = t_sub(t_arr(&B.vertices[4 * (size_t)B.indices[3 * k + 2]]), p0);
+                    const T3 h = t_cross(ld, e2);
+                    const float a = t_dot(e1, h);
+                    if (std::fabs(a) < 1e-6f) continue;
+                    const float f = 1.0f / a;
+                    const T3 s = t_sub(o, p0);
+                    const float u = f * t_dot(s, h);
+                    if (!(u >= 0.0f && u <= 1.0f)) continue;
+                    const T3 q = t_cross(s, e1);
+                    const float v = f * t_dot(ld, q);
+                    if (v < 0.0f || u + v > 1.0f) continue;
+                    const float t = f * t_dot(e2, q);
+                    if (t > 1e-4f && t < best_t) best_t = t, bu = u, bv = v, hit = &tb, htri = k;
+                }
+            }
+            if (!hit) break;   // a miss adds nothing and ends the path
+            const Batch3D &B = *hit->b;
+            const float w = (1.0f - bu) - bv;
+            const uint32_t i0 = B.indices[3 * htri], i1 = B.indices[3 * htri + 1], i2 = B.indices[3 * htri + 2];
+            const float uvhx = (w * B.uvs[2 * i0] + bu * B.uvs[2 * i1]) + bv * B.uvs[2 * i2];
+            const float uvhy = (w * B.uvs[2 * i0 + 1] + bu * B.uvs[2 * i1 + 1]) + bv * B.uvs[2 * i2 + 1];
+            const T3 n0 = t_arr(&B.normals[3 * i0]), n1 = t_arr(&B.normals[3 * i1]), n2 = t_arr(&B.normals[3 * i2]);
+            T3 n = t_normalized({(n0.x * w + n1.x * bu) + n2.x * bv, (n0.y * w + n1.y * bu) + n2.y * bv, (n0.z * w + n1.z * bu) + n2.z * bv});
+            if (t_dot(n, d) > 0.0f) n = {-n.x, -n.y, -n.z};
+            const T3 world = t_add(o, t_scale(d, best_t));
+            // evaluate_hit (trace.rs:377-475)
+            uint32_t px[3] = {0u, 0u, 0u};
+            const PixelSource &src = B.source_;
+            if (src.kind == RXR_SOURCE_PIXEL) {
+                for (int c = 0; c < 3; ++c) px[c] = src.pixel[c];
+            } else if (src.kind == RXR_SOURCE_STATIC_TILE || src.kind == RXR_SOURCE_DYNAMIC_TILE) {
+                const Tile &tile = src.kind == RXR_SOURCE_STATIC_TILE ? assets->tile_list[src.index] : scene->dynamic_textures[src.index];
+                t_sample(tile.textures[scene->animation_frame % tile.textures.size()], uvhx, uvhy, sample_mode, B.repeat_mode_, px);
+            } else if (src.kind == RXR_SOURCE_TERRAIN && hit->chunk && hit->chunk->has_terrain_texture) {   // chunk.rs:133-151
+                const Chunk &C = *hit->chunk;
+                const Texture &tex = C.terrain_texture;
+                const float ppt = (float)((int32_t)tex.width / C.size);
+                const float pixel_x = ((world.x / 1.0f) - (float)C.origin[0]) * ppt, pixel_y = ((world.z / 1.0f) - (float)C.origin[1]) * ppt;
+                const uint32_t tx = std::min(t_as_u32(t_clamp(std::floor(pixel_x), 0.0f, (float)tex.width - 1.0f)), tex.width - 1u);
+                const uint32_t ty = std::min(t_as_u32(t_clamp(std::floor(pixel_y), 0.0f, (float)tex.height - 1.0f)), tex.height - 1u);
+                for (int c = 0; c < 3; ++c) px[c] = tex.data[((size_t)ty * tex.width + tx) * 4 + c];
+            }
+            const T3 tex_lin = {srgb[px[0]], srgb[px[1]], srgb[px[2]]};
+            float specular_weight = 0.0f;
+            T3 emissive{0.0f, 0.0f, 0.0f};
+            if (B.has_material) {
+                const float inv = 1.0f / 255.0f;
+                const float value = t_modify(B.material_modifier, {(float)px[0] * inv, (float)px[1] * inv, (float)px[2] * inv}, B.material_value);
+                if (B.material_role == 0) specular_weight = 1.0f - value;
+                else if (B.material_role == 1 || B.material_role == 2) specular_weight = value;
+                else if (B.material_role == 4) emissive = t_scale(t_scale(tex_lin, B.material_value), 10.0f);
+            }
+            const T3 albedo = tex_lin;
+            if (emissive.x != 0.0f || emissive.y != 0.0f || emissive.z != 0.0f) {
+                ret = t_add(ret, t_mul(emissive, thr));
+                break;
+            }
+            T3 direct{0.0f, 0.0f, 0.0f};
+            for (const rxr_light &l : lights) {
+                T3 lc;
+                if (t_radiance(l, world, n, hash_anim, lc)) direct = t_add(direct, t_scale(lc, 10.0f));
+            }
+            ret = t_add(ret, t_mul(direct, t_mul(thr, t_div(albedo, T_PI))));
+            const uint32_t slot = 2u + 4u * bounce;
+            const float r_spec = rxr_trace_rand(seed, frame, i, slot), r1 = rxr_trace_rand(seed, frame, i, slot + 1u);
+            const float r2 = rxr_trace_rand(seed, frame, i, slot + 2u), r_roulette = rxr_trace_rand(seed, frame, i, slot + 3u);
+            const float p_spec = t_clamp(specular_weight, 0.0f, 1.0f), p_diff = 1.0f - p_spec;
+            const bool choose_spec = r_spec < p_spec;
+            const float pdf = choose_spec ? p_spec : p_diff;
+            T3 nd;
+            if (choose_spec) {
+                nd = t_sub(d, t_scale(n, 2.0f * t_dot(d, n)));
+                thr = t_scale(thr, specular_weight / pdf);
+            } else {   // sample_cosine (trace.rs:493-512)
+                const float phi = (2.0f * T_PI) * r1, r = std::sqrt(r2);
+                const T3 local = {std::cos(phi) * r, std::sin(phi) * r, std::sqrt(1.0f - r2)};
+                const T3 a = std::fabs(n.x) > 0.1f ? T3{0.0f, 1.0f, 0.0f} : T3{1.0f, 0.0f, 0.0f};
+                const T3 v = t_normalized(t_cross(n, a)), u = t_cross(v, n);
+                nd = t_normalized(t_add(t_add(t_scale(u, local.x), t_scale(v, local.y)), t_scale(n, local.z)));
+                thr = t_mul(thr, t_div(t_scale(albedo, p_diff), pdf * T_PI));
+            }
+            o = t_add(t_add(o, t_scale(nd, best_t)), t_scale(n, 0.01f));   // ray.at(t) along the NEW direction (trace.rs:301-309)
+            d = nd;
+            const float p = t_clamp(std::fmax(thr.x, std::fmax(thr.y, thr.z)), 0.001f, 1.0f);
+            if (r_roulette > p) break;
+            thr = t_scale(thr, 1.0f / p);
+        }
+        return ret;
+    }
+};
+}  // namespace
+
+std::vector<uint8_t> AccumBuffer::to_u8_vec() const {
+    std::vector<uint8_t> out(pixels.size());
+    auto as_u8 = [](float x) { return (uint8_t)std::min(t_as_u32(x), 255u); };
+    for (size_t i = 0; i < pixels.size(); ++i) {
+        const float x = pixels[i];
+        if (i % 4 == 3) {
+            out[i] = as_u8(t_clamp(x, 0.0f, 1.0f) * 255.0f + 0.5f);
+        } else {
+            const float srgb = x <= 0.0031308f ? x * 12.92f : 1.055f * std::pow(x, 1.0f / 2.4f) - 0.055f;
+            out[i] = as_u8(t_clamp(srgb, 0.0f, 1.0f) * 255.0f + 0.5f);
+        }
+    }
+    return out;
+}
+
+int Tracer::trace(uint32_t camera_kind, const float *camera, const Scene &scene, AccumBuffer &accum, const Assets &assets, uint32_t n_frames,
+                  uint32_t seed, uint32_t bounces, bool cpu, unsigned threads) const {
+    if (!camera || !accum.width || !accum.height || accum.pixels.size() != accum.width * accum.height * 4 || !n_frames || camera_kind > RXR_TRACE_CAMERA_ISO) {
+        g_error = "Tracer::trace: NULL camera, an unknown camera kind, an empty buffer or no frames";
+        return RXR_ERR_INVALID;
+    }
+    if (bounces > RXR_TRACE_MAX_BOUNCES) {
+        g_error = "Tracer::trace: more than RXR_TRACE_MAX_BOUNCES bounces";
+        return RXR_ERR_UNSUPPORTED;
+    }
+    std::vector<rxr_light> lights(scene.lights);
+    lights.insert(lights.end(), scene.dynamic_lights.begin(), scene.dynamic_lights.end());
+    if (cpu) {
+        CpuTrace T{};
+        T.kind = camera_kind, T.width = (uint32_t)accum.width, T.height = (uint32_t)accum.height, T.seed = seed, T.bounces = bounces;
+        T.sample_mode = sample_mode;
+        uint32_t h = (uint32_t)scene.animation_frame;   // hash_u32 (trace.rs:119-128)
+        h = (h ^ 61u) ^ (h >> 16), h = h + (h << 3), h ^= h >> 4, h = h * 0x27d4eb2du, h ^= h >> 15;
+        T.hash_anim = h;
+        T.pos = t_arr(camera), T.fwd = t_arr(camera + 3), T.right = t_arr(camera + 6), T.up = t_arr(camera + 9);
+        T.half_w = camera[12], T.half_h = camera[13];
+        T.scene = &scene, T.assets = &assets, T.lights = lights;
+        (void)rxr_trace_srgb_table(nullptr, T.srgb);
+        auto add = [&](const Batch3D &b, const Chunk *c) -> bool {
+            if (b.triangle_count() && b.normals.size() / 3 < b.vertex_count()) return false;
+            if (b.source_.kind == RXR_SOURCE_STATIC_TILE || b.source_.kind == RXR_SOURCE_DYNAMIC_TILE) {
+                const std::vector<Tile> &tiles = b.source_.kind == RXR_SOURCE_STATIC_TILE ? assets.tile_list : scene.dynamic_textures;
+                if (b.triangle_count() && (b.source_.index >= tiles.size() || tiles[b.source_.index].textures.empty())) return false;
+            }
+            if (b.source_.kind == RXR_SOURCE_TERRAIN && c && c->has_terrain_texture && c->size < 1) return false;
+            T.batches.push_back({&b, c});
+            return true;
+        };
+        bool ok = true;
+        for (const Chunk &c : scene.chunks) {   // (the opacity and overlay lists take no part)
+            for (const Batch3D &b : c.batches3d) ok = ok && add(b, &c);
+            for (const Batch3D &b : c.terrain_batch3d) ok = ok && add(b, &c);
+        }
+        for (const Batch3D &b : scene.d3_static) ok = ok && add(b, nullptr);
+        for (const Batch3D &b : scene.d3_dynamic) ok = ok && add(b, nullptr);
+        if (!ok) {
+            g_error = "Tracer::trace: a batch without normals, with a tile that does not exist or in a chunk of size 0 (the reference panics)";
+            return RXR_ERR_INVALID;
+        }
+        const uint32_t n = T.width * T.height;
+        unsigned nt = threads ? threads : std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+        nt = std::max(1u, std::min(nt, n));
+        for (uint32_t k = 0; k < n_frames; ++k) {
+            const uint32_t frame = (uint32_t)accum.frame;
+            const float t = 1.0f / ((float)accum.frame + 1.0f), keep = 1.0f - t;
+            auto rows = [&](unsigned worker) {
+                for (uint32_t i = worker; i < n; i += nt) {   // (interleaved: neighbouring pixels cost alike)
+                    const T3 ret = T.sample(i, frame);
+                    float *p = &accum.pixels[4 * (size_t)i];
+                    p[0] = p[0] * keep + ret.x * t, p[1] = p[1] * keep + ret.y * t, p[2] = p[2] * keep + ret.z * t, p[3] = p[3] * keep + 1.0f * t;
+                }
+            };
+            std::vector<std::thread> pool;
+            for (unsigned w = 1; w < nt; ++w) pool.emplace_back(rows, w);
+            rows(0);
+            for (std::thread &th : pool) th.join();
+            accum.frame += 1;
+        }
+        return RXR_OK;
+    }
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::string err;
+    rxr_ctx *ctx = context(&err);
+    if (!ctx) return RXR_ERR_NO_DEVICE;
+    // the tiles and the 3D batches, as Rasterizer::upload registers them
+    SequenceSlots slots;
+    std::vector<const Tile *> dyn_tiles;
+    for (const Tile &t : scene.dynamic_textures) dyn_tiles.push_back(&t);
+    for (int pass = 0; pass < 2; ++pass)
+        for (const auto &kv : pass == 0 ? assets.entity_tiles : assets.item_tiles)
+            for (size_t k = 0; k < kv.second.size(); ++k) {
+                (pass == 0 ? slots.entity : slots.item)[{kv.first, (uint32_t)k}] = (uint32_t)dyn_tiles.size();
+                dyn_tiles.push_back(&kv.second[k]);
+            }
+    if (g_tex_static_gen != assets.generation || g_tex_dynamic_gen != scene.dynamic_textures_generation) {
+        std::vector<rxr_texture> ts, td;
+        std::vector<rxr_tile> tiles_s, tiles_d;
+        tile_views(assets.tile_list, ts, tiles_s);
+        size_t nd = 0;
+        for (const Tile *t : dyn_tiles) nd += t->textures.size();
+        td.reserve(nd);
+        for (const Tile *t : dyn_tiles) {
+            rxr_tile rt{};
+            rt.textures = td.data() + td.size();
+            rt.n_textures = (uint32_t)t->textures.size();
+            for (const Texture &x : t->textures) td.push_back(rxr_texture{x.data.data(), x.width, x.height});
+            tiles_d.push_back(rt);
+        }
+        const int rc = rxr_set_textures(ctx, tiles_s.data(), (uint32_t)tiles_s.size(), tiles_d.data(), (uint32_t)tiles_d.size());
+        if (rc != RXR_OK) {
+            g_error = rxr_last_error(ctx);
+            return rc;
+        }
+        g_tex_static_gen = assets.generation;
+        g_tex_dynamic_gen = scene.dynamic_textures_generation;
+    }
+    std::vector<rxr_mesh3d> meshes;
+    uint64_t full = 0, geometry = 0;
+    if (!scene_meshes(scene, &slots, meshes, nullptr, full, geometry)) {
+        g_error = "Tracer::trace: a batch with triangles but without normals cannot be registered (rxr_set_meshes)";
+        return RXR_ERR_INVALID;
+    }
+    if (full != g_mesh_fingerprint || !g_mesh_fingerprint) {
+        const int rc = register_meshes(ctx, meshes, full, geometry);
+        if (rc != RXR_OK) return rc;
+    }
+    std::vector<uint32_t> kinds;
+    std::vector<float> values;
+    for (const Batch3D *b : scene.batches3d_in_order()) {
+        kinds.push_back(b->has_material ? b->material_role : RXR_TRACE_NO_MATERIAL);
+        kinds.push_back(b->has_material ? b->material_modifier : 0u);
+        values.push_back(b->material_value);
+    }
+    std::vector<int32_t> chunk_rec;
+    for (const Chunk &c : scene.chunks) chunk_rec.insert(chunk_rec.end(), {c.origin[0], c.origin[1], c.size});
+    int rc = rxr_set_trace_scene(ctx, kinds.data(), values.data(), (uint32_t)meshes.size(), lights.data(), (uint32_t)lights.size(), sample_mode,
+                                 (uint64_t)scene.animation_frame, chunk_rec.data(), (uint32_t)scene.chunks.size());
+    if (rc == RXR_OK) rc = rxr_trace(ctx, camera_kind, camera, (uint32_t)accum.width, (uint32_t)accum.height, (uint32_t)accum.frame, n_frames, seed, bounces, accum.pixels.data());
+    if (rc != RXR_OK) {
+        g_error = rxr_last_error(ctx);
+        return rc;
+    }
+    accum.frame += n_frames;
+    return RXR_OK;
 }
 
 // ---- Terrain --------------------------------------------------------------------------------------

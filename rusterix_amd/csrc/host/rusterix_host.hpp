@@ -165,6 +165,10 @@ public:
     int shader_ = -1;
     bool has_profile_id = false;
     uint32_t profile_id_ = 0;
+    // Option<Material> (src/shapestack/material.rs:115-121; only the path tracer reads it): role and modifier as their to_u8 / from_u8 numbers
+    bool has_material = false;
+    uint32_t material_role = 0, material_modifier = 0;
+    float material_value = 1.0f;
     // geometry stamp for the device-projection cache: re-stamped by every mutator below; code that edits the
     // public vectors directly calls touch().  Copies keep the stamp (same content).
     uint64_t geometry_stamp = next_generation();
@@ -301,6 +305,34 @@ public:
     // uploaded in between: the bytes are gone, build the chunk again).
     int refresh_chunk_textures();
 };
+// src/tracer/buffer.rs: linear RGBA f32, [height][width][4], and the number of frames averaged into it
+class AccumBuffer {
+public:
+    size_t width = 0, height = 0, frame = 0;
+    std::vector<float> pixels;
+    AccumBuffer(size_t w, size_t h) : width(w), height(h), pixels(w * h * 4, 0.0f) {}
+    void reset() { frame = 0; }
+    std::vector<uint8_t> to_u8_vec() const;   // :78-91, on the host (std::pow)
+};
+
+// src/tracer/trace.rs: the path tracer over a Scene.  trace() runs n_frames samples a pixel on the device (rxr_set_trace_scene +
+// rxr_trace, include/rxr.h): it registers the scene's textures and 3D batches as Rasterizer::upload and Scene::intersect do, hands
+// over every batch's material, scene.lights chained with scene.dynamic_lights and the chunks' origin and size, and advances
+// accum.frame.  `camera`: RXR_TRACE_CAMERA_* and the RXR_TRACE_CAMERA_FLOATS floats the camera's create_ray computes before it looks
+// at the pixel.  cpu == true: the same loop on host threads (threads == 0: one per core, at most 16) with the library's generator
+// (rxr_trace_rand) and sRGB table (rxr_trace_srgb_table), no device needed -- every float equals the device's until a path's first
+// diffuse bounce, where cos and sin are the host's.  A terrain-sourced batch samples the chunk's host terrain_texture there; on the
+// device it needs the registration of Scene::resident_chunk_textures (else RXR_ERR_UNSUPPORTED).  A miss adds nothing (no render
+// graph); `background` is kept for API parity only, as in the reference, where nothing reads it.  Returns RXR_OK or a negative rxr_status.
+class Tracer {
+public:
+    uint32_t sample_mode = RXR_SAMPLE_NEAREST;
+    bool has_background = false;
+    uint8_t background[4] = {0, 0, 0, 0};
+    int trace(uint32_t camera_kind, const float *camera, const Scene &scene, AccumBuffer &accum, const Assets &assets, uint32_t n_frames,
+              uint32_t seed, uint32_t bounces = RXR_TRACE_MAX_BOUNCES, bool cpu = false, unsigned threads = 0) const;
+};
+
 // how many times Rasterizer::upload has called rxr_set_chunk_textures with textures (tests: an unchanged scene registers nothing)
 uint64_t chunk_texture_registrations();
 

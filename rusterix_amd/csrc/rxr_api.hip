@@ -180,7 +180,7 @@ void rxr_destroy(rxr_ctx *ctx) {
                       &ctx->d_list2d, &ctx->d_large2d,
                       &ctx->d_list, &ctx->d_large, &ctx->d_counters, &ctx->d_fb,
                       &ctx->d_vm_code, &ctx->d_programs, &ctx->d_patterns, &ctx->d_pattern_data, &ctx->d_palette,
-                      &ctx->d_isect_tris, &ctx->d_isect_misc, &ctx->d_isect_keys,
+                      &ctx->d_isect_tris, &ctx->d_isect_misc, &ctx->d_isect_keys, &ctx->d_trace_scene, &ctx->d_trace_paths, &ctx->d_trace_keys,
                       &ctx->d_bake_jobs, &ctx->d_bake_fault,
                       &ctx->d_terrain_cells, &ctx->d_terrain_tex, &ctx->d_terrain_texels, &ctx->d_terrain_weights,
                       &ctx->d_heights, &ctx->d_heights_tk, &ctx->d_heights_mask, &ctx->d_gen, &ctx->d_excl, &ctx->d_excl_scratch, &ctx->ctex.pool, &ctx->ctex.flags};
@@ -225,6 +225,7 @@ int rxr_set_textures(rxr_ctx *ctx, const rxr_tile *static_tiles, uint32_t n_stat
         int qrc = rxr_quiesce(ctx);  // a render (possibly on the caller's stream) may still read the old texels
         if (qrc != RXR_OK) return qrc;
     }
+    ctx->trace_set = false;  // (rxr_trace.hip: its mesh records name textures of the old set)
     ctx->h_tex.clear();
     ctx->tiles_static.clear();
     ctx->tiles_dynamic.clear();
@@ -301,6 +302,7 @@ int rxr_set_meshes(rxr_ctx *ctx, const rxr_mesh3d *meshes, uint32_t n_meshes) {
     ctx->has_frame = false;
     ctx->meshes_valid = false;  // (rxr_intersect.hip: until this call completes)
     ctx->isect_ready = false;
+    ctx->trace_set = false;
     size_t vin = 0, tin = 0, vout = 0, tout = 0;
     for (uint32_t i = 0; i < n_meshes; ++i) {
         const rxr_mesh3d &m = meshes[i];

@@ -238,6 +238,7 @@ int rxr_set_chunk_textures(rxr_ctx *ctx, const rxr_texture *textures, uint32_t n
         T.shader_first.clear();
         T.shader_slots.clear();
         ctx->has_frame = false;
+        ctx->trace_set = false;   // (rxr_trace.hip: its terrain records name slots of the pool)
         return RXR_OK;
     }
     // a pool of its own first: until everything has succeeded the previous registration stays as it was
@@ -280,6 +281,7 @@ int rxr_set_chunk_textures(rxr_ctx *ctx, const rxr_texture *textures, uint32_t n
     T.shader_first.assign(chunk_shader_first, chunk_shader_first + n_chunks + 1);
     T.shader_slots.assign(chunk_shader_slots, chunk_shader_slots + (chunk_shader_first[n_chunks] ? chunk_shader_first[n_chunks] : 0u));
     T.set = true;
+    ctx->trace_set = false;
     ctx->has_frame = false;   // (the resident frame names the frame blob's texels, or the pool that was just freed)
     return RXR_OK;
 }

@@ -40,6 +40,7 @@ enum : uint32_t {
     Q_MESH_UPDATE,   // rxr_update_meshes: the staged copies of the caller's host arrays (both forms block; the lane orders nothing else)
     Q_CHUNK_TEX,     // rxr_set_chunk_textures / rxr_update_chunk_textures: the staged copies of the caller's host texels (all forms block)
     Q_EXCL,          // rxr_generated_meshes_to: the resident generator records, the resident excluded sectors and the call scratch
+    Q_TRACE,         // rxr_trace_to: the trace scene, the path state and its keys (it takes Q_ISECT as well: the triangle records)
     Q_LANES
 };
 #define RXR_MAX_TILE_ROWS 2048u   // frames of at most 32768 rows
@@ -268,6 +269,15 @@ struct rxr_ctx {
     bool isect_ready = false;        // d_isect_tris / d_isect_misc describe the current meshes (rxr_set_meshes clears it)
     uint32_t isect_nseg = 0, isect_stride = 0;
     size_t isect_off_pid = 0;        // words into d_isect_misc
+
+    // path tracing (rxr_trace.hip): buffers of its own, like the intersect's.  d_trace_scene: the blob of rxr_set_trace_scene -- the
+    // segment table over the participating meshes, one record per mesh (texel source, repeat mode, material), the lights, the
+    // sRGB table and one record per terrain-sourced mesh (trace_off: their byte offsets); d_trace_paths: per pixel origin, direction, throughput, radiance and the live flag;
+    // d_trace_keys: per ray and segment the (t, triangle) minimum of a batch of rays.
+    DevBuf d_trace_scene, d_trace_paths, d_trace_keys;
+    bool trace_set = false;          // d_trace_scene describes the current meshes and textures (rxr_set_meshes / rxr_set_textures / rxr_set_chunk_textures clear it)
+    size_t trace_off[5] = {};
+    uint32_t trace_nseg = 0, trace_n_lights = 0, trace_sample_mode = 0, trace_hash_anim = 0;
 
     // shader-texture bakes (rxr_bake.hip): buffers of their own, like the intersect's -- a bake touches neither the frame state nor the
     // compiled programs.  d_bake_jobs: the program index per bake of the launches in flight (a ring of bake_jobs_cap words, filled

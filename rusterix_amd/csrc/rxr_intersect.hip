@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "../../include/rusterix_vek.hpp"  // (RXR_VEK_FUSED_MATVEC: the screen rays' Mat4 * Vec4 follows the host's choice)
+#include "rxr_isect.h"
 #include "rxr_query.h"
 
 namespace {
@@ -71,33 +72,7 @@ struct IsectArgs {
     unsigned long long *keys;          // [rays of the batch][nseg]
 };
 
-struct F3 {
-    float x, y, z;
-};
-__device__ __forceinline__ F3 sub3(F3 a, F3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ float dot3(F3 a, F3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ F3 cross3(F3 a, F3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ F3 normalized3(F3 a) {
-    const float m = sqrtf(dot3(a, a));
-    return {a.x / m, a.y / m, a.z / m};
-}
-__device__ __forceinline__ F3 load3(const float *p, uint64_t i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
-
-// Batch3D::intersect's test of one triangle (batch3d.rs:870-897); true: accepted, with its t (and u, v)
-__device__ __forceinline__ bool mt_test(F3 o, F3 d, F3 p0, F3 e1, F3 e2, float &t, float &u, float &v) {
-    const F3 h = cross3(d, e2);
-    const float a = dot3(e1, h);
-    if (fabsf(a) < 1e-6f) return false;
-    const float f = 1.0f / a;
-    const F3 s = sub3(o, p0);
-    u = f * dot3(s, h);
-    if (!(u >= 0.0f && u <= 1.0f)) return false;
-    const F3 q = cross3(s, e1);
-    v = f * dot3(d, q);
-    if (v < 0.0f || u + v > 1.0f) return false;
-    t = f * dot3(e2, q);
-    return t > 1e-4f;
-}
+using namespace isect;   // F3 and its vek arithmetic, mt_test (Batch3D::intersect's triangle test), last_le: rxr_isect.h
 
 __device__ __forceinline__ void load_tri(const IsectArgs &A, uint32_t g, F3 &p0, F3 &e1, F3 &e2) {
     const float *p = A.tris + g;
@@ -107,15 +82,6 @@ __device__ __forceinline__ void load_tri(const IsectArgs &A, uint32_t g, F3 &p0,
     e2 = {p[6 * s], p[7 * s], p[8 * s]};
 }
 
-// last index i in [lo, hi) with a[i] <= x (a non-decreasing, a[lo] <= x)
-__device__ __forceinline__ uint32_t last_le(const uint32_t *a, uint32_t lo, uint32_t hi, uint32_t x) {
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (a[mid] <= x) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 __device__ __forceinline__ uint32_t seg_of(const IsectArgs &A, uint32_t g) {
     uint32_t lo = 0, hi = A.nseg;
     while (hi - lo > 1) {
@@ -386,22 +352,15 @@ int isect_prepare(rxr_ctx *ctx, hipStream_t s) {
     return RXR_OK;
 }
 
-// the whole intersect on device arrays, queued on `s`
-int isect_run(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n, uint32_t flags, const IsectOut &out, hipStream_t s) {
-    if (!ctx->meshes_valid) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_intersect: the last rxr_set_meshes failed: no meshes are registered");
-    int rc = rxr_query_begin(ctx, ctx->lane[Q_ISECT], s);  // (the scratch of an intersect on another stream)
-    if (rc != RXR_OK || (rc = isect_prepare(ctx, s)) != RXR_OK) return rc;
-    const uint32_t ntri = ctx->PP.n_tris_in, nseg = ctx->isect_nseg;
-    uint32_t per_batch = n;
-    if (nseg && (uint64_t)n * nseg > ISECT_KEYS_MAX)
-        per_batch = (uint32_t)std::max<uint64_t>(ISECT_WG, ISECT_KEYS_MAX / nseg / ISECT_WG * ISECT_WG);
-    if ((rc = rxr_ensure(ctx, ctx->d_isect_keys, std::max<size_t>((size_t)std::min(per_batch, n) * nseg * 8, 256))) != RXR_OK) return rc;
+// the kernels' view of the resident records, over the segment table `segs` (the mesh_pid words are the picking table's: only
+// k_isect_fold reads them)
+IsectArgs isect_args(rxr_ctx *ctx, const void *segs, uint32_t nseg, const float *origins, const float *dirs, unsigned long long *keys) {
     IsectArgs A{};
-    A.ntri = ntri;
+    A.ntri = ctx->PP.n_tris_in;
     A.nseg = nseg;
     A.stride = ctx->isect_stride;
     A.tris = (const float *)ctx->d_isect_tris.p;
-    A.segs = (const IsectSeg *)ctx->d_isect_misc.p;
+    A.segs = (const IsectSeg *)segs;
     A.mesh_pid = (const uint32_t *)ctx->d_isect_misc.p + ctx->isect_off_pid;
     A.tin_prefix = ctx->PP.tin_prefix;
     A.vin_prefix = ctx->PP.vin_prefix;
@@ -411,27 +370,45 @@ int isect_run(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n,
     A.obj_normals = ctx->PP.obj_normals;
     A.origins = origins;
     A.dirs = dirs;
-    A.keys = (unsigned long long *)ctx->d_isect_keys.p;
+    A.keys = keys;
+    return A;
+}
+
+// the keys of rays r0 .. r0 + nr (A.keys holds at least nr * nseg of them), queued on `s`
+int isect_closest(rxr_ctx *ctx, const IsectArgs &A, uint32_t r0, uint32_t nr, hipStream_t s) {
+    const uint32_t ntri = A.ntri;
+    if (!ntri || !A.nseg || !nr) return RXR_OK;
+    HIPCHK(ctx, hipMemsetAsync(A.keys, 0xFF, (size_t)nr * A.nseg * 8, s));
+    if (nr <= ISECT_FEW_RAYS) {
+        const dim3 grid((ntri + ISECT_WG - 1) / ISECT_WG, (nr + ISECT_RAYS_PER_Y - 1) / ISECT_RAYS_PER_Y);
+        hipLaunchKernelGGL(k_isect_by_tri, grid, dim3(ISECT_WG), 0, s, A, r0, nr);
+    } else {
+        // enough workgroups to fill the device: split the triangle range when the rays alone do not
+        const uint32_t ray_groups = (nr + ISECT_WG - 1) / ISECT_WG;
+        const uint32_t max_slices = std::max(1u, (ntri + 1023u) / 1024u);
+        const uint32_t slices = std::min(max_slices, std::max(1u, (4096u + ray_groups - 1) / ray_groups));
+        const uint32_t slice = (ntri + slices - 1) / slices;
+        const dim3 grid(ray_groups, (ntri + slice - 1) / slice);
+        hipLaunchKernelGGL(k_isect_by_ray, grid, dim3(ISECT_WG), 0, s, A, r0, nr, slice);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    return RXR_OK;
+}
+
+// the whole intersect on device arrays, queued on `s`
+int isect_run(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n, uint32_t flags, const IsectOut &out, hipStream_t s) {
+    if (!ctx->meshes_valid) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_intersect: the last rxr_set_meshes failed: no meshes are registered");
+    int rc = rxr_query_begin(ctx, ctx->lane[Q_ISECT], s);  // (the scratch of an intersect on another stream)
+    if (rc != RXR_OK || (rc = isect_prepare(ctx, s)) != RXR_OK) return rc;
+    const uint32_t nseg = ctx->isect_nseg;
+    const uint32_t per_batch = rxr_isect_batch_rays(n, nseg);
+    if ((rc = rxr_ensure(ctx, ctx->d_isect_keys, std::max<size_t>((size_t)std::min(per_batch, n) * nseg * 8, 256))) != RXR_OK) return rc;
+    IsectArgs A = isect_args(ctx, ctx->d_isect_misc.p, nseg, origins, dirs, (unsigned long long *)ctx->d_isect_keys.p);
     IsectOut O = out;
     O.full = (flags & RXR_INTERSECT_FULL) ? 1u : 0u;
     for (uint32_t r0 = 0; r0 < n; r0 += per_batch) {
         const uint32_t nr = std::min(per_batch, n - r0);
-        if (ntri && nseg) {
-            HIPCHK(ctx, hipMemsetAsync(A.keys, 0xFF, (size_t)nr * nseg * 8, s));
-            if (nr <= ISECT_FEW_RAYS) {
-                const dim3 grid((ntri + ISECT_WG - 1) / ISECT_WG, (nr + ISECT_RAYS_PER_Y - 1) / ISECT_RAYS_PER_Y);
-                hipLaunchKernelGGL(k_isect_by_tri, grid, dim3(ISECT_WG), 0, s, A, r0, nr);
-            } else {
-                // enough workgroups to fill the device: split the triangle range when the rays alone do not
-                const uint32_t ray_groups = (nr + ISECT_WG - 1) / ISECT_WG;
-                const uint32_t max_slices = std::max(1u, (ntri + 1023u) / 1024u);
-                const uint32_t slices = std::min(max_slices, std::max(1u, (4096u + ray_groups - 1) / ray_groups));
-                const uint32_t slice = (ntri + slices - 1) / slices;
-                const dim3 grid(ray_groups, (ntri + slice - 1) / slice);
-                hipLaunchKernelGGL(k_isect_by_ray, grid, dim3(ISECT_WG), 0, s, A, r0, nr, slice);
-            }
-            HIPCHK(ctx, hipGetLastError());
-        }
+        if ((rc = isect_closest(ctx, A, r0, nr, s)) != RXR_OK) return rc;
         hipLaunchKernelGGL(k_isect_fold, dim3((nr + ISECT_WG - 1) / ISECT_WG), dim3(ISECT_WG), 0, s, A, r0, nr, O);
         HIPCHK(ctx, hipGetLastError());
     }
@@ -439,6 +416,20 @@ int isect_run(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n,
 }
 
 }  // namespace
+
+// ---- rxr_isect.h: the same records and kernels for the path tracer ------------------------------------------------------------
+int rxr_isect_prepare(rxr_ctx *ctx, hipStream_t s) { return isect_prepare(ctx, s); }
+
+uint32_t rxr_isect_batch_rays(uint32_t n_rays, uint32_t nseg) {
+    if (nseg && (uint64_t)n_rays * nseg > ISECT_KEYS_MAX)
+        return (uint32_t)std::max<uint64_t>(ISECT_WG, ISECT_KEYS_MAX / nseg / ISECT_WG * ISECT_WG);
+    return n_rays;
+}
+
+int rxr_isect_closest(rxr_ctx *ctx, const void *dev_segs, uint32_t nseg, const float *dev_origins, const float *dev_dirs, uint32_t r0,
+                      uint32_t nr, unsigned long long *dev_keys, hipStream_t s) {
+    return isect_closest(ctx, isect_args(ctx, dev_segs, nseg, dev_origins, dev_dirs, dev_keys), r0, nr, s);
+}
 
 extern "C" {
 

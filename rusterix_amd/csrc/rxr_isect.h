@@ -1,0 +1,67 @@
+// rxr_isect.h -- what the path tracer (rxr_trace.hip) shares with the ray picking of rxr_intersect.hip: the vek arithmetic and
+// Batch3D::intersect's triangle test as device functions, and the host entry points that build the resident triangle records and run
+// the closest-hit kernels over a segment table of the caller's.  Private to those two files.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+struct rxr_ctx;
+
+namespace isect {
+
+struct F3 {
+    float x, y, z;
+};
+__device__ __forceinline__ F3 sub3(F3 a, F3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ float dot3(F3 a, F3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ F3 cross3(F3 a, F3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ F3 normalized3(F3 a) {
+    const float m = sqrtf(dot3(a, a));
+    return {a.x / m, a.y / m, a.z / m};
+}
+__device__ __forceinline__ F3 load3(const float *p, uint64_t i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
+
+// Batch3D::intersect's test of one triangle (batch3d.rs:870-897); true: accepted, with its t (and u, v)
+__device__ __forceinline__ bool mt_test(F3 o, F3 d, F3 p0, F3 e1, F3 e2, float &t, float &u, float &v) {
+    const F3 h = cross3(d, e2);
+    const float a = dot3(e1, h);
+    if (fabsf(a) < 1e-6f) return false;
+    const float f = 1.0f / a;
+    const F3 s = sub3(o, p0);
+    u = f * dot3(s, h);
+    if (!(u >= 0.0f && u <= 1.0f)) return false;
+    const F3 q = cross3(s, e1);
+    v = f * dot3(d, q);
+    if (v < 0.0f || u + v > 1.0f) return false;
+    t = f * dot3(e2, q);
+    return t > 1e-4f;
+}
+
+// last index i in [lo, hi) with a[i] <= x (a non-decreasing, a[lo] <= x)
+__device__ __forceinline__ uint32_t last_le(const uint32_t *a, uint32_t lo, uint32_t hi, uint32_t x) {
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a[mid] <= x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+}  // namespace isect
+
+// A segment of the closest-hit kernels: six words, global triangles [begin, end) of meshes [mesh0, mesh1), the fold's rule and a
+// profile id.  The segments of a table are in triangle order and cover every registered triangle; a segment is never empty.
+#define RXR_ISECT_SEG_WORDS 6u
+#define RXR_ISECT_NO_HIT (~0ull)
+
+// the (p0, edge1, edge2) records of the current meshes (ctx->d_isect_tris, ctx->isect_stride), built once per rxr_set_meshes; queued
+// on `s` inside the picking lane (the caller has ordered `s` behind it)
+int rxr_isect_prepare(rxr_ctx *ctx, hipStream_t s);
+// the largest number of rays rxr_isect_closest takes at once for a table of nseg segments (a multiple of a workgroup)
+uint32_t rxr_isect_batch_rays(uint32_t n_rays, uint32_t nseg);
+// keys[(r - r0) * nseg + s] for rays r0 .. r0 + nr of origins / dirs [..][3] (device memory): the minimum of (t's bits << 32 | global
+// triangle) over segment s's triangles that Batch3D::intersect accepts, RXR_ISECT_NO_HIT for none -- the kernels of rxr_intersect,
+// with its choice between a thread per triangle and a thread per ray, over the table dev_segs.  Queued on `s`.
+int rxr_isect_closest(rxr_ctx *ctx, const void *dev_segs, uint32_t nseg, const float *dev_origins, const float *dev_dirs, uint32_t r0,
+                      uint32_t nr, unsigned long long *dev_keys, hipStream_t s);

@@ -114,6 +114,16 @@ def rxr_abi():
         "rxr_read_chunk_texture": (i32, [vp, u32, C.POINTER(u32), C.POINTER(u32), vp]),
         "rxr_debug_chunk_tex_constants": (None, [C.POINTER(u32)]),
         "rxr_debug_chunk_tex_launches": (u32, [vp]),
+        "rxr_set_textures": (i32, [vp, vp, u32, vp, u32]),
+        "rxr_set_meshes": (i32, [vp, vp, u32]),
+        "rxr_check_trace_scene": (i32, [vp, vp, u32, vp, u32, u32, C.c_char_p, u32]),
+        "rxr_set_trace_scene": (i32, [vp, vp, vp, u32, vp, u32, u32, C.c_uint64, vp, u32]),
+        "rxr_trace_srgb_table": (i32, [vp, vp]),
+        "rxr_trace_rand": (C.c_float, [u32, u32, u32, u32]),
+        "rxr_trace": (i32, [vp, u32, vp, u32, u32, u32, u32, u32, u32, vp]),
+        "rxr_trace_to": (i32, [vp, u32, vp, u32, u32, u32, u32, u32, u32, vp, vp]),
+        "rxr_accum_to_rgba": (i32, [vp, vp, u32, u32, vp]),
+        "rxr_accum_to_rgba_to": (i32, [vp, vp, u32, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
