@@ -695,6 +695,28 @@ int rxr_intersect_to(rxr_ctx *ctx, const float *dev_origins, const float *dev_di
  * hip_stream (NULL = the context's stream).  Multi-device handles: RXR_ERR_UNSUPPORTED. */
 int rxr_screen_rays_to(rxr_ctx *ctx, const float *inverse_view, const float *inverse_projection, float width, float height,
                        uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, float *dev_origins, float *dev_dirs, void *hip_stream);
+/* Opt-in: cull the many-ray queries (rxr_intersect / _to with more than 64 rays, every round of rxr_trace / _to) with a tree of boxes
+ * that the context builds on the device over the resident triangles (rusterix_amd/csrc/rxr_ray_accel.hip), lazily before the next such
+ * query and again after every rxr_set_meshes / rxr_update_meshes.  Every output word stays what the brute-force kernels write: the
+ * tree only skips triangles whose test would reject the ray, by a padded box test whose margin is measured, not proven (DESIGN.md
+ * section 19).  RXR_RAY_ACCEL_OFF is the default; _COUNT is _ON plus a count of the ray-triangle tests a call runs (a second kernel
+ * instantiation: _ON does not pay for it).  Any other mode: RXR_ERR_INVALID.  Multi-device handles: member 0. */
+#define RXR_RAY_ACCEL_OFF 0u
+#define RXR_RAY_ACCEL_ON 1u
+#define RXR_RAY_ACCEL_COUNT 2u
+int rxr_set_ray_accel(rxr_ctx *ctx, uint32_t mode);
+/* blocking; out[..]: */
+#define RXR_RAY_ACCEL_INFO_MODE 0u        /* RXR_RAY_ACCEL_*                                                              */
+#define RXR_RAY_ACCEL_INFO_VALID 1u       /* 1: the tree describes the current meshes (the four words below: 0 otherwise) */
+#define RXR_RAY_ACCEL_INFO_TRIANGLES 2u
+#define RXR_RAY_ACCEL_INFO_NODES 3u
+#define RXR_RAY_ACCEL_INFO_LEVELS 4u
+#define RXR_RAY_ACCEL_INFO_WILD 5u        /* triangles that are always tested (not finite, or too thin for a box)         */
+#define RXR_RAY_ACCEL_INFO_BUILDS 6u      /* builds since rxr_create                                                      */
+#define RXR_RAY_ACCEL_INFO_BATCHES 7u     /* batches of rays that went through the tree since rxr_create                  */
+#define RXR_RAY_ACCEL_INFO_TESTS 8u       /* ray-triangle tests of the last call under RXR_RAY_ACCEL_COUNT                */
+#define RXR_RAY_ACCEL_INFO_WORDS 9u
+int rxr_ray_accel_info(rxr_ctx *ctx, uint64_t out[RXR_RAY_ACCEL_INFO_WORDS]);
 
 /* ---- running a program over an image: the shader-texture bake (rusterix_amd/csrc/rxr_bake.hip) -------------------------------
  * Rusteria::shade (rusteria/src/lib.rs:161-210) over a width x height RenderBuffer, as Chunk::add_shader runs it at 64 x 64 for

@@ -17,6 +17,8 @@ import numpy as np
 
 # ---- enums (include/rxr.h) ---------------------------------------------------------------------
 SAMPLE_NEAREST, SAMPLE_LINEAR = 0, 1
+RAY_ACCEL_OFF, RAY_ACCEL_ON, RAY_ACCEL_COUNT = 0, 1, 2   # rxr_set_ray_accel's modes (include/rxr.h)
+RAY_ACCEL_INFO = ("mode", "valid", "triangles", "nodes", "levels", "wild", "builds", "batches", "tests")   # rxr_ray_accel_info's words
 REPEAT_CLAMP_XY, REPEAT_REPEAT_XY, REPEAT_REPEAT_X, REPEAT_REPEAT_Y = 0, 1, 2, 3
 MODE_TRIANGLES, MODE_LINES, MODE_LINE_STRIP, MODE_LINE_LOOP = 0, 1, 2, 3
 CULL_OFF, CULL_FRONT, CULL_BACK = 0, 1, 2
@@ -465,6 +467,11 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
     if has_intersect:
         L.scene_intersect = fn("scene_intersect", i32, vp, pf, pf, u32, u32, pf, pu, pu, pf, pf, pf)
         L.rasterizer_screen_ray = fn("rasterizer_screen_ray", None, vp, f32, f32, pf, pf)
+    has_ray_accel = hasattr(lib, prefix + "scene_set_ray_accel")
+    if has_ray_accel:
+        L.scene_set_ray_accel = fn("scene_set_ray_accel", None, vp, u32)
+        L.scene_ray_accel = fn("scene_ray_accel", u32, vp)
+        L.scene_ray_accel_info = fn("scene_ray_accel_info", i32, vp, C.POINTER(C.c_uint64))
 
     # the path tracer (product host library only): Scene.trace, AccumBuffer, Batch3D.material
     has_trace = hasattr(lib, prefix + "scene_trace")
@@ -1019,6 +1026,29 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
             if not has_chunk_textures:
                 raise NotImplementedError(f"{name}: no resident chunk textures in this library")
             L.scene_set_resident_chunk_textures(self._h, 1 if on else 0)
+
+        @property
+        def ray_accel(self):
+            """Scene::ray_accel (opt-in; 0 off, the default; 1 on; 2 on and counting): intersect() with more than 64 rays and trace()
+            cull their ray-triangle tests with a box tree the context builds on the device (rxr_set_ray_accel, include/rxr.h).  The
+            results are the same words."""
+            return int(L.scene_ray_accel(self._h)) if has_ray_accel else 0
+
+        @ray_accel.setter
+        def ray_accel(self, mode):
+            if not has_ray_accel:
+                raise NotImplementedError(f"{name}: no ray box tree in this library")
+            L.scene_set_ray_accel(self._h, int(mode))
+
+        def ray_accel_info(self):
+            """rxr_ray_accel_info of the context as a dict: mode, valid, triangles, nodes, levels, wild, builds, batches, tests"""
+            if not has_ray_accel:
+                raise NotImplementedError(f"{name}: no ray box tree in this library")
+            out = (C.c_uint64 * len(RAY_ACCEL_INFO))()
+            rc = L.scene_ray_accel_info(self._h, out)
+            if rc != 0:
+                raise RasterizeError(rc, last_error())
+            return dict(zip(RAY_ACCEL_INFO, (int(x) for x in out)))
 
         def projected_batch3d(self, list_kind, index, chunk=-1):
             """Outputs of clip_and_project for one batch (after rasterize): dict of numpy arrays."""

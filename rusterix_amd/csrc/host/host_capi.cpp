@@ -149,6 +149,10 @@ void rxh_chunk_add_shader_texture(void *s, int chunk, const uint8_t *rgba, uint3
 // ---- resident chunk textures (Scene::resident_chunk_textures) ----------------------------------------
 void rxh_scene_set_resident_chunk_textures(void *s, int on) { ((Scene *)s)->resident_chunk_textures = on != 0; }
 int rxh_scene_resident_chunk_textures(void *s) { return ((Scene *)s)->resident_chunk_textures ? 1 : 0; }
+// ---- the ray box tree (Scene::ray_accel): RXR_RAY_ACCEL_* ---------------------------------------------
+void rxh_scene_set_ray_accel(void *s, uint32_t mode) { ((Scene *)s)->ray_accel = mode; }
+uint32_t rxh_scene_ray_accel(void *s) { return ((Scene *)s)->ray_accel; }
+int rxh_scene_ray_accel_info(void *s, uint64_t *out) { return ((Scene *)s)->ray_accel_info(out); }
 // Chunk::textures_generation (0 for a bad index) and Chunk::touch_textures
 uint64_t rxh_chunk_textures_generation(void *s, int chunk) {
     Scene *sc = (Scene *)s;

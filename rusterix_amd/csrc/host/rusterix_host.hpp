@@ -300,6 +300,12 @@ public:
     // when a chunk's textures_generation differs from the one registered, when chunks were added or removed, or when another scene's
     // registration is held; a scene with the option off removes a registration it finds.
     bool resident_chunk_textures = false;
+    // Opt-in, off by default (RXR_RAY_ACCEL_OFF): intersect() and Tracer::trace hand the mode to the context (rxr_set_ray_accel,
+    // include/rxr.h), which then culls its many-ray queries with a box tree built on the device over the registered triangles.  The
+    // results are the same words; RXR_RAY_ACCEL_COUNT also counts the ray-triangle tests (ray_accel_info).
+    uint32_t ray_accel = RXR_RAY_ACCEL_OFF;
+    // rxr_ray_accel_info of the context: RXR_RAY_ACCEL_INFO_WORDS words.  RXR_OK or a negative rxr_status.
+    int ray_accel_info(uint64_t *out) const;
     // the host copies of the textures the device holds newer bytes of (Chunk::terrain_texture_stale), read back through
     // rxr_read_chunk_texture.  RXR_OK, or RXR_ERR_INVALID when the context no longer holds this scene's registration (another scene was
     // uploaded in between: the bytes are gone, build the chunk again).

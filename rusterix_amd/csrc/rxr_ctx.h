@@ -270,6 +270,16 @@ struct rxr_ctx {
     uint32_t isect_nseg = 0, isect_stride = 0;
     size_t isect_off_pid = 0;        // words into d_isect_misc
 
+    // the opt-in box tree over the same triangles (rxr_ray_accel.hip; rxr_set_ray_accel).  d_accel_tris / d_accel_perm: the records in
+    // sorted order and each position's global triangle; d_accel_nodes: the levels, leaves first; d_accel_stats: two 64-bit words, the
+    // ray-triangle tests of the last counted call and the wild triangles; d_accel_scratch: the build's keys and the sort's scratch.
+    DevBuf d_accel_tris, d_accel_perm, d_accel_nodes, d_accel_stats, d_accel_scratch;
+    uint32_t accel_mode = 0;         // RXR_RAY_ACCEL_*
+    bool accel_ready = false;        // the tree describes the records of isect_ready (isect_prepare clears it with them)
+    bool accel_stats_zeroed = false;
+    uint32_t accel_ntri = 0, accel_nodes = 0, accel_levels = 0;
+    uint64_t accel_builds = 0, accel_batches = 0;
+
     // path tracing (rxr_trace.hip): buffers of its own, like the intersect's.  d_trace_scene: the blob of rxr_set_trace_scene -- the
     // segment table over the participating meshes, one record per mesh (texel source, repeat mode, material), the lights, the
     // sRGB table and one record per terrain-sourced mesh (trace_off: their byte offsets); d_trace_paths: per pixel origin, direction, throughput, radiance and the live flag;

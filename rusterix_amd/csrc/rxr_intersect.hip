@@ -303,7 +303,9 @@ __global__ __launch_bounds__(ISECT_WG) void k_screen_rays(ScreenRayArgs S) {
 
 // the segments and per-triangle records of the current meshes (once per rxr_set_meshes), queued on `s`
 int isect_prepare(rxr_ctx *ctx, hipStream_t s) {
-    if (ctx->isect_ready) return RXR_OK;
+    const bool want_accel = ctx->accel_mode != RXR_RAY_ACCEL_OFF;   // (the box tree of rxr_ray_accel.hip: built with the records, or when switched on)
+    if (ctx->isect_ready) return want_accel && !ctx->accel_ready ? rxr_ray_accel_build(ctx, s) : RXR_OK;
+    ctx->accel_ready = false;
     const uint32_t n_meshes = (uint32_t)ctx->meshes.size();
     std::vector<uint32_t> &h = ctx->isect_host;
     h.clear();
@@ -349,7 +351,7 @@ int isect_prepare(rxr_ctx *ctx, hipStream_t s) {
         HIPCHK(ctx, hipGetLastError());
     }
     ctx->isect_ready = true;
-    return RXR_OK;
+    return want_accel ? rxr_ray_accel_build(ctx, s) : RXR_OK;
 }
 
 // the kernels' view of the resident records, over the segment table `segs` (the mesh_pid words are the picking table's: only
@@ -379,6 +381,8 @@ int isect_closest(rxr_ctx *ctx, const IsectArgs &A, uint32_t r0, uint32_t nr, hi
     const uint32_t ntri = A.ntri;
     if (!ntri || !A.nseg || !nr) return RXR_OK;
     HIPCHK(ctx, hipMemsetAsync(A.keys, 0xFF, (size_t)nr * A.nseg * 8, s));
+    if (nr > ISECT_FEW_RAYS && rxr_ray_accel_takes(ctx))   // opt-in: the same keys through the box tree
+        return rxr_ray_accel_closest(ctx, A.segs, A.nseg, A.origins, A.dirs, r0, nr, A.keys, s);
     if (nr <= ISECT_FEW_RAYS) {
         const dim3 grid((ntri + ISECT_WG - 1) / ISECT_WG, (nr + ISECT_RAYS_PER_Y - 1) / ISECT_RAYS_PER_Y);
         hipLaunchKernelGGL(k_isect_by_tri, grid, dim3(ISECT_WG), 0, s, A, r0, nr);
@@ -399,7 +403,7 @@ int isect_closest(rxr_ctx *ctx, const IsectArgs &A, uint32_t r0, uint32_t nr, hi
 int isect_run(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n, uint32_t flags, const IsectOut &out, hipStream_t s) {
     if (!ctx->meshes_valid) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_intersect: the last rxr_set_meshes failed: no meshes are registered");
     int rc = rxr_query_begin(ctx, ctx->lane[Q_ISECT], s);  // (the scratch of an intersect on another stream)
-    if (rc != RXR_OK || (rc = isect_prepare(ctx, s)) != RXR_OK) return rc;
+    if (rc != RXR_OK || (rc = isect_prepare(ctx, s)) != RXR_OK || (rc = rxr_ray_accel_begin_call(ctx, s)) != RXR_OK) return rc;
     const uint32_t nseg = ctx->isect_nseg;
     const uint32_t per_batch = rxr_isect_batch_rays(n, nseg);
     if ((rc = rxr_ensure(ctx, ctx->d_isect_keys, std::max<size_t>((size_t)std::min(per_batch, n) * nseg * 8, 256))) != RXR_OK) return rc;

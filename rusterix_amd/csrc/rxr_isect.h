@@ -65,3 +65,22 @@ uint32_t rxr_isect_batch_rays(uint32_t n_rays, uint32_t nseg);
 // with its choice between a thread per triangle and a thread per ray, over the table dev_segs.  Queued on `s`.
 int rxr_isect_closest(rxr_ctx *ctx, const void *dev_segs, uint32_t nseg, const float *dev_origins, const float *dev_dirs, uint32_t r0,
                       uint32_t nr, unsigned long long *dev_keys, hipStream_t s);
+
+// ---- rxr_ray_accel.hip: the opt-in box tree behind rxr_isect_closest's many-ray path (rxr_set_ray_accel, include/rxr.h) -----------
+#ifndef RXR_RAY_ACCEL_LEAF               // (-D: the A-B runs of profiles/ray_accel/README.md)
+#define RXR_RAY_ACCEL_LEAF 8u            // sorted positions per leaf
+#endif
+#ifndef RXR_RAY_ACCEL_WIDTH
+#define RXR_RAY_ACCEL_WIDTH 8u           // nodes per parent
+#endif
+#define RXR_RAY_ACCEL_KAPPA_CAP 4096.0f  // a triangle whose |e1| |e2| / |e1 x e2| is above it is always tested
+#define RXR_RAY_ACCEL_C 4096.0f          // the pad's constant (tests/ray_accel_ref.py measures it; profiles/ray_accel/README.md)
+// the tree over the current meshes, queued on `s` behind the records of rxr_isect_prepare (which calls it while the mode is on)
+int rxr_ray_accel_build(rxr_ctx *ctx, hipStream_t s);
+// does rxr_isect_closest's many-ray path go through the tree?
+bool rxr_ray_accel_takes(const rxr_ctx *ctx);
+// the start of a picking or tracing call: the count of RXR_RAY_ACCEL_COUNT starts again
+int rxr_ray_accel_begin_call(rxr_ctx *ctx, hipStream_t s);
+// rxr_isect_closest's keys for more than a few rays, through the tree
+int rxr_ray_accel_closest(rxr_ctx *ctx, const void *dev_segs, uint32_t nseg, const float *dev_origins, const float *dev_dirs, uint32_t r0,
+                          uint32_t nr, unsigned long long *dev_keys, hipStream_t s);

@@ -505,7 +505,7 @@ int trace_run(rxr_ctx *ctx, const TraceCamera &cam, uint32_t first_frame, uint32
     // the triangle records are the picking lane's, the rest this lane's
     int rc = rxr_query_begin(ctx, ctx->lane[Q_ISECT], s);
     if (rc != RXR_OK || (rc = rxr_query_begin(ctx, ctx->lane[Q_TRACE], s)) != RXR_OK) return rc;
-    if ((rc = rxr_isect_prepare(ctx, s)) != RXR_OK) return rc;
+    if ((rc = rxr_isect_prepare(ctx, s)) != RXR_OK || (rc = rxr_ray_accel_begin_call(ctx, s)) != RXR_OK) return rc;
     const uint32_t nseg = ctx->trace_nseg, ntri = ctx->PP.n_tris_in;
     const uint32_t per_batch = std::max(1u, rxr_isect_batch_rays(n, nseg));
     const size_t n3 = align_up((size_t)n * 12, 256);

@@ -23,6 +23,8 @@ F = np.float32
 CAMERA_FIRSTP, CAMERA_ORBIT, CAMERA_ISO = 0, 1, 2
 NO_MATERIAL = 0xFFFFFFFF
 MAX_BOUNCES = 8
+RAY_ACCEL_OFF, RAY_ACCEL_ON, RAY_ACCEL_COUNT = 0, 1, 2   # rxr_set_ray_accel's modes (include/rxr.h)
+RAY_ACCEL_INFO = ("mode", "valid", "triangles", "nodes", "levels", "wild", "builds", "batches", "tests")   # rxr_ray_accel_info's words
 MATTE, GLOSSY, METALLIC, TRANSPARENT, EMISSIVE = range(5)                       # MaterialRole, src/shapestack/material.rs:8-14
 MOD_NONE, MOD_LUMINANCE, MOD_SATURATION, MOD_INV_LUMINANCE, MOD_INV_SATURATION = range(5)   # MaterialModifier::from_u8, :66-76
 SOURCE_OTHER, SOURCE_STATIC_TILE, SOURCE_DYNAMIC_TILE, SOURCE_PIXEL, SOURCE_TERRAIN = range(5)
@@ -235,6 +237,35 @@ class Tracer:
         cos = np.array([(c["origin"][0], c["origin"][1], c["size"]) for c in chunks] + [(0, 0, 0)], np.int32)
         self._check(self.rxr.rxr_set_trace_scene(self.ctx, kinds.ctypes.data, values.ctypes.data, len(mats), C.cast(arr, C.c_void_p), len(lights),
                                                  int(sample_mode), int(animation_frame), cos.ctypes.data, len(chunks)))
+
+    @property
+    def ray_accel(self):
+        """rxr_set_ray_accel's mode (0 off, the default; 1 on; 2 on and counting): trace() and intersect() with more than 64 rays
+        cull their ray-triangle tests with a box tree built on the device; the results are the same words"""
+        return self.ray_accel_info()["mode"]
+
+    @ray_accel.setter
+    def ray_accel(self, mode):
+        self._check(self.rxr.rxr_set_ray_accel(self.ctx, int(mode)))
+
+    def ray_accel_info(self):
+        """rxr_ray_accel_info as a dict: mode, valid, triangles, nodes, levels, wild, builds, batches, tests"""
+        out = (C.c_uint64 * len(RAY_ACCEL_INFO))()
+        self._check(self.rxr.rxr_ray_accel_info(self.ctx, out))
+        return dict(zip(RAY_ACCEL_INFO, (int(x) for x in out)))
+
+    def intersect(self, origins, dirs, full=False):
+        """rxr_intersect over the meshes of set_meshes: a dict of t, mesh, triangle, hitpoint and, with full=True, uv and normal"""
+        o = np.ascontiguousarray(np.asarray(origins, F).reshape(-1, 3))
+        d = np.ascontiguousarray(np.asarray(dirs, F).reshape(-1, 3))
+        n = len(o)
+        out = dict(t=np.zeros(n, F), mesh=np.zeros(n, np.uint32), triangle=np.zeros(n, np.uint32), hitpoint=np.zeros((n, 3), F))
+        if full:
+            out["uv"], out["normal"] = np.zeros((n, 2), F), np.zeros((n, 3), F)
+        self._check(self.rxr.rxr_intersect(self.ctx, o.ctypes.data, d.ctypes.data, n, 1 if full else 0, out["t"].ctypes.data, out["mesh"].ctypes.data,
+                                           out["triangle"].ctypes.data, out["hitpoint"].ctypes.data, out["uv"].ctypes.data if full else None,
+                                           out["normal"].ctypes.data if full else None))
+        return out
 
     def srgb_table(self):
         out = np.zeros(256, F)

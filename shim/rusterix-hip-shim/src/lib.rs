@@ -84,6 +84,22 @@ pub fn set_light_math(exact: bool) -> bool {
     }
 }
 
+/// Opt-in culling of the device's many-ray queries with a box tree built over the resident triangles (include/rxr.h
+/// `rxr_set_ray_accel`): `on = false` is the library's default.  The queries' results are the same words either way.  Returns false
+/// when there is no device context.
+pub fn set_ray_accel(on: bool) -> bool {
+    let mut guard = STATE.lock().unwrap();
+    let st = guard.get_or_insert_with(Caches::default);
+    if st.ctx.is_none() && !st.tried {
+        st.tried = true;
+        st.ctx = create_context();
+    }
+    match &st.ctx {
+        Some(ctx) => unsafe { rxr_set_ray_accel(ctx.0, if on { RXR_RAY_ACCEL_ON } else { RXR_RAY_ACCEL_OFF }) == RXR_OK },
+        None => false,
+    }
+}
+
 fn fnv(h: &mut u64, bytes: &[u8]) {
     for b in bytes {
         *h = (*h ^ *b as u64).wrapping_mul(1099511628211);
