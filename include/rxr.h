@@ -927,6 +927,50 @@ int rxr_terrain_meshes(rxr_ctx *ctx, const int32_t *chunk_coords /* [n][2] */, u
 int rxr_terrain_meshes_to(rxr_ctx *ctx, const int32_t *chunk_coords, uint32_t n, int32_t chunk_size, uint32_t *dev_counts,
                           float *dev_vertices, uint32_t *dev_indices, float *dev_normals, void *hip_stream);
 
+/* ---- vertex normals: Batch3D::compute_vertex_normals (rusterix_amd/csrc/rxr_normals.hip) ------------------------------------------
+ * The smooth normals of n meshes of ANY topology (src/batch/batch3d.rs:771-809), exact to the bit, in the strided layout
+ * rxr_terrain_meshes[_to] writes and rxr_update_meshes[_to] reads, so the three chain with no repacking: counts [n][2] = vertices,
+ * triangles of mesh i; vertices [n][vertex_stride][4] (w is not read); indices [n][triangle_stride][3], mesh-local; normals
+ * [n][vertex_stride][3].  Every f32 operation once, in the reference's order, nothing fused:
+ *   per triangle t, normal = normalized(cross(p1 - p0, p2 - p0)) -- vek's cross; the dot product left to right, a square root and
+ *   three divisions, all correctly rounded.  Per vertex the sum STARTS AT +0.0 (a lone face normal with a -0.0 component comes out as
+ *   +0.0) and takes the normals of the triangles that name it IN ASCENDING TRIANGLE INDEX; a vertex named twice by one triangle is
+ *   added twice and counted twice.  With count > 0 the normal is normalized(sum / (count as f32)), with count == 0 it is
+ *   (+0.0, +0.0, +0.0).
+ * Kept as it is: a degenerate triangle is 0 / 0 = NaN in all three components and poisons its three vertices (a NaN is a NaN: sign and
+ * payload are the device's); a sum of length zero divides by zero.  Float addition is not associative: the device adds a vertex's
+ * normals in one thread, in that order, without atomics.
+ * Written: exactly the first counts[i][0] normals of mesh i; slots past a mesh's counts are NOT written (and never read).
+ * Two routes, chosen per call from triangle_stride: at or below the bound (RXR_VERTEX_NORMALS_SMALL_MAX in the environment, read at
+ * each call, overrides it; 0 sends everything through the general route; a workgroup holds at most 6825 triangles) one workgroup per
+ * mesh with the triangles in LDS, above it face normals in scratch, one stable sort of the corners by (mesh, vertex) and one thread
+ * per vertex over its segment.  The bytes are the same.  The call is split into launches of a bounded number of triangle and vertex
+ * slots, at least one mesh (RXR_VERTEX_NORMALS_LAUNCH_SLOTS overrides the bound).  Changes no frame, pool, picking or mesh state.
+ * Replaces: Batch3D::compute_vertex_normals, src/batch/batch3d.rs:771-809 (Scene::compute_static_normals / compute_dynamic_normals,
+ * src/scene.rs:203-215, call it per batch). */
+#define RXR_VERTEX_NORMALS_ROUTE_SMALL 1
+#define RXR_VERTEX_NORMALS_ROUTE_GENERAL 2
+/* what rxr_vertex_normals refuses in its counts and indices, without a context: RXR_OK, or RXR_ERR_INVALID and in `message` (cut to
+ * message_capacity, NUL-terminated; may be NULL) the first offending mesh and why -- a count above its stride, an index not below its
+ * mesh's vertex count -- or: NULL counts / indices with non-zero work, byte sizes that overflow. */
+int rxr_check_vertex_normals(const uint32_t *counts, const uint32_t *indices, uint32_t n, uint32_t vertex_stride, uint32_t triangle_stride,
+                             char *message, uint32_t message_capacity);
+/* Host memory, blocking.  Validates before anything is queued: whatever rxr_check_vertex_normals refuses, or NULL vertices / normals
+ * with vertex_stride > 0, is RXR_ERR_INVALID and NOTHING IS WRITTEN.  n == 0 does nothing.  Multi-device handles: member 0. */
+int rxr_vertex_normals(rxr_ctx *ctx, uint32_t n, const uint32_t *counts /* [n][2] vertices, triangles */,
+                       const float *vertices /* [n][VS][4] */, const uint32_t *indices /* [n][TS][3], mesh-local */,
+                       float *normals /* [n][VS][3] */, uint32_t vertex_stride, uint32_t triangle_stride);
+/* the same on DEVICE arrays (each one's first and last byte are checked to be memory of the context's device; 4-byte aligned; an array
+ * of 0 bytes is not looked at), queued on hip_stream (NULL = the context's stream): behind a producer of vertices and before
+ * rxr_update_meshes_to on one stream, no geometry crosses PCIe.  Asynchronous.  The counts are device memory, so this form cannot
+ * refuse after the fact; instead it never reads out of range: a mesh whose counts exceed the strides is SKIPPED WHOLE (none of its
+ * normals are written), a triangle with an index at or above its mesh's vertex count contributes to no vertex.  dev_refused [n] (may
+ * be NULL) receives per mesh the number of triangles refused that way: 0 for a clean mesh, 0xFFFFFFFF for a skipped one.
+ * RXR_ERR_INVALID: a pointer that fails the check, byte sizes that overflow.  Multi-device handles: RXR_ERR_UNSUPPORTED (use rxr_member). */
+int rxr_vertex_normals_to(rxr_ctx *ctx, uint32_t n, const uint32_t *dev_counts, const float *dev_vertices,
+                          const uint32_t *dev_indices, float *dev_normals, uint32_t *dev_refused /* [n], may be NULL */,
+                          uint32_t vertex_stride, uint32_t triangle_stride, void *hip_stream);
+
 /* ---- generated terrain heights: TerrainGenerator::sample_height_at (rusterix_amd/csrc/rxr_terrain_gen.hip) ------------------------
  * The height field the 3D chunk builder and the region server evaluate (src/chunkbuilder/terrain_generator.rs:57-163, :488-509):
  * per point the maximum of a smoothstep cone per control vertex times the map-edge falloff (interpolate_height_at, :650-714,

@@ -544,8 +544,14 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
     if has_mesh_update:
         L.scene_rebuild_terrain_meshes = fn("scene_rebuild_terrain_meshes", i32, vp, vp, C.POINTER(C.c_int32), u32, pu)
 
+    # vertex normals of whole batch lists, on the CPU or the device (product host library only)
+    has_vertex_normals = hasattr(lib, prefix + "scene_compute_normals")
+    if has_vertex_normals:
+        L.scene_compute_normals = fn("scene_compute_normals", i32, vp, i32, i32)
+        L.scene_batch3d_normals = fn("scene_batch3d_normals", i32, vp, i32, i32, u32, pf, u32)
+
     # resident chunk textures (product host library only)
-    has_chunk_textures = hasattr(lib, prefix + "terrain_rebuild_chunk_textures")
+    has_chunk_textures =hasattr(lib, prefix + "terrain_rebuild_chunk_textures")
     if has_chunk_textures:
         L.scene_set_resident_chunk_textures = fn("scene_set_resident_chunk_textures", None, vp, i32)
         L.scene_resident_chunk_textures = fn("scene_resident_chunk_textures", i32, vp)
@@ -1013,6 +1019,35 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
             if rc < 0:
                 raise RasterizeError(rc, last_error())
             return rc
+
+        def _compute_normals(self, dynamic, device, threads):
+            if not has_vertex_normals:
+                raise NotImplementedError(f"{name}: no Scene::compute_*_normals in this library")
+            rc = L.scene_compute_normals(self._h, dynamic, 1 if device else (2 if threads else 0))
+            if rc != 0:
+                raise RasterizeError(rc, last_error())
+            return self
+
+        def compute_static_normals(self, device=False, threads=False):
+            """Scene::compute_static_normals (reference src/scene.rs:203-207): Batch3D::compute_vertex_normals for every d3_static
+            batch -- on the calling thread, with threads=True one batch a task over the host's worker pool, or with device=True all
+            batches in one strided device call (rxr_vertex_normals, include/rxr.h).  The bits are the same."""
+            return self._compute_normals(0, device, threads)
+
+        def compute_dynamic_normals(self, device=False, threads=False):
+            """Scene::compute_dynamic_normals (reference src/scene.rs:210-214): the same for every d3_dynamic batch"""
+            return self._compute_normals(1, device, threads)
+
+        def batch3d_normals(self, list_kind, index, chunk=-1):
+            """the object-space normals a batch of the scene holds: [n][3] float32"""
+            if not has_vertex_normals:
+                raise NotImplementedError(f"{name}: no Scene::compute_*_normals in this library")
+            n = L.scene_batch3d_normals(self._h, list_kind, chunk, index, None, 0)
+            if n < 0:
+                raise IndexError("no such batch")
+            out = np.zeros((n, 3), np.float32)
+            L.scene_batch3d_normals(self._h, list_kind, chunk, index, _fp(out), n)
+            return out
 
         @property
         def resident_chunk_textures(self):
@@ -1664,6 +1699,46 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         if rc != 0:
             raise RasterizeError(rc, (rxr.rxr_last_error(ctx) or b"").decode())
 
+    def vertex_normals(counts, vertices, indices, normals=None):
+        """rxr_vertex_normals (include/rxr.h) on the process-wide context, over host arrays in the layout of rxr_terrain_meshes: counts
+        [n][2], vertices [n][VS][4], indices [n][TS][3]; the strides are the arrays' second extents.  Returns normals [n][VS][3]: the
+        array given (slots past a mesh's vertex count keep what they held) or a new one of zeros.  Raises RasterizeError with the
+        library's message when the call is refused."""
+        if not has_vertex_normals:
+            raise NotImplementedError(f"{name}: no vertex normals in this library")
+        from .libs import rxr_abi
+
+        v, i = np.ascontiguousarray(vertices, np.float32), np.ascontiguousarray(indices, np.uint32)
+        if v.ndim != 3 or i.ndim != 3 or v.shape[0] != i.shape[0] or v.shape[2] != 4 or i.shape[2] != 3:
+            raise ValueError("vertices must be [n][VS][4] and indices [n][TS][3]")
+        n = v.shape[0]
+        c = _u32(counts, (n, 2))
+        nr = np.zeros((n, v.shape[1], 3), np.float32) if normals is None else normals
+        if nr.dtype != np.float32 or nr.shape != (n, v.shape[1], 3) or not nr.flags.c_contiguous:
+            raise ValueError("normals must be a contiguous float32 array [n][VS][3]")
+        rxr = rxr_abi()
+        ctx = lib.rxh_context()
+        rc = rxr.rxr_vertex_normals(ctx, n, c.ctypes.data, v.ctypes.data, i.ctypes.data, nr.ctypes.data, v.shape[1], i.shape[1])
+        if rc != 0:
+            raise RasterizeError(rc, (rxr.rxr_last_error(ctx) or b"").decode())
+        return nr
+
+    def vertex_normals_to(n, counts, vertices, indices, normals, vertex_stride, triangle_stride, refused=None, stream=None):
+        """rxr_vertex_normals_to (include/rxr.h) on the process-wide context: the arrays are device memory, given as objects with a
+        data_ptr() (torch tensors) or as addresses; `stream` is a torch stream, a hipStream_t address or None (the context's stream).
+        Asynchronous.  Raises RasterizeError when a pointer fails the library's checks."""
+        if not has_vertex_normals:
+            raise NotImplementedError(f"{name}: no vertex normals in this library")
+        from .libs import rxr_abi
+
+        ptr = lambda a: None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else int(a)) or None
+        rxr = rxr_abi()
+        ctx = lib.rxh_context()
+        s = getattr(stream, "cuda_stream", stream)
+        rc = rxr.rxr_vertex_normals_to(ctx, n, ptr(counts), ptr(vertices), ptr(indices), ptr(normals), ptr(refused), vertex_stride, triangle_stride, s)
+        if rc != 0:
+            raise RasterizeError(rc, (rxr.rxr_last_error(ctx) or b"").decode())
+
     def chunk_texture_registrations():
         """how many times an upload has registered a scene's chunk textures (Scene.resident_chunk_textures): an unchanged scene adds none"""
         if not has_chunk_textures:
@@ -1672,6 +1747,7 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
 
     return types.SimpleNamespace(
         name=name, lib=lib, prefix=prefix, raw=L, update_meshes=update_meshes, chunk_texture_registrations=chunk_texture_registrations,
+        vertex_normals=vertex_normals, vertex_normals_to=vertex_normals_to,
         Scene=Scene, Batch3D=Batch3D, Batch2D=Batch2D, Chunk=Chunk, Assets=Assets, Rasterizer=Rasterizer, Terrain=Terrain, TerrainGenerator=TerrainGenerator,
         D3OrbitCamera=D3OrbitCamera, D3FirstPCamera=D3FirstPCamera, AccumBuffer=AccumBuffer,
         # shared value types

@@ -619,6 +619,20 @@ int rxh_scene_batch3d_copy(void *s, int list, int chunk, uint32_t i, float *pv4,
     return 0;
 }
 
+// Scene::compute_static_normals (dynamic == 0) / compute_dynamic_normals; route: Scene::NORMALS_CPU, _DEVICE, _POOL
+int rxh_scene_compute_normals(void *s, int dynamic, int route) {
+    return dynamic ? ((Scene *)s)->compute_dynamic_normals(route) : ((Scene *)s)->compute_static_normals(route);
+}
+// the object-space normals of one batch: its vertex count, and (n3 given, room for `capacity` vertices) their values
+int rxh_scene_batch3d_normals(void *s, int list, int chunk, uint32_t i, float *n3, uint32_t capacity) {
+    auto *l = list3d((Scene *)s, list, chunk);
+    if (!l || i >= l->size()) return RXR_ERR_INVALID;
+    const Batch3D &b = (*l)[i];
+    const size_t nv = b.normals.size() / 3;
+    if (n3) memcpy(n3, b.normals.data(), std::min<size_t>(nv, capacity) * 12);
+    return (int)nv;
+}
+
 // ---- cameras ----------------------------------------------------------------------------------------
 void rxh_camera_orbit(const float *center3, float distance, float azimuth, float elevation, float fov, float near, float far,
                       float w, float h, float *view16, float *proj16) {

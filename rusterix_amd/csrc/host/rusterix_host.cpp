@@ -1898,6 +1898,55 @@ int Scene::rebuild_terrain_meshes(const Terrain &terrain, const int32_t *coords,
     return 1;
 }
 
+int Scene::compute_normals(std::vector<Batch3D> &batches, int route) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);   // (the worker pool runs one job at a time)
+    const size_t n = batches.size();
+    if (route == NORMALS_CPU) {
+        for (Batch3D &b : batches) b.compute_vertex_normals();
+        return RXR_OK;
+    }
+    if (route == NORMALS_POOL) {
+        size_t work = 0;
+        for (const Batch3D &b : batches) work += b.triangle_count() * 64 + b.vertex_count() * 32;
+        rxr_parallel::run(n, work, [&](size_t i) { batches[i].compute_vertex_normals(); });
+        return RXR_OK;
+    }
+    if (route != NORMALS_DEVICE) {
+        g_error = "Scene::compute_normals: no such route";
+        return RXR_ERR_INVALID;
+    }
+    std::string err;
+    rxr_ctx *ctx = context(&err);
+    if (!ctx) return RXR_ERR_NO_DEVICE;
+    if (!n) return RXR_OK;
+    size_t VS = 0, TS = 0;
+    for (const Batch3D &b : batches) VS = std::max(VS, b.vertex_count()), TS = std::max(TS, b.triangle_count());
+    if (n > 0xFFFFFFFFull || VS > 0xFFFFFFFFull || TS > 0xFFFFFFFFull) {
+        g_error = "Scene::compute_normals: more batches, vertices or triangles than the device call counts";
+        return RXR_ERR_INVALID;
+    }
+    std::vector<uint32_t> counts(2 * n), indices(n * TS * 3, 0u);
+    std::vector<float> vertices(n * VS * 4, 0.0f), normals(n * VS * 3, 0.0f);
+    for (size_t i = 0; i < n; ++i) {
+        const Batch3D &b = batches[i];
+        counts[2 * i] = (uint32_t)b.vertex_count();
+        counts[2 * i + 1] = (uint32_t)b.triangle_count();
+        std::copy(b.vertices.begin(), b.vertices.begin() + b.vertex_count() * 4, vertices.begin() + i * VS * 4);
+        std::copy(b.indices.begin(), b.indices.begin() + b.triangle_count() * 3, indices.begin() + i * TS * 3);
+    }
+    const int rc = rxr_vertex_normals(ctx, (uint32_t)n, counts.data(), vertices.data(), indices.data(), normals.data(), (uint32_t)VS, (uint32_t)TS);
+    if (rc != RXR_OK) {
+        g_error = rxr_last_error(ctx);
+        return rc;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        Batch3D &b = batches[i];
+        b.normals.assign(normals.begin() + i * VS * 3, normals.begin() + i * VS * 3 + b.vertex_count() * 3);
+        b.touch();
+    }
+    return RXR_OK;
+}
+
 void Rasterizer::screen_ray(float x, float y, float origin[3], float dir[3]) const {
     const float ndc_x = 2.0f * (x / width) - 1.0f;
     const float ndc_y = 1.0f - 2.0f * (y / height);  // flip y

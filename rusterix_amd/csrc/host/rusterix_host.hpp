@@ -295,6 +295,18 @@ public:
     //      geometry replaced and touch()ed: the next upload registers again.
     //   a negative rxr_status otherwise.
     int rebuild_terrain_meshes(const class Terrain &terrain, const int32_t *coords, uint32_t n, const uint32_t *chunks_);
+    // src/scene.rs:203-215: Batch3D::compute_vertex_normals for every batch of d3_static / d3_dynamic.  `route`:
+    //   NORMALS_CPU     batch after batch on the calling thread (the reference's loop; where it panics -- an index out of range -- so does this)
+    //   NORMALS_POOL    one batch a task over the host's worker pool, as the reference's par_iter_mut (what tools/vertex_normals_bench.py
+    //                   measures the device against)
+    //   NORMALS_DEVICE  the batches packed into ONE strided call of rxr_vertex_normals (include/rxr.h; strides = the largest counts)
+    //                   and the normals written back into the batches: the same bits.  A batch with an index out of range is refused
+    //                   (RXR_ERR_INVALID, nothing written).
+    // Every batch is touch()ed.  Returns RXR_OK or a negative rxr_status.
+    enum : int { NORMALS_CPU = 0, NORMALS_DEVICE = 1, NORMALS_POOL = 2 };
+    int compute_static_normals(int route = NORMALS_CPU) { return compute_normals(d3_static, route); }
+    int compute_dynamic_normals(int route = NORMALS_CPU) { return compute_normals(d3_dynamic, route); }
+    static int compute_normals(std::vector<Batch3D> &batches, int route);
     // Opt-in, off by default: Rasterizer::upload registers the chunks' terrain and shader textures once (rxr_set_chunk_textures,
     // include/rxr.h) and sends frames without them, instead of handing every texel over with every frame.  The registration is made again
     // when a chunk's textures_generation differs from the one registered, when chunks were added or removed, or when another scene's

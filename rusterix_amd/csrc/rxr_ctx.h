@@ -41,6 +41,7 @@ enum : uint32_t {
     Q_CHUNK_TEX,     // rxr_set_chunk_textures / rxr_update_chunk_textures: the staged copies of the caller's host texels (all forms block)
     Q_EXCL,          // rxr_generated_meshes_to: the resident generator records, the resident excluded sectors and the call scratch
     Q_TRACE,         // rxr_trace_to: the trace scene, the path state and its keys (it takes Q_ISECT as well: the triangle records)
+    Q_NORMALS,       // rxr_vertex_normals_to: the general route's scratch (face normals, corner keys, the sort's own)
     Q_LANES
 };
 #define RXR_MAX_TILE_ROWS 2048u   // frames of at most 32768 rows
@@ -344,6 +345,12 @@ struct rxr_ctx {
     std::vector<float> excl_boxes;
     std::vector<uint32_t> excl_voff{0u};   // ... and of the vertex offsets (a round's work counts the vertices of a box's active sectors)
     uint32_t excl_launches = 0;       // classification launches of the last mesh call (rxr_debug_terrain_excl_launches)
+
+    // vertex normals (rxr_normals.hip): d_nrm_scratch: the general route's face normals, corner keys and values (in and out) and the
+    // sort's scratch, reused launch after launch; nothing is resident between calls.
+    DevBuf d_nrm_scratch;
+    uint32_t nrm_route = 0;           // the last call's route: 0 none yet, RXR_VERTEX_NORMALS_ROUTE_* (rxr_debug_vertex_normals)
+    uint32_t nrm_launches = 0;        // ... and its launches: workgroup-per-mesh launches, or rounds of the general route
 
     FrameStream fstream;    // rxr_stream_begin .. rxr_upload_frame
     int last_upload_streamed = 0;  // 0 plain, 1 streamed (copied), 2 streamed out of page-locked arrays

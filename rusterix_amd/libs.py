@@ -106,6 +106,11 @@ def rxr_abi():
         "rxr_generated_meshes": (i32, [vp, vp, u32, u32, u32, vp, vp]),
         "rxr_generated_meshes_to": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
         "rxr_debug_terrain_excl_launches": (u32, [vp]),
+        "rxr_check_vertex_normals": (i32, [vp, vp, u32, u32, u32, C.c_char_p, u32]),
+        "rxr_vertex_normals": (i32, [vp, u32, vp, vp, vp, vp, u32, u32]),
+        "rxr_vertex_normals_to": (i32, [vp, u32, vp, vp, vp, vp, vp, u32, u32, vp]),
+        "rxr_debug_vertex_normals": (u32, [vp, C.POINTER(u32)]),
+        "rxr_debug_vertex_normals_constants": (None, [C.POINTER(u32)]),
         "rxr_update_meshes": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, u32]),
         "rxr_update_meshes_to": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, u32, vp]),
         "rxr_mesh_bounds": (i32, [vp, u32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),

@@ -208,6 +208,22 @@ pub fn update_meshes(mesh_indices: &[u32], counts: &[u32], vertices: &[f32], ind
     }
 }
 
+// ---- vertex normals (include/rxr.h rxr_vertex_normals) ------------------------------------------------------------
+/// `Batch3D::compute_vertex_normals` for n meshes in one device call, bit for bit the reference's sums (ascending triangle index, from
+/// +0.0).  The slices are in the layout `rxr_terrain_meshes` writes and `update_meshes` reads: `counts` [n][2] (vertices, triangles),
+/// `vertices` [n][vertex_stride][4], `indices` [n][triangle_stride][3] mesh-local, `normals` [n][vertex_stride][3]: the first
+/// counts[i][0] normals of mesh i are written, the rest are left alone.  False: no device context, slices too short, or the library
+/// refused (a count above its stride, an index not below its mesh's vertex count): nothing was written.
+pub fn vertex_normals(counts: &[u32], vertices: &[f32], indices: &[u32], normals: &mut [f32], vertex_stride: u32, triangle_stride: u32) -> bool {
+    let guard = STATE.lock().unwrap();
+    let Some(ctx) = guard.as_ref().and_then(|st| st.ctx.as_ref()) else { return false };
+    let (n, vs, ts) = (counts.len() / 2, vertex_stride as usize, triangle_stride as usize);
+    if vertices.len() < n * vs * 4 || indices.len() < n * ts * 3 || normals.len() < n * vs * 3 {
+        return false;
+    }
+    unsafe { rxr_vertex_normals(ctx.0, n as u32, counts.as_ptr(), vertices.as_ptr(), indices.as_ptr(), normals.as_mut_ptr(), vertex_stride, triangle_stride) == RXR_OK }
+}
+
 /// The object-space box (lo, hi) the device context holds for registered mesh `mesh_index` (`rxr_mesh_bounds`): debugging.
 pub fn mesh_bounds(mesh_index: u32) -> Option<([f32; 3], [f32; 3])> {
     let guard = STATE.lock().unwrap();
