@@ -984,8 +984,8 @@ int rxr_vertex_normals_to(rxr_ctx *ctx, uint32_t n, const uint32_t *dev_counts, 
  * f32::min skips a NaN, so a ridge without edges is at distance +inf and contributes 0.0; clamp(0.0, 1.0) keeps a NaN and -0.0;
  * ridge contributions are added and linedefs folded in list order, a linedef only when its influence > 0.0, the over-influence
  * correction last.  TerrainConfig's idw_power and max_influence_distance are read by nothing in the reference and do not cross this
- * boundary; apply_exclusions is rxr_generated_meshes below; partition_by_tiles, mesh_fix_winding and the blend batches stay host
- * work, fed by those meshes. */
+ * boundary; apply_exclusions is rxr_generated_meshes below and partition_by_tiles rxr_generated_tile_meshes behind it
+ * (mesh_fix_winding never swaps such a mesh); the blend batches stay host work. */
 #define RXR_TERRAIN_GEN_CONTROL_POINT_FLOATS 4u /* x, y, height, smoothness (the caller has applied config.smoothness's default)   */
 #define RXR_TERRAIN_GEN_RIDGE_FLOATS 4u         /* height, plateau_width, falloff_distance, falloff_steepness                      */
 #define RXR_TERRAIN_GEN_RIDGE_EDGE_FLOATS 4u    /* x0, y0, x1, y1, in the sector's linedef order                                    */
@@ -1093,6 +1093,74 @@ int rxr_generated_meshes(rxr_ctx *ctx, const float *boxes, uint32_t n, uint32_t 
  * Multi-device handles: RXR_ERR_UNSUPPORTED (use rxr_member). */
 int rxr_generated_meshes_to(rxr_ctx *ctx, const float *boxes, uint32_t n, uint32_t subdivisions, uint32_t stride,
                             uint32_t *dev_counts, float *dev_vertices, void *hip_stream);
+
+/* ---- generated terrain tile meshes: TerrainGenerator::partition_by_tiles (rusterix_amd/csrc/rxr_terrain_excl.hip) --------------------
+ * The last step of TerrainGenerator::generate (src/chunkbuilder/terrain_generator.rs:954-1034) over the (vertices, indices, uvs) of
+ * apply_exclusions above, uvs[i] = [v.x, v.z]: one mesh per tile, with its uvs and mesh-local indices, in the strided layout
+ * rxr_vertex_normals[_to] and rxr_update_meshes[_to] read -- so that on ONE stream
+ *     rxr_generated_tile_meshes_to -> rxr_vertex_normals_to -> rxr_update_meshes_to
+ * takes the dirty chunks of a generated terrain to the renderer and no geometry crosses PCIe (moving a control point changes
+ * heights and no count: which triangles survive, and which tile one belongs to, depend on x and z alone).
+ *   per triangle, in index order   center_u = (uv0[0] + uv1[0] + uv2[0]) / 3.0 -- added left to right, then divided, every operation
+ *                      rounded to f32, no reciprocal --, center_v likewise; tile_cell = (center_u.floor() as i32, center_v.floor()
+ *                      as i32) (saturating, a NaN is 0); its TILE SLOT is the one registered for that cell, else slot 0.
+ *   per tile           its triangles in ascending triangle order; the vertex list is built by FIRST USE, walking those triangles'
+ *                      corners in order: a vertex not seen before in this tile gets the next index and is copied with its uv; a vertex
+ *                      two tiles share is copied into both.
+ * Which tile a cell's pixel source resolves to (tile_from_tile_list, else the default) is the caller's knowledge and stays on the
+ * host: the caller numbers its tiles, slot 0 being the default tile, and registers cells with slots.
+ * GROUP ORDER.  The reference returns the tiles in the iteration order of a hash map, which is unspecified; here it is defined: the
+ * groups of a box are in ASCENDING TILE SLOT, and a group exists iff at least one kept triangle has that slot.
+ * mesh_fix_winding (src/chunkbuilder/surface_mesh_builder.rs:201-239), which the reference's consumer runs on every group, never
+ * swaps a generated mesh and is not run (DESIGN.md section 21 has the argument, tests/test_terrain_tiles_cpu.py holds it).  The
+ * consumer's uv flip, its second grouping by GeoId and the blend batches stay host work.
+ * Every count, slot, index, x, z and uv is the reference's to the bit; h is the word rxr_generated_grids gives for that grid point. */
+#define RXR_TERRAIN_TILES_MAX_CELLS (1u << 20)
+#define RXR_TERRAIN_TILES_MAX_TILES (1u << 12)
+#define RXR_TERRAIN_TILES_MAX_GROUPS 64u
+/* validation only, no context: the status rxr_set_terrain_tiles would return and, in `message`, the reason.  RXR_ERR_UNSUPPORTED:
+ * n_cells above RXR_TERRAIN_TILES_MAX_CELLS, n_tiles above RXR_TERRAIN_TILES_MAX_TILES.  RXR_ERR_INVALID: n_tiles == 0, a NULL array
+ * with a non-zero count, a slot >= n_tiles, a cell listed twice. */
+int rxr_check_terrain_tiles(const int32_t *cells, const uint32_t *slots, uint32_t n_cells, uint32_t n_tiles, char *message,
+                            uint32_t message_capacity);
+/* makes the tile overrides resident: cell i = (x, z) of a 1 x 1 world cell has tile slot slots[i] < n_tiles; every other cell has
+ * slot 0.  The cells may come in any order (they are sorted here, the device searches them).  n_cells == 0 is legal: everything is
+ * slot 0; never called is n_cells == 0, n_tiles == 1.  Replaces the previous map; waits for queued tile-mesh calls.  Independent of
+ * rxr_set_terrain_generator and rxr_set_terrain_exclusions.  Arrays are read before the call returns.  A refused call leaves the
+ * resident map as it was.  Multi-device handles: member 0. */
+int rxr_set_terrain_tiles(rxr_ctx *ctx, const int32_t *cells /* [n_cells][2] */, const uint32_t *slots /* [n_cells] */,
+                          uint32_t n_cells, uint32_t n_tiles);
+/* the tile meshes of n chunk boxes [n][4] in one call, grids, heights and exclusions as in rxr_generated_meshes.  Mesh slot
+ * m = box * max_groups + group:
+ *   box_counts  [n][4]                            (steps_x, steps_y, active_sectors, n_groups)
+ *   counts      [n * max_groups][2]               (n_vertices, n_triangles); (0, 0) for a group slot at or past n_groups
+ *   group_tiles [n * max_groups]                  the group's tile slot; 0xFFFFFFFF past n_groups
+ *   vertices    [n * max_groups][vertex_stride][4]      [x, h, z, 1.0]
+ *   uvs         [n * max_groups][vertex_stride][2]      [x, z]
+ *   indices     [n * max_groups][triangle_stride][3]    mesh-local
+ * box_counts, counts and group_tiles are written whole; vertex, uv and index slots past a mesh's counts are NOT written.  A grid
+ * without a cell (a step below 2) has no triangle and so no group.
+ * Refused before anything is queued, with nothing written -- RXR_ERR_INVALID: no rxr_set_terrain_generator yet, subdivisions == 0,
+ * max_groups == 0, a NULL pointer, sizes that overflow, a box with 2 * cells > triangle_stride or whose one group can exceed
+ * vertex_stride (cells = (steps_x - 1) * (steps_y - 1); 6 * cells where a sector is active, else steps_x * steps_y: one group can
+ * own the whole box), a box that CAN have more than max_groups groups; RXR_ERR_UNSUPPORTED: max_groups above
+ * RXR_TERRAIN_TILES_MAX_GROUPS.  The group bound is conservative: slot 0 plus the distinct non-zero slots among the override cells
+ * between the floor of the grid's first and the ceil of its last coordinate on both axes -- whether or not slot 0 occurs, and
+ * counting override cells whose triangles all end up excluded.  A box can therefore be refused that would have fitted.  (With
+ * coordinates so large that a centre's rounding is not small against a third of a cell, every registered slot counts.)
+ * n == 0 does nothing.  Host memory, blocking.  Rounds as rxr_generated_meshes: a classification and a tile emission launch each,
+ * RXR_TERRAIN_EXCL_LAUNCH_POINTS cuts them too.  Changes no frame, bake, picking or mesh state.  Multi-device handles: member 0.
+ * Replaces: generate_grid .. partition_by_tiles, :460-509, :747-879, :954-1034, and mesh_fix_winding per group. */
+int rxr_generated_tile_meshes(rxr_ctx *ctx, const float *boxes, uint32_t n, uint32_t subdivisions, uint32_t max_groups,
+                              uint32_t vertex_stride, uint32_t triangle_stride, uint32_t *box_counts, uint32_t *counts,
+                              uint32_t *group_tiles, float *vertices, float *uvs, uint32_t *indices);
+/* the same into DEVICE arrays (each one's first and last byte are checked to be memory of the context's device; 4-byte aligned),
+ * queued on hip_stream (NULL = the context's stream); boxes is host memory and is read before the call returns.  Asynchronous.
+ * Multi-device handles: RXR_ERR_UNSUPPORTED (use rxr_member). */
+int rxr_generated_tile_meshes_to(rxr_ctx *ctx, const float *boxes, uint32_t n, uint32_t subdivisions, uint32_t max_groups,
+                                 uint32_t vertex_stride, uint32_t triangle_stride, uint32_t *dev_box_counts, uint32_t *dev_counts,
+                                 uint32_t *dev_group_tiles, float *dev_vertices, float *dev_uvs, uint32_t *dev_indices,
+                                 void *hip_stream);
 
 /* ---- path tracing the resident scene: Tracer::trace (rusterix_amd/csrc/rxr_trace.hip) ----------------------------------------------
  * The reference's second renderer (src/tracer/trace.rs:105-475 into an AccumBuffer, src/tracer/buffer.rs) over the meshes of

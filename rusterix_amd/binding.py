@@ -538,11 +538,16 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         L.terrain_generator_set_exclusions = fn("terrain_generator_set_exclusions", i32, vp, pf, pu, pf, u32, u32)
         L.terrain_generator_meshes = fn("terrain_generator_meshes", i32, vp, pf, u32, u32, i32, pu, pf)
         L.terrain_generator_points_in_sector = fn("terrain_generator_points_in_sector", None, vp, pf, u32, u32, C.POINTER(C.c_uint8))
+        L.terrain_generator_set_tiles = fn("terrain_generator_set_tiles", i32, vp, pi_, pu, u32, u32)
+        L.terrain_generator_tile_meshes = fn("terrain_generator_tile_meshes", i32, vp, pf, u32, u32, u32, u32, i32, pu, pu, pu, pf, pf, pu)
 
     # registered meshes updated in place (product host library only)
     has_mesh_update = hasattr(lib, prefix + "scene_rebuild_terrain_meshes")
     if has_mesh_update:
         L.scene_rebuild_terrain_meshes = fn("scene_rebuild_terrain_meshes", i32, vp, vp, C.POINTER(C.c_int32), u32, pu)
+    has_tile_mesh_update = hasattr(lib, prefix + "scene_rebuild_generated_tile_meshes")
+    if has_tile_mesh_update:
+        L.scene_rebuild_generated_tile_meshes = fn("scene_rebuild_generated_tile_meshes", i32, vp, vp, C.POINTER(C.c_float), u32, pu, u32)
 
     # vertex normals of whole batch lists, on the CPU or the device (product host library only)
     has_vertex_normals = hasattr(lib, prefix + "scene_compute_normals")
@@ -1020,6 +1025,24 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
                 raise RasterizeError(rc, last_error())
             return rc
 
+        def rebuild_generated_tile_meshes(self, generator, boxes, chunks, max_groups):
+            """The same for the generated terrain: the batches3d of scene chunk chunks[i] (all of them) are the tile groups of boxes[i]
+            ([n][4]) in ascending tile slot, at most max_groups of them; their geometry is generated, partitioned by tiles, given normals and
+            written over the registered meshes on the device (rxr_generated_tile_meshes_to + rxr_vertex_normals_to +
+            rxr_update_meshes_to on one stream).  Returns 0 for that fast path or 1 for the fallback (counts changed, or no registration
+            of this geometry is held): the batches' geometry was replaced on the host and the next rasterize registers the scene
+            again.  A chunk whose number of groups changed raises: which tile a new batch shows is the caller's to say."""
+            if not has_tile_mesh_update:
+                raise NotImplementedError(f"{name}: no in-place update of generated tile meshes in this library")
+            bb = np.ascontiguousarray(np.asarray(boxes, np.float32).reshape(-1, 4))
+            ch = np.ascontiguousarray(np.asarray(chunks, np.uint32).reshape(-1))
+            if len(bb) != len(ch):
+                raise ValueError("boxes and chunks must have the same length")
+            rc = L.scene_rebuild_generated_tile_meshes(self._h, generator._h, _fp(bb), len(bb), _up(ch), int(max_groups))
+            if rc < 0:
+                raise RasterizeError(rc, last_error())
+            return rc
+
         def _compute_normals(self, dynamic, device, threads):
             if not has_vertex_normals:
                 raise NotImplementedError(f"{name}: no Scene::compute_*_normals in this library")
@@ -1422,6 +1445,44 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
 
         def generate_meshes_cpu(self, boxes, stride, fill=0.0):
             return self._meshes(boxes, stride, False, fill)
+
+        def set_tiles(self, cells=(), slots=(), n_tiles=1):
+            """the tile overrides of partition_by_tiles (:954-1034), every pixel source resolved to a tile SLOT by the caller (slot 0:
+            the default tile): cells [N][2] int32 (x, z of a 1 x 1 world cell) and slots [N] < n_tiles"""
+            cc = np.ascontiguousarray(np.asarray(cells, np.int32).reshape(-1, 2))
+            sl = np.ascontiguousarray(np.asarray(slots, np.uint32).reshape(-1))
+            if len(cc) != len(sl):
+                raise ValueError("cells and slots must have the same length")
+            rc = L.terrain_generator_set_tiles(self._h, cc.ctypes.data_as(C.POINTER(C.c_int32)) if len(cc) else None, _up(sl) if len(sl) else None, len(sl), int(n_tiles))
+            if rc != 0:
+                raise ValueError(last_error())
+            return self
+
+        def _tile_meshes(self, boxes, max_groups, vertex_stride, triangle_stride, device, fill):
+            b = np.ascontiguousarray(np.asarray(boxes, np.float32).reshape(-1, 4))
+            n, mg, vs, ts = b.shape[0], int(max_groups), int(vertex_stride), int(triangle_stride)
+            m = max(n * mg, 1)
+            box_counts, counts, group_tiles = np.zeros((max(n, 1), 4), np.uint32), np.zeros((m, 2), np.uint32), np.full(m, 0xFFFFFFFF, np.uint32)
+            vertices, uvs = np.full((m, max(vs, 1), 4), fill, np.float32), np.full((m, max(vs, 1), 2), fill, np.float32)
+            indices = np.zeros((m, max(ts, 1), 3), np.uint32)
+            rc = L.terrain_generator_tile_meshes(self._h, _fp(b) if n else None, n, mg, vs, ts, 1 if device else 0, _up(box_counts), _up(counts), _up(group_tiles),
+                                                 _fp(vertices), _fp(uvs), _up(indices))
+            if rc != 0:
+                raise RasterizeError(rc, last_error())
+            k = n * mg
+            return (box_counts[:n], counts[:k].reshape(n, mg, 2), group_tiles[:k].reshape(n, mg), vertices[:k, :vs].reshape(n, mg, vs, 4),
+                    uvs[:k, :vs].reshape(n, mg, vs, 2), indices[:k, :ts].reshape(n, mg, ts, 3))
+
+        def generate_tile_meshes(self, boxes, max_groups, vertex_stride, triangle_stride, fill=0.0):
+            """partition_by_tiles (:954-1034) behind generate_grid, interpolate_heights and apply_exclusions for [n][4] chunk boxes in
+            one device call (rxr_generated_tile_meshes), mesh slot = box * max_groups + group, groups in ascending tile slot:
+            box_counts [n][4] = (steps_x, steps_y, active_sectors, n_groups), counts [n][max_groups][2] = (vertices, triangles),
+            group_tiles [n][max_groups], vertices [..][vertex_stride][4], uvs [..][vertex_stride][2], indices
+            [..][triangle_stride][3]; vertex and uv slots past a mesh's counts keep `fill`"""
+            return self._tile_meshes(boxes, max_groups, vertex_stride, triangle_stride, True, fill)
+
+        def generate_tile_meshes_cpu(self, boxes, max_groups, vertex_stride, triangle_stride, fill=0.0):
+            return self._tile_meshes(boxes, max_groups, vertex_stride, triangle_stride, False, fill)
 
     class Assets:
         """reference src/server/assets.rs (`tile_list`, `.textures(..)` builder)."""

@@ -331,6 +331,18 @@ int rxh_terrain_generator_meshes(void *g, const float *boxes, uint32_t n, uint32
     ((TerrainGenerator *)g)->generate_meshes_cpu(boxes, n, stride, counts, vertices);
     return RXR_OK;
 }
+// the tile overrides of rxr_set_terrain_tiles (include/rxr.h); 0, or what rxr_check_terrain_tiles refuses (nothing changes then)
+int rxh_terrain_generator_set_tiles(void *g, const int32_t *cells, const uint32_t *slots, uint32_t n, uint32_t n_tiles) {
+    return ((TerrainGenerator *)g)->set_tiles(cells, slots, n, n_tiles);
+}
+// n boxes in the layout of rxr_generated_tile_meshes: on the device, or (device == 0) the CPU partition_by_tiles
+int rxh_terrain_generator_tile_meshes(void *g, const float *boxes, uint32_t n, uint32_t max_groups, uint32_t vertex_stride, uint32_t triangle_stride, int device,
+                                      uint32_t *box_counts, uint32_t *counts, uint32_t *group_tiles, float *vertices, float *uvs, uint32_t *indices) {
+    TerrainGenerator *t = (TerrainGenerator *)g;
+    if (device) return t->generate_tile_meshes(boxes, n, max_groups, vertex_stride, triangle_stride, box_counts, counts, group_tiles, vertices, uvs, indices);
+    t->generate_tile_meshes_cpu(boxes, n, max_groups, vertex_stride, triangle_stride, box_counts, counts, group_tiles, vertices, uvs, indices);
+    return RXR_OK;
+}
 // point_in_sector for n points [n][2] against sector s on the CPU: inside [n] (1 / 0)
 void rxh_terrain_generator_points_in_sector(void *g, const float *points, uint32_t n, uint32_t s, uint8_t *inside) {
     for (uint32_t i = 0; i < n; ++i) inside[i] = ((TerrainGenerator *)g)->point_in_sector(points[2 * (size_t)i], points[2 * (size_t)i + 1], s) ? 1 : 0;
@@ -338,6 +350,10 @@ void rxh_terrain_generator_points_in_sector(void *g, const float *points, uint32
 // Scene::rebuild_terrain_meshes: 0 (updated in place on the device), 1 (fallback: the batches were replaced on the host) or a negative rxr_status
 int rxh_scene_rebuild_terrain_meshes(void *s, void *t, const int32_t *coords, uint32_t n, const uint32_t *chunks) {
     return ((Scene *)s)->rebuild_terrain_meshes(*(const Terrain *)t, coords, n, chunks);
+}
+// Scene::rebuild_generated_tile_meshes: 0 (updated in place on the device), 1 (the batches were replaced on the host) or a negative rxr_status
+int rxh_scene_rebuild_generated_tile_meshes(void *s, void *g, const float *boxes, uint32_t n, const uint32_t *chunks, uint32_t max_groups) {
+    return ((Scene *)s)->rebuild_generated_tile_meshes(*(const TerrainGenerator *)g, boxes, n, chunks, max_groups);
 }
 // Terrain::bake_chunk on the CPU: side * side * 4 bytes; RXR_OK or a negative rxr_status
 int rxh_terrain_bake_chunk(void *t, int32_t cx, int32_t cy, int32_t ppt, uint8_t *rgba) {

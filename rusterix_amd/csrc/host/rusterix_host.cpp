@@ -494,6 +494,7 @@ uint64_t g_terrain_gen = 0;   // the Terrain::generation the context's resident 
 uint64_t g_heights_gen = 0;   // the Terrain::heights_generation the context's resident heights were registered from (0: none)
 uint64_t g_generator_gen = 0; // the TerrainGenerator::generation the context's resident generator records were registered from (0: none)
 uint64_t g_exclusion_gen = 0; // ... and the one its resident excluded sectors were registered from (0: none)
+uint64_t g_tiles_gen = 0;     // ... and the one its resident tile overrides were registered from (0: none)
 // (RXR_DEVICE_PROJECTION=1 in the environment makes device projection the initial choice, as in the Rust shim: shim/.../lib.rs)
 bool g_device_projection = [] { const char *e = getenv("RXR_DEVICE_PROJECTION"); return e && e[0] == '1'; }();
 bool g_device_edges = !(getenv("RXR_HOST_EDGES") && atoi(getenv("RXR_HOST_EDGES")) != 0);
@@ -537,6 +538,7 @@ void drop_context_locked() {
     g_heights_gen = 0;
     g_generator_gen = 0;
     g_exclusion_gen = 0;
+    g_tiles_gen = 0;
     g_ctex_held = false;
     g_ctex_gens.clear();
 }
@@ -1508,6 +1510,7 @@ int Terrain::build_chunk_at(int32_t cx, int32_t cy, int32_t ppt, Chunk &chunk) c
 
 // (rxr_api.hip; see Scene::rebuild_terrain_meshes)
 extern "C" void *rxr_mirror_scratch(rxr_ctx *ctx, size_t bytes);
+extern "C" int rxr_mirror_read(rxr_ctx *ctx, void *host, const void *dev, size_t bytes);
 
 namespace {
 // does the context hold the registration made from exactly these chunks' textures?
@@ -1895,6 +1898,134 @@ int Scene::rebuild_terrain_meshes(const Terrain &terrain, const int32_t *coords,
         b.normals = std::move(built[i].normals);
         b.touch();
     }
+    return 1;
+}
+
+int Scene::rebuild_generated_tile_meshes(const TerrainGenerator &gen, const float *boxes, uint32_t n, const uint32_t *chunks_, uint32_t max_groups) {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    const std::string who = "Scene::rebuild_generated_tile_meshes: ";
+    std::string err;
+    rxr_ctx *ctx = context(&err);
+    if (!ctx) return RXR_ERR_NO_DEVICE;
+    if (!g_device_projection) {
+        g_error = who + "device projection is off (set_device_projection): there are no registered meshes to update";
+        return RXR_ERR_UNSUPPORTED;
+    }
+    if (!n) return 0;
+    if (!boxes || !chunks_ || !max_groups) {
+        g_error = who + "NULL array or max_groups == 0";
+        return RXR_ERR_INVALID;
+    }
+    // each batch's position in batches3d_in_order(): per chunk opacity, batches, terrain; a named chunk's `batches3d` are its tile
+    // groups in ascending slot (terrain_batch3d is the reference's Option<Batch3D>: it holds one batch)
+    std::vector<uint32_t> first_of_chunk(chunks.size() + 1, 0);
+    for (size_t c = 0; c < chunks.size(); ++c)
+        first_of_chunk[c + 1] = first_of_chunk[c] + (uint32_t)(chunks[c].batches3d_opacity.size() + chunks[c].batches3d.size() + chunks[c].terrain_batch3d.size());
+    bool all_full = true;
+    size_t VS = 0, TS = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t c = chunks_[i];
+        if (c >= chunks.size() || chunks[c].batches3d.size() > max_groups) {
+            g_error = who + "chunks[" + std::to_string(i) + "] = " + std::to_string(c) + " is not a chunk with at most max_groups batches3d";
+            return RXR_ERR_INVALID;
+        }
+        all_full = all_full && chunks[c].batches3d.size() == max_groups;
+        int32_t sx, sy;
+        gen.grid_steps(boxes + 4 * (size_t)i, sx, sy);
+        const size_t points = (sx > 0 && sy > 0) ? (size_t)sx * (size_t)sy : 0, cells = (sx > 1 && sy > 1) ? (size_t)(sx - 1) * (size_t)(sy - 1) : 0;
+        VS = std::max(VS, std::max(points, 6 * cells)), TS = std::max(TS, 2 * cells);
+    }
+    if (VS > 0xFFFFFFFFull || TS > 0xFFFFFFFFull) {
+        g_error = who + "a box has more vertices or triangles than the device call counts";
+        return RXR_ERR_INVALID;
+    }
+    const size_t M = (size_t)n * max_groups;
+    std::vector<rxr_mesh3d> meshes;
+    uint64_t full = 0, geometry = 0;
+    // the fast path needs a registration made by a device-projected upload of exactly this geometry (rebuild_terrain_meshes)
+    const bool held = scene_meshes(*this, nullptr, meshes, nullptr, full, geometry) && g_mesh_fingerprint != 0 && geometry == g_mesh_geometry_fingerprint;
+    if (held && rxr_member_count(ctx) == 1) {
+        int rc = gen.register_records(ctx);
+        if (rc != RXR_OK || (rc = gen.register_exclusions(ctx)) != RXR_OK || (rc = gen.register_tiles(ctx)) != RXR_OK) return rc;
+        auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+        const size_t o_c = up((size_t)n * 16), o_g = o_c + up(M * 8), o_v = o_g + up(M * 4), o_u = o_v + up(M * VS * 16), o_i = o_u + up(M * VS * 8), o_n = o_i + up(M * TS * 12),
+                     total = o_n + up(M * VS * 12);
+        uint8_t *d = (uint8_t *)rxr_mirror_scratch(ctx, total);
+        if (!d) {
+            g_error = rxr_last_error(ctx);
+            return RXR_ERR_OOM;
+        }
+        uint32_t *db = (uint32_t *)d, *dc = (uint32_t *)(d + o_c), *dg = (uint32_t *)(d + o_g), *di = (uint32_t *)(d + o_i);
+        float *dv = (float *)(d + o_v), *du = (float *)(d + o_u), *dn = (float *)(d + o_n);
+        // one stream (the context's): tile meshes -> vertex normals -> update; no geometry crosses PCIe
+        rc = rxr_generated_tile_meshes_to(ctx, boxes, n, gen.subdivisions, max_groups, (uint32_t)VS, (uint32_t)TS, db, dc, dg, dv, du, di, nullptr);
+        // box_counts and counts come back (16 bytes a box, 8 a mesh slot) and are held against the chunks' batches BEFORE anything is
+        // written over a registered mesh: a chunk whose number of groups changed is refused here, and counts that changed send the
+        // whole call to the host path with nothing committed
+        std::vector<uint32_t> got(o_g / 4);
+        if (rc == RXR_OK) rc = rxr_mirror_read(ctx, got.data(), d, o_g);
+        if (rc != RXR_OK) {
+            g_error = rxr_last_error(ctx);
+            return rc;
+        }
+        bool same_counts = true;
+        for (uint32_t i = 0; i < n; ++i) {
+            const Chunk &c = chunks[chunks_[i]];
+            const uint32_t n_groups = got[4 * (size_t)i + 3];
+            if (n_groups != c.batches3d.size()) {
+                g_error = who + "chunks[" + std::to_string(i) + "] has " + std::to_string(c.batches3d.size()) + " batches3d and its box " + std::to_string(n_groups) +
+                          " tile groups: which tile a new batch shows is the caller's to say";
+                return RXR_ERR_INVALID;
+            }
+            for (size_t g = 0; g < c.batches3d.size(); ++g) {
+                const uint32_t *mc = got.data() + o_c / 4 + 2 * ((size_t)i * max_groups + g);
+                same_counts = same_counts && mc[0] == c.batches3d[g].vertex_count() && mc[1] == c.batches3d[g].triangle_count();
+            }
+        }
+        if (same_counts) rc = rxr_vertex_normals_to(ctx, (uint32_t)M, dc, dv, di, dn, nullptr, (uint32_t)VS, (uint32_t)TS, nullptr);
+        if (rc != RXR_OK) {
+            g_error = rxr_last_error(ctx);
+            return rc;
+        }
+        if (!same_counts) rc = RXR_ERR_INVALID;   // (the host path below)
+        // a chunk's registered meshes are its groups; a chunk with fewer than max_groups of them leaves mesh slots no mesh answers to,
+        // so the update is one call when every chunk is full and one call per chunk otherwise
+        std::vector<uint32_t> mesh_index;
+        for (uint32_t i = 0; i < n && rc == RXR_OK; ++i) {
+            const Chunk &c = chunks[chunks_[i]];
+            for (size_t g = 0; g < c.batches3d.size(); ++g) mesh_index.push_back(first_of_chunk[chunks_[i]] + (uint32_t)c.batches3d_opacity.size() + (uint32_t)g);
+            if (all_full && i + 1 < n) continue;
+            const size_t m0 = all_full ? 0 : (size_t)i * max_groups;
+            if (!mesh_index.empty())
+                rc = rxr_update_meshes_to(ctx, mesh_index.data(), (uint32_t)mesh_index.size(), dc + 2 * m0, dv + m0 * VS * 4, di + m0 * TS * 3, dn + m0 * VS * 3, (uint32_t)VS, (uint32_t)TS, nullptr);
+            mesh_index.clear();
+        }
+        if (rc == RXR_OK) return 0;
+        if (rc != RXR_ERR_INVALID) {
+            g_error = rxr_last_error(ctx);
+            return rc;
+        }
+        // refused (counts changed): the host path below replaces every named chunk's batches, and the next upload registers them again
+    }
+    std::vector<uint32_t> box_counts(4 * (size_t)n), counts(2 * M), group_tiles(M), indices(M * TS * 3);
+    std::vector<float> vertices(M * VS * 4), uvs(M * VS * 2);
+    gen.generate_tile_meshes_cpu(boxes, n, max_groups, (uint32_t)VS, (uint32_t)TS, box_counts.data(), counts.data(), group_tiles.data(), vertices.data(), uvs.data(), indices.data());
+    for (uint32_t i = 0; i < n; ++i)
+        if (box_counts[4 * (size_t)i + 3] != chunks[chunks_[i]].batches3d.size()) {
+            g_error = who + "chunks[" + std::to_string(i) + "] has " + std::to_string(chunks[chunks_[i]].batches3d.size()) + " batches3d and its box " +
+                      std::to_string(box_counts[4 * (size_t)i + 3]) + " tile groups (or more than max_groups): which tile a new batch shows is the caller's to say";
+            return RXR_ERR_INVALID;
+        }
+    for (uint32_t i = 0; i < n; ++i)
+        for (size_t g = 0; g < chunks[chunks_[i]].batches3d.size(); ++g) {
+            Batch3D &b = chunks[chunks_[i]].batches3d[g];   // (material, transform and cull mode stay the batch's own)
+            const size_t m = (size_t)i * max_groups + g, nv = counts[2 * m], nt = counts[2 * m + 1];
+            b.vertices.assign(vertices.begin() + m * VS * 4, vertices.begin() + (m * VS + nv) * 4);
+            b.uvs.assign(uvs.begin() + m * VS * 2, uvs.begin() + (m * VS + nv) * 2);
+            b.indices.assign(indices.begin() + m * TS * 3, indices.begin() + (m * TS + nt) * 3);
+            b.compute_vertex_normals();
+            b.touch();
+        }
     return 1;
 }
 
@@ -2662,6 +2793,155 @@ int TerrainGenerator::generate_meshes(const float *boxes, uint32_t n, uint32_t s
     int rc = register_records(ctx);
     if (rc != RXR_OK || (rc = register_exclusions(ctx)) != RXR_OK) return rc;
     rc = rxr_generated_meshes(ctx, boxes, n, subdivisions, stride, counts, vertices);
+    if (rc != RXR_OK) g_error = rxr_last_error(ctx);
+    return rc;
+}
+
+// ---- the generated terrain's tiles (:954-1034) ------------------------------------------------------
+int TerrainGenerator::set_tiles(const int32_t *cells, const uint32_t *slots, uint32_t n, uint32_t n_tiles_) {
+    char message[256] = "";
+    const int rc = rxr_check_terrain_tiles(cells, slots, n, n_tiles_, message, sizeof message);
+    if (rc != RXR_OK) {
+        g_error = std::string("TerrainGenerator::set_tiles: ") + message;
+        return rc;
+    }
+    tile_cells.assign(cells, cells + 2 * (size_t)n);
+    tile_slots.assign(slots, slots + n);
+    n_tiles = n_tiles_;
+    tile_overrides.clear();   // the reference is handed its FxHashMap ready: built here, once
+    for (size_t i = 0; i < tile_slots.size(); ++i) tile_overrides[{tile_cells[2 * i], tile_cells[2 * i + 1]}] = tile_slots[i];
+    touch();
+    return RXR_OK;
+}
+
+namespace {
+// Rust's `x as i32`: saturating, a NaN is 0
+int32_t f32_as_i32(float x) {
+    if (x != x) return 0;
+    if (x >= 2147483648.0f) return INT32_MAX;
+    if (x <= -2147483648.0f) return INT32_MIN;
+    return (int32_t)x;
+}
+}  // namespace
+
+std::vector<TerrainGenerator::TileGroup> TerrainGenerator::partition_by_tiles(const float *vertices, const uint32_t *indices, size_t n_indices, const float *uvs) const {
+    std::map<uint32_t, std::vector<uint32_t>> per_tile;   // (ordered: the groups come in ascending slot)
+    for (size_t t = 0; t + 3 <= n_indices; t += 3) {
+        const uint32_t i0 = indices[t], i1 = indices[t + 1], i2 = indices[t + 2];
+        const float *uv0 = uvs + 2 * (size_t)i0, *uv1 = uvs + 2 * (size_t)i1, *uv2 = uvs + 2 * (size_t)i2;
+        const float center_u = (uv0[0] + uv1[0] + uv2[0]) / 3.0f;
+        const float center_v = (uv0[1] + uv1[1] + uv2[1]) / 3.0f;
+        const std::pair<int32_t, int32_t> tile_cell{f32_as_i32(std::floor(center_u)), f32_as_i32(std::floor(center_v))};
+        const auto found = tile_overrides.find(tile_cell);
+        const uint32_t tile_id = found != tile_overrides.end() ? found->second : 0u;
+        std::vector<uint32_t> &batch = per_tile[tile_id];
+        batch.insert(batch.end(), indices + t, indices + t + 3);
+    }
+    std::vector<TileGroup> result;
+    for (const auto &entry : per_tile) {
+        TileGroup g;
+        g.slot = entry.first;
+        std::map<uint32_t, uint32_t> vertex_remap;
+        for (const uint32_t old_idx : entry.second) {
+            uint32_t new_idx;
+            const auto existing = vertex_remap.find(old_idx);
+            if (existing != vertex_remap.end()) {
+                new_idx = existing->second;
+            } else {
+                new_idx = (uint32_t)(g.vertices.size() / 3);
+                vertex_remap[old_idx] = new_idx;
+                g.vertices.insert(g.vertices.end(), vertices + 3 * (size_t)old_idx, vertices + 3 * (size_t)old_idx + 3);
+                g.uvs.insert(g.uvs.end(), uvs + 2 * (size_t)old_idx, uvs + 2 * (size_t)old_idx + 2);
+            }
+            g.indices.push_back(new_idx);
+        }
+        result.push_back(std::move(g));
+    }
+    return result;
+}
+
+void TerrainGenerator::generate_tile_meshes_cpu(const float *boxes, uint32_t n, uint32_t max_groups, uint32_t vertex_stride, uint32_t triangle_stride, uint32_t *box_counts,
+                                                uint32_t *counts, uint32_t *group_tiles, float *vertices, float *uvs_out, uint32_t *indices_out) const {
+    const uint32_t S = (uint32_t)(excluded_boxes.size() / 4);
+    // (vertices, indices, uvs) of every box as apply_exclusions returns them (:823-824): heights and keep flags over the worker pool
+    struct Mesh {
+        std::vector<float> v, uvs;
+        std::vector<uint32_t> idx;
+    };
+    std::vector<Mesh> meshes(n);
+    size_t work = 0;
+    for (uint32_t b = 0; b < n; ++b) {
+        const float *box = boxes + 4 * (size_t)b;
+        int32_t sx, sy;
+        grid_steps(box, sx, sy);
+        std::vector<uint32_t> active;
+        for (uint32_t s = 0; s < S; ++s)
+            if (sector_active(s, box)) active.push_back(s);
+        uint32_t *c = box_counts + 4 * (size_t)b;
+        c[0] = (uint32_t)std::max(sx, 0), c[1] = (uint32_t)std::max(sy, 0), c[2] = (uint32_t)active.size(), c[3] = 0;
+        for (uint32_t g = 0; g < max_groups; ++g) {
+            const size_t m = (size_t)b * max_groups + g;
+            counts[2 * m] = counts[2 * m + 1] = 0u, group_tiles[m] = 0xFFFFFFFFu;
+        }
+        const uint64_t points = (uint64_t)c[0] * c[1], cells = (c[0] > 1 && c[1] > 1) ? (uint64_t)(c[0] - 1) * (c[1] - 1) : 0;
+        if (!cells || (active.empty() ? points : 6 * cells) > vertex_stride || 2 * cells > triangle_stride) continue;
+        const std::vector<float> grid = generate_grid(box, sx, sy);
+        std::vector<float> heights(grid.size() / 2);
+        interpolate_heights(grid.data(), heights.size(), heights.data());
+        Mesh &mesh = meshes[b];
+        mesh.v = apply_exclusions(grid.data(), heights.data(), sx, sy, active);
+        if (active.empty()) {
+            mesh.idx = triangulate(sx, sy);
+        } else {
+            mesh.idx.resize(mesh.v.size() / 3);
+            for (size_t i = 0; i < mesh.idx.size(); ++i) mesh.idx[i] = (uint32_t)i;
+        }
+        mesh.uvs.resize(mesh.v.size() / 3 * 2);
+        for (size_t i = 0; i < mesh.v.size() / 3; ++i) mesh.uvs[2 * i] = mesh.v[3 * i], mesh.uvs[2 * i + 1] = mesh.v[3 * i + 2];   // generate_uvs (:882-888)
+        work += mesh.idx.size() * 64;
+    }
+    // partition_by_tiles, one box a task over the pool (the boxes are independent; inside a box the reference's walk, in its order)
+    std::lock_guard<std::recursive_mutex> lk(g_mu);   // (the worker pool runs one job at a time)
+    rxr_parallel::run(n, work, [&](size_t b) {
+        const Mesh &mesh = meshes[b];
+        if (mesh.idx.empty()) return;
+        const std::vector<TileGroup> groups = partition_by_tiles(mesh.v.data(), mesh.idx.data(), mesh.idx.size(), mesh.uvs.data());
+        if (groups.size() > max_groups) return;
+        box_counts[4 * b + 3] = (uint32_t)groups.size();
+        for (size_t g = 0; g < groups.size(); ++g) {
+            const TileGroup &t = groups[g];
+            const size_t m = b * max_groups + g, nv = t.vertices.size() / 3;
+            counts[2 * m] = (uint32_t)nv, counts[2 * m + 1] = (uint32_t)(t.indices.size() / 3), group_tiles[m] = t.slot;
+            float *o = vertices + m * vertex_stride * 4, *u = uvs_out + m * vertex_stride * 2;
+            for (size_t i = 0; i < nv; ++i) {
+                o[4 * i] = t.vertices[3 * i], o[4 * i + 1] = t.vertices[3 * i + 1], o[4 * i + 2] = t.vertices[3 * i + 2], o[4 * i + 3] = 1.0f;
+                u[2 * i] = t.uvs[2 * i], u[2 * i + 1] = t.uvs[2 * i + 1];
+            }
+            std::copy(t.indices.begin(), t.indices.end(), indices_out + m * triangle_stride * 3);
+        }
+    });
+}
+
+int TerrainGenerator::register_tiles(rxr_ctx *ctx) const {
+    if (g_tiles_gen == generation) return RXR_OK;
+    const int rc = rxr_set_terrain_tiles(ctx, tile_cells.data(), tile_slots.data(), (uint32_t)tile_slots.size(), n_tiles);
+    if (rc != RXR_OK) {
+        g_error = rxr_last_error(ctx);
+        return rc;
+    }
+    g_tiles_gen = generation;
+    return RXR_OK;
+}
+
+int TerrainGenerator::generate_tile_meshes(const float *boxes, uint32_t n, uint32_t max_groups, uint32_t vertex_stride, uint32_t triangle_stride, uint32_t *box_counts,
+                                           uint32_t *counts, uint32_t *group_tiles, float *vertices, float *uvs, uint32_t *indices) const {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::string err;
+    rxr_ctx *ctx = context(&err);
+    if (!ctx) return RXR_ERR_NO_DEVICE;
+    int rc = register_records(ctx);
+    if (rc != RXR_OK || (rc = register_exclusions(ctx)) != RXR_OK || (rc = register_tiles(ctx)) != RXR_OK) return rc;
+    rc = rxr_generated_tile_meshes(ctx, boxes, n, subdivisions, max_groups, vertex_stride, triangle_stride, box_counts, counts, group_tiles, vertices, uvs, indices);
     if (rc != RXR_OK) g_error = rxr_last_error(ctx);
     return rc;
 }

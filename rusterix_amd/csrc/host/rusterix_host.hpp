@@ -295,6 +295,12 @@ public:
     //      geometry replaced and touch()ed: the next upload registers again.
     //   a negative rxr_status otherwise.
     int rebuild_terrain_meshes(const class Terrain &terrain, const int32_t *coords, uint32_t n, const uint32_t *chunks_);
+    // the same for the GENERATED terrain: chunk chunks_[i]'s batches3d -- all of them; terrain_batch3d is an Option and holds one --
+    // are the tile groups of boxes[i] in ascending tile slot (TerrainGenerator::generate_tile_meshes), at most max_groups of them.  Held registration: rxr_generated_tile_meshes_to ->
+    // rxr_vertex_normals_to -> rxr_update_meshes_to on the context's stream, returns 0.  Refused by the update (counts changed), or
+    // no registration held: the batches' geometry is replaced on the host (the CPU partition, Batch3D::compute_vertex_normals),
+    // returns 1, and the next upload registers the scene again.  A chunk whose number of groups changed is RXR_ERR_INVALID.
+    int rebuild_generated_tile_meshes(const class TerrainGenerator &gen, const float *boxes, uint32_t n, const uint32_t *chunks_, uint32_t max_groups);
     // src/scene.rs:203-215: Batch3D::compute_vertex_normals for every batch of d3_static / d3_dynamic.  `route`:
     //   NORMALS_CPU     batch after batch on the calling thread (the reference's loop; where it panics -- an index out of range -- so does this)
     //   NORMALS_POOL    one batch a task over the host's worker pool, as the reference's par_iter_mut (what tools/vertex_normals_bench.py
@@ -453,8 +459,8 @@ private:
 
 // src/chunkbuilder/terrain_generator.rs: the height field of the generated 3D terrain, over the lists TerrainGenerator::generate
 // collects from the Map (:255-294), flattened as rxr_set_terrain_generator takes them (include/rxr.h).  The CPU functions are plain
-// transcriptions (nothing hoisted); the device forms register the lists when they changed.  apply_exclusions is generate_meshes;
-// partition_by_tiles, mesh_fix_winding and the blend batches are the caller's, fed by those meshes.
+// transcriptions (nothing hoisted); the device forms register the lists when they changed.  apply_exclusions is generate_meshes,
+// partition_by_tiles generate_tile_meshes (mesh_fix_winding never swaps such a mesh); the blend batches are the caller's.
 class TerrainGenerator {
 public:
     uint32_t subdivisions = 1;                        // TerrainConfig.subdivisions (:24)
@@ -504,9 +510,37 @@ public:
     // rxr_generated_meshes).  RXR_OK or a negative rxr_status; there is no fall-back to the CPU.
     int generate_meshes(const float *boxes, uint32_t n, uint32_t stride, uint32_t *counts, float *vertices) const;
 
+    // the tile overrides (the reference's FxHashMap<(i32, i32), PixelSource>, every pixel source resolved to a tile SLOT by the
+    // caller, slot 0 the default tile), flattened as rxr_set_terrain_tiles takes them.  RXR_OK, or what rxr_check_terrain_tiles
+    // refuses (nothing changes then)
+    std::vector<int32_t> tile_cells;                  // [N][2]: x, z
+    std::vector<uint32_t> tile_slots;                 // [N]
+    uint32_t n_tiles = 1;
+    std::map<std::pair<int32_t, int32_t>, uint32_t> tile_overrides;   // the same as a map, built by set_tiles (partition_by_tiles looks cells up in it)
+    int set_tiles(const int32_t *cells, const uint32_t *slots, uint32_t n, uint32_t n_tiles_);
+    // partition_by_tiles (:954-1034) over vertices [V][3], indices [3 T] and uvs [V][2], line by line, the dictionary walk included.
+    // The groups come in ascending tile slot (the reference's order is a hash map's)
+    struct TileGroup {
+        uint32_t slot;
+        std::vector<float> vertices, uvs;             // [..][3], [..][2]
+        std::vector<uint32_t> indices;
+    };
+    std::vector<TileGroup> partition_by_tiles(const float *vertices, const uint32_t *indices, size_t n_indices, const float *uvs) const;
+    // n boxes [n][4] on the CPU, in the layout of rxr_generated_tile_meshes (a box whose layout does not fit the strides or
+    // max_groups gets its box_counts with n_groups = 0 and nothing else): heights and keep flags over the worker pool box by box,
+    // then the partition one box a task over the pool
+    void generate_tile_meshes_cpu(const float *boxes, uint32_t n, uint32_t max_groups, uint32_t vertex_stride, uint32_t triangle_stride, uint32_t *box_counts,
+                                  uint32_t *counts, uint32_t *group_tiles, float *vertices, float *uvs, uint32_t *indices) const;
+    // ... and on the device (the three registrations when their lists changed, then rxr_generated_tile_meshes).  RXR_OK or a
+    // negative rxr_status; there is no fall-back to the CPU.
+    int generate_tile_meshes(const float *boxes, uint32_t n, uint32_t max_groups, uint32_t vertex_stride, uint32_t triangle_stride, uint32_t *box_counts,
+                             uint32_t *counts, uint32_t *group_tiles, float *vertices, float *uvs, uint32_t *indices) const;
+
 private:
+    friend class Scene;   // (rebuild_generated_tile_meshes registers the lists)
     int register_records(rxr_ctx *ctx) const;
     int register_exclusions(rxr_ctx *ctx) const;
+    int register_tiles(rxr_ctx *ctx) const;
 };
 
 // src/rasterizer.rs:35-193

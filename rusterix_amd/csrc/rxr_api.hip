@@ -183,7 +183,7 @@ void rxr_destroy(rxr_ctx *ctx) {
                       &ctx->d_isect_tris, &ctx->d_isect_misc, &ctx->d_isect_keys, &ctx->d_accel_tris, &ctx->d_accel_perm, &ctx->d_accel_nodes, &ctx->d_accel_stats, &ctx->d_accel_scratch, &ctx->d_trace_scene, &ctx->d_trace_paths, &ctx->d_trace_keys,
                       &ctx->d_bake_jobs, &ctx->d_bake_fault,
                       &ctx->d_terrain_cells, &ctx->d_terrain_tex, &ctx->d_terrain_texels, &ctx->d_terrain_weights,
-                      &ctx->d_heights, &ctx->d_heights_tk, &ctx->d_heights_mask, &ctx->d_gen, &ctx->d_excl, &ctx->d_excl_scratch, &ctx->d_nrm_scratch, &ctx->ctex.pool, &ctx->ctex.flags};
+                      &ctx->d_heights, &ctx->d_heights_tk, &ctx->d_heights_mask, &ctx->d_gen, &ctx->d_excl, &ctx->d_excl_scratch, &ctx->d_tiles, &ctx->d_nrm_scratch, &ctx->ctex.pool, &ctx->ctex.flags};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (QueryLane &q : ctx->lane) {
@@ -588,6 +588,15 @@ void *rxr_mirror_scratch(rxr_ctx *ctx, size_t bytes) {
     if (hipSetDevice(ctx->device) != hipSuccess) return nullptr;
     if (rxr_ensure(ctx, ctx->d_mirror_scratch, bytes ? bytes : 16) != RXR_OK) return nullptr;
     return ctx->d_mirror_scratch.p;
+}
+
+// ... and a few words of it read back: waits for what the context's stream has queued, then copies.  RXR_OK or a negative rxr_status.
+int rxr_mirror_read(rxr_ctx *ctx, void *host, const void *dev, size_t bytes) {
+    if (!ctx || ctx->group || !host || !dev) return RXR_ERR_INVALID;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return RXR_OK;
 }
 
 // ---- the 2D half of the device-side projection (row N1): Batch2D::project's inputs, registered once ---------------------------

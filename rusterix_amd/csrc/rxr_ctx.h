@@ -346,6 +346,16 @@ struct rxr_ctx {
     std::vector<uint32_t> excl_voff{0u};   // ... and of the vertex offsets (a round's work counts the vertices of a box's active sectors)
     uint32_t excl_launches = 0;       // classification launches of the last mesh call (rxr_debug_terrain_excl_launches)
 
+    // tile overrides of the generated terrain's chunk meshes (rxr_terrain_excl.hip, partition_by_tiles): the resident map of
+    // rxr_set_terrain_tiles, independent of the generator and the exclusions.  d_tiles: the cells' keys [n] (u64: x then z, each
+    // with its sign bit flipped, ascending) and behind them their tile slots [n]; tile_keys / tile_slots: their host copies (how many
+    // groups a chunk box can have is bounded on the host, and decides what the call refuses).
+    DevBuf d_tiles;
+    uint32_t tile_cells = 0, tile_count = 1;
+    std::vector<uint64_t> tile_keys;
+    std::vector<uint32_t> tile_slots;
+    uint32_t tile_launches = 0;       // emission launches of the last tile-mesh call (rxr_debug_terrain_tile_launches)
+
     // vertex normals (rxr_normals.hip): d_nrm_scratch: the general route's face normals, corner keys and values (in and out) and the
     // sort's scratch, reused launch after launch; nothing is resident between calls.
     DevBuf d_nrm_scratch;

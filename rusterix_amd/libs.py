@@ -106,6 +106,11 @@ def rxr_abi():
         "rxr_generated_meshes": (i32, [vp, vp, u32, u32, u32, vp, vp]),
         "rxr_generated_meshes_to": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),
         "rxr_debug_terrain_excl_launches": (u32, [vp]),
+        "rxr_check_terrain_tiles": (i32, [vp, vp, u32, u32, C.c_char_p, u32]),
+        "rxr_set_terrain_tiles": (i32, [vp, vp, vp, u32, u32]),
+        "rxr_generated_tile_meshes": (i32, [vp, vp, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp]),
+        "rxr_generated_tile_meshes_to": (i32, [vp, vp, u32, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp]),
+        "rxr_debug_terrain_tile_launches": (u32, [vp]),
         "rxr_check_vertex_normals": (i32, [vp, vp, u32, u32, u32, C.c_char_p, u32]),
         "rxr_vertex_normals": (i32, [vp, u32, vp, vp, vp, vp, u32, u32]),
         "rxr_vertex_normals_to": (i32, [vp, u32, vp, vp, vp, vp, vp, u32, u32, vp]),

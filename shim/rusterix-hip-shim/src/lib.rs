@@ -224,6 +224,53 @@ pub fn vertex_normals(counts: &[u32], vertices: &[f32], indices: &[u32], normals
     unsafe { rxr_vertex_normals(ctx.0, n as u32, counts.as_ptr(), vertices.as_ptr(), indices.as_ptr(), normals.as_mut_ptr(), vertex_stride, triangle_stride) == RXR_OK }
 }
 
+// ---- generated terrain tile meshes (include/rxr.h rxr_set_terrain_tiles, rxr_generated_tile_meshes) ---------------
+/// Makes the tile overrides of `TerrainGenerator::partition_by_tiles` resident: `cells` [n][2] (x, z of a 1 x 1 world cell) and
+/// `slots` [n], each below `n_tiles`; slot 0 is the default tile and every cell not listed has it.  The caller resolves each
+/// override's `PixelSource` to a tile (`tile_from_tile_list`, else the default) and numbers the tiles.  False: no device context,
+/// slices that do not fit, or the library refused (a cell listed twice, a slot out of range): the resident map is unchanged.
+pub fn set_terrain_tiles(cells: &[i32], slots: &[u32], n_tiles: u32) -> bool {
+    let guard = STATE.lock().unwrap();
+    let Some(ctx) = guard.as_ref().and_then(|st| st.ctx.as_ref()) else { return false };
+    if cells.len() != 2 * slots.len() {
+        return false;
+    }
+    unsafe { rxr_set_terrain_tiles(ctx.0, cells.as_ptr(), slots.as_ptr(), slots.len() as u32, n_tiles) == RXR_OK }
+}
+
+/// The output of `generated_tile_meshes`, mesh slot m = box * max_groups + group, the groups of a box in ascending tile slot.
+pub struct TileMeshes {
+    pub box_counts: Vec<u32>,  // [n][4]: steps_x, steps_y, active_sectors, n_groups
+    pub counts: Vec<u32>,      // [n * max_groups][2]: vertices, triangles
+    pub group_tiles: Vec<u32>, // [n * max_groups]: the tile slot, 0xFFFFFFFF past n_groups
+    pub vertices: Vec<f32>,    // [n * max_groups][vertex_stride][4]: x, h, z, 1.0
+    pub uvs: Vec<f32>,         // [n * max_groups][vertex_stride][2]: x, z
+    pub indices: Vec<u32>,     // [n * max_groups][triangle_stride][3], mesh-local
+}
+
+/// `TerrainGenerator::generate` up to and including `partition_by_tiles` for the chunk boxes `boxes` [n][4] in one device call,
+/// against the generator, exclusions and tiles made resident before.  The layout is what `vertex_normals` and `update_meshes` read.
+/// `None`: no device context, or the library refused (a box that can exceed a stride or `max_groups`, no generator resident).
+pub fn generated_tile_meshes(boxes: &[f32], subdivisions: u32, max_groups: u32, vertex_stride: u32, triangle_stride: u32) -> Option<TileMeshes> {
+    let guard = STATE.lock().unwrap();
+    let ctx = guard.as_ref()?.ctx.as_ref()?;
+    let n = boxes.len() / 4;
+    let (m, vs, ts) = (n * max_groups as usize, vertex_stride as usize, triangle_stride as usize);
+    let mut out = TileMeshes {
+        box_counts: vec![0u32; 4 * n],
+        counts: vec![0u32; 2 * m],
+        group_tiles: vec![0xFFFF_FFFFu32; m],
+        vertices: vec![0f32; m * vs * 4],
+        uvs: vec![0f32; m * vs * 2],
+        indices: vec![0u32; m * ts * 3],
+    };
+    let rc = unsafe {
+        rxr_generated_tile_meshes(ctx.0, boxes.as_ptr(), n as u32, subdivisions, max_groups, vertex_stride, triangle_stride, out.box_counts.as_mut_ptr(),
+                                  out.counts.as_mut_ptr(), out.group_tiles.as_mut_ptr(), out.vertices.as_mut_ptr(), out.uvs.as_mut_ptr(), out.indices.as_mut_ptr())
+    };
+    (rc == RXR_OK).then_some(out)
+}
+
 /// The object-space box (lo, hi) the device context holds for registered mesh `mesh_index` (`rxr_mesh_bounds`): debugging.
 pub fn mesh_bounds(mesh_index: u32) -> Option<([f32; 3], [f32; 3])> {
     let guard = STATE.lock().unwrap();
