@@ -141,6 +141,7 @@ int rxr_create(rxr_ctx **out, int device_id) {
     if (const char *sm = getenv("RXR_SMALL_MODE")) {
         if (sm[0] >= '0' && sm[0] <= '2') ctx->small_mode = (uint32_t)(sm[0] - '0');
     }
+    if (const char *hs = getenv("RXR_HOST_SETUP")) ctx->host_setup_on = hs[0] != '0';  // tests / A-B runs: 0 keeps the k_setup3d launch of small frames
     if (const char *lf = getenv("RXR_LIST_CAPACITY_FLOOR")) {  // tests: a small floor makes ordinary scenes overflow their bin lists
         const long v = atol(lf);
         if (v > 0) ctx->list_floor = (size_t)v;
@@ -893,9 +894,23 @@ static int render_impl(rxr_ctx *ctx, const RenderSpec &spec, void *dev_pixels, h
     const bool d3 = P.tiles_y && (P.flags & RXR_FLAG_D3_ACTIVE);
     P.fused_small = (d3 && P.n_tris3d <= RXR_STAGE_TRIS) ? ctx->small_mode : 0u;
     if (P.kernel_level != KL_COMMON && P.fused_small == 1u) P.fused_small = 2u;  // k_raster_vm reads the records k_setup3d writes
+    ctx->last_setup_route = 0u;
     if (d3 && P.fused_small) {
         if (ctx->frame_uses_meshes) rxr_launch_project(&ctx->PP, s);
-        if (P.fused_small == 2u) rxr_launch_setup(&P, s);  // records only; no counters, bins or lists are touched
+        // The frame's own records, made by rxr_upload_frame for the band [0, height), serve every render whose band starts on a tile row
+        // and ends on one or at the frame's height: the only words of a record that depend on the band are its pixel box's min_y / max_y,
+        // and whatever reads them (visit, the tile reject and covers_plainly of scan_implicit) compares them with rows of launched tiles or
+        // of pixels inside the band -- with the same answer under the whole-frame clamp.  Under any other band a tile's set of active lanes,
+        // and with it the wave votes of the relaxed paths, would differ: such a render keeps the launch with its own clamp.
+        const bool band_on_tiles = P.row0 % RXR_TILE_H == 0u && (P.row1 % RXR_TILE_H == 0u || P.row1 == P.height);
+        if (P.fused_small == 2u && ctx->host_records && band_on_tiles) {
+            P.tri_setup = (TriSetup *)((uint8_t *)ctx->d_frame.p + ctx->off_host_setup);  // (read only: no launch of this render writes records)
+            P.tri_shade = (TriShade *)((uint8_t *)ctx->d_frame.p + ctx->off_host_shade);
+            ctx->last_setup_route = 1u;
+        } else if (P.fused_small == 2u) {
+            rxr_launch_setup(&P, s);  // records only; no counters, bins or lists are touched
+            ctx->last_setup_route = 2u;
+        }
     }
     use_spans = use_spans && rxr_raster_takes_spans(&P) != 0;  // (the kernel this launch gets must be one that looks the table up)
     if (use_spans) {
@@ -953,6 +968,7 @@ static int render_impl(rxr_ctx *ctx, const RenderSpec &spec, void *dev_pixels, h
         if (P.blockscan_scatter) ctx->parity ^= 1u;
         if (ctx->frame_uses_meshes) project_meshes();
         rxr_launch_setup(&P, s);
+        ctx->last_setup_route = 2u;
         rxr_launch_blockscan(&P, s);
     } else if (prepass) {
         ctx->scratch_dirty = true;
@@ -965,6 +981,7 @@ static int render_impl(rxr_ctx *ctx, const RenderSpec &spec, void *dev_pixels, h
         ctx->parity ^= 1u;
         if (ctx->frame_uses_meshes) project_meshes();
         rxr_launch_setup(&P, s);
+        ctx->last_setup_route = 2u;
         ScanArgs A{};
         A.n = P.tiles_x * P.tiles_y;
         A.list_capacity = P.list_capacity;
@@ -2251,6 +2268,48 @@ extern "C" uint32_t rxr_debug_rerenders(rxr_ctx *ctx) { return (ctx && !ctx->gro
 extern "C" const char *rxr_debug_last_raster_kernel(rxr_ctx *ctx) {
     if (ctx && ctx->group) ctx = rxr_member(ctx, 0);
     return ctx ? ctx->last_raster_kernel : "";
+}
+// tests: what the context's most recent render did for the set-up records of a small frame: 0 nothing (no 3D pass, the fused
+// mode), 1 it read the records rxr_upload_frame made on the host, 2 it launched k_setup3d; a multi-device handle answers for member 0
+extern "C" uint32_t rxr_debug_last_setup_route(rxr_ctx *ctx) {
+    if (ctx && ctx->group) ctx = rxr_member(ctx, 0);
+    return ctx ? ctx->last_setup_route : 0u;
+}
+// tests: the resident host-projected frame's set-up records (n x 96 and n x 80 bytes, n = *n_tris <= capacity_tris) as k_setup3d writes them
+// for the whole-frame band -- into zeroed scratch: it leaves the records of a workgroup without a drawable triangle alone -- and, when the
+// frame carries them, as rxr_upload_frame made them on the host, read back from the frame blob.  Returns 1 with both pairs filled, 0 when
+// the frame has no host-made records (only the device's pair is filled), a negative status otherwise (all four pointers are required).
+// CLOBBERS the context's scratch records (zeroed, then whole-frame records): harmless, since every render that reads scratch launches
+// k_setup3d into it first.
+extern "C" int rxr_debug_setup_records(rxr_ctx *ctx, void *host_setup, void *host_shade, void *dev_setup, void *dev_shade, uint32_t capacity_tris,
+                                       uint32_t *n_tris) {
+    if (!ctx || ctx->group || !n_tris || !dev_setup || !dev_shade || !host_setup || !host_shade) return RXR_ERR_INVALID;
+    if (!ctx->has_frame || ctx->frame_uses_meshes) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_debug_setup_records: no host-projected frame");
+    const size_t n = ctx->P.n_tris3d;
+    *n_tris = (uint32_t)n;
+    if (n > capacity_tris) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_debug_setup_records: capacity too small");
+    if (hipSetDevice(ctx->device) != hipSuccess || rxr_quiesce(ctx) != RXR_OK) return RXR_ERR_HIP;
+    if (n) {
+        RasterParams P = ctx->P;
+        P.row0 = 0;
+        P.row1 = P.height;
+        P.tile_y0 = 0;
+        P.tile_stride = 1;
+        P.tiles_y = (P.height + RXR_TILE_H - 1u) / RXR_TILE_H;
+        P.fused_small = 2u;
+        bool ok = hipMemsetAsync(P.tri_setup, 0, n * sizeof(TriSetup), ctx->stream) == hipSuccess &&
+                  hipMemsetAsync(P.tri_shade, 0, n * sizeof(TriShade), ctx->stream) == hipSuccess;
+        if (ok) rxr_launch_setup(&P, ctx->stream);
+        ok = ok && hipGetLastError() == hipSuccess;
+        ok = ok && hipMemcpyAsync(dev_setup, P.tri_setup, n * sizeof(TriSetup), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+        ok = ok && hipMemcpyAsync(dev_shade, P.tri_shade, n * sizeof(TriShade), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+        if (ok && ctx->host_records) {
+            ok = ok && hipMemcpyAsync(host_setup, (uint8_t *)ctx->d_frame.p + ctx->off_host_setup, n * sizeof(TriSetup), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+            ok = ok && hipMemcpyAsync(host_shade, (uint8_t *)ctx->d_frame.p + ctx->off_host_shade, n * sizeof(TriShade), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+        }
+        if (!(hipStreamSynchronize(ctx->stream) == hipSuccess && ok)) return rxr_fail(ctx, RXR_ERR_HIP, "rxr_debug_setup_records: a HIP call failed");
+    }
+    return ctx->host_records ? 1 : 0;
 }
 extern "C" const char *rxr_debug_jit_info(rxr_ctx *ctx) {
     if (!ctx) return "";

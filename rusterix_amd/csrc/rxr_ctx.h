@@ -224,6 +224,14 @@ struct rxr_ctx {
     bool programs_static = false;    // every program of the set has a stack depth that is a function of the pc (tag_static_depths)
     uint32_t small_mode = 2;         // RasterParams.fused_small for frames with <= RXR_STAGE_TRIS triangles;
                                      // RXR_SMALL_MODE=0|1|2 overrides it (tests / A-B runs)
+    // Small host-projected frames (small_mode 2): rxr_upload_frame builds the TriSetup / TriShade records on the host, for the whole-frame
+    // band, into two sections of the frame blob (rxr_tri_records, rxr_device.h); a render whose band lies on tile rows reads them there and
+    // launches no k_setup3d.  The sections are immutable until the next upload.
+    bool host_setup_on = true;       // RXR_HOST_SETUP=0 (read by rxr_create) keeps the launch (tests / A-B runs)
+    bool host_records = false;       // the resident frame carries them ...
+    size_t off_host_setup = 0, off_host_shade = 0;  // ... at these offsets of d_frame
+    uint32_t last_setup_route = 0;   // what the last render did for the set-up records: 0 nothing (no 3D pass), 1 the blob's host-made
+                                     // records, 2 a k_setup3d launch (rxr_debug_last_setup_route: tests)
 
     // device-side projection (rxr_set_meshes)
     std::vector<HostMesh> meshes;

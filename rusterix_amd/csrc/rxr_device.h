@@ -6,6 +6,7 @@
 #ifdef RXR_JIT
 #include "rxr.h"  // (hiprtc: the sources are in-memory headers with plain names, rxr_jit.hip)
 #else
+#include <math.h>  // (rxr_tri_records on the host)
 #include "../../include/rxr.h"
 #endif
 
@@ -366,6 +367,173 @@ struct LightFast {
     uint32_t pad[2];
 };
 static_assert(sizeof(LightFast) == 48, "LightFast: 32 bytes for the loop + 16 for the culling step");
+
+// Edges for one USED triangle slot of mesh M (batch3d.rs:706-739 + edge.rs:12-24) from the x and y of its three projected vertices: the
+// front-facing test, the winding swap of the cull mode, Edges::new([v0,v1,v2], [v1,v2,v0]).  `evis`: edge_visibility of the slot (appended
+// fans: true, :731-732).  Shared by k_proj_edges, by make_setup (rxr_kernels.hip) for frames whose set-up builds the records itself, and by
+// rxr_upload_frame for the small frames whose set-up records the host builds (plain C++: a host compiler reads it too).
+RXR_HD inline rxr_edges edges_from_xy(uint32_t cull_mode, bool evis, float x0, float y0, float x1, float y1, float x2, float y2) {
+    rxr_edges E;
+    // is_front_facing, :742-746
+    const bool front = ((x1 - x0) * (y2 - y0) - (y1 - y0) * (x2 - x0)) > 0.0f;
+    bool visible, swap;
+    if (cull_mode == RXR_CULL_OFF) {
+        swap = front;
+        visible = true;
+    } else if (cull_mode == RXR_CULL_FRONT) {
+        swap = false;
+        visible = !front;
+    } else {
+        swap = front;
+        visible = front;
+    }
+    if (swap) {
+        const float tx = x1, ty = y1;
+        x1 = x2; y1 = y2;
+        x2 = tx; y2 = ty;
+    }
+    // Edges::new([v0,v1,v2], [v1,v2,v0]): a = y1 - y0, b = x0 - x1, c = x1*y0 - y1*x0
+    const float px[3] = {x0, x1, x2}, py[3] = {y0, y1, y2};
+    const float qx[3] = {x1, x2, x0}, qy[3] = {y1, y2, y0};
+    for (int i = 0; i < 3; ++i) {
+        E.a[i] = qy[i] - py[i];
+        E.b[i] = px[i] - qx[i];
+        E.c[i] = qx[i] * py[i] - qy[i] * px[i];
+    }
+    E.visible = (evis && visible) ? 1u : 0u;
+    return E;
+}
+
+// ---- one triangle's TriSetup / TriShade records: THE definition ------------------------------------------------------------------
+// The arithmetic that turns a drawable triangle's fetched values into its two records (per-triangle constants of the reference's
+// per-fragment formulas, rasterizer.rs:989-995, 1054-1072, 1754-1767, and the clamped pixel box, :998-1017 with the tile replaced
+// by whole width x row band).  make_setup (rxr_kernels.hip) fetches on the device and calls it; rxr_upload_frame (rxr_upload.hip)
+// calls it on the host for small host-projected frames, whose records then travel in the frame blob and need no set-up launch.
+// Host and device code are compiled with -ffp-contract=off and without fast-math and the operators below are correctly rounded on
+// both sides: the same expression gives the same float (tests/test_gpu_host_setup.py compares the records byte for byte).
+// TriShade's two spare words carry the batch's texture descriptor (shade3d_begin)
+#ifndef TS_DESC_VALID
+#define TS_DESC_VALID 0x80000000u
+#endif
+// Rust's `x as u32` (saturating, NaN -> 0), the one definition: the compare-and-select form, and on the device the conversion
+// instruction that does exactly that (rxr_exact_math.h: rxm::sat_u32_ref / rxm::sat_u32 are these two; rxr_selftest_math compares them)
+RXR_HD inline uint32_t rxr_as_u32_ref(float x) {
+    if (!(x > 0.0f)) return 0u;  // NaN, negatives, zero
+    if (x >= 4294967296.0f) return 0xFFFFFFFFu;
+    return (uint32_t)x;
+}
+RXR_HD inline uint32_t rxr_as_u32(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t r;
+    asm("v_cvt_u32_f32_e32 %0, %1" : "=v"(r) : "v"(x));
+    return r;
+#else
+    return rxr_as_u32_ref(x);
+#endif
+}
+// ... then clamped to an index range (`as usize` behind a clamp against the screen or a texture's size)
+RXR_HD inline uint32_t rxr_sat_index(float x, uint32_t hi) {
+    const uint32_t r = rxr_as_u32(x);
+    return r < hi ? r : hi;
+}
+struct TriRecordIn {
+    float v[3][4];          // projected vertices
+    float uv[3][2];
+    float n[3][3];          // zeros for a batch without DB_HAS_NORMALS
+    rxr_edges E;            // (visible: the caller has looked)
+    uint32_t batch;         // index of the batch, and of its header: flags, profile id, texel source, repeat mode
+    uint32_t bflags, profile_id, repeat_mode;
+    int32_t tex;
+    DevTexDesc desc;        // DevTexDesc[tex]; read only for a plain texture (tex >= 0, no DB_TERRAIN, repeat_mode < 4)
+    uint32_t sample_mode;   // RasterParams.sample_mode (the NaN-uv rule)
+    uint32_t width, row0, row1;  // the pixel box is clamped to [0, width) x [row0, row1)
+    uint32_t has_clip;      // ... and, for a batch whose box test needs it, to the pixels the reference draws the batch in
+    uint32_t clip[4];       // x0, x1, y0, y1
+};
+// false: no pixel can be produced (empty box); the records are complete all the same
+RXR_HD inline bool rxr_tri_records(const TriRecordIn &in, TriSetup &S, TriShade &H) {
+    const float *v0 = in.v[0], *v1 = in.v[1], *v2 = in.v[2];
+    for (int k = 0; k < 3; ++k) {
+        S.ea[k] = in.E.a[k];
+        S.eb[k] = in.E.b[k];
+        S.ec[k] = in.E.c[k];
+    }
+    S.v0x = v0[0]; S.v0y = v0[1]; S.v1x = v1[0]; S.v1y = v1[1]; S.v2x = v2[0]; S.v2y = v2[1];
+    {
+        float acx = v2[0] - v0[0], acy = v2[1] - v0[1], abx = v1[0] - v0[0], aby = v1[1] - v0[1];
+        S.area = acx * aby - acy * abx;
+    }
+    S.iz0 = 1.0f / v0[2];
+    S.iz1 = 1.0f / v1[2];
+    S.iz2 = 1.0f / v2[2];
+    S.batch = in.batch;
+    S.bflags = in.bflags;
+    S.profile_id = in.profile_id;
+
+    H.iw0 = 1.0f / v0[3];
+    H.iw1 = 1.0f / v1[3];
+    H.iw2 = 1.0f / v2[3];
+    H.u0w = in.uv[0][0] / v0[3]; H.u1w = in.uv[1][0] / v1[3]; H.u2w = in.uv[2][0] / v2[3];
+    H.v0w = in.uv[0][1] / v0[3]; H.v1w = in.uv[1][1] / v1[3]; H.v2w = in.uv[2][1] / v2[3];
+    for (int k = 0; k < 3; ++k) {
+        H.n0[k] = in.n[0][k];
+        H.n1[k] = in.n[1][k];
+        H.n2[k] = in.n[2][k];
+    }
+    H.pad[0] = H.pad[1] = 0;
+    // The batch's texture descriptor rides in the record's two spare words (TS_DESC_VALID | w | h << 13 | repeat mode << 26 | the
+    // descriptor's two flag bits << 28; the texel offset in the other word): the shading pass goes from the winner's record -- whose
+    // load it has long issued -- straight to the texels, instead of batch header -> descriptor -> texels: two dependent round trips
+    // fewer in front of every texel (shade3d_begin).  Plain textures of at most 8191 x 8191 texels; everything else (constant pixels,
+    // terrain, larger textures) leaves the words zero and takes the header's way.
+    if (in.tex >= 0 && !(in.bflags & DB_TERRAIN) && in.repeat_mode < 4u) {
+        const DevTexDesc d = in.desc;
+        if (d.w - 1u < 8191u && d.h - 1u < 8191u) {
+            H.pad[0] = d.offset;
+            H.pad[1] = TS_DESC_VALID | d.w | (d.h << 13) | (in.repeat_mode << 26) | ((d.all_opaque & 3u) << 28);
+        }
+    }
+    // Bilinear sampling turns a NaN texture coordinate into NaN in EVERY channel (texture.rs:414-460: v00 + dx * (v10 - v00)), alpha
+    // included, and `NaN as u8` is 0: such a fragment is not written (:1408) even when every texel of its texture is opaque -- the one
+    // case in which a batch without DB_ALPHA_TEST needs the per-fragment test all the same.  A coordinate is NaN only when the
+    // perspective terms misbehave (a vertex on the eye plane: 1 / w = inf, uv / w = inf or NaN; 1 / w of both signs: the interpolated
+    // 1 / w can vanish; a ratio beyond 2^20 between them: the quotient can overflow), so the TRIANGLE carries the flag: it then walks
+    // with the cut-outs and its fragments are sampled in the visibility pass.  (Nearest sampling reads a texel for any coordinate.)
+    if (in.sample_mode != RXR_SAMPLE_NEAREST && in.tex >= 0 && !(S.bflags & (DB_ALPHA_TEST | DB_FULL_ALPHA | DB_OPACITY_LIST))) {
+        const float t9[9] = {H.iw0, H.iw1, H.iw2, H.u0w, H.u1w, H.u2w, H.v0w, H.v1w, H.v2w};
+        bool risky = false;
+        for (int k = 0; k < 9; ++k) risky = risky || !(__builtin_fabsf(t9[k]) < __builtin_huge_valf());   // inf or NaN
+        const float lo = fminf(__builtin_fabsf(H.iw0), fminf(__builtin_fabsf(H.iw1), __builtin_fabsf(H.iw2)));
+        const float hi = fmaxf(__builtin_fabsf(H.iw0), fmaxf(__builtin_fabsf(H.iw1), __builtin_fabsf(H.iw2)));
+        const bool same_sign = (H.iw0 > 0.0f && H.iw1 > 0.0f && H.iw2 > 0.0f) || (H.iw0 < 0.0f && H.iw1 < 0.0f && H.iw2 < 0.0f);
+        risky = risky || !same_sign || !(hi <= lo * 1048576.0f);
+#ifndef RXR_TEST_NO_NAN_UV_RULE   // (a build that undoes the rule: tests/test_gpu_special_inputs.py and the seed in tests/test_gpu_rows.py must notice)
+        if (risky) S.bflags |= DB_ALPHA_TEST;
+#endif
+    }
+
+    // clamped pixel box, rasterizer.rs:998-1017 with the tile replaced by (whole width) x (row band); `as usize`, then the 16-bit fields
+    float min_xf = fminf(v0[0], fminf(v1[0], v2[0])), max_xf = fmaxf(v0[0], fmaxf(v1[0], v2[0]));
+    float min_yf = fminf(v0[1], fminf(v1[1], v2[1])), max_yf = fmaxf(v0[1], fmaxf(v1[1], v2[1]));
+    uint32_t min_x = rxr_sat_index(fmaxf(floorf(min_xf), 0.0f), 0xFFFFu);
+    uint32_t max_x = rxr_sat_index(fminf(ceilf(max_xf), (float)in.width), 0xFFFFu);
+    uint32_t min_y = rxr_sat_index(fmaxf(floorf(min_yf), (float)in.row0), 0xFFFFu);
+    uint32_t max_y = rxr_sat_index(fminf(ceilf(max_yf), (float)in.row1), 0xFFFFu);
+    // only the pixels of the tiles that pass the reference's batch box test (rxr_ref_tile_span above), for a batch whose box
+    // arithmetic that test cannot be trusted with -- and for every batch of a launch narrowed to row spans: the spans are made of these
+    // rectangles, so a triangle is then counted only into bins whose workgroups run and hand them back zeroed (the box of an ordinary
+    // batch can end short of its triangles: `x + width` rounds below the maximum, or a caller's box does not enclose them)
+    if (in.has_clip) {
+        min_x = min_x > in.clip[0] ? min_x : in.clip[0];
+        max_x = max_x < in.clip[1] ? max_x : in.clip[1];
+        min_y = min_y > in.clip[2] ? min_y : in.clip[2];
+        max_y = max_y < in.clip[3] ? max_y : in.clip[3];
+    }
+    const bool live = min_x < max_x && min_y < max_y;
+    S.bx = live ? (min_x | (max_x << 16)) : 0u;
+    S.by = live ? (min_y | (max_y << 16)) : 0u;
+    return live;
+}
 
 // kernel parameter block (passed by value; lives in the kernarg segment -> scalar loads)
 #if defined(__HIPCC__) || defined(RXR_JIT)  // (HIP's vector types: a plain C++ compiler gets everything above)

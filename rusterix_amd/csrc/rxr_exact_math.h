@@ -26,6 +26,7 @@
 #ifndef RXR_JIT
 #include <hip/hip_runtime.h>
 #endif
+#include "rxr_device.h"  // (rxr_as_u32: the one definition of Rust's saturating cast)
 
 namespace rxm {
 
@@ -222,16 +223,9 @@ __device__ __forceinline__ void normalize3_z(float x, float y, float z, float &o
 // of range, so the compiler may not be asked for it; the instruction is named directly.  Checked against the compare-and-
 // select form over a strided sweep of ALL float bit patterns in every test run (rxr_selftest_math, kind 10).
 // sat_u32_ref is that compare-and-select form.
-__device__ __forceinline__ uint32_t sat_u32_ref(float x) {
-    if (!(x > 0.0f)) return 0u;  // NaN, negatives, zero
-    if (x >= 4294967296.0f) return 0xFFFFFFFFu;
-    return (uint32_t)x;
-}
-__device__ __forceinline__ uint32_t sat_u32(float x) {
-    uint32_t r;
-    asm("v_cvt_u32_f32_e32 %0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
+// (both are defined in rxr_device.h, where the host's set-up records need the cast too)
+__device__ __forceinline__ uint32_t sat_u32_ref(float x) { return rxr_as_u32_ref(x); }
+__device__ __forceinline__ uint32_t sat_u32(float x) { return rxr_as_u32(x); }
 
 // Maximum over the 64 lanes of a wave of NON-NEGATIVE floats (+0, denormals, normals, +inf: their order is the order of their bit
 // patterns as unsigned integers), returned in a scalar register.  Six v_max_u32 with DPP operands -- inside each quad, across the

@@ -36,9 +36,6 @@
 #include "rxr_route.h"
 #endif
 
-// TriShade's two spare words carry the batch's texture descriptor (make_setup, shade3d_begin)
-#define TS_DESC_VALID 0x80000000u
-
 #include "rxr_device.h"
 #include "rxr_exact_math.h"
 #include "rxr_project.h"
@@ -195,7 +192,7 @@ __device__ __forceinline__ uint32_t sat_u8(float x) { return min(rxm::sat_u32(x)
 __device__ __forceinline__ float byte_over_255(uint32_t b) { return rxm::div1_known((float)b, 255.0f, true); }
 __device__ __forceinline__ uint32_t sat_u32(float x) { return rxm::sat_u32(x); }
 // `x as usize` followed by a clamp to [0, hi] (hi < 2^31)
-__device__ __forceinline__ uint32_t sat_index(float x, uint32_t hi) { return min(rxm::sat_u32(x), hi); }
+__device__ __forceinline__ uint32_t sat_index(float x, uint32_t hi) { return rxr_sat_index(x, hi); }
 
 // lib.rs:64-68
 __device__ __forceinline__ uint32_t f32_to_u8_saturated(float x) {
@@ -1226,107 +1223,56 @@ __device__ __forceinline__ bool make_setup(const RasterParams &P, uint32_t t, Tr
         return false;
     }
 
+    // the fetch; the arithmetic is rxr_tri_records (rxr_device.h), which the host runs as well for the frames whose records it builds
     const uint32_t i0 = ix0 + vbase, i1 = ix1 + vbase, i2 = ix2 + vbase;
-    float4 v0 = P.pv[i0], v1 = P.pv[i1], v2 = P.pv[i2];
-
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        S.ea[k] = E.a[k];
-        S.eb[k] = E.b[k];
-        S.ec[k] = E.c[k];
-    }
-    S.v0x = v0.x; S.v0y = v0.y; S.v1x = v1.x; S.v1y = v1.y; S.v2x = v2.x; S.v2y = v2.y;
-    {
-        float acx = v2.x - v0.x, acy = v2.y - v0.y, abx = v1.x - v0.x, aby = v1.y - v0.y;
-        S.area = acx * aby - acy * abx;
-    }
-    S.iz0 = 1.0f / v0.z;
-    S.iz1 = 1.0f / v1.z;
-    S.iz2 = 1.0f / v2.z;
-    S.batch = lo;
-    S.bflags = B.flags;
-    S.profile_id = B.profile_id;
-
-    H.iw0 = 1.0f / v0.w;
-    H.iw1 = 1.0f / v1.w;
-    H.iw2 = 1.0f / v2.w;
-    float2 uv0 = P.uv[i0], uv1 = P.uv[i1], uv2 = P.uv[i2];
-    H.u0w = uv0.x / v0.w; H.u1w = uv1.x / v1.w; H.u2w = uv2.x / v2.w;
-    H.v0w = uv0.y / v0.w; H.v1w = uv1.y / v1.w; H.v2w = uv2.y / v2.w;
+    const float4 v0 = P.pv[i0], v1 = P.pv[i1], v2 = P.pv[i2];
+    const float2 uv0 = P.uv[i0], uv1 = P.uv[i1], uv2 = P.uv[i2];
+    TriRecordIn in;
+    in.v[0][0] = v0.x; in.v[0][1] = v0.y; in.v[0][2] = v0.z; in.v[0][3] = v0.w;
+    in.v[1][0] = v1.x; in.v[1][1] = v1.y; in.v[1][2] = v1.z; in.v[1][3] = v1.w;
+    in.v[2][0] = v2.x; in.v[2][1] = v2.y; in.v[2][2] = v2.z; in.v[2][3] = v2.w;
+    in.uv[0][0] = uv0.x; in.uv[0][1] = uv0.y; in.uv[1][0] = uv1.x; in.uv[1][1] = uv1.y; in.uv[2][0] = uv2.x; in.uv[2][1] = uv2.y;
     if (B.flags & DB_HAS_NORMALS) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            H.n0[k] = P.nrm[3 * (size_t)i0 + k];
-            H.n1[k] = P.nrm[3 * (size_t)i1 + k];
-            H.n2[k] = P.nrm[3 * (size_t)i2 + k];
+            in.n[0][k] = P.nrm[3 * (size_t)i0 + k];
+            in.n[1][k] = P.nrm[3 * (size_t)i1 + k];
+            in.n[2][k] = P.nrm[3 * (size_t)i2 + k];
         }
     } else {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) H.n0[k] = H.n1[k] = H.n2[k] = 0.0f;
+        for (int k = 0; k < 3; ++k) in.n[0][k] = in.n[1][k] = in.n[2][k] = 0.0f;
     }
-    H.pad[0] = H.pad[1] = 0;
-    // The batch's texture descriptor rides in the record's two spare words (TS_DESC_VALID | w | h << 13 | repeat mode << 26 | the
-    // descriptor's two flag bits << 28; the texel offset in the other word): the shading pass goes from the winner's record -- whose
-    // load it has long issued -- straight to the texels, instead of batch header -> descriptor -> texels: two dependent round trips
-    // fewer in front of every texel (shade3d_begin).  Plain textures of at most 8191 x 8191 texels; everything else (constant pixels,
-    // terrain, larger textures) leaves the words zero and takes the header's way.
-    if (B.tex >= 0 && !(B.flags & DB_TERRAIN) && B.repeat_mode < 4u) {
-        const DevTexDesc d = P.tex[B.tex];
-        if (d.w - 1u < 8191u && d.h - 1u < 8191u) {
-            H.pad[0] = d.offset;
-            H.pad[1] = TS_DESC_VALID | d.w | (d.h << 13) | (B.repeat_mode << 26) | ((d.all_opaque & 3u) << 28);
-        }
-    }
-    // Bilinear sampling turns a NaN texture coordinate into NaN in EVERY channel (texture.rs:414-460: v00 + dx * (v10 - v00)), alpha
-    // included, and `NaN as u8` is 0: such a fragment is not written (:1408) even when every texel of its texture is opaque -- the one
-    // case in which a batch without DB_ALPHA_TEST needs the per-fragment test all the same.  A coordinate is NaN only when the
-    // perspective terms misbehave (a vertex on the eye plane: 1 / w = inf, uv / w = inf or NaN; 1 / w of both signs: the interpolated
-    // 1 / w can vanish; a ratio beyond 2^20 between them: the quotient can overflow), so the TRIANGLE carries the flag: it then walks
-    // with the cut-outs and its fragments are sampled in the visibility pass.  (Nearest sampling reads a texel for any coordinate.)
-    if (P.sample_mode != RXR_SAMPLE_NEAREST && B.tex >= 0 && !(S.bflags & (DB_ALPHA_TEST | DB_FULL_ALPHA | DB_OPACITY_LIST))) {
-        const float t9[9] = {H.iw0, H.iw1, H.iw2, H.u0w, H.u1w, H.u2w, H.v0w, H.v1w, H.v2w};
-        bool risky = false;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) risky = risky || !(__builtin_fabsf(t9[k]) < __builtin_huge_valf());   // inf or NaN
-        const float lo = fminf(__builtin_fabsf(H.iw0), fminf(__builtin_fabsf(H.iw1), __builtin_fabsf(H.iw2)));
-        const float hi = fmaxf(__builtin_fabsf(H.iw0), fmaxf(__builtin_fabsf(H.iw1), __builtin_fabsf(H.iw2)));
-        const bool same_sign = (H.iw0 > 0.0f && H.iw1 > 0.0f && H.iw2 > 0.0f) || (H.iw0 < 0.0f && H.iw1 < 0.0f && H.iw2 < 0.0f);
-        risky = risky || !same_sign || !(hi <= lo * 1048576.0f);
-#ifndef RXR_TEST_NO_NAN_UV_RULE   // (a build that undoes the rule: tests/test_gpu_special_inputs.py and the seed in tests/test_gpu_rows.py must notice)
-        if (risky) S.bflags |= DB_ALPHA_TEST;
-#endif
-    }
-
-    // clamped pixel box, rasterizer.rs:998-1017 with the tile replaced by (whole width) x (row band)
-    float min_xf = fminf(v0.x, fminf(v1.x, v2.x)), max_xf = fmaxf(v0.x, fmaxf(v1.x, v2.x));
-    float min_yf = fminf(v0.y, fminf(v1.y, v2.y)), max_yf = fmaxf(v0.y, fmaxf(v1.y, v2.y));
-    uint32_t min_x = sat_index(fmaxf(floorf(min_xf), 0.0f), 0xFFFFu);
-    uint32_t max_x = sat_index(fminf(ceilf(max_xf), (float)P.width), 0xFFFFu);
-    uint32_t min_y = sat_index(fmaxf(floorf(min_yf), (float)P.row0), 0xFFFFu);
-    uint32_t max_y = sat_index(fminf(ceilf(max_yf), (float)P.row1), 0xFFFFu);
-    // only the pixels of the tiles that pass the reference's batch box test (rxr_device.h, rxr_ref_tile_span), for a batch whose box
-    // arithmetic that test cannot be trusted with -- and for every batch of a launch narrowed to row spans: the spans are made of these
-    // rectangles, so a triangle is then counted only into bins whose workgroups run and hand them back zeroed (the box of an ordinary
-    // batch can end short of its triangles: `x + width` rounds below the maximum, or a caller's box does not enclose them)
+    in.E = E;
+    in.batch = lo;
+    in.bflags = B.flags;
+    in.profile_id = B.profile_id;
+    in.repeat_mode = B.repeat_mode;
+    in.tex = B.tex;
+    in.desc = DevTexDesc{};
+    if (B.tex >= 0 && !(B.flags & DB_TERRAIN) && B.repeat_mode < 4u) in.desc = P.tex[B.tex];
+    in.sample_mode = P.sample_mode;
+    in.width = P.width;
+    in.row0 = P.row0;
+    in.row1 = P.row1;
+    // the clip rectangle of the pixel box (rxr_tri_records): the pixels of the tiles that pass the reference's batch box test
+    in.has_clip = 0u;
+    in.clip[0] = in.clip[1] = in.clip[2] = in.clip[3] = 0u;
     if (P.batch_clip3d) {   // uniform: host-projected, some batch is risky or the frame takes row spans
         const uint4 c = P.batch_clip3d[lo];
-        min_x = max(min_x, c.x); max_x = min(max_x, c.y); min_y = max(min_y, c.z); max_y = min(max_y, c.w);
+        in.has_clip = 1u;
+        in.clip[0] = c.x; in.clip[1] = c.y; in.clip[2] = c.z; in.clip[3] = c.w;
     } else if (P.dev_bbox) {   // device-projected: the box is here
         const DevBBox bb = P.dev_bbox[lo];
         auto dec = [](uint32_t e) { return __uint_as_float((e & 0x80000000u) ? (e ^ 0x80000000u) : ~e); };
         const float bx = dec(bb.min_x), by = dec(bb.min_y), bw = dec(bb.max_x) - bx, bh = dec(bb.max_y) - by;
         if (P.row_spans || rxr_box_is_risky(bx, by, bw, bh)) {   // (row_spans: k_spans_from_meshes made them from these boxes, the same way)
-            uint32_t x0, x1, y0, y1;
-            rxr_ref_tile_span_quick(bx, bw, P.width, P.ref_tile, 0.0f, x0, x1);
-            rxr_ref_tile_span_quick(by, bh, P.height, P.ref_tile, 0.0f, y0, y1);
-            min_x = max(min_x, x0); max_x = min(max_x, x1); min_y = max(min_y, y0); max_y = min(max_y, y1);
+            in.has_clip = 1u;
+            rxr_ref_tile_span_quick(bx, bw, P.width, P.ref_tile, 0.0f, in.clip[0], in.clip[1]);
+            rxr_ref_tile_span_quick(by, bh, P.height, P.ref_tile, 0.0f, in.clip[2], in.clip[3]);
         }
     }
-
-    bool live = min_x < max_x && min_y < max_y;
-    S.bx = live ? (min_x | (max_x << 16)) : 0u;
-    S.by = live ? (min_y | (max_y << 16)) : 0u;
-    return live;
+    return rxr_tri_records(in, S, H);
 }
 
 }  // namespace

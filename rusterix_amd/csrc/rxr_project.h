@@ -8,6 +8,7 @@
 #else
 #include "../../include/rxr.h"
 #endif
+#include "rxr_device.h"
 
 // Output layout per mesh (capacity based, so that triangle ids keep the reference's submission order
 // without a cross-mesh compaction): vertices [vout_base, vout_base + n_verts + 4*n_tris),
@@ -71,40 +72,9 @@ struct ProjectParams {
 };
 
 #if defined(__HIPCC__) || defined(RXR_JIT)
-// Edges for one USED triangle slot of mesh M (batch3d.rs:706-739 + edge.rs:12-24) from its three projected vertices: the front-facing
-// test, the winding swap of the cull mode, Edges::new([v0,v1,v2], [v1,v2,v0]).  `evis`: edge_visibility of the slot (appended fans:
-// true, :731-732).  Shared by k_proj_edges and, for frames whose set-up builds the records itself, make_setup (rxr_kernels.hip).
-__device__ __forceinline__ rxr_edges edges_from_vertices(uint32_t cull_mode, bool evis, float4 v0, float4 v1, float4 v2) {
-    rxr_edges E;
-    // is_front_facing, :742-746
-    const bool front = ((v1.x - v0.x) * (v2.y - v0.y) - (v1.y - v0.y) * (v2.x - v0.x)) > 0.0f;
-    bool visible, swap;
-    if (cull_mode == RXR_CULL_OFF) {
-        swap = front;
-        visible = true;
-    } else if (cull_mode == RXR_CULL_FRONT) {
-        swap = false;
-        visible = !front;
-    } else {
-        swap = front;
-        visible = front;
-    }
-    if (swap) {
-        const float4 tmp = v1;
-        v1 = v2;
-        v2 = tmp;
-    }
-    // Edges::new([v0,v1,v2], [v1,v2,v0]): a = y1 - y0, b = x0 - x1, c = x1*y0 - y1*x0
-    const float px[3] = {v0.x, v1.x, v2.x}, py[3] = {v0.y, v1.y, v2.y};
-    const float qx[3] = {v1.x, v2.x, v0.x}, qy[3] = {v1.y, v2.y, v0.y};
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        E.a[i] = qy[i] - py[i];
-        E.b[i] = px[i] - qx[i];
-        E.c[i] = qx[i] * py[i] - qy[i] * px[i];
-    }
-    E.visible = (evis && visible) ? 1u : 0u;
-    return E;
+// (edges_from_xy, rxr_device.h: Edges::new behind the winding swap of the cull mode, shared with the host)
+RXR_HD __forceinline__ rxr_edges edges_from_vertices(uint32_t cull_mode, bool evis, float4 v0, float4 v1, float4 v2) {
+    return edges_from_xy(cull_mode, evis, v0.x, v0.y, v1.x, v1.y, v2.x, v2.y);
 }
 #endif
 

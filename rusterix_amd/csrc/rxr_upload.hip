@@ -11,6 +11,7 @@
 
 #include "../../include/rusterix_vek.hpp"  // host-side Mat4 products for the device-projection path
 #include "rxr_ctx.h"
+#include "rxr_host_setup.h"
 #include "rxr_parallel.h"
 
 extern "C" uint32_t rxr_span_meshes_max(void);
@@ -63,7 +64,7 @@ static void light_fast_record(const rxr_light &l, uint32_t hash_anim, LightFast 
 }
 
 struct Layout {
-    size_t off_b3, off_base, off_pv, off_uv, off_nrm, off_idx, off_edges, off_tinfo, off_clip3d, off_lights, off_lights_fast, off_occ, off_ld, off_chunks, off_tdesc,
+    size_t off_b3, off_base, off_pv, off_uv, off_nrm, off_idx, off_edges, off_tinfo, off_host_setup, off_host_shade, off_clip3d, off_lights, off_lights_fast, off_occ, off_ld, off_chunks, off_tdesc,
         off_ltex, off_b2, off_p2, off_bg, total;
 };
 
@@ -593,6 +594,11 @@ struct FrameBuild {
     long span_budget = 400000;  // row updates
     Layout L{};
     bool with_tri_info = false, any_risky3d = false, with_clip3d = false;  // (lay_out)
+    // a small host-projected frame: the TriSetup / TriShade records are built here, for the band [0, height), and travel in the blob --
+    // its renders on tile rows launch no k_setup3d (lay_out; build_setup_records; render_impl)
+    bool host_setup = false;
+    uint32_t d2_box[4] = {0xFFFFu, 0u, 0xFFFFu, 0u};  // union of the 2D primitives' pixel boxes (fold_d2_box)
+    bool d2_folded = false;
     uint8_t *st = nullptr;  // ctx->h_stage, once it is large enough (reserve), and the sections the phases share (clip3d: null without with_clip3d)
     DevBatch *b3 = nullptr; uint32_t *base = nullptr; uint4 *clip3d = nullptr; Prim2D *p2 = nullptr;
     size_t p2cur = 0, t2cur = 0;
@@ -866,6 +872,12 @@ struct FrameBuild {
         BlobCursor take = streamed ? layout_prefix(n_b3, S.total_cap_v, S.total_cap_t, L) : layout_prefix(n_b3, n_v3, n_t3, L);
         with_tri_info = !use_meshes && n_t3 > 0 && n_t3 <= RXR_TRI_INFO_MAX;
         L.off_tinfo = take(with_tri_info ? n_t3 * sizeof(uint2) : 0);
+        // (not a streamed hand-over: its arrays may have left for the device out of the caller's page-locked memory, never read here)
+        host_setup = ctx->host_setup_on && ctx->small_mode == 2u && !use_meshes && !streamed && n_t3 > 0 && n_t3 <= RXR_STAGE_TRIS;
+        if (host_setup) {  // (no other frame's blob changes)
+            L.off_host_setup = take(n_t3 * sizeof(TriSetup));
+            L.off_host_shade = take(n_t3 * sizeof(TriShade));
+        }
         // host-projected 3D batches: per batch the pixels the reference draws it in (rxr_ref_tile_span), to which make_setup clips the pixel
         // boxes of its triangles.  Needed for a batch whose bounding-box arithmetic the reference's per-tile test cannot be trusted with
         // (rxr_device.h), and for EVERY batch of a frame whose raster grid is narrowed to row spans (spans_active, decided below from the same
@@ -1261,6 +1273,33 @@ struct FrameBuild {
         return RXR_OK;
     }
 
+    // The set-up records of a small host-projected frame, by the function that defines them (rxr_tri_records, rxr_device.h): what
+    // k_setup3d would write for the band [0, height), from the same values -- the arrays, headers, descriptors, the triangle table and
+    // the clip rectangles as the earlier phases have put them into the staging blob, indexed the way make_setup indexes them on the
+    // device.  A triangle that can never produce a pixel (invisible edge record, skipped batch) keeps an all-zero record, as there.
+    // Needs to know whether the frame takes row spans (content_rows_and_spans): every pixel box is then clipped to its batch's tiles.
+    void build_setup_records() {
+        TriSetup *ts = (TriSetup *)(st + L.off_host_setup);
+        TriShade *th = (TriShade *)(st + L.off_host_shade);
+        memset(ts, 0, n_t3 * sizeof(TriSetup));
+        memset(th, 0, n_t3 * sizeof(TriShade));
+        HostSetupSource src{};
+        src.pv = (const float *)(st + L.off_pv);
+        src.uv = (const float *)(st + L.off_uv);
+        src.nrm = (const float *)(st + L.off_nrm);
+        src.idx = (const uint32_t *)(st + L.off_idx);
+        src.edges = st + L.off_edges;
+        src.edgeless = edgeless3d == 1;
+        src.tri_info = (const uint32_t *)(st + L.off_tinfo);
+        src.batches = b3;
+        src.tex = (const DevTexDesc *)(st + L.off_tdesc);
+        src.clip = (any_risky3d || ctx->spans_active) ? (const uint32_t *)clip3d : nullptr;  // (RasterParams.batch_clip3d != NULL)
+        src.sample_mode = f->sample_mode;
+        src.width = f->width;
+        src.height = f->height;
+        for (size_t t = 0; t < n_t3; ++t) rxr_host_tri_records(src, t, ts[t], th[t]);
+    }
+
     int ship_blob() {
         if (arrays_shipped) {
             // the projected arrays [off_pv, off_tinfo) left while they were being copied; what surrounds them follows
@@ -1270,6 +1309,26 @@ struct FrameBuild {
             HIPCHK(ctx, hipMemcpyAsync(ctx->d_frame.p, st, L.total, hipMemcpyHostToDevice, ctx->stream));
         }
         return RXR_OK;
+    }
+
+    // tiles outside the union of the 2D pixel boxes skip the 2D pass without touching memory; the union also belongs to the content rows
+    // and the row spans (once per upload: before content_rows_and_spans, wherever that runs)
+    void fold_d2_box() {
+        if (d2_folded) return;
+        d2_folded = true;
+        uint32_t bx0 = 0xFFFFu, bx1 = 0, by0 = 0xFFFFu, by1 = 0;
+        for (size_t i = 0; i < (use_meshes2d ? 0 : p2cur); ++i) {  // (device-projected: the records do not exist yet -- RasterParams.d2_box_dev)
+            uint32_t a = p2[i].bx & 0xFFFFu, b = p2[i].bx >> 16, c = p2[i].by & 0xFFFFu, d = p2[i].by >> 16;
+            if (a < b && c < d) {
+                bx0 = std::min(bx0, a); bx1 = std::max(bx1, b); by0 = std::min(by0, c); by1 = std::max(by1, d);
+            }
+        }
+        d2_box[0] = bx0; d2_box[1] = bx1; d2_box[2] = by0; d2_box[3] = by1;
+        if (by0 < by1) {  // (the 2D pass only ever writes inside its primitives' pixel boxes)
+            content_y0 = std::min(content_y0, by0);
+            content_y1 = std::max(content_y1, std::min(by1, f->height));
+            add_span(bx0, std::min(bx1, f->width), by0, std::min(by1, f->height));
+        }
     }
 
     int fill_raster_params() {
@@ -1370,23 +1429,9 @@ struct FrameBuild {
         P.vm_fault = ctx->d_host_status + HS_VM_FAULT;
         P.staircase_overflow = ctx->d_host_status + HS_STAIRCASE;
         P.time = f->time;
-        {
-            // tiles outside the union of the 2D pixel boxes skip the 2D pass without touching memory
-            uint32_t bx0 = 0xFFFFu, bx1 = 0, by0 = 0xFFFFu, by1 = 0;
-            for (size_t i = 0; i < (use_meshes2d ? 0 : p2cur); ++i) {  // (device-projected: the records do not exist yet -- d2_box_dev below)
-                uint32_t a = p2[i].bx & 0xFFFFu, b = p2[i].bx >> 16, c = p2[i].by & 0xFFFFu, d = p2[i].by >> 16;
-                if (a < b && c < d) {
-                    bx0 = std::min(bx0, a); bx1 = std::max(bx1, b); by0 = std::min(by0, c); by1 = std::max(by1, d);
-                }
-            }
-            P.d2_box[0] = bx0; P.d2_box[1] = bx1; P.d2_box[2] = by0; P.d2_box[3] = by1;
-            if (by0 < by1) {  // (the 2D pass only ever writes inside its primitives' pixel boxes)
-                content_y0 = std::min(content_y0, by0);
-                content_y1 = std::max(content_y1, std::min(by1, f->height));
-                add_span(bx0, std::min(bx1, f->width), by0, std::min(by1, f->height));
-            }
-            P.d2_box_dev = use_meshes2d ? ctx->PP2.d2_box : nullptr;  // (the device builds these records: their boxes are not known here)
-        }
+        fold_d2_box();
+        memcpy(P.d2_box, d2_box, sizeof(P.d2_box));
+        P.d2_box_dev = use_meshes2d ? ctx->PP2.d2_box : nullptr;  // (the device builds these records: their boxes are not known here)
         P.list2d_capacity = ctx->list2d_capacity;
         P.any_lights = f->n_lights ? 1u : 0u;
         P.has_opacity = has_opacity ? 1u : 0u;
@@ -1412,7 +1457,7 @@ struct FrameBuild {
         P.batches3d = (const DevBatch *)(d + L.off_b3);
         P.batch_tri_base = (const uint32_t *)(d + L.off_base);
         P.tri_info = with_tri_info ? (const uint2 *)(d + L.off_tinfo) : nullptr;
-        P.batch_clip3d = any_risky3d ? (const uint4 *)(d + L.off_clip3d) : nullptr;   // (and below, when the frame takes row spans)
+        P.batch_clip3d = any_risky3d ? (const uint4 *)(d + L.off_clip3d) : nullptr;   // (and when the frame takes row spans: clip_to_spans)
         P.ref_tile = f->tile_size;
         P.tri_setup = (TriSetup *)ctx->d_tri_setup.p;
         P.tri_shade = (TriShade *)ctx->d_tri_shade.p;
@@ -1483,30 +1528,36 @@ struct FrameBuild {
 
     int content_rows_and_spans() {
         int rc;
-        RasterParams &P = ctx->P;
+        const bool has_brush = f->has_brush_preview != 0;  // (RasterParams.has_brush)
+        fold_d2_box();
         // Known content rows: host-projected batches only (the device-projected ones have their boxes on the device), 3D mode (the miss
         // colour is then the constant [0,0,0,255], :420-461; in 2D mode the background is evaluated per pixel), no brush preview (it paints
         // missed pixels, :435-458).  RXR_CONTENT_ROWS=0 switches the clamp off (A-B runs, tests).
         const bool content_clamp = !(getenv("RXR_CONTENT_ROWS") && atoi(getenv("RXR_CONTENT_ROWS")) == 0);  // (read per upload: tests switch it on a live context)
-        ctx->content_known = content_clamp && !use_meshes && !use_meshes2d && (f->flags & RXR_FLAG_D3_ACTIVE) && !P.has_brush && f->tile_size > 0;
+        ctx->content_known = content_clamp && !use_meshes && !use_meshes2d && (f->flags & RXR_FLAG_D3_ACTIVE) && !has_brush && f->tile_size > 0;
         ctx->content_row0 = std::min(content_y0, content_y1);
         ctx->content_row1 = content_y1;
         ctx->spans_active = false;
         if (ctx->content_known && spans_fit() && ctx->content_row0 < ctx->content_row1 && row_spans_on()) {
             const uint32_t r0 = ctx->content_row0 / RXR_TILE_H, r1 = std::min((ctx->content_row1 + RXR_TILE_H - 1u) / RXR_TILE_H, n_tile_rows);
             if ((rc = ship_row_spans(r0, r1, false, ctx->spans_active)) != RXR_OK) return rc;
-            if (ctx->spans_active) P.batch_clip3d = (const uint4 *)((uint8_t *)ctx->d_frame.p + L.off_clip3d);  // every triangle inside its batch's tiles: the bins it counts lie in the spans
         }
         // Device-projected 3D meshes: their boxes are made on the device, frame by frame -- the table goes there holding what is known here
         // (the pixel box of a host-projected 2D pass) and k_spans_from_meshes completes it behind the projections (render_impl).  The grid is not narrowed
         // (nothing here knows by how much); the workgroups outside the spans leave at once.  Large frames only: what a dense one pays is the
         // table's kernel, a fill launch that finds nothing to fill and the look-up in front of every tile.
         ctx->dev_spans = false;
-        if (content_clamp && use_meshes && (f->flags & RXR_FLAG_D3_ACTIVE) && !P.has_brush && f->tile_size > 0 && spans_fit() && n_b3 &&
+        if (content_clamp && use_meshes && (f->flags & RXR_FLAG_D3_ACTIVE) && !has_brush && f->tile_size > 0 && spans_fit() && n_b3 &&
             n_b3 <= rxr_span_meshes_max() && (size_t)n_tile_rows * n_tile_cols >= 4u * content_min_tiles() && row_spans_on()) {
             if ((rc = ship_row_spans(0u, 0u, true, ctx->dev_spans)) != RXR_OK) return rc;
         }
         return RXR_OK;
+    }
+
+    // a frame under row spans: every triangle inside its batch's tiles, so that the bins it is counted into lie in the spans (behind
+    // fill_raster_params AND content_rows_and_spans, whichever order they ran in)
+    void clip_to_spans() {
+        if (ctx->spans_active) ctx->P.batch_clip3d = (const uint4 *)((uint8_t *)ctx->d_frame.p + L.off_clip3d);
     }
 };
 
@@ -1528,6 +1579,7 @@ extern "C" int rxr_upload_frame(rxr_ctx *ctx, const rxr_frame *f) {
         return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_upload_frame: RXR_BG_HOST_PIXELS without background_pixels");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->has_frame = false;
+    ctx->host_records = false;
     // Were this frame's 3D batches handed over while they were projected (rxr_stream_begin / rxr_stream_batch3d)?  Then their arrays
     // are in the blob already, or on their way.  Anything that does not match -- a batch missing, other arrays than the ones streamed,
     // a failure on the way -- and the frame takes the plain path below from scratch.
@@ -1568,13 +1620,22 @@ extern "C" int rxr_upload_frame(rxr_ctx *ctx, const rxr_frame *f) {
     B.write_lights_chunks_textures();
     if ((rc = B.headers2d()) != RXR_OK) return rc;
     if ((rc = B.size_scratch()) != RXR_OK) return rc;
+    // (a frame whose set-up records are built here has to know first whether it takes row spans: the records go out with the blob)
+    if (B.host_setup) {
+        if ((rc = B.content_rows_and_spans()) != RXR_OK) return rc;
+        B.build_setup_records();
+    }
     if ((rc = B.ship_blob()) != RXR_OK) return rc;
     if ((rc = B.fill_raster_params()) != RXR_OK) return rc;
     if (e2e_timing)
         fprintf(stderr, "rxr_e2e_timing upload: validate+size %.3f, wait for the previous frame %.3f, headers %.3f, arrays (copy + ship) %.3f, rest %.3f ms\n", B.ut_validated,
                 B.ut_quiesced - B.ut_validated, B.ut_headers - B.ut_quiesced, B.ut_arrays - B.ut_headers, B.ut_ms() - B.ut_arrays);
     ctx->n_tris2d = (uint32_t)B.t2cur;
-    if ((rc = B.content_rows_and_spans()) != RXR_OK) return rc;
+    if (!B.host_setup && (rc = B.content_rows_and_spans()) != RXR_OK) return rc;
+    B.clip_to_spans();
+    ctx->host_records = B.host_setup;
+    ctx->off_host_setup = B.L.off_host_setup;
+    ctx->off_host_shade = B.L.off_host_shade;
     ctx->has_frame = true;
     ctx->rendered = false;
     ctx->upload_ordered_on = nullptr;
