@@ -697,7 +697,7 @@ int rxr_screen_rays_to(rxr_ctx *ctx, const float *inverse_view, const float *inv
                        uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, float *dev_origins, float *dev_dirs, void *hip_stream);
 /* Opt-in: cull the many-ray queries (rxr_intersect / _to with more than 64 rays, every round of rxr_trace / _to) with a tree of boxes
  * that the context builds on the device over the resident triangles (rusterix_amd/csrc/rxr_ray_accel.hip), lazily before the next such
- * query and again after every rxr_set_meshes / rxr_update_meshes.  Every output word stays what the brute-force kernels write: the
+ * query and again after every rxr_set_meshes / rxr_update_meshes (rxr_set_ray_refresh below: refitted instead).  Every output word stays what the brute-force kernels write: the
  * tree only skips triangles whose test would reject the ray, by a padded box test whose margin is measured, not proven (DESIGN.md
  * section 19).  RXR_RAY_ACCEL_OFF is the default; _COUNT is _ON plus a count of the ray-triangle tests a call runs (a second kernel
  * instantiation: _ON does not pay for it).  Any other mode: RXR_ERR_INVALID.  Multi-device handles: member 0. */
@@ -717,6 +717,47 @@ int rxr_set_ray_accel(rxr_ctx *ctx, uint32_t mode);
 #define RXR_RAY_ACCEL_INFO_TESTS 8u       /* ray-triangle tests of the last call under RXR_RAY_ACCEL_COUNT                */
 #define RXR_RAY_ACCEL_INFO_WORDS 9u
 int rxr_ray_accel_info(rxr_ctx *ctx, uint64_t out[RXR_RAY_ACCEL_INFO_WORDS]);
+/* Opt-in: what rxr_update_meshes / _to leaves for the next rxr_intersect / rxr_trace.  RXR_RAY_REFRESH_FULL, the
+ * default: the pick records and the tree are invalid, the next query builds all of them again.  RXR_RAY_REFRESH_RANGED: a successful
+ * update adds the meshes it named to a set on the context (a union; a refused update adds nothing, rxr_set_meshes empties it), and the
+ * next query rewrites only those meshes' pick records and, when a tree stands and rxr_set_ray_accel's mode is on, their sorted records,
+ * the leaves over them and the leaves' ancestors, each node by the build's own arithmetic -- the tree keeps the order of its last
+ * build, RXR_RAY_ACCEL_INFO_BUILDS does not move and RXR_RAY_ACCEL_INFO_VALID is 1 only when nothing is pending.  With the accel mode
+ * off a standing tree is dropped instead.  Every output word of a query is the same under both modes.  Switching to _FULL while meshes
+ * are pending invalidates as _FULL would have.  Any other mode: RXR_ERR_INVALID.  Multi-device handles: member 0. */
+#define RXR_RAY_REFRESH_FULL 0u
+#define RXR_RAY_REFRESH_RANGED 1u
+int rxr_set_ray_refresh(rxr_ctx *ctx, uint32_t mode);
+/* a refit that rewrites up to this many leaves runs all levels in one launch of one workgroup, more take one launch per level
+ * (profiles/ray_refresh/README.md has the sweep) */
+#define RXR_RAY_REFIT_SMALL_MAX 256u
+#define RXR_RAY_REFIT_NONE 0u
+#define RXR_RAY_REFIT_SMALL 1u
+#define RXR_RAY_REFIT_GENERAL 2u
+/* not blocking; out[..]: */
+#define RXR_RAY_REFRESH_INFO_MODE 0u       /* RXR_RAY_REFRESH_*                                                          */
+#define RXR_RAY_REFRESH_INFO_PENDING 1u    /* meshes named by updates since the last query                               */
+#define RXR_RAY_REFRESH_INFO_REFRESHES 2u  /* ranged refreshes of the pick records since rxr_create                      */
+#define RXR_RAY_REFRESH_INFO_REFITS 3u     /* ... of which refitted a tree                                               */
+#define RXR_RAY_REFRESH_INFO_TRIANGLES 4u  /* triangles whose records the last refresh rewrote                           */
+#define RXR_RAY_REFRESH_INFO_LEAVES 5u     /* leaves its refit rewrote (0: no refit)                                     */
+#define RXR_RAY_REFRESH_INFO_NODES 6u      /* nodes of all levels its refit rewrote, the leaves included                 */
+#define RXR_RAY_REFRESH_INFO_ROUTE 7u      /* RXR_RAY_REFIT_* of the last refresh                                        */
+#define RXR_RAY_REFRESH_INFO_WORDS 8u
+int rxr_ray_refresh_info(rxr_ctx *ctx, uint64_t out[RXR_RAY_REFRESH_INFO_WORDS]);
+/* For tests and tools, blocking: recomputes into scratch every pick record from the pools (the kernel of the full pass) and, where a
+ * tree stands, every sorted record, leaf and level from the resident order (the build's kernels), and counts what differs from the
+ * resident arrays bit for bit.  Pending meshes are not refreshed first: the call reports the arrays as they stand.  out[..]: */
+#define RXR_RAY_REFRESH_VERIFY_PICK_WORDS 0u    /* words of the pick records that differ                                 */
+#define RXR_RAY_REFRESH_VERIFY_SORTED_WORDS 1u  /* words of the tree's sorted records that differ                        */
+#define RXR_RAY_REFRESH_VERIFY_NODES 2u         /* nodes that differ in any bit                                          */
+#define RXR_RAY_REFRESH_VERIFY_WILD 3u          /* the recomputed count of RXR_RAY_ACCEL_INFO_WILD                       */
+#define RXR_RAY_REFRESH_VERIFY_CHECKED 4u       /* bit 0: pick records stood and were compared, bit 1: a tree did        */
+#define RXR_RAY_REFRESH_VERIFY_WORDS 5u
+int rxr_ray_refresh_verify(rxr_ctx *ctx, uint64_t out[RXR_RAY_REFRESH_VERIFY_WORDS]);
+/* drops the tree: the next many-ray query with the accel mode on builds it from scratch (a refit keeps the order of the last build;
+ * after many updates a fresh order may cull better).  Pick records and pending meshes are left alone.  Multi-device handles: member 0. */
+int rxr_ray_accel_invalidate(rxr_ctx *ctx);
 
 /* ---- running a program over an image: the shader-texture bake (rusterix_amd/csrc/rxr_bake.hip) -------------------------------
  * Rusteria::shade (rusteria/src/lib.rs:161-210) over a width x height RenderBuffer, as Chunk::add_shader runs it at 64 x 64 for

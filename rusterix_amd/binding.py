@@ -19,6 +19,8 @@ import numpy as np
 SAMPLE_NEAREST, SAMPLE_LINEAR = 0, 1
 RAY_ACCEL_OFF, RAY_ACCEL_ON, RAY_ACCEL_COUNT = 0, 1, 2   # rxr_set_ray_accel's modes (include/rxr.h)
 RAY_ACCEL_INFO = ("mode", "valid", "triangles", "nodes", "levels", "wild", "builds", "batches", "tests")   # rxr_ray_accel_info's words
+RAY_REFRESH_FULL, RAY_REFRESH_RANGED = 0, 1   # rxr_set_ray_refresh's modes (include/rxr.h)
+RAY_REFRESH_INFO = ("mode", "pending", "refreshes", "refits", "triangles", "leaves", "nodes", "route")   # rxr_ray_refresh_info's words
 REPEAT_CLAMP_XY, REPEAT_REPEAT_XY, REPEAT_REPEAT_X, REPEAT_REPEAT_Y = 0, 1, 2, 3
 MODE_TRIANGLES, MODE_LINES, MODE_LINE_STRIP, MODE_LINE_LOOP = 0, 1, 2, 3
 CULL_OFF, CULL_FRONT, CULL_BACK = 0, 1, 2
@@ -472,6 +474,11 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         L.scene_set_ray_accel = fn("scene_set_ray_accel", None, vp, u32)
         L.scene_ray_accel = fn("scene_ray_accel", u32, vp)
         L.scene_ray_accel_info = fn("scene_ray_accel_info", i32, vp, C.POINTER(C.c_uint64))
+    has_ray_refresh = hasattr(lib, prefix + "scene_set_ray_refresh")
+    if has_ray_refresh:
+        L.scene_set_ray_refresh = fn("scene_set_ray_refresh", None, vp, u32)
+        L.scene_ray_refresh = fn("scene_ray_refresh", u32, vp)
+        L.scene_ray_refresh_info = fn("scene_ray_refresh_info", i32, vp, C.POINTER(C.c_uint64))
 
     # the path tracer (product host library only): Scene.trace, AccumBuffer, Batch3D.material
     has_trace = hasattr(lib, prefix + "scene_trace")
@@ -1107,6 +1114,29 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
             if rc != 0:
                 raise RasterizeError(rc, last_error())
             return dict(zip(RAY_ACCEL_INFO, (int(x) for x in out)))
+
+        @property
+        def ray_refresh(self):
+            """Scene::ray_refresh (opt-in; 0 full, the default; 1 ranged): after an rxr_update_meshes on the shared context the next
+            intersect() or trace() rewrites only the updated meshes' pick records and refits the box tree instead of building both
+            again (rxr_set_ray_refresh, include/rxr.h).  The results are the same words."""
+            return int(L.scene_ray_refresh(self._h)) if has_ray_refresh else 0
+
+        @ray_refresh.setter
+        def ray_refresh(self, mode):
+            if not has_ray_refresh:
+                raise NotImplementedError(f"{name}: no ranged ray refresh in this library")
+            L.scene_set_ray_refresh(self._h, int(mode))
+
+        def ray_refresh_info(self):
+            """rxr_ray_refresh_info of the context as a dict: mode, pending, refreshes, refits, triangles, leaves, nodes, route"""
+            if not has_ray_refresh:
+                raise NotImplementedError(f"{name}: no ranged ray refresh in this library")
+            out = (C.c_uint64 * len(RAY_REFRESH_INFO))()
+            rc = L.scene_ray_refresh_info(self._h, out)
+            if rc != 0:
+                raise RasterizeError(rc, last_error())
+            return dict(zip(RAY_REFRESH_INFO, (int(x) for x in out)))
 
         def projected_batch3d(self, list_kind, index, chunk=-1):
             """Outputs of clip_and_project for one batch (after rasterize): dict of numpy arrays."""

@@ -153,6 +153,10 @@ int rxh_scene_resident_chunk_textures(void *s) { return ((Scene *)s)->resident_c
 void rxh_scene_set_ray_accel(void *s, uint32_t mode) { ((Scene *)s)->ray_accel = mode; }
 uint32_t rxh_scene_ray_accel(void *s) { return ((Scene *)s)->ray_accel; }
 int rxh_scene_ray_accel_info(void *s, uint64_t *out) { return ((Scene *)s)->ray_accel_info(out); }
+// ---- the ranged refresh after mesh updates (Scene::ray_refresh): RXR_RAY_REFRESH_* ----------------------
+void rxh_scene_set_ray_refresh(void *s, uint32_t mode) { ((Scene *)s)->ray_refresh = mode; }
+uint32_t rxh_scene_ray_refresh(void *s) { return ((Scene *)s)->ray_refresh; }
+int rxh_scene_ray_refresh_info(void *s, uint64_t *out) { return ((Scene *)s)->ray_refresh_info(out); }
 // Chunk::textures_generation (0 for a bad index) and Chunk::touch_textures
 uint64_t rxh_chunk_textures_generation(void *s, int chunk) {
     Scene *sc = (Scene *)s;

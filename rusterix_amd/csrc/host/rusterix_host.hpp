@@ -324,6 +324,12 @@ public:
     uint32_t ray_accel = RXR_RAY_ACCEL_OFF;
     // rxr_ray_accel_info of the context: RXR_RAY_ACCEL_INFO_WORDS words.  RXR_OK or a negative rxr_status.
     int ray_accel_info(uint64_t *out) const;
+    // Opt-in, RXR_RAY_REFRESH_FULL by default: what an rxr_update_meshes on the shared context leaves for the next intersect() or
+    // Tracer::trace -- handed over next to ray_accel (rxr_set_ray_refresh, include/rxr.h).  RXR_RAY_REFRESH_RANGED rewrites only the
+    // updated meshes' records and refits the tree; the results are the same words.
+    uint32_t ray_refresh = RXR_RAY_REFRESH_FULL;
+    // rxr_ray_refresh_info of the context: RXR_RAY_REFRESH_INFO_WORDS words.  RXR_OK or a negative rxr_status.
+    int ray_refresh_info(uint64_t *out) const;
     // the host copies of the textures the device holds newer bytes of (Chunk::terrain_texture_stale), read back through
     // rxr_read_chunk_texture.  RXR_OK, or RXR_ERR_INVALID when the context no longer holds this scene's registration (another scene was
     // uploaded in between: the bytes are gone, build the chunk again).

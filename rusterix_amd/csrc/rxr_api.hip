@@ -181,7 +181,7 @@ void rxr_destroy(rxr_ctx *ctx) {
                       &ctx->d_list2d, &ctx->d_large2d,
                       &ctx->d_list, &ctx->d_large, &ctx->d_counters, &ctx->d_fb,
                       &ctx->d_vm_code, &ctx->d_programs, &ctx->d_patterns, &ctx->d_pattern_data, &ctx->d_palette,
-                      &ctx->d_isect_tris, &ctx->d_isect_misc, &ctx->d_isect_keys, &ctx->d_accel_tris, &ctx->d_accel_perm, &ctx->d_accel_nodes, &ctx->d_accel_stats, &ctx->d_accel_scratch, &ctx->d_trace_scene, &ctx->d_trace_paths, &ctx->d_trace_keys,
+                      &ctx->d_isect_tris, &ctx->d_isect_misc, &ctx->d_isect_keys, &ctx->d_accel_tris, &ctx->d_accel_perm, &ctx->d_accel_nodes, &ctx->d_accel_stats, &ctx->d_accel_scratch, &ctx->d_refresh_table, &ctx->d_refresh_verify, &ctx->d_trace_scene, &ctx->d_trace_paths, &ctx->d_trace_keys,
                       &ctx->d_bake_jobs, &ctx->d_bake_fault,
                       &ctx->d_terrain_cells, &ctx->d_terrain_tex, &ctx->d_terrain_texels, &ctx->d_terrain_weights,
                       &ctx->d_heights, &ctx->d_heights_tk, &ctx->d_heights_mask, &ctx->d_gen, &ctx->d_excl, &ctx->d_excl_scratch, &ctx->d_tiles, &ctx->d_nrm_scratch, &ctx->ctex.pool, &ctx->ctex.flags};
@@ -303,6 +303,8 @@ int rxr_set_meshes(rxr_ctx *ctx, const rxr_mesh3d *meshes, uint32_t n_meshes) {
     ctx->has_frame = false;
     ctx->meshes_valid = false;  // (rxr_intersect.hip: until this call completes)
     ctx->isect_ready = false;
+    ctx->refresh_named.clear();   // (meshes pending a ranged refresh: the next query takes the full path)
+    ctx->refresh_pending = 0;
     ctx->trace_set = false;
     size_t vin = 0, tin = 0, vout = 0, tout = 0;
     for (uint32_t i = 0; i < n_meshes; ++i) {
@@ -515,7 +517,17 @@ static int update_run(rxr_ctx *ctx, const char *who, const uint32_t *mesh_indice
         memcpy(h.aabb_lo, rec[i].lo, 12);
         memcpy(h.aabb_hi, rec[i].hi, 12);
     }
-    ctx->isect_ready = false;  // (the next pick builds its records again, as after rxr_set_meshes)
+    if (ctx->refresh_mode == RXR_RAY_REFRESH_RANGED && ctx->isect_ready) {
+        // the records stay; the next pick rewrites the named meshes' (rxr_set_ray_refresh; without records there is nothing to keep)
+        ctx->refresh_named.resize(ctx->meshes.size(), 0);
+        for (uint32_t i = 0; i < n; ++i) {
+            uint8_t &named = ctx->refresh_named[mesh_indices[i]];
+            ctx->refresh_pending += named ? 0u : 1u;
+            named = 1;
+        }
+    } else {
+        ctx->isect_ready = false;  // (the next pick builds its records again, as after rxr_set_meshes)
+    }
     ctx->has_frame = false;    // (the resident frame's cull decisions and row spans came from the old boxes)
     return RXR_OK;
 }

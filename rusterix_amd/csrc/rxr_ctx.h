@@ -275,7 +275,7 @@ struct rxr_ctx {
     DevBuf d_isect_tris, d_isect_misc, d_isect_keys;
     std::vector<uint32_t> isect_host;
     bool meshes_valid = true;        // false while / after an rxr_set_meshes that did not complete
-    bool isect_ready = false;        // d_isect_tris / d_isect_misc describe the current meshes (rxr_set_meshes clears it)
+    bool isect_ready = false;        // d_isect_tris / d_isect_misc describe the current meshes but for those of refresh_named (rxr_set_meshes clears it)
     uint32_t isect_nseg = 0, isect_stride = 0;
     size_t isect_off_pid = 0;        // words into d_isect_misc
 
@@ -288,6 +288,18 @@ struct rxr_ctx {
     bool accel_stats_zeroed = false;
     uint32_t accel_ntri = 0, accel_nodes = 0, accel_levels = 0;
     uint64_t accel_builds = 0, accel_batches = 0;
+
+    // ranged refresh after rxr_update_meshes (rxr_set_ray_refresh).  refresh_named: one byte per registered mesh,
+    // 1 while an update named it and no query has run since (refresh_pending of them; only ever set while isect_ready);
+    // d_refresh_table: the dirty meshes' triangle ranges and the refit's node intervals (refresh_host: their host copy, kept alive for
+    // the asynchronous upload); d_refresh_verify: rxr_ray_refresh_verify's recomputed arrays and its four counters.
+    uint32_t refresh_mode = 0;       // RXR_RAY_REFRESH_*
+    std::vector<uint8_t> refresh_named;
+    uint32_t refresh_pending = 0;
+    DevBuf d_refresh_table, d_refresh_verify;
+    std::vector<uint32_t> refresh_host;
+    uint64_t refresh_count = 0, refit_count = 0;
+    uint32_t refresh_last_tris = 0, refresh_last_leaves = 0, refresh_last_nodes = 0, refresh_last_route = 0;
 
     // path tracing (rxr_trace.hip): buffers of its own, like the intersect's.  d_trace_scene: the blob of rxr_set_trace_scene -- the
     // segment table over the participating meshes, one record per mesh (texel source, repeat mode, material), the lights, the

@@ -301,10 +301,93 @@ __global__ __launch_bounds__(ISECT_WG) void k_screen_rays(ScreenRayArgs S) {
     S.dirs[3 * i] = d.x, S.dirs[3 * i + 1] = d.y, S.dirs[3 * i + 2] = d.z;
 }
 
+// after rxr_update_meshes under RXR_RAY_REFRESH_RANGED: the same record for the triangles of the dirty meshes alone, a thread each
+// (k_isect_prep's operations on the same operands: the same bits)
+__global__ __launch_bounds__(ISECT_WG) void k_isect_refresh(IsectArgs A, RxrDirtyTris D, float *out) {
+    const uint32_t t = blockIdx.x * ISECT_WG + threadIdx.x;
+    if (t >= D.total) return;
+    const uint32_t i = last_le(D.pre, 0, D.n, t);
+    const uint32_t g = D.base[i] + (t - D.pre[i]);
+    if (g >= A.ntri) return;   // (a table that went wrong must not write out of bounds)
+    const uint32_t vb = D.vbase[i];
+    const float4 v0 = A.obj_verts[vb + A.obj_idx[3ull * g]];
+    const float4 v1 = A.obj_verts[vb + A.obj_idx[3ull * g + 1]];
+    const float4 v2 = A.obj_verts[vb + A.obj_idx[3ull * g + 2]];
+    const size_t s = A.stride;
+    float *p = out + g;
+    p[0] = v0.x, p[s] = v0.y, p[2 * s] = v0.z;
+    p[3 * s] = v1.x - v0.x, p[4 * s] = v1.y - v0.y, p[5 * s] = v1.z - v0.z;
+    p[6 * s] = v2.x - v0.x, p[7 * s] = v2.y - v0.y, p[8 * s] = v2.z - v0.z;
+}
+
+// RXR_RAY_REFRESH_RANGED: the records of the meshes that updates named since the last query, rewritten in place, and the tree above
+// them refitted (or dropped while its mode is off); queued on `s`.  The segments and profile ids depend on counts and lists alone,
+// which an update cannot change.
+int isect_refresh(rxr_ctx *ctx, hipStream_t s) {
+    const uint32_t n_meshes = (uint32_t)ctx->meshes.size();
+    std::vector<uint32_t> &h = ctx->refresh_host;
+    h.clear();
+    std::vector<uint32_t> ranges, vbase;
+    for (uint32_t m = 0; m < n_meshes && m < ctx->refresh_named.size(); ++m) {
+        const DevMesh &M = ctx->meshes[m].dev;
+        if (!ctx->refresh_named[m] || !M.n_tris) continue;
+        ranges.push_back(M.tin_base);
+        ranges.push_back(M.tin_base + M.n_tris);
+        vbase.push_back(M.vin_base);
+    }
+    ctx->refresh_named.clear();
+    ctx->refresh_pending = 0;
+    const uint32_t nd = (uint32_t)vbase.size();
+    uint32_t total = 0;
+    for (uint32_t i = 0; i < nd; ++i) h.push_back(ranges[2 * i]);
+    h.insert(h.end(), vbase.begin(), vbase.end());
+    for (uint32_t i = 0; i < nd; ++i) {
+        h.push_back(total);
+        total += ranges[2 * i + 1] - ranges[2 * i];
+    }
+    h.push_back(total);
+    const bool tree = ctx->accel_ready && ctx->accel_nodes != 0;
+    const bool refit = tree && ctx->accel_mode != RXR_RAY_ACCEL_OFF && total != 0;
+    if (ctx->accel_ready && ctx->accel_mode == RXR_RAY_ACCEL_OFF) ctx->accel_ready = false;   // (mode off pays nothing; the next switch-on builds)
+    RxrRefitLaunch R{};
+    if (refit) R = rxr_ray_accel_refit_plan(ctx, ranges.data(), nd, h);
+    ++ctx->refresh_count;
+    ctx->refresh_last_tris = total;
+    ctx->refresh_last_leaves = refit ? R.total[0] : 0u;
+    ctx->refresh_last_nodes = 0;
+    for (uint32_t k = 0; refit && k < R.n_levels; ++k) ctx->refresh_last_nodes += R.total[k];
+    ctx->refresh_last_route = R.route;
+    if (!total) return RXR_OK;
+    int rc;
+    if ((rc = rxr_ensure(ctx, ctx->d_refresh_table, h.size() * 4)) != RXR_OK) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->d_refresh_table.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, s));
+    const uint32_t *tab = (const uint32_t *)ctx->d_refresh_table.p;
+    const RxrDirtyTris D{tab, tab + nd, tab + 2 * (size_t)nd, nd, total};
+    IsectArgs A{};
+    A.ntri = ctx->PP.n_tris_in;
+    A.stride = ctx->isect_stride;
+    A.obj_idx = ctx->PP.obj_idx;
+    A.obj_verts = ctx->PP.obj_verts;
+    hipLaunchKernelGGL(k_isect_refresh, dim3((total + ISECT_WG - 1) / ISECT_WG), dim3(ISECT_WG), 0, s, A, D, (float *)ctx->d_isect_tris.p);
+    HIPCHK(ctx, hipGetLastError());
+    if (!refit) return RXR_OK;
+    ++ctx->refit_count;
+    return rxr_ray_accel_refit(ctx, D, R, tab, s);
+}
+
 // the segments and per-triangle records of the current meshes (once per rxr_set_meshes), queued on `s`
 int isect_prepare(rxr_ctx *ctx, hipStream_t s) {
     const bool want_accel = ctx->accel_mode != RXR_RAY_ACCEL_OFF;   // (the box tree of rxr_ray_accel.hip: built with the records, or when switched on)
-    if (ctx->isect_ready) return want_accel && !ctx->accel_ready ? rxr_ray_accel_build(ctx, s) : RXR_OK;
+    if (ctx->isect_ready) {
+        int rc = ctx->refresh_pending ? isect_refresh(ctx, s) : RXR_OK;
+        if (rc != RXR_OK) {
+            ctx->isect_ready = false;   // (the set is gone and the records are stale: the next query takes the full path)
+            return rc;
+        }
+        return want_accel && !ctx->accel_ready ? rxr_ray_accel_build(ctx, s) : RXR_OK;
+    }
+    ctx->refresh_named.clear();
+    ctx->refresh_pending = 0;
     ctx->accel_ready = false;
     const uint32_t n_meshes = (uint32_t)ctx->meshes.size();
     std::vector<uint32_t> &h = ctx->isect_host;
@@ -424,6 +507,21 @@ int isect_run(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n,
 // ---- rxr_isect.h: the same records and kernels for the path tracer ------------------------------------------------------------
 int rxr_isect_prepare(rxr_ctx *ctx, hipStream_t s) { return isect_prepare(ctx, s); }
 
+int rxr_isect_prep_into(rxr_ctx *ctx, float *out, hipStream_t s) {
+    const uint32_t ntri = ctx->PP.n_tris_in;
+    if (!ntri) return RXR_OK;
+    IsectArgs A{};
+    A.ntri = ntri;
+    A.stride = ctx->isect_stride;
+    A.tin_prefix = ctx->PP.tin_prefix;
+    A.vin_prefix = ctx->PP.vin_prefix;
+    A.obj_idx = ctx->PP.obj_idx;
+    A.obj_verts = ctx->PP.obj_verts;
+    hipLaunchKernelGGL(k_isect_prep, dim3((ntri + ISECT_WG - 1) / ISECT_WG), dim3(ISECT_WG), 0, s, A, (uint32_t)ctx->meshes.size(), out);
+    HIPCHK(ctx, hipGetLastError());
+    return RXR_OK;
+}
+
 uint32_t rxr_isect_batch_rays(uint32_t n_rays, uint32_t nseg) {
     if (nseg && (uint64_t)n_rays * nseg > ISECT_KEYS_MAX)
         return (uint32_t)std::max<uint64_t>(ISECT_WG, ISECT_KEYS_MAX / nseg / ISECT_WG * ISECT_WG);
@@ -481,6 +579,34 @@ int rxr_intersect_to(rxr_ctx *ctx, const float *dev_origins, const float *dev_di
     O.uv = dev_uv;
     O.normal = dev_normal;
     return isect_run(ctx, dev_origins, dev_dirs, n_rays, flags, O, hip_stream ? (hipStream_t)hip_stream : ctx->stream);
+}
+
+int rxr_set_ray_refresh(rxr_ctx *ctx, uint32_t mode) {
+    if (!ctx) return RXR_ERR_INVALID;
+    if (mode > RXR_RAY_REFRESH_RANGED) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_set_ray_refresh: mode must be RXR_RAY_REFRESH_FULL or _RANGED");
+    if (ctx->group) return rxr_as_member0(ctx, [&](rxr_ctx *m) { return rxr_set_ray_refresh(m, mode); });
+    if (mode == RXR_RAY_REFRESH_FULL && ctx->refresh_pending) {   // what the updates would have done under _FULL
+        ctx->isect_ready = false;
+        ctx->refresh_named.clear();
+        ctx->refresh_pending = 0;
+    }
+    ctx->refresh_mode = mode;
+    return RXR_OK;
+}
+
+int rxr_ray_refresh_info(rxr_ctx *ctx, uint64_t out[RXR_RAY_REFRESH_INFO_WORDS]) {
+    if (!ctx) return RXR_ERR_INVALID;
+    if (!out) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_ray_refresh_info: out is NULL");
+    if (ctx->group) return rxr_as_member0(ctx, [&](rxr_ctx *m) { return rxr_ray_refresh_info(m, out); });
+    out[RXR_RAY_REFRESH_INFO_MODE] = ctx->refresh_mode;
+    out[RXR_RAY_REFRESH_INFO_PENDING] = ctx->refresh_pending;
+    out[RXR_RAY_REFRESH_INFO_REFRESHES] = ctx->refresh_count;
+    out[RXR_RAY_REFRESH_INFO_REFITS] = ctx->refit_count;
+    out[RXR_RAY_REFRESH_INFO_TRIANGLES] = ctx->refresh_last_tris;
+    out[RXR_RAY_REFRESH_INFO_LEAVES] = ctx->refresh_last_leaves;
+    out[RXR_RAY_REFRESH_INFO_NODES] = ctx->refresh_last_nodes;
+    out[RXR_RAY_REFRESH_INFO_ROUTE] = ctx->refresh_last_route;
+    return RXR_OK;
 }
 
 int rxr_screen_rays_to(rxr_ctx *ctx, const float *inverse_view, const float *inverse_projection, float width, float height, uint32_t x0,

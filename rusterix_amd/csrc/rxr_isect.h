@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <vector>
 
 struct rxr_ctx;
 
@@ -81,6 +82,26 @@ int rxr_ray_accel_build(rxr_ctx *ctx, hipStream_t s);
 bool rxr_ray_accel_takes(const rxr_ctx *ctx);
 // the start of a picking or tracing call: the count of RXR_RAY_ACCEL_COUNT starts again
 int rxr_ray_accel_begin_call(rxr_ctx *ctx, hipStream_t s);
+// ---- the ranged refresh after rxr_update_meshes (rxr_set_ray_refresh) -----------------------------------------
+// The dirty triangles of a refresh, as the kernels of both files read them: per dirty mesh (in mesh order, none empty) its first global
+// triangle = its first sorted position, its first vertex in the pools, and the prefix of the dirty meshes' triangle counts
+// (pre[n] = total).  Device memory.
+struct RxrDirtyTris {
+    const uint32_t *base, *vbase, *pre;
+    uint32_t n, total;
+};
+// A refit's node intervals inside the refresh table (word offsets; rxr_ray_refresh.h computes the intervals): per level n_iv[k] first
+// nodes at off[k] and n_iv[k] + 1 prefix counts behind them; total[k] dirty nodes.
+struct RxrRefitLaunch {
+    uint32_t route, n_levels;    // RXR_RAY_REFIT_*
+    uint32_t off[24], n_iv[24], total[24];
+};
+// appends the intervals above the position ranges (n pairs begin, end; increasing) to `table` and chooses the route; nothing is queued
+RxrRefitLaunch rxr_ray_accel_refit_plan(const rxr_ctx *ctx, const uint32_t *ranges, uint32_t n, std::vector<uint32_t> &table);
+// the dirty positions' sorted records (the wild count kept exact), then the leaves and levels of `R`, over the uploaded table; on `s`
+int rxr_ray_accel_refit(rxr_ctx *ctx, const RxrDirtyTris &D, const RxrRefitLaunch &R, const uint32_t *dev_table, hipStream_t s);
+// k_isect_prep over every registered triangle into `out` (nine arrays, ctx->isect_stride apart), on `s`: rxr_ray_refresh_verify
+int rxr_isect_prep_into(rxr_ctx *ctx, float *out, hipStream_t s);
 // rxr_isect_closest's keys for more than a few rays, through the tree
 int rxr_ray_accel_closest(rxr_ctx *ctx, const void *dev_segs, uint32_t nseg, const float *dev_origins, const float *dev_dirs, uint32_t r0,
                           uint32_t nr, unsigned long long *dev_keys, hipStream_t s);

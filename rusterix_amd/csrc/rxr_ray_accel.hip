@@ -17,6 +17,8 @@
 //   k_accel_records      the nine SoA record arrays in sorted order (the operations of k_isect_prep: the same bits) and perm[pos] = g
 //   k_accel_leaves       a leaf per ACCEL_L consecutive positions: box over the pool's vertices, largest kappa, largest |coordinate|
 //   k_accel_level        a node per ACCEL_W consecutive nodes of the level below, up to one root.  Implicit: no child pointers.
+// Refit (opt-in, rxr_set_ray_refresh; the kernels after the walk): after rxr_update_meshes under RXR_RAY_REFRESH_RANGED nothing above
+// is run again -- the dirty meshes' sorted records, the leaves over them and their ancestors are rewritten over the same perm.
 // A triangle is WILD -- its leaf and every ancestor get an infinite box and are always entered -- when a value of its record is not
 // finite or its kappa = |e1| |e2| / |e1 x e2| is not finite or above ACCEL_KAPPA_CAP.
 //
@@ -30,9 +32,11 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 
 #include "rxr_isect.h"
 #include "rxr_query.h"
+#include "rxr_ray_refresh.h"
 
 namespace {
 
@@ -186,9 +190,14 @@ __device__ __forceinline__ void finish_node(AccelNode &N) {
     N.maxabs = m;
 }
 
-__global__ __launch_bounds__(ACCEL_WG) void k_accel_leaves(AccelBuild B, uint32_t n_leaves) {
-    const uint32_t leaf = blockIdx.x * ACCEL_WG + threadIdx.x;
-    if (leaf >= n_leaves) return;
+__device__ __forceinline__ void close_node(AccelNode &N, bool wild) {
+    if (wild) make_wild(N);
+    else finish_node(N);
+}
+
+// a leaf's node from the pools, through the resident order: the one sequential loop both the build and a refit run (the same
+// operations in the same order: the same bits, signs of zero included)
+__device__ __forceinline__ AccelNode leaf_node(const AccelBuild &B, uint32_t leaf) {
     AccelNode N = empty_node();
     bool wild = false;
     const uint32_t p0 = leaf * ACCEL_L, p1 = min(p0 + ACCEL_L, B.ntri);
@@ -205,9 +214,22 @@ __global__ __launch_bounds__(ACCEL_WG) void k_accel_leaves(AccelBuild B, uint32_
             N.kappa = fmaxf(N.kappa, T.kappa);
         }
     }
-    if (wild) make_wild(N);
-    else finish_node(N);
-    B.nodes[leaf] = N;
+    close_node(N, wild);
+    return N;
+}
+
+// one child folded into its parent (close_node closes it): the statements of k_accel_level's loop, for the refit kernels.  (The build
+// kernel keeps its own copy: calling this from it changes its register allocation, and its instructions are pinned.)
+__device__ __forceinline__ void fold_child(AccelNode &N, bool &wild, const AccelNode &C) {
+    wild |= !(C.maxabs < INFINITY);
+    grow(N, {C.lo[0], C.lo[1], C.lo[2]}), grow(N, {C.hi[0], C.hi[1], C.hi[2]});
+    N.kappa = fmaxf(N.kappa, C.kappa);
+}
+
+__global__ __launch_bounds__(ACCEL_WG) void k_accel_leaves(AccelBuild B, uint32_t n_leaves) {
+    const uint32_t leaf = blockIdx.x * ACCEL_WG + threadIdx.x;
+    if (leaf >= n_leaves) return;
+    B.nodes[leaf] = leaf_node(B, leaf);
 }
 
 __global__ __launch_bounds__(ACCEL_WG) void k_accel_level(AccelNode *nodes, uint32_t child_off, uint32_t n_children, uint32_t off, uint32_t n) {
@@ -341,6 +363,155 @@ __global__ __launch_bounds__(ACCEL_WG) void k_accel_by_ray(AccelArgs A, uint32_t
     }
 }
 
+// ---- the ranged refit after rxr_update_meshes (rxr_set_ray_refresh) ------------------------------------------
+// The order of the last build stays (perm is not touched): a dirty mesh's triangles keep their range of sorted positions, so their
+// records, the leaves over those positions and the leaves' ancestors are rewritten, each by the build's arithmetic over the same
+// perm.  The tree's duty -- never skip a triangle mt_test would accept -- does not depend on the order the triangles sit in.
+
+// wild as tri_info decides it, from a sorted record (v0, e1, e2 are its nine words: the same operands, the same kappa)
+__device__ __forceinline__ bool record_wild(F3 v0, F3 e1, F3 e2) {
+    const F3 n = cross3(e1, e2);
+    const float kappa = (sqrtf(dot3(e1, e1)) * sqrtf(dot3(e2, e2))) / sqrtf(dot3(n, n));
+    return !(finite3(v0) && finite3(e1) && finite3(e2)) || !(kappa <= ACCEL_KAPPA_CAP);
+}
+
+// a thread per dirty sorted position: the record of k_accel_records; stats[1] moves by (wild now) - (wild before), one atomic a wave
+__global__ __launch_bounds__(ACCEL_WG) void k_accel_refresh_records(AccelBuild B, RxrDirtyTris D) {
+    const uint32_t t = blockIdx.x * ACCEL_WG + threadIdx.x;
+    bool was = false, is = false;
+    if (t < D.total) {
+        const uint32_t i = last_le(D.pre, 0, D.n, t);
+        const uint32_t pos = D.base[i] + (t - D.pre[i]);
+        const uint32_t g = pos < B.ntri ? B.perm[pos] : 0xFFFFFFFFu;
+        if (g < B.ntri) {   // (k_accel_records leaves such a position alone, and k_accel_keys never counted it)
+            const size_t s = B.stride;
+            float *p = B.tris + pos;
+            was = record_wild({p[0], p[s], p[2 * s]}, {p[3 * s], p[4 * s], p[5 * s]}, {p[6 * s], p[7 * s], p[8 * s]});
+            const TriInfo T = tri_info(B, g);
+            is = T.wild;
+            p[0] = T.v0.x, p[s] = T.v0.y, p[2 * s] = T.v0.z;
+            p[3 * s] = T.e1.x, p[4 * s] = T.e1.y, p[5 * s] = T.e1.z;
+            p[6 * s] = T.e2.x, p[7 * s] = T.e2.y, p[8 * s] = T.e2.z;
+        }
+    }
+    const long long delta = (long long)__popcll(__ballot(is && !was)) - (long long)__popcll(__ballot(was && !is));
+    if (delta && __lane_id() == 0) atomicAdd(B.stats + 1, (unsigned long long)delta);   // (modulo 2^64: the sum never leaves [0, ntri])
+}
+
+// the dirty nodes of one level: n_iv intervals, first nodes lo[], prefix counts pre[] (pre[n_iv] = total)
+struct RefitLevel {
+    const uint32_t *lo, *pre;
+    uint32_t n_iv, total;
+};
+__device__ __forceinline__ uint32_t refit_node(const RefitLevel &R, uint32_t t) {
+    const uint32_t i = last_le(R.pre, 0, R.n_iv, t);
+    return R.lo[i] + (t - R.pre[i]);
+}
+// the slot of node c among the level's dirty nodes, or 0xFFFFFFFF for a node that is not dirty
+__device__ __forceinline__ uint32_t refit_slot(const RefitLevel &R, uint32_t c) {
+    if (!R.n_iv || c < R.lo[0]) return 0xFFFFFFFFu;
+    const uint32_t i = last_le(R.lo, 0, R.n_iv, c);
+    return c - R.lo[i] < R.pre[i + 1] - R.pre[i] ? R.pre[i] + (c - R.lo[i]) : 0xFFFFFFFFu;
+}
+
+// general route: a launch per level, a thread per dirty node
+__global__ __launch_bounds__(ACCEL_WG) void k_accel_refit_leaves(AccelBuild B, RefitLevel R, uint32_t n_leaves) {
+    const uint32_t t = blockIdx.x * ACCEL_WG + threadIdx.x;
+    if (t >= R.total) return;
+    const uint32_t leaf = refit_node(R, t);
+    if (leaf >= n_leaves) return;
+    B.nodes[leaf] = leaf_node(B, leaf);
+}
+
+__global__ __launch_bounds__(ACCEL_WG) void k_accel_refit_level(AccelNode *nodes, uint32_t child_off, uint32_t n_children, uint32_t off, uint32_t n, RefitLevel R) {
+    const uint32_t t = blockIdx.x * ACCEL_WG + threadIdx.x;
+    if (t >= R.total) return;
+    const uint32_t i = refit_node(R, t);
+    if (i >= n) return;
+    AccelNode N = empty_node();
+    bool wild = false;
+    const uint32_t c0 = i * ACCEL_W, c1 = min(c0 + ACCEL_W, n_children);
+    for (uint32_t c = c0; c < c1; ++c) fold_child(N, wild, nodes[child_off + c]);
+    close_node(N, wild);
+    nodes[off + i] = N;
+}
+
+// small route: one workgroup, every level, a barrier between levels.  S holds the nodes of the level just written, in slot order; a
+// parent takes a child this launch rewrote from S and any other from global memory, so nothing written here is read back through
+// global memory.  A level's nodes overwrite S in place: parent slot j only reads child slots >= j (every dirty parent has a dirty child
+// of its own), a pass of ACCEL_WG parents computes, meets at a barrier, then writes slots below the next pass's children.
+struct RefitSmall {
+    uint32_t n_levels;
+    uint32_t off[ACCEL_MAX_LEVELS], n_iv[ACCEL_MAX_LEVELS], total[ACCEL_MAX_LEVELS];   // RxrRefitLaunch's
+};
+__global__ __launch_bounds__(ACCEL_WG) void k_accel_refit_small(AccelBuild B, AccelLevels V, RefitSmall Q, const uint32_t *table) {
+    __shared__ AccelNode S[RXR_RAY_REFIT_SMALL_MAX];
+    RefitLevel R{table + Q.off[0], table + Q.off[0] + Q.n_iv[0], Q.n_iv[0], min(Q.total[0], RXR_RAY_REFIT_SMALL_MAX)};
+    for (uint32_t t = threadIdx.x; t < R.total; t += ACCEL_WG) {
+        const uint32_t leaf = refit_node(R, t);
+        if (leaf >= V.cnt[0]) continue;
+        const AccelNode N = leaf_node(B, leaf);
+        S[t] = N;
+        B.nodes[leaf] = N;
+    }
+    __syncthreads();
+    for (uint32_t k = 1; k < Q.n_levels; ++k) {
+        const RefitLevel C = R;   // the level below: its dirty nodes are in S
+        R = RefitLevel{table + Q.off[k], table + Q.off[k] + Q.n_iv[k], Q.n_iv[k], min(Q.total[k], C.total)};
+        const uint32_t child_off = V.off[k - 1], n_children = V.cnt[k - 1];
+        for (uint32_t t0 = 0; t0 < R.total; t0 += ACCEL_WG) {   // (uniform: every thread meets both barriers)
+            const uint32_t t = t0 + threadIdx.x;
+            const uint32_t i = t < R.total ? refit_node(R, t) : 0xFFFFFFFFu;
+            const bool live = i < V.cnt[k];
+            AccelNode N = empty_node();
+            if (live) {
+                bool wild = false;
+                const uint32_t c0 = i * ACCEL_W, c1 = min(c0 + ACCEL_W, n_children);
+                for (uint32_t c = c0; c < c1; ++c) {
+                    const uint32_t slot = refit_slot(C, c);
+                    const AccelNode Ch = slot < C.total ? S[slot] : B.nodes[child_off + c];
+                    fold_child(N, wild, Ch);
+                }
+                close_node(N, wild);
+            }
+            __syncthreads();
+            if (live) {
+                S[t] = N;
+                B.nodes[V.off[k] + i] = N;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// rxr_ray_refresh_verify: words of a[r * stride + i] and b[..] (rows r < rows, i < n) that differ; nodes (8 words) that differ; the
+// wild triangles as k_accel_keys counts them
+__global__ __launch_bounds__(ACCEL_WG) void k_accel_diff_words(const uint32_t *a, const uint32_t *b, uint32_t n, uint32_t stride, uint32_t rows, unsigned long long *out) {
+    const uint32_t i = blockIdx.x * ACCEL_WG + threadIdx.x;
+    uint32_t d = 0;
+    if (i < n)
+        for (uint32_t r = 0; r < rows; ++r) d += a[(size_t)r * stride + i] != b[(size_t)r * stride + i];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) d += __shfl_xor(d, off);
+    if (d && __lane_id() == 0) atomicAdd(out, (unsigned long long)d);
+}
+__global__ __launch_bounds__(ACCEL_WG) void k_accel_diff_nodes(const AccelNode *a, const AccelNode *b, uint32_t n, unsigned long long *out) {
+    const uint32_t i = blockIdx.x * ACCEL_WG + threadIdx.x;
+    bool differ = false;
+    if (i < n) {
+        const uint32_t *x = (const uint32_t *)(a + i), *y = (const uint32_t *)(b + i);
+        for (int w = 0; w < 8; ++w) differ |= x[w] != y[w];
+    }
+    const unsigned long long m = __ballot(differ);
+    if (m && __lane_id() == 0) atomicAdd(out, (unsigned long long)__popcll(m));
+}
+__global__ __launch_bounds__(ACCEL_WG) void k_accel_count_wild(AccelBuild B, unsigned long long *out) {
+    const uint32_t g = blockIdx.x * ACCEL_WG + threadIdx.x;
+    const bool wild = g < B.ntri && tri_info(B, g).wild;
+    const unsigned long long w = __ballot(wild);
+    if (w && __lane_id() == 0) atomicAdd(out, (unsigned long long)__popcll(w));
+}
+
 AccelLevels accel_levels(uint32_t ntri) {
     AccelLevels V{};
     uint32_t n = (ntri + ACCEL_L - 1) / ACCEL_L, off = 0;
@@ -429,6 +600,78 @@ int rxr_ray_accel_build(rxr_ctx *ctx, hipStream_t s) {
     return RXR_OK;
 }
 
+namespace {
+
+// the resident tree as the build's kernels see it (no build scratch: the refit and the verification read perm, never the keys)
+AccelBuild accel_resident(rxr_ctx *ctx) {
+    AccelBuild B{};
+    B.ntri = ctx->accel_ntri;
+    B.n_meshes = (uint32_t)ctx->meshes.size();
+    B.stride = ctx->isect_stride;
+    B.tin_prefix = ctx->PP.tin_prefix;
+    B.vin_prefix = ctx->PP.vin_prefix;
+    B.obj_idx = ctx->PP.obj_idx;
+    B.obj_verts = ctx->PP.obj_verts;
+    B.perm = (const uint32_t *)ctx->d_accel_perm.p;
+    B.tris = (float *)ctx->d_accel_tris.p;
+    B.nodes = (AccelNode *)ctx->d_accel_nodes.p;
+    B.stats = (unsigned long long *)ctx->d_accel_stats.p;
+    return B;
+}
+
+}  // namespace
+
+RxrRefitLaunch rxr_ray_accel_refit_plan(const rxr_ctx *ctx, const uint32_t *ranges, uint32_t n, std::vector<uint32_t> &table) {
+    static_assert(RXR_REFIT_MAX_LEVELS == ACCEL_MAX_LEVELS, "rxr_ray_refresh.h mirrors the tree's shape");
+    const RxrRefitPlan P = rxr_refit_plan(ctx->accel_ntri, ACCEL_L, ACCEL_W, ranges, n);
+    RxrRefitLaunch R{};
+    R.n_levels = P.n_levels;
+    for (uint32_t k = 0; k < P.n_levels; ++k) {
+        R.off[k] = (uint32_t)table.size();
+        R.n_iv[k] = (uint32_t)P.iv[k].size();
+        R.total[k] = P.dirty[k];
+        for (const RxrRefitInterval &c : P.iv[k]) table.push_back(c.lo);
+        uint32_t pre = 0;
+        for (const RxrRefitInterval &c : P.iv[k]) {
+            table.push_back(pre);
+            pre += c.hi - c.lo + 1;
+        }
+        table.push_back(pre);
+    }
+    // RXR_RAY_REFIT_SMALL_MAX=<n> in the environment lowers the bound (0: always a launch per level): the sweep of tools/ray_refresh_bench.py
+    static const uint32_t small_max = [] {
+        const char *e = getenv("RXR_RAY_REFIT_SMALL_MAX");
+        return e ? std::min<uint32_t>((uint32_t)strtoul(e, nullptr, 10), RXR_RAY_REFIT_SMALL_MAX) : RXR_RAY_REFIT_SMALL_MAX;
+    }();
+    R.route = !P.n_levels || !P.dirty[0] ? RXR_RAY_REFIT_NONE : P.dirty[0] <= small_max ? RXR_RAY_REFIT_SMALL : RXR_RAY_REFIT_GENERAL;
+    return R;
+}
+
+int rxr_ray_accel_refit(rxr_ctx *ctx, const RxrDirtyTris &D, const RxrRefitLaunch &R, const uint32_t *dev_table, hipStream_t s) {
+    if (R.route == RXR_RAY_REFIT_NONE) return RXR_OK;
+    const AccelBuild B = accel_resident(ctx);
+    const AccelLevels V = accel_levels(B.ntri);
+    const dim3 wg(ACCEL_WG);
+    hipLaunchKernelGGL(k_accel_refresh_records, dim3((D.total + ACCEL_WG - 1) / ACCEL_WG), wg, 0, s, B, D);
+    HIPCHK(ctx, hipGetLastError());
+    if (R.route == RXR_RAY_REFIT_SMALL) {
+        RefitSmall Q{};
+        Q.n_levels = R.n_levels;
+        for (uint32_t k = 0; k < R.n_levels; ++k) Q.off[k] = R.off[k], Q.n_iv[k] = R.n_iv[k], Q.total[k] = R.total[k];
+        hipLaunchKernelGGL(k_accel_refit_small, dim3(1), wg, 0, s, B, V, Q, dev_table);
+        HIPCHK(ctx, hipGetLastError());
+        return RXR_OK;
+    }
+    for (uint32_t k = 0; k < R.n_levels; ++k) {
+        const RefitLevel L{dev_table + R.off[k], dev_table + R.off[k] + R.n_iv[k], R.n_iv[k], R.total[k]};
+        const dim3 grid((L.total + ACCEL_WG - 1) / ACCEL_WG);
+        if (k == 0) hipLaunchKernelGGL(k_accel_refit_leaves, grid, wg, 0, s, B, L, V.cnt[0]);
+        else hipLaunchKernelGGL(k_accel_refit_level, grid, wg, 0, s, B.nodes, V.off[k - 1], V.cnt[k - 1], V.off[k], V.cnt[k], L);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    return RXR_OK;
+}
+
 bool rxr_ray_accel_takes(const rxr_ctx *ctx) { return ctx->accel_mode != RXR_RAY_ACCEL_OFF && ctx->accel_ready && ctx->accel_nodes != 0; }
 
 int rxr_ray_accel_begin_call(rxr_ctx *ctx, hipStream_t s) {
@@ -480,7 +723,7 @@ int rxr_ray_accel_info(rxr_ctx *ctx, uint64_t out[RXR_RAY_ACCEL_INFO_WORDS]) {
         if (rc != RXR_OK) return rc;
         HIPCHK(ctx, hipMemcpy(stats, ctx->d_accel_stats.p, 16, hipMemcpyDeviceToHost));
     }
-    const bool valid = ctx->isect_ready && ctx->accel_ready;
+    const bool valid = ctx->isect_ready && ctx->accel_ready && !ctx->refresh_pending;   // (pending: rxr_set_ray_refresh)
     out[RXR_RAY_ACCEL_INFO_MODE] = ctx->accel_mode;
     out[RXR_RAY_ACCEL_INFO_VALID] = valid ? 1u : 0u;
     out[RXR_RAY_ACCEL_INFO_TRIANGLES] = valid ? ctx->accel_ntri : 0u;
@@ -490,6 +733,70 @@ int rxr_ray_accel_info(rxr_ctx *ctx, uint64_t out[RXR_RAY_ACCEL_INFO_WORDS]) {
     out[RXR_RAY_ACCEL_INFO_BUILDS] = ctx->accel_builds;
     out[RXR_RAY_ACCEL_INFO_BATCHES] = ctx->accel_batches;
     out[RXR_RAY_ACCEL_INFO_TESTS] = stats[0];
+    return RXR_OK;
+}
+
+int rxr_ray_accel_invalidate(rxr_ctx *ctx) {
+    if (!ctx) return RXR_ERR_INVALID;
+    if (ctx->group) return rxr_as_member0(ctx, [&](rxr_ctx *m) { return rxr_ray_accel_invalidate(m); });
+    ctx->accel_ready = false;
+    return RXR_OK;
+}
+
+int rxr_ray_refresh_verify(rxr_ctx *ctx, uint64_t out[RXR_RAY_REFRESH_VERIFY_WORDS]) {
+    if (!ctx) return RXR_ERR_INVALID;
+    if (!out) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_ray_refresh_verify: out is NULL");
+    if (ctx->group) return rxr_as_member0(ctx, [&](rxr_ctx *m) { return rxr_ray_refresh_verify(m, out); });
+    for (uint32_t i = 0; i < RXR_RAY_REFRESH_VERIFY_WORDS; ++i) out[i] = 0;
+    if (!ctx->meshes_valid || !ctx->isect_ready) return RXR_OK;   // (no records stand: nothing to compare)
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = rxr_quiesce(ctx);
+    if (rc != RXR_OK) return rc;
+    const uint32_t ntri = ctx->PP.n_tris_in;
+    const size_t stride = ctx->isect_stride;
+    const bool tree = ctx->accel_ready && ctx->accel_nodes != 0 && ctx->accel_ntri == ntri;
+    out[RXR_RAY_REFRESH_VERIFY_CHECKED] = 1u | (tree ? 2u : 0u);
+    if (!ntri) return RXR_OK;
+    BlobCursor take;
+    const size_t o_cnt = take(64), o_pick = take(9 * stride * 4), o_sorted = take(tree ? 9 * stride * 4 : 0),
+                 o_nodes = take(tree ? (size_t)ctx->accel_nodes * sizeof(AccelNode) : 0);
+    if ((rc = rxr_ensure(ctx, ctx->d_refresh_verify, take.o)) != RXR_OK) return rc;
+    uint8_t *sc = (uint8_t *)ctx->d_refresh_verify.p;
+    unsigned long long *cnt = (unsigned long long *)(sc + o_cnt);
+    hipStream_t s = ctx->stream;
+    const dim3 per_tri((ntri + ACCEL_WG - 1) / ACCEL_WG), wg(ACCEL_WG);
+    HIPCHK(ctx, hipMemsetAsync(cnt, 0, 64, s));
+    if ((rc = rxr_isect_prep_into(ctx, (float *)(sc + o_pick), s)) != RXR_OK) return rc;
+    hipLaunchKernelGGL(k_accel_diff_words, per_tri, wg, 0, s, (const uint32_t *)ctx->d_isect_tris.p, (const uint32_t *)(sc + o_pick), ntri, (uint32_t)stride, 9u, cnt);
+    HIPCHK(ctx, hipGetLastError());
+    if (tree) {
+        AccelBuild B = accel_resident(ctx);
+        const AccelLevels V = accel_levels(ntri);
+        hipLaunchKernelGGL(k_accel_count_wild, per_tri, wg, 0, s, B, cnt + 3);
+        HIPCHK(ctx, hipGetLastError());
+        B.tris = (float *)(sc + o_sorted);
+        B.nodes = (AccelNode *)(sc + o_nodes);
+        hipLaunchKernelGGL(k_accel_records, per_tri, wg, 0, s, B);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_accel_leaves, dim3((V.cnt[0] + ACCEL_WG - 1) / ACCEL_WG), wg, 0, s, B, V.cnt[0]);
+        HIPCHK(ctx, hipGetLastError());
+        for (uint32_t k = 1; k < V.n; ++k) {
+            hipLaunchKernelGGL(k_accel_level, dim3((V.cnt[k] + ACCEL_WG - 1) / ACCEL_WG), wg, 0, s, B.nodes, V.off[k - 1], V.cnt[k - 1], V.off[k], V.cnt[k]);
+            HIPCHK(ctx, hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_accel_diff_words, per_tri, wg, 0, s, (const uint32_t *)ctx->d_accel_tris.p, (const uint32_t *)B.tris, ntri, (uint32_t)stride, 9u, cnt + 1);
+        HIPCHK(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_accel_diff_nodes, dim3((ctx->accel_nodes + ACCEL_WG - 1) / ACCEL_WG), wg, 0, s, (const AccelNode *)ctx->d_accel_nodes.p, (const AccelNode *)B.nodes,
+                           ctx->accel_nodes, cnt + 2);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    unsigned long long h[4] = {0, 0, 0, 0};
+    HIPCHK(ctx, hipMemcpyAsync(h, cnt, 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    out[RXR_RAY_REFRESH_VERIFY_PICK_WORDS] = h[0];
+    out[RXR_RAY_REFRESH_VERIFY_SORTED_WORDS] = h[1];
+    out[RXR_RAY_REFRESH_VERIFY_NODES] = h[2];
+    out[RXR_RAY_REFRESH_VERIFY_WILD] = h[3];
     return RXR_OK;
 }
 

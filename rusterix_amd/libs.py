@@ -79,6 +79,10 @@ def rxr_abi():
         "rxr_screen_rays_to": (i32, [vp, vp, vp, C.c_float, C.c_float, u32, u32, u32, u32, vp, vp, vp]),
         "rxr_set_ray_accel": (i32, [vp, u32]),
         "rxr_ray_accel_info": (i32, [vp, C.POINTER(C.c_uint64)]),
+        "rxr_set_ray_refresh": (i32, [vp, u32]),
+        "rxr_ray_refresh_info": (i32, [vp, C.POINTER(C.c_uint64)]),
+        "rxr_ray_refresh_verify": (i32, [vp, C.POINTER(C.c_uint64)]),
+        "rxr_ray_accel_invalidate": (i32, [vp]),
         "rxr_check_bake": (i32, [vp, u32, C.c_char_p, u32]),
         "rxr_bake_shaders": (i32, [vp, vp, u32, u32, u32, vp, vp]),
         "rxr_bake_shaders_to": (i32, [vp, vp, u32, u32, u32, vp, vp, vp]),

@@ -25,6 +25,9 @@ NO_MATERIAL = 0xFFFFFFFF
 MAX_BOUNCES = 8
 RAY_ACCEL_OFF, RAY_ACCEL_ON, RAY_ACCEL_COUNT = 0, 1, 2   # rxr_set_ray_accel's modes (include/rxr.h)
 RAY_ACCEL_INFO = ("mode", "valid", "triangles", "nodes", "levels", "wild", "builds", "batches", "tests")   # rxr_ray_accel_info's words
+RAY_REFRESH_FULL, RAY_REFRESH_RANGED = 0, 1   # rxr_set_ray_refresh's modes (include/rxr.h)
+RAY_REFRESH_INFO = ("mode", "pending", "refreshes", "refits", "triangles", "leaves", "nodes", "route")   # rxr_ray_refresh_info's words
+RAY_REFRESH_VERIFY = ("pick_words", "sorted_words", "nodes", "wild", "checked")   # rxr_ray_refresh_verify's words
 MATTE, GLOSSY, METALLIC, TRANSPARENT, EMISSIVE = range(5)                       # MaterialRole, src/shapestack/material.rs:8-14
 MOD_NONE, MOD_LUMINANCE, MOD_SATURATION, MOD_INV_LUMINANCE, MOD_INV_SATURATION = range(5)   # MaterialModifier::from_u8, :66-76
 SOURCE_OTHER, SOURCE_STATIC_TILE, SOURCE_DYNAMIC_TILE, SOURCE_PIXEL, SOURCE_TERRAIN = range(5)
@@ -253,6 +256,32 @@ class Tracer:
         out = (C.c_uint64 * len(RAY_ACCEL_INFO))()
         self._check(self.rxr.rxr_ray_accel_info(self.ctx, out))
         return dict(zip(RAY_ACCEL_INFO, (int(x) for x in out)))
+
+    @property
+    def ray_refresh(self):
+        """rxr_set_ray_refresh's mode (0 full, the default: a mesh update invalidates the pick records and the tree; 1 ranged: the
+        next query rewrites the updated meshes' records and refits the tree); the results are the same words"""
+        return self.ray_refresh_info()["mode"]
+
+    @ray_refresh.setter
+    def ray_refresh(self, mode):
+        self._check(self.rxr.rxr_set_ray_refresh(self.ctx, int(mode)))
+
+    def ray_refresh_info(self):
+        """rxr_ray_refresh_info as a dict: mode, pending, refreshes, refits, triangles, leaves, nodes, route"""
+        out = (C.c_uint64 * len(RAY_REFRESH_INFO))()
+        self._check(self.rxr.rxr_ray_refresh_info(self.ctx, out))
+        return dict(zip(RAY_REFRESH_INFO, (int(x) for x in out)))
+
+    def ray_refresh_verify(self):
+        """rxr_ray_refresh_verify as a dict (blocking; tests and tools): pick_words, sorted_words, nodes, wild, checked"""
+        out = (C.c_uint64 * len(RAY_REFRESH_VERIFY))()
+        self._check(self.rxr.rxr_ray_refresh_verify(self.ctx, out))
+        return dict(zip(RAY_REFRESH_VERIFY, (int(x) for x in out)))
+
+    def ray_accel_invalidate(self):
+        """rxr_ray_accel_invalidate: the next many-ray query with the tree on builds it from scratch"""
+        self._check(self.rxr.rxr_ray_accel_invalidate(self.ctx))
 
     def intersect(self, origins, dirs, full=False):
         """rxr_intersect over the meshes of set_meshes: a dict of t, mesh, triangle, hitpoint and, with full=True, uv and normal"""

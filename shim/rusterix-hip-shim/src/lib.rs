@@ -100,6 +100,22 @@ pub fn set_ray_accel(on: bool) -> bool {
     }
 }
 
+/// Opt-in: after `rxr_update_meshes` the next device ray query rewrites only the updated meshes' pick records and refits the box tree
+/// instead of building both again (include/rxr.h `rxr_set_ray_refresh`): `ranged = false` is the library's default.  The queries'
+/// results are the same words either way.  Returns false when there is no device context.
+pub fn set_ray_refresh(ranged: bool) -> bool {
+    let mut guard = STATE.lock().unwrap();
+    let st = guard.get_or_insert_with(Caches::default);
+    if st.ctx.is_none() && !st.tried {
+        st.tried = true;
+        st.ctx = create_context();
+    }
+    match &st.ctx {
+        Some(ctx) => unsafe { rxr_set_ray_refresh(ctx.0, if ranged { RXR_RAY_REFRESH_RANGED } else { RXR_RAY_REFRESH_FULL }) == RXR_OK },
+        None => false,
+    }
+}
+
 fn fnv(h: &mut u64, bytes: &[u8]) {
     for b in bytes {
         *h = (*h ^ *b as u64).wrapping_mul(1099511628211);

@@ -6,16 +6,20 @@ block; per out-of-line device function its whole body.  Normalised: comments, bl
     tools/kernel_text_sha.py rxr_kernels.s               # name, sha of the text, sha of the descriptor
     tools/kernel_text_sha.py before.s after.s            # the same side by side; exit status 1 when a column differs
     tools/kernel_text_sha.py --rename NEW=OLD before.s after.s   # a symbol whose mangled name had to change: NEW reads as OLD everywhere
+    tools/kernel_text_sha.py --local-labels before.s after.s     # functions were added ahead of others: a block label .LBB<f>_<b> carries
+                                                                 # its function's position <f> in the file, which then moves; read as .LBB_<b>
 """
 import hashlib
 import re
 import sys
 
 
-def functions(path, renames=()):
+def functions(path, renames=(), local_labels=False):
     text = open(path).read()
     for new, old in renames:
         text = text.replace(new, old)
+    if local_labels:
+        text = re.sub(r"\.LBB\d+_(\d+)", r".LBB_\1", text)
     lines = text.split("\n")
     out, desc = {}, {}
     i = 0
@@ -49,14 +53,16 @@ def sha(lines):
 
 
 def main(args):
-    renames, paths = [], []
+    renames, paths, local_labels = [], [], False
     while args:
         a = args.pop(0)
         if a == "--rename":
             renames.append(tuple(args.pop(0).split("=", 1)))
+        elif a == "--local-labels":
+            local_labels = True
         else:
             paths.append(a)
-    tables = [functions(p, renames) for p in paths]
+    tables = [functions(p, renames, local_labels) for p in paths]
     names = sorted(set().union(*(t[0] for t in tables)), key=lambda n: (n not in tables[0][1], n))
     differ = 0
     for n in names:
