@@ -496,6 +496,11 @@ int rxr_set_projection2d(rxr_ctx *ctx, const float *mat3);
 int rxr_read_projected_mesh(rxr_ctx *ctx, uint32_t index, uint32_t counts[2], float *projected_vertices, float *clipped_uvs,
                             float *clipped_normals, uint32_t *clipped_indices, rxr_edges *edges, float bounding_box[5],
                             uint32_t capacity_vertices, uint32_t capacity_triangles);
+/* debugging / tests: the 16-pixel tile rows [out[0], out[1]) of the resident frame that any 3D triangle can reach, as rxr_upload_frame
+ * found them from the triangles' edge functions (small host-projected frames whose set-up records it builds; the raster kernel of such
+ * a frame skips the 3D passes outside them); 0, 0xFFFFFFFF when the range is "all rows" (every other frame, RXR_D3_ROWS=0, a brush
+ * preview); 0, 0 when no triangle reaches any row.  -1: no context, a multi-device handle or no frame. */
+int rxr_debug_d3_rows(rxr_ctx *ctx, uint32_t out[2]);
 
 /* replaces the context's shader programs, pattern bank and palette (stay resident until the next call;
  * NULL or an empty set removes them).  Programs are restricted to what a per-fragment evaluation can

@@ -1836,8 +1836,21 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
             raise NotImplementedError(f"{name}: no resident chunk textures in this library")
         return int(L.chunk_texture_registrations())
 
+    def d3_rows():
+        """rxr_debug_d3_rows (include/rxr.h) on the process-wide context: the tile rows (t0, t1) of the resident frame that anything 3D
+        can reach, as the last upload found them; None when the range is "all rows"."""
+        if not hasattr(lib, "rxh_context"):
+            raise NotImplementedError(f"{name}: no device context in this library")
+        from .libs import rxr_abi
+
+        out = (C.c_uint32 * 2)()
+        if rxr_abi().rxr_debug_d3_rows(C.c_void_p(lib.rxh_context()), out) != 0:
+            raise RuntimeError("rxr_debug_d3_rows: no resident frame")
+        return None if (out[0], out[1]) == (0, 0xFFFFFFFF) else (int(out[0]), int(out[1]))
+
     return types.SimpleNamespace(
         name=name, lib=lib, prefix=prefix, raw=L, update_meshes=update_meshes, chunk_texture_registrations=chunk_texture_registrations,
+        d3_rows=d3_rows,
         vertex_normals=vertex_normals, vertex_normals_to=vertex_normals_to,
         Scene=Scene, Batch3D=Batch3D, Batch2D=Batch2D, Chunk=Chunk, Assets=Assets, Rasterizer=Rasterizer, Terrain=Terrain, TerrainGenerator=TerrainGenerator,
         D3OrbitCamera=D3OrbitCamera, D3FirstPCamera=D3FirstPCamera, AccumBuffer=AccumBuffer,

@@ -2204,6 +2204,13 @@ extern "C" int rxr_debug_content(rxr_ctx *ctx, uint32_t *out) {
     out[3] = ctx->spans_active ? 1u : (ctx->dev_spans ? 2u : 0u);  // (2: completed on the device from the meshes' boxes)
     return 0;
 }
+// tests: the tile rows anything 3D of the resident frame can reach (rxr_ctx::d3_trow0 / 1; include/rxr.h)
+extern "C" int rxr_debug_d3_rows(rxr_ctx *ctx, uint32_t *out) {
+    if (!ctx || ctx->group || !out || !ctx->has_frame) return -1;
+    out[0] = ctx->d3_trow0;
+    out[1] = ctx->d3_trow1;
+    return 0;
+}
 // tests: the scratch words the next launch assumes clear, read back after the context's streams have drained.  Checked:
 //   buffer 0: every word of d_bin_count -- bin_count (rxr_device.h RasterParams.bin_count: "all-zero between launches", k_raster hands its
 //             bin back) and k_blockscan's per-block group counts behind it (RasterParams.blk_cnt: "all-zero between launches: k_blockscan

@@ -390,6 +390,10 @@ struct rxr_ctx {
     // whole frame): outside them every pixel is the 3D miss colour, which render_impl writes with a fill instead of launching tiles there
     bool content_known = false;
     uint32_t content_row0 = 0, content_row1 = 0;
+    // Tile rows [d3_trow0, d3_trow1) hold everything 3D of the resident frame (RasterParams.d3_trow0 / 1): from the edge functions of the
+    // records build_setup_records has just made, so small host-projected frames only; 0, 0xFFFFFFFF otherwise (all rows).  Not part of
+    // the content rows or the spans: it changes no route, only what a launched workgroup of k_raster[_rl] does
+    uint32_t d3_trow0 = 0, d3_trow1 = 0xFFFFFFFFu;
     // ... and per frame tile row the tile columns [x, y) it can draw in (RasterParams.row_spans): built by rxr_upload_frame from the batch
     // boxes in page-locked memory, copied to the device and used when they leave out enough of the content rows (spans_active)
     uint2 *h_row_spans = nullptr;    // RXR_MAX_TILE_ROWS entries, page-locked

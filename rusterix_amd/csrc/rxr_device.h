@@ -535,6 +535,85 @@ RXR_HD inline bool rxr_tri_records(const TriRecordIn &in, TriSetup &S, TriShade 
     return live;
 }
 
+// Exact trivial reject of a triangle for a whole rectangle of pixels, x0 .. x0 + w - 1 by y0 .. y0 + h - 1: Edges::evaluate computes
+// r = (a*x + b*y) + c per pixel centre and rejects r < 0.  Rounded multiplication and addition are monotone, so over the rectangle's
+// pixel centres r is largest at the corner that maximises a*x and b*y separately; if even that corner is rejected, every pixel of
+// the rectangle is.  (NaN coefficients compare false and never reject.)  THE definition of the raster kernels' tile test (one tile,
+// or the pair kernels' two on top of each other: rxr_kernels.hip) and of the host's tile-row range below (a whole tile row; N = 1: one
+// edge at a time, for its search) -- plain C++ without contraction on either side.
+#if defined(__HIPCC__) || defined(RXR_JIT)
+#define RXR_HD_INLINE __host__ __device__ __forceinline__
+#else
+#define RXR_HD_INLINE inline
+#endif
+template <int N = 3>
+RXR_HD_INLINE bool rxr_rect_outside_edges(const float *ea, const float *eb, const float *ec, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h) {
+    const float x_lo = (float)x0 + 0.5f, x_hi = (float)(x0 + w - 1u) + 0.5f;
+    const float y_lo = (float)y0 + 0.5f, y_hi = (float)(y0 + h - 1u) + 0.5f;
+#if defined(__HIPCC__) || defined(RXR_JIT)
+#pragma unroll
+#endif
+    for (int i = 0; i < N; ++i) {
+        const float xm = ea[i] >= 0.0f ? x_hi : x_lo;
+        const float ym = eb[i] >= 0.0f ? y_hi : y_lo;
+        const float r = ea[i] * xm + eb[i] * ym + ec[i];
+        if (r < 0.0f) return true;
+    }
+    return false;
+}
+// The tile rows [t0, t1) of a frame `width` pixels wide in which the triangle of record S can produce a pixel (t0 == t1 == 0: none; an
+// all-zero record -- invisible edge record, skipped batch -- or an empty pixel box reaches nothing).  A row is out when its pixel box
+// misses it or rxr_rect_outside_edges rejects the row's rectangle, all `width` columns by the 16 rows of the tile row:
+// what the kernel's own tile test would answer for every tile of the row, since each tile's rectangle lies inside the row's.  Over
+// the rows of the box an edge's reject is monotone in the row index -- with b >= 0 the corner is the row's last pixel row and r does
+// not decrease downwards: the rejected rows are a prefix; with b < 0 (or NaN: never rejects) the corner is the first pixel row and they
+// are a suffix -- so each edge narrows the range by a binary search, at most 8 evaluations for the 135 tile rows of a 4K frame.
+// (Where an infinite product meets an opposite infinity r is NaN from there on in the direction of growth: still a prefix / suffix.)
+RXR_HD inline void rxr_tri_tile_rows(const TriSetup &S, uint32_t width, uint32_t tile_h, uint32_t &t0, uint32_t &t1) {
+    t0 = t1 = 0u;
+    const uint32_t min_x = S.bx & 0xFFFFu, max_x = S.bx >> 16, min_y = S.by & 0xFFFFu, max_y = S.by >> 16;
+    if (!(min_x < max_x && min_y < max_y) || width == 0u) return;
+    uint32_t lo = min_y / tile_h, hi = (max_y + tile_h - 1u) / tile_h;  // (the rows the pixel box meets)
+    for (int i = 0; i < 3 && lo < hi; ++i) {
+        const float *a = &S.ea[i], *b = &S.eb[i], *c = &S.ec[i];
+        if (*b >= 0.0f) {
+            // the first row of [lo, hi) that is not rejected (hi: none)
+            uint32_t l = lo, h = hi;
+            while (l < h) {
+                const uint32_t m = l + (h - l) / 2u;
+                if (rxr_rect_outside_edges<1>(a, b, c, 0u, m * tile_h, width, tile_h)) l = m + 1u;
+                else h = m;
+            }
+            lo = l;
+        } else {
+            // one past the last row of [lo, hi) that is not rejected (lo: none)
+            uint32_t l = lo, h = hi;
+            while (l < h) {
+                const uint32_t m = l + (h - l) / 2u;
+                if (rxr_rect_outside_edges<1>(a, b, c, 0u, m * tile_h, width, tile_h)) h = m;
+                else l = m + 1u;
+            }
+            hi = l;
+        }
+    }
+    if (lo < hi) {
+        t0 = lo;
+        t1 = hi;
+    }
+}
+// ... and the union over a frame's records, one at a time: [r0, r1) starts as (0xFFFFFFFF, 0) and stays so while nothing reaches a row.
+// A triangle whose pixel box already lies in rows of the union cannot widen it and is not searched.
+RXR_HD inline void rxr_union_tile_rows(const TriSetup &S, uint32_t width, uint32_t tile_h, uint32_t &r0, uint32_t &r1) {
+    const uint32_t min_y = S.by & 0xFFFFu, max_y = S.by >> 16;
+    if (min_y < max_y && r0 <= min_y / tile_h && (max_y + tile_h - 1u) / tile_h <= r1) return;
+    uint32_t t0, t1;
+    rxr_tri_tile_rows(S, width, tile_h, t0, t1);
+    if (t0 < t1) {
+        r0 = t0 < r0 ? t0 : r0;
+        r1 = t1 > r1 ? t1 : r1;
+    }
+}
+
 // kernel parameter block (passed by value; lives in the kernarg segment -> scalar loads)
 #if defined(__HIPCC__) || defined(RXR_JIT)  // (HIP's vector types: a plain C++ compiler gets everything above)
 struct RasterParams {
@@ -567,12 +646,19 @@ struct RasterParams {
     uint32_t list2d_capacity;
     uint32_t list_capacity;
     uint32_t ref_tile;             // the reference's tile_size (rxr_frame.tile_size): only the batch box test of RISKY batches depends on it
+    uint32_t d3_trow0;             // small host-projected frames (fused_small 2, records made at upload): the FRAME tile rows [d3_trow0, d3_trow1)
+                                   // that any 3D triangle can reach (rxr_tri_tile_rows over the frame's records, rxr_upload_frame); k_raster[_rl]
+                                   // skip the 3D passes of a workgroup outside them -- its pixels are misses.  0, 0xFFFFFFFF: all rows.
+                                   // (The two words fill what were alignment holes in front of the two pointers, in the 64 bytes of the
+                                   // kernarg segment that hold fused_small: no other field moves, and the test in front of every tile
+                                   // waits for no cache line that the kernel did not fetch at that point before)
     const uint4 *batch_clip3d;     // host-projected frames with a risky 3D batch or under row spans: per batch the pixels (x0, x1, y0, y1) the
                                    // reference draws it in (rxr_ref_tile_span; skipped batches: the whole frame); NULL otherwise.  make_setup
                                    // clips the pixel boxes (device-projected frames: from dev_bbox, for risky boxes and under row_spans)
     uint32_t fused_small;          // small-scene mode (whole frame <= RXR_STAGE_TRIS triangles): 0 = binned pipeline,
                                    // 1 = fully fused (k_raster_fused builds the records itself, no pre-pass launch),
                                    // 2 = implicit list (k_setup3d writes the records, no scan / fill / bins; default)
+    uint32_t d3_trow1;             // (see d3_trow0)
 
     // geometry inputs (indexed, as handed over by the host)
     const float4 *pv;              // projected_vertices

@@ -2158,23 +2158,10 @@ __device__ __forceinline__ void visit_cover(const TriSetup &S, uint32_t t, uint3
     }
 }
 
-// Exact trivial reject of a triangle for a whole tile: Edges::evaluate computes r = (a*x + b*y) + c per
-// pixel centre and rejects r < 0.  Rounded multiplication and addition are monotone, so over the tile's
-// pixel centres r is largest at the corner that maximises a*x and b*y separately; if even that corner
-// is rejected, every pixel of the tile is.  (NaN coefficients compare false and never reject.)
-__device__ __forceinline__ bool tile_outside_edges(const float *ea, const float *eb, const float *ec, uint32_t tile_x0, uint32_t tile_y0px,
-                                                   uint32_t th = RXR_TILE_H) {
-    const float x_lo = (float)tile_x0 + 0.5f, x_hi = (float)(tile_x0 + RXR_TILE_W - 1u) + 0.5f;
-    const float y_lo = (float)tile_y0px + 0.5f, y_hi = (float)(tile_y0px + th - 1u) + 0.5f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float xm = ea[i] >= 0.0f ? x_hi : x_lo;
-        const float ym = eb[i] >= 0.0f ? y_hi : y_lo;
-        const float r = ea[i] * xm + eb[i] * ym + ec[i];
-        if (r < 0.0f) return true;
-    }
-    return false;
-}
+// Exact trivial reject of a triangle for a whole tile (rxr_rect_outside_edges, rxr_device.h: the definition, which the host asks of
+// whole tile rows -- rxr_tri_tile_rows).  A name for the call, not a function of its own: one more level of inlining between the kernels
+// and the shared definition changed the register allocation of thirteen kernels that have nothing else to do with it.
+#define tile_outside_edges(ea, eb, ec, tile_x0, tile_y0px) rxr_rect_outside_edges((ea), (eb), (ec), (tile_x0), (tile_y0px), RXR_TILE_W, RXR_TILE_H)
 
 // The converse: Edges::evaluate accepts EVERY pixel centre of the tile.  Over the tile r = (a*x + b*y) + c is smallest at the corner
 // that minimises a*x and b*y separately (the same monotonicity); if that corner's r -- the same expression -- is a number >= 0,
@@ -3162,7 +3149,20 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
         }
     }
 
-    if (P.flags & RXR_FLAG_D3_ACTIVE) {
+    // Small frames whose records the host made (fused_small 2): the tile rows outside [d3_trow0, d3_trow1) are out of every triangle's
+    // reach (rxr_tri_tile_rows, the tile reject below asked of whole rows at upload), so a workgroup there would stage the records,
+    // reject them all, pass four barriers and find `hit` false in every lane.  It takes the miss colour at once: two scalar compares,
+    // uniform over the workgroup and in front of every barrier.  k_raster and k_raster_rl only (the kernels such frames get; the
+    // other instantiations do not carry the test).
+    constexpr bool D3_ROWS = !FUSED && !ROWS && LV == Level::Common;
+    bool d3_skip = false;
+    if constexpr (D3_ROWS) {
+        const uint32_t trow = P.tile_y0 + ty * P.tile_stride;
+        d3_skip = P.fused_small == 2u && (trow < P.d3_trow0 || trow >= P.d3_trow1);
+    }
+    if (D3_ROWS && d3_skip) {
+        color = pack4(0u, 0u, 0u, 255u);  // miss (:420-461; fused_small is only ever non-zero in 3D mode: render_impl)
+    } else if (P.flags & RXR_FLAG_D3_ACTIVE) {
         constexpr bool fused = FUSED;
         uint32_t b0 = 0, b1 = 0;
         uint32_t my_bin_count = 0;
@@ -3353,7 +3353,7 @@ __device__ __forceinline__ void scan_lists_pair(const RasterParams &P, Stage &st
             keep = id < P.n_tris3d && !(min_x >= tile_x0 + RXR_TILE_W || max_x <= tile_x0 || min_y >= tile_y0px + 2u * RXR_TILE_H || max_y <= tile_y0px);
             // the lower bin's entry is the upper bin's entry too when its box begins above the lower tile
             if (base + tid >= n_large + n_a && min_y < y_lower) keep = false;
-            if (keep && tile_outside_edges(R.ea, R.eb, R.ec, tile_x0, tile_y0px, 2u * RXR_TILE_H)) keep = false;
+            if (keep && rxr_rect_outside_edges(R.ea, R.eb, R.ec, tile_x0, tile_y0px, RXR_TILE_W, 2u * RXR_TILE_H)) keep = false;
         }
         const unsigned long long mk = __ballot(keep);
         const uint32_t before = (uint32_t)__popcll(mk & ((1ull << lane) - 1ull));

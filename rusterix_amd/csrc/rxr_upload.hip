@@ -1297,7 +1297,22 @@ struct FrameBuild {
         src.sample_mode = f->sample_mode;
         src.width = f->width;
         src.height = f->height;
-        for (size_t t = 0; t < n_t3; ++t) rxr_host_tri_records(src, t, ts[t], th[t]);
+        // ... and, from the records just written, the tile rows that anything 3D can reach (rxr_tri_tile_rows: the kernel's own tile
+        // reject, asked of whole tile rows): the union over all triangles, opacity-list batches included, as one range.  The pixel boxes
+        // of triangles clipped at the near plane are clamped to the whole height and a 2D primitive anywhere pins the content rows; only
+        // the edge functions know that the rows above a room's walls are empty.  k_raster[_rl] skip the 3D passes of a workgroup
+        // outside the range (raster_tile).  Not with a brush preview (it paints missed pixels, :435-458), not for 2D-only frames
+        // (nothing looks); RXR_D3_ROWS=0 (read per upload) switches it off for A-B runs and tests.  Nothing is kept across uploads.
+        const bool d3_rows = !(getenv("RXR_D3_ROWS") && atoi(getenv("RXR_D3_ROWS")) == 0) && (f->flags & RXR_FLAG_D3_ACTIVE) && !f->has_brush_preview;
+        uint32_t r0 = 0xFFFFFFFFu, r1 = 0u;
+        for (size_t t = 0; t < n_t3; ++t) {
+            rxr_host_tri_records(src, t, ts[t], th[t]);
+            if (d3_rows) rxr_union_tile_rows(ts[t], f->width, RXR_TILE_H, r0, r1);
+        }
+        if (d3_rows) {
+            ctx->d3_trow0 = r0 < r1 ? r0 : 0u;  // (no triangle reaches anything: the empty range)
+            ctx->d3_trow1 = r0 < r1 ? r1 : 0u;
+        }
     }
 
     int ship_blob() {
@@ -1360,6 +1375,8 @@ struct FrameBuild {
         memcpy(P.sun_dir, f->sun_dir, 12);
         P.day_factor = f->day_factor;
         P.n_tris3d = (uint32_t)n_t3;
+        P.d3_trow0 = ctx->d3_trow0;  // (build_setup_records, or all rows)
+        P.d3_trow1 = ctx->d3_trow1;
         P.n_batches3d = n_b3;
         P.n_lights = f->n_lights;
         P.n_occluders = f->n_occluders;
@@ -1580,6 +1597,8 @@ extern "C" int rxr_upload_frame(rxr_ctx *ctx, const rxr_frame *f) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->has_frame = false;
     ctx->host_records = false;
+    ctx->d3_trow0 = 0u;  // (all rows, until build_setup_records says otherwise)
+    ctx->d3_trow1 = 0xFFFFFFFFu;
     // Were this frame's 3D batches handed over while they were projected (rxr_stream_begin / rxr_stream_batch3d)?  Then their arrays
     // are in the blob already, or on their way.  Anything that does not match -- a batch missing, other arrays than the ones streamed,
     // a failure on the way -- and the frame takes the plain path below from scratch.

@@ -64,6 +64,7 @@ def rxr_abi():
         "rxr_debug_last_raster_kernel": (C.c_char_p, [vp]),
         "rxr_debug_content": (i32, [vp, C.POINTER(u32)]),
         "rxr_debug_last_setup_route": (u32, [vp]),
+        "rxr_debug_d3_rows": (i32, [vp, C.POINTER(u32)]),
         "rxr_debug_setup_records": (i32, [vp, vp, vp, vp, vp, u32, C.POINTER(u32)]),
         "rxr_render_download": (i32, [vp, vp]),
         "rxr_download_rows": (i32, [vp, vp, u32, u32]),
