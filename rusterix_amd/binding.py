@@ -15,6 +15,8 @@ import types
 
 import numpy as np
 
+from .abi import RXR_ERR_HIP, RXR_ERR_INVALID, RXR_ERR_NO_DEVICE, RXR_ERR_OOM, RXR_ERR_UNSUPPORTED, RXR_OK, rxr_light  # noqa: F401
+
 # ---- enums (include/rxr.h) ---------------------------------------------------------------------
 SAMPLE_NEAREST, SAMPLE_LINEAR = 0, 1
 RAY_ACCEL_OFF, RAY_ACCEL_ON, RAY_ACCEL_COUNT = 0, 1, 2   # rxr_set_ray_accel's modes (include/rxr.h)
@@ -30,29 +32,7 @@ HOST_SOURCE_ENTITY_TILE, HOST_SOURCE_ITEM_TILE = 64, 65  # never cross the ABI: 
 LIST_CHUNK_OPACITY, LIST_CHUNK, LIST_CHUNK_TERRAIN, LIST_STATIC, LIST_DYNAMIC, LIST_OVERLAY = range(6)
 BG_NONE, BG_VGRADIENT, BG_HOST_PIXELS, BG_GRID = 0, 1, 2, 3
 
-RXR_OK, RXR_ERR_INVALID, RXR_ERR_NO_DEVICE, RXR_ERR_HIP, RXR_ERR_UNSUPPORTED, RXR_ERR_OOM = 0, -1, -2, -3, -4, -5
-
-
-class RxrLight(C.Structure):
-    """rxr_light == CompiledLight (reference src/map/light.rs:456-477)."""
-
-    _fields_ = [
-        ("light_type", C.c_uint32),
-        ("position", C.c_float * 3),
-        ("color", C.c_float * 3),
-        ("intensity", C.c_float),
-        ("emitting", C.c_uint32),
-        ("start_distance", C.c_float),
-        ("end_distance", C.c_float),
-        ("flicker", C.c_float),
-        ("direction", C.c_float * 3),
-        ("cone_angle", C.c_float),
-        ("normal", C.c_float * 3),
-        ("width", C.c_float),
-        ("height", C.c_float),
-        ("from_linedef", C.c_uint32),
-    ]
-
+RxrLight = rxr_light   # == CompiledLight (reference src/map/light.rs:456-477)
 
 TERRAIN_BLEND_NONE, TERRAIN_BLEND_RADIUS, TERRAIN_BLEND_OFFSET = 0, 1, 2   # include/rxr.h RXR_TERRAIN_BLEND_*
 
@@ -367,10 +347,7 @@ class Program:
 
 def pinned_pixels(rxr, nbytes):
     """a uint8 array of `nbytes` in page-locked, device-readable memory from the library's own allocator (rxr_alloc_pinned: nothing of
-    the malloc heap is locked) and the function that frees it; (None, None) when there is no such memory"""
-    rxr.rxr_alloc_pinned.restype = C.c_void_p
-    rxr.rxr_alloc_pinned.argtypes = [C.c_size_t]
-    rxr.rxr_free_pinned.argtypes = [C.c_void_p]
+    the malloc heap is locked) and the function that frees it; (None, None) when there is no such memory.  `rxr`: the typed library (libs.rxr_abi())"""
     p = rxr.rxr_alloc_pinned(nbytes)
     if not p:
         return None, None

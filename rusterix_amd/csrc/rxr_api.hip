@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "rxr_debug.h"
 #include "rxr_query.h"
 
 thread_local LaunchTimes *rxr_launch_times = nullptr;  // rxr_launch.h: the profiling slot of the render this thread is queueing

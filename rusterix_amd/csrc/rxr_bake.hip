@@ -30,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "rxr_debug.h"
 #include "rxr_query.h"
 #include "rxr_vm.h"
 

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "rxr_debug.h"
 #include "rxr_query.h"
 
 // One launch: at most RXR_CHUNK_TEX_LAUNCH sources, each copied into its slot in segments of RXR_CHUNK_TEX_SEGMENT texels.  Everything the

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "rxr_ctx.h"
+#include "rxr_debug.h"
 #include "rxr_route.h"
 
 #include <dirent.h>

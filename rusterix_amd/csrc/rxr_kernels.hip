@@ -32,6 +32,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "rxr_debug.h"
 #include "rxr_launch.h"
 #include "rxr_route.h"
 #endif

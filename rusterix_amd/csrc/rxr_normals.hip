@@ -31,6 +31,7 @@
 #include <cstring>
 #include <string>
 
+#include "rxr_debug.h"
 #include "rxr_query.h"
 #include "rxr_exact_math.h"
 

@@ -41,6 +41,7 @@
 #include <string>
 #include <vector>
 
+#include "rxr_debug.h"
 #include "rxr_query.h"
 #include "rxr_exact_math.h"
 

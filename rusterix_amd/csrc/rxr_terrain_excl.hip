@@ -42,6 +42,7 @@
 #include <string>
 #include <vector>
 
+#include "rxr_debug.h"
 #include "rxr_terrain_gen.h"
 
 #define EXCL_LAUNCH_BOXES 64u     // boxes a round carries in its kernels' arguments (48 bytes each)

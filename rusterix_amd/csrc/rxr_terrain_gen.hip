@@ -40,6 +40,7 @@
 #include <string>
 #include <vector>
 
+#include "rxr_debug.h"
 #include "rxr_terrain_gen.h"
 
 #define GEN_LAUNCH_BOXES 128u   // boxes a grid launch carries in its arguments (16 bytes each)

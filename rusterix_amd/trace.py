@@ -16,12 +16,12 @@ import ctypes as C
 
 import numpy as np
 
+from .abi import (RXR_TRACE_CAMERA_FIRSTP as CAMERA_FIRSTP, RXR_TRACE_CAMERA_ISO as CAMERA_ISO, RXR_TRACE_CAMERA_ORBIT as CAMERA_ORBIT,
+                  RXR_TRACE_NO_MATERIAL as NO_MATERIAL, rxr_mesh3d as _Mesh3D, rxr_texture as _Texture, rxr_tile as _Tile)
 from .binding import RxrLight
 from .libs import rxr_abi
 
 F = np.float32
-CAMERA_FIRSTP, CAMERA_ORBIT, CAMERA_ISO = 0, 1, 2
-NO_MATERIAL = 0xFFFFFFFF
 MAX_BOUNCES = 8
 RAY_ACCEL_OFF, RAY_ACCEL_ON, RAY_ACCEL_COUNT = 0, 1, 2   # rxr_set_ray_accel's modes (include/rxr.h)
 RAY_ACCEL_INFO = ("mode", "valid", "triangles", "nodes", "levels", "wild", "builds", "batches", "tests")   # rxr_ray_accel_info's words
@@ -131,29 +131,6 @@ def mesh(vertices, indices, uvs, normals, list=LIST_STATIC, chunk=-1, source=(SO
     return dict(vertices=np.ascontiguousarray(vertices, F).reshape(-1, 4), indices=np.ascontiguousarray(indices, np.uint32).reshape(-1, 3),
                 uvs=np.ascontiguousarray(uvs, F).reshape(-1, 2), normals=np.ascontiguousarray(normals, F).reshape(-1, 3), list=int(list),
                 chunk=int(chunk), source=source, repeat_mode=int(repeat_mode), material=material)
-
-
-class _Source(C.Structure):
-    _fields_ = [("kind", C.c_uint32), ("index", C.c_uint32), ("pixel", C.c_uint8 * 4)]
-
-
-class _Mesh3D(C.Structure):
-    """rxr_mesh3d (include/rxr.h)"""
-    _fields_ = [("vertices", C.c_void_p), ("indices", C.c_void_p), ("uvs", C.c_void_p), ("normals", C.c_void_p),
-                ("n_vertices", C.c_uint32), ("n_triangles", C.c_uint32), ("transform_3d", C.c_float * 16), ("cull_mode", C.c_uint32),
-                ("repeat_mode", C.c_uint32), ("source", _Source), ("ambient_color", C.c_float * 3), ("shader", C.c_int32),
-                ("has_profile_id", C.c_uint32), ("profile_id", C.c_uint32), ("list", C.c_uint32), ("chunk", C.c_int32)]
-
-
-class _Texture(C.Structure):
-    _fields_ = [("rgba", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
-
-
-class _Tile(C.Structure):
-    _fields_ = [("textures", C.POINTER(_Texture)), ("n_textures", C.c_uint32)]
-
-
-assert C.sizeof(_Mesh3D) == 160 and C.sizeof(_Texture) == 16 and C.sizeof(_Tile) == 16
 
 
 def _tiles(tiles):

@@ -12,16 +12,13 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "rxr.h"
+#include "../rusterix_amd/csrc/rxr_debug.h" /* rxr.h and the test entry points */
 
 #define W 171u
 #define H 107u
 #define NA 6u  /* triangles with normals */
 #define NB 5u  /* triangles without */
 #define NT (NA + NB)
-
-uint32_t rxr_debug_last_setup_route(rxr_ctx *ctx);    /* (test entry points: not in rxr.h) */
-int rxr_debug_setup_records(rxr_ctx *ctx, void *host_setup, void *host_shade, void *dev_setup, void *dev_shade, uint32_t capacity_tris, uint32_t *n_tris);
 
 static float va[NA * 3][4], vb[NB * 3][4], uvs[NA * 3][2], na[NA * 3][3];
 static uint32_t idx[NA * 3], vis[NA];

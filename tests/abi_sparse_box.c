@@ -9,16 +9,13 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "rxr.h"
+#include "../rusterix_amd/csrc/rxr_debug.h" /* rxr.h and the test entry points */
 
 #define W 480u
 #define H 480u
 #define NX 16u
 #define NY 10u
 #define NS (NX * NY)
-
-int rxr_debug_scratch(rxr_ctx *ctx, uint32_t *out);    /* (test entry points: not in rxr.h) */
-int rxr_debug_content(rxr_ctx *ctx, uint32_t *out);
 
 static float big_v[3][4] = {{290.0f, 190.0f, 0.5f, 1.0f}, {325.0f, 200.0f, 0.5f, 1.0f}, {290.0f, 210.0f, 0.5f, 1.0f}};
 static uint32_t big_i[3] = {0, 1, 2};

@@ -11,7 +11,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "rxr.h"
+#include "../rusterix_amd/csrc/rxr_debug.h" /* rxr.h and the test entry points */
 
 #define W 160u
 #define H 96u
@@ -211,7 +211,6 @@ int main(void) {
                        "malloc'ed arrays locked with rxr_pin_host_buffer, pulled by the device");
                 (void)rxr_synchronize(ctx);
                 {   /* the frame really came out of the registered block (2 = pulled by the device), not from scratch */
-                    extern int rxr_debug_stream_info(rxr_ctx *);
                     const int mode = rxr_debug_stream_info(ctx);
                     printf("%-72s mode=%d %s\n", "... handed over by the pull kernel", mode, mode == 2 ? "yes" : "NO");
                     if (mode != 2) ++failures;

@@ -414,8 +414,7 @@ def check_set(programs):
     lib = rusterix_amd.rxr_abi()
     s, keep = R.shader_set(programs)
     msg = C.create_string_buffer(512)
-    raw = rusterix_amd.load_rxr()
-    rc = raw.rxr_check_shaders(C.byref(s), None, msg, 512)
+    rc = lib.rxr_check_shaders(C.byref(s), None, msg, 512)
     out, said = [], [msg.value.decode()]
     for i in range(len(programs)):
         out.append(lib.rxr_check_bake(C.cast(C.byref(s), C.c_void_p), i, msg, 512))

@@ -14,28 +14,13 @@ import ctypes as C
 
 import numpy as np
 
+from rusterix_amd.abi import rxr_function as RxrFunction, rxr_program as RxrProgram, rxr_shader_set as RxrShaderSet
 from rusterix_amd.binding import Program
 
 GAMMA = float(np.float32(0.4545))          # `let gamma_correction = 0.4545` is an f32 in the reference
 BAND = 17.0 * 2.0 ** -24 * 255.0           # (the measured Pow maximum: profiles/libm_ulp/README.md)
 FIELDS = ["uv", "color", "roughness", "metallic", "emissive", "opacity", "bump", "normal", "hitpoint", "time"]
 SIZES = [(64, 64), (1, 1), (63, 65), (80, 80), (81, 1), (257, 3)]   # (width, height): the bake's own size, partial last workgroups, the reference's tile edge
-
-
-# ---- the C structs of include/rxr.h that rxr_check_bake / rxr_set_shaders read ---------------------------------------------------
-class RxrFunction(C.Structure):
-    _fields_ = [("words", C.POINTER(C.c_uint32)), ("n_words", C.c_uint32)]
-
-
-class RxrProgram(C.Structure):
-    _fields_ = [("n_globals", C.c_uint32), ("shade_index", C.c_int32), ("shade_locals", C.c_uint32),
-                ("functions", C.POINTER(RxrFunction)), ("n_functions", C.c_uint32)]
-
-
-class RxrShaderSet(C.Structure):
-    _fields_ = [("programs", C.POINTER(RxrProgram)), ("n_programs", C.c_uint32), ("patterns", C.c_void_p), ("n_patterns", C.c_uint32),
-                ("normal_patterns", C.c_void_p), ("n_normal_patterns", C.c_uint32), ("palette_rgb", C.c_void_p),
-                ("palette_present", C.c_void_p), ("n_palette", C.c_uint32)]
 
 
 def shader_set(programs):
@@ -47,7 +32,7 @@ def shader_set(programs):
         for k, f in enumerate(p.functions):
             arr = np.asarray(f if len(f) else [0], np.uint32)
             keep.append(arr)
-            fns[k] = RxrFunction(arr.ctypes.data_as(C.POINTER(C.c_uint32)), len(f))
+            fns[k] = RxrFunction(arr.ctypes.data, len(f))
         keep.append(fns)
         progs[i] = RxrProgram(p.globals, p.shade_index, p.shade_locals, fns, len(p.functions))
     keep.append(progs)

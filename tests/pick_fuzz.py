@@ -13,6 +13,7 @@ import re
 
 import numpy as np
 
+from rusterix_amd.abi import rxr_mesh3d as Mesh3D
 from tests import intersect_ref as R
 
 F = np.float32
@@ -228,20 +229,6 @@ def host_scene(api, meshes):
     return scene
 
 
-class Source(C.Structure):
-    _fields_ = [("kind", C.c_uint32), ("index", C.c_uint32), ("pixel", C.c_uint8 * 4)]
-
-
-class Mesh3D(C.Structure):
-    """rxr_mesh3d (include/rxr.h), offsets as in tests/abi_layout_asserts.h"""
-    _fields_ = [("vertices", C.c_void_p), ("indices", C.c_void_p), ("uvs", C.c_void_p), ("normals", C.c_void_p),
-                ("n_vertices", C.c_uint32), ("n_triangles", C.c_uint32), ("transform_3d", C.c_float * 16), ("cull_mode", C.c_uint32),
-                ("repeat_mode", C.c_uint32), ("source", Source), ("ambient_color", C.c_float * 3), ("shader", C.c_int32),
-                ("has_profile_id", C.c_uint32), ("profile_id", C.c_uint32), ("list", C.c_uint32), ("chunk", C.c_int32)]
-
-
-assert C.sizeof(Mesh3D) == 160 and Mesh3D.transform_3d.offset == 40 and Mesh3D.source.offset == 112 and Mesh3D.shader.offset == 136
-assert Mesh3D.has_profile_id.offset == 140 and Mesh3D.list.offset == 148 and Mesh3D.chunk.offset == 152
 IDENTITY = (C.c_float * 16)(*np.eye(4, dtype=F).ravel())
 
 
@@ -268,8 +255,6 @@ class PickContext:
         import rusterix_amd
 
         self.rxr = rusterix_amd.rxr_abi()
-        self.rxr.rxr_set_meshes.restype = C.c_int
-        self.rxr.rxr_set_meshes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         self.ctx = C.c_void_p()
         rc = self.rxr.rxr_create(C.byref(self.ctx), device)
         if rc != 0:

@@ -8,11 +8,11 @@ HeightSpec is the neutral description the tests build terrains with: it answers 
 import numpy as np
 
 from tests.terrain_ref import as_i32, round_away
+from rusterix_amd.abi import RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED, RXR_OK
 
 F = np.float32
 STEPS = 1500                     # RXR_TERRAIN_MARCH_STEPS
 F32_MAX = np.finfo(np.float32).max
-RXR_OK, RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED = 0, -1, -4
 
 
 def march_table():

@@ -10,15 +10,10 @@ import ctypes as C
 
 import numpy as np
 
+from rusterix_amd.abi import RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED, RXR_OK, rxr_texture as RxrTexture  # noqa: F401
+
 F = np.float32
 NONE, RADIUS, OFFSET = 0, 1, 2          # RXR_TERRAIN_BLEND_* (include/rxr.h)
-RXR_OK, RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED = 0, -1, -4
-
-
-class RxrTexture(C.Structure):
-    """rxr_texture (include/rxr.h)"""
-
-    _fields_ = [("rgba", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
 
 
 def round_away(v):

@@ -58,7 +58,7 @@ def test_refuses_read_before_write_of_a_carried_field(field):
         rc, msg = check_bake([P(["UV", "SetColor"]), prog], 1)
         assert rc == B.RXR_ERR_UNSUPPORTED and field.lower() in msg, (field, rc, msg)
     if field == "Normal":   # the raster loops assign `normal` before every call: for frames this program is fine, for a bake it is not
-        lib = rusterix_amd.load_rxr()
+        lib = rusterix_amd.rxr_abi()
         s, keep = R.shader_set([P([field, "SetColor", ("Push", 0.3, 0.4, 0.5), "Set" + field])])
         assert lib.rxr_check_shaders(C.byref(s), None, None, 0) == 0
         assert check_bake([P(["UV", "SetColor"]), P([field, "SetColor", ("Push", 0.3, 0.4, 0.5), "Set" + field])], 0)[0] == 0   # the OTHER program of the set bakes

@@ -11,17 +11,9 @@ import pytest
 
 import rusterix_amd
 from rusterix_amd import binding as B
+from rusterix_amd.abi import RXR_ERR_INVALID, RXR_OK, rxr_texture as Tex
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RXR_OK, RXR_ERR_INVALID = 0, -1
-
-
-class Tex(C.Structure):
-    """rxr_texture"""
-    _fields_ = [("rgba", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
-
-
-assert C.sizeof(Tex) == 16
 
 
 def check(sizes, terrain, first, slots, n_chunks=None, null=(), with_bytes=True):

@@ -10,13 +10,13 @@ import rusterix_amd
 from rusterix_amd import binding as B
 from rusterix_amd import scenes
 from rusterix_amd.binding import Program
+from rusterix_amd.abi import RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED, RXR_OK
 from tests import bake_ref as R
 from tests.bake_ref import P
 
 pytestmark = pytest.mark.gpu
 
 TOLERANCE = 1    # bytes of programs that use sin / cos / pow / atan2 / ln (the project's tolerance for these opcodes)
-RXR_OK, RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED = 0, -1, -4
 
 
 def scene_of(api, programs):
@@ -245,7 +245,6 @@ def test_errors_leave_the_context_usable(oracle, product):
     empty = product.Scene.empty()
     frame_still_renders(oracle, product)      # (a frame without programs: the context's set is empty)
     ctx = context_of(product)
-    rxr.rxr_set_shaders.argtypes = [C.c_void_p, C.c_void_p]
     assert rxr.rxr_set_shaders(ctx, None) == RXR_OK
     assert rxr.rxr_bake_shaders(ctx, zero.ctypes.data, 1, 4, 4, out.ctypes.data, None) == RXR_ERR_INVALID and "no shader set" in last_error(rxr, ctx)
     with pytest.raises(B.RasterizeError) as e:

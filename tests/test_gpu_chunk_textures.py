@@ -13,28 +13,12 @@ import pytest
 import rusterix_amd
 from rusterix_amd import binding as B
 from rusterix_amd import scenes
+from rusterix_amd.abi import RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED, RXR_OK, rxr_chunk as Chunk, rxr_frame as Frame, rxr_texture as Tex
 from tests.test_gpu_bake import CHECKER
 from tests.test_gpu_chunks import floor_quad, terrain_texture
-from tests.test_gpu_mesh_update import Frame
 
 pytestmark = pytest.mark.gpu
-RXR_OK, RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED = 0, -1, -4
 W, H = 208, 144
-
-
-class Tex(C.Structure):
-    """rxr_texture"""
-    _fields_ = [("rgba", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
-
-
-class Chunk(C.Structure):
-    """rxr_chunk (include/rxr.h), offsets as in tests/abi_layout_asserts.h"""
-    _fields_ = [("occluders", C.c_void_p), ("n_occluders", C.c_uint32), ("program_base", C.c_uint32), ("n_programs", C.c_uint32),
-                ("shader_textures", C.c_void_p), ("n_shader_textures", C.c_uint32), ("terrain_texture", C.c_void_p), ("origin", C.c_int32 * 2),
-                ("size", C.c_int32)]
-
-
-assert C.sizeof(Chunk) == 64 and Chunk.shader_textures.offset == 24 and Chunk.terrain_texture.offset == 40 and Chunk.size.offset == 56
 
 
 def constants():
@@ -246,7 +230,6 @@ def test_refusals_change_nothing():
 def test_frames_must_match_the_registration():
     """a frame with another n_chunks, or one that carries its own chunk textures, is refused while a registration is held"""
     with Pool() as p:
-        p.rxr.rxr_upload_frame.restype, p.rxr.rxr_upload_frame.argtypes = C.c_int, [C.c_void_p, C.c_void_p]
         data = texels(600, 8, 8)
         tex = Tex(data.ctypes.data, 8, 8)
         chunks = (Chunk * 2)()
@@ -256,15 +239,15 @@ def test_frames_must_match_the_registration():
         def upload(n_chunks):
             f = Frame()
             f.abi_version, f.width, f.height, f.tile_size, f.scaled2, f.flags = 5, 64, 64, 32, 1.0, 1 << 1
-            f.chunks, f.n_chunks = C.cast(chunks, C.c_void_p), n_chunks
+            f.chunks, f.n_chunks = chunks, n_chunks
             return p.rxr.rxr_upload_frame(p.ctx, C.byref(f))
 
-        chunks[1].terrain_texture = C.cast(C.pointer(tex), C.c_void_p)
+        chunks[1].terrain_texture = C.pointer(tex)
         assert upload(2) == RXR_OK, p.error()                  # no registration: the frame carries its textures
         p.register([(8, 8)], [data], n_chunks=2)
         assert upload(2) == RXR_ERR_INVALID and "chunk 1 carries its own" in p.error()
         chunks[1].terrain_texture = None
-        chunks[0].shader_textures, chunks[0].n_shader_textures = C.cast(C.pointer(tex), C.c_void_p), 1
+        chunks[0].shader_textures, chunks[0].n_shader_textures = C.pointer(tex), 1
         assert upload(2) == RXR_ERR_INVALID and "chunk 0 carries its own" in p.error()
         chunks[0].shader_textures, chunks[0].n_shader_textures = None, 0
         assert upload(1) == RXR_ERR_INVALID and "1 chunks" in p.error() and "registered the textures of 2" in p.error()
@@ -273,7 +256,7 @@ def test_frames_must_match_the_registration():
         assert upload(2) == RXR_ERR_INVALID and "size 0" in p.error()
         chunks[0].size = 8
         assert p.register([], [], n_chunks=0) == RXR_OK        # removed: frames carry their textures again
-        chunks[1].terrain_texture = C.cast(C.pointer(tex), C.c_void_p)
+        chunks[1].terrain_texture = C.pointer(tex)
         assert upload(2) == RXR_OK, p.error()
 
 

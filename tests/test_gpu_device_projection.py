@@ -12,23 +12,15 @@ import pytest
 import rusterix_amd
 from rusterix_amd import binding as B
 from rusterix_amd import scenes
+from rusterix_amd.abi import rxr_edges as RxrEdges
 
 pytestmark = pytest.mark.gpu
-
-
-class RxrEdges(C.Structure):
-    _fields_ = [("a", C.c_float * 3), ("b", C.c_float * 3), ("c", C.c_float * 3), ("visible", C.c_uint32)]
 
 
 @pytest.fixture()
 def devproj(product):
     lib = product.lib
-    lib.rxh_set_device_projection.argtypes = [C.c_int]
-    lib.rxh_context.restype = C.c_void_p
-    rxr = C.CDLL(rusterix_amd.lib_paths()["rxr"])
-    rxr.rxr_read_projected_mesh.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float),
-                                            C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(RxrEdges), C.POINTER(C.c_float),
-                                            C.c_uint32, C.c_uint32]
+    rxr = rusterix_amd.rxr_abi()
 
     def read_mesh(index, cap_v, cap_t):
         counts = (C.c_uint32 * 2)()
@@ -323,8 +315,7 @@ def test_sparse_frames_take_their_row_spans_from_the_device_boxes(oracle, produc
     assert_scratch_clean(product, kind)
     assert np.array_equal(got, ref), f"{kind}: {(got != ref).any(axis=2).sum()} pixels differ"
     lib = product.lib
-    rxr = C.CDLL(__import__("rusterix_amd").lib_paths()["rxr"])   # (a handle of its own: the argtypes set below stay here)
-    lib.rxh_context.restype = C.c_void_p
+    rxr = __import__("rusterix_amd").rxr_abi()
     info = (C.c_uint32 * 4)()
     assert rxr.rxr_debug_content(C.c_void_p(lib.rxh_context()), info) == 0
     assert info[0] == 0 and info[3] == 2, list(info)     # (no rows known to the host; the table is the device's)
@@ -341,9 +332,6 @@ def test_sparse_frames_take_their_row_spans_from_the_device_boxes(oracle, produc
     monkeypatch.delenv("RXR_ROW_SPANS")
     assert np.array_equal(off, ref)
     # row bands of one resident frame (every band launch completes the table again: idempotent), then the pipelined download
-    lib.rxh_rasterizer_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    rxr.rxr_render_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
-    rxr.rxr_download_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]
     r = cfg.setup()
     assert lib.rxh_rasterizer_upload(r._h, cfg.scene._h, cfg.width, cfg.height, cfg.tile_size, cfg.assets._h) == 0
     ctx = C.c_void_p(lib.rxh_context())
@@ -354,7 +342,6 @@ def test_sparse_frames_take_their_row_spans_from_the_device_boxes(oracle, produc
         assert_scratch_clean(product, f"{kind}: band [{a}, {b})")
         assert rxr.rxr_download_rows(ctx, bands.ctypes.data_as(C.POINTER(C.c_uint8)), a, b) == 0   # (full-frame layout: row r at r * width * 4)
     assert np.array_equal(bands, ref), kind
-    rxr.rxr_render_download.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
     piped = np.full_like(got, 7)
     assert rxr.rxr_render_download(ctx, piped.ctypes.data_as(C.POINTER(C.c_uint8))) == 0
     assert_scratch_clean(product, f"{kind}: pipelined download")
@@ -380,14 +367,9 @@ def test_pipelined_download_of_a_sparse_device_projected_frame(product, devproj,
     piped[...] = scenes.render(cfg)                 # Rasterizer::rasterize -> rxr_render_download
     assert np.array_equal(piped, want), f"{(piped != want).any(axis=2).sum()} pixels differ"
     lib = product.lib
-    rxr = C.CDLL(__import__("rusterix_amd").lib_paths()["rxr"])   # (a handle of its own: the argtypes set below stay here)
-    lib.rxh_context.restype = C.c_void_p
+    rxr = __import__("rusterix_amd").rxr_abi()
     info = (C.c_uint32 * 4)()
     assert rxr.rxr_debug_content(C.c_void_p(lib.rxh_context()), info) == 0 and info[3] == 2, list(info)
-    lib.rxh_rasterizer_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    rxr.rxr_render_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
-    rxr.rxr_download_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]
-    rxr.rxr_render_download.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
     r = cfg.setup()
     assert lib.rxh_rasterizer_upload(r._h, cfg.scene._h, cfg.width, cfg.height, cfg.tile_size, cfg.assets._h) == 0
     ctx = C.c_void_p(lib.rxh_context())
@@ -462,8 +444,7 @@ def test_pipelined_download_trims_row_ends_of_a_frame_without_empty_rows(oracle,
     piped = np.full_like(ref, 7)
     piped[...] = scenes.render(cfg)
     assert np.array_equal(piped, ref), f"{(piped != ref).any(axis=2).sum()} pixels differ"
-    rxr = C.CDLL(__import__("rusterix_amd").lib_paths()["rxr"])
-    product.lib.rxh_context.restype = C.c_void_p
+    rxr = __import__("rusterix_amd").rxr_abi()
     info = (C.c_uint32 * 4)()
     assert rxr.rxr_debug_content(C.c_void_p(product.lib.rxh_context()), info) == 0
     assert info[3] == (2 if device_projected else 1), list(info)

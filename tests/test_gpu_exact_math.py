@@ -16,10 +16,7 @@ KINDS = ["div2", "div3", "div3_self", "normalize3", "sqrt", "pow", "div1", "stat
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_short_sequences_are_bit_identical(product, seed):
-    lib = C.CDLL(__import__("rusterix_amd").lib_paths()["rxr"])
-    lib.rxr_selftest_math.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
-    lib.rxr_selftest_math.restype = C.c_int
-    product.lib.rxh_context.restype = C.c_void_p
+    lib = __import__("rusterix_amd").rxr_abi()
     ctx = product.lib.rxh_context()
     assert ctx
     out = (C.c_uint64 * len(KINDS))()

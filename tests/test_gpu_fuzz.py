@@ -116,7 +116,6 @@ def test_random_scene_device_projection(product, seed):
     import ctypes as C
 
     lib = product.lib
-    lib.rxh_set_device_projection.argtypes = [C.c_int]
     w, h = 176, 107
     lib.rxh_set_device_projection(0)
     want = scenes.render(build(product, 100 + seed, w, h)).copy()

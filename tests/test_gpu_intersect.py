@@ -12,11 +12,11 @@ import pytest
 import rusterix_amd
 from rusterix_amd import binding as B
 from rusterix_amd import scenes
+from rusterix_amd.abi import RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED, RXR_OK
 from tests import intersect_ref as R
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-RXR_OK, RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED = 0, -1, -4
 
 
 @pytest.fixture()
@@ -338,8 +338,6 @@ def test_frames_around_intersect_calls_are_identical(product, plain_context, dev
     px = np.zeros(cfg.width * cfg.height * 4, np.uint8)
     assert rxr.rxr_render_download(ctx, px.ctypes.data) == RXR_OK
     assert np.array_equal(px.reshape(before.shape), before)
-    rxr.rxr_debug_scratch.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    rxr.rxr_debug_scratch.restype = C.c_int
     words = (C.c_uint32 * 4)()
     assert rxr.rxr_debug_scratch(ctx, words) == 0
     assert list(words) == [0, 0, 0, 0]

@@ -24,13 +24,13 @@ import pytest
 
 import rusterix_amd
 from rusterix_amd import scenes
+from rusterix_amd.abi import RXR_OK
 from tests import intersect_ref as R
 from tests import pick_fuzz as P
 from tests.test_gpu_intersect import bbox_eye, build, plain_context  # noqa: F401  (plain_context: a fixture)
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-RXR_OK = 0
 
 
 @pytest.fixture(scope="module")

@@ -21,7 +21,6 @@ CHILD = textwrap.dedent('''
 
     prod = rusterix_amd.load()
     host = prod.lib
-    host.rxh_set_device_projection.argtypes = [C.c_int]
 
     def rss_mb():
         for line in open("/proc/self/status"):

@@ -14,32 +14,13 @@ import pytest
 
 import rusterix_amd
 from rusterix_amd import binding as B
+from rusterix_amd.abi import RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED, RXR_OK, rxr_frame as Frame
 from tests import mesh_update_ref as M
 from tests.pick_fuzz import IDENTITY, Mesh3D, PickContext
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 W, H = 160, 96
-RXR_OK, RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED = 0, -1, -4
-
-
-class Frame(C.Structure):
-    """rxr_frame (include/rxr.h), offsets as in tests/abi_layout_asserts.h"""
-    _fields_ = [("abi_version", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("tile_size", C.c_uint32),
-                ("inverse_view", C.c_float * 16), ("inverse_projection", C.c_float * 16), ("camera_pos", C.c_float * 3),
-                ("translationd2", C.c_float * 2), ("scaled2", C.c_float), ("hash_anim", C.c_uint32), ("animation_frame", C.c_uint64),
-                ("flags", C.c_uint32), ("background_color", C.c_uint8 * 4), ("ambient", C.c_float * 4), ("sun_dir", C.c_float * 3),
-                ("day_factor", C.c_float), ("sample_mode", C.c_uint32), ("time", C.c_float), ("background_kind", C.c_uint32),
-                ("background_pixels", C.c_void_p), ("batches3d", C.c_void_p), ("n_batches3d", C.c_uint32), ("batches2d", C.c_void_p),
-                ("n_batches2d", C.c_uint32), ("lights", C.c_void_p), ("n_lights", C.c_uint32), ("occluders", C.c_void_p),
-                ("n_occluders", C.c_uint32), ("linedefs", C.c_void_p), ("n_linedefs", C.c_uint32), ("chunks", C.c_void_p),
-                ("n_chunks", C.c_uint32), ("n_shader_programs", C.c_uint32), ("use_meshes", C.c_uint32), ("view", C.c_float * 16),
-                ("projection", C.c_float * 16), ("mesh_transforms", C.c_void_p), ("background_grid", C.c_float * 4),
-                ("has_brush_preview", C.c_uint32), ("brush_position", C.c_float * 3), ("brush_radius", C.c_float), ("brush_falloff", C.c_float)]
-
-
-assert C.sizeof(Frame) == 528 and Frame.animation_frame.offset == 176 and Frame.background_pixels.offset == 240 and Frame.lights.offset == 280
-assert Frame.use_meshes.offset == 344 and Frame.view.offset == 348 and Frame.mesh_transforms.offset == 480 and Frame.brush_falloff.offset == 524
 
 
 def camera(product, position=(0.0, 0.0, 0.0), center=(0.0, 0.0, -6.0)):
@@ -58,10 +39,6 @@ class Ctx(PickContext):
 
     def __init__(self):
         super().__init__()
-        r = self.rxr
-        r.rxr_upload_frame.restype, r.rxr_upload_frame.argtypes = C.c_int, [C.c_void_p, C.c_void_p]
-        r.rxr_read_projected_mesh.restype = C.c_int
-        r.rxr_read_projected_mesh.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 7 + [C.c_uint32, C.c_uint32]
         self.meshes = []
 
     def set_meshes(self, meshes, expect=RXR_OK):
@@ -90,7 +67,7 @@ class Ctx(PickContext):
         f.background_color = (C.c_uint8 * 4)(10, 20, 30, 255)
         f.ambient = (C.c_float * 4)(0.4, 0.4, 0.4, 1.0)
         light = (B.RxrLight * 1)(LIGHT)
-        f.lights, f.n_lights = C.cast(light, C.c_void_p), 1
+        f.lights, f.n_lights = light, 1
         f.use_meshes = 1
         rc = self.rxr.rxr_upload_frame(self.ctx, C.byref(f))
         assert rc == RXR_OK, f"rxr_upload_frame: {rc}: {self.error()}"
@@ -457,7 +434,6 @@ def terrain_scene(api, heights):
 
 @pytest.fixture()
 def devproj(product):
-    product.lib.rxh_set_device_projection.argtypes = [C.c_int]
     product.lib.rxh_set_device_projection(1)
     yield product
     product.lib.rxh_set_device_projection(0)
@@ -508,7 +484,6 @@ def test_the_mirror_refuses_without_device_projection_and_falls_back_without_a_r
     with pytest.raises(B.RasterizeError) as e:
         scene.rebuild_terrain_meshes(t, [(1, 0)], [1])
     assert e.value.code == RXR_ERR_UNSUPPORTED
-    product.lib.rxh_set_device_projection.argtypes = [C.c_int]
     product.lib.rxh_set_device_projection(1)
     try:
         # no frame of this scene has been uploaded: the context holds other geometry, the next upload registers from the host arrays

@@ -311,11 +311,7 @@ def test_row_bands_equal_full_frame(product):
     cfg = scenes.map_scene(product, width=640, height=360, logo_size=64, n_lights=4)
     full = scenes.render(cfg).copy()
     lib = product.lib
-    rxr = C.CDLL(__import__("rusterix_amd").lib_paths()["rxr"])
-    lib.rxh_context.restype = C.c_void_p
-    lib.rxh_rasterizer_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    rxr.rxr_render_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
-    rxr.rxr_download_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]
+    rxr = __import__("rusterix_amd").rxr_abi()
     r = cfg.setup()
     assert lib.rxh_rasterizer_upload(r._h, cfg.scene._h, cfg.width, cfg.height, cfg.tile_size, cfg.assets._h) == 0
     ctx = lib.rxh_context()
@@ -404,8 +400,7 @@ def test_rows_without_content_are_filled_not_rastered(oracle, product, kind, mon
     else:
         assert len(hit_rows) and (hit_rows.min() > 32 or hit_rows.max() < cfg.height - 32), "the scene leaves no rows empty: it tests nothing"
     lib = product.lib
-    rxr = C.CDLL(__import__("rusterix_amd").lib_paths()["rxr"])
-    lib.rxh_context.restype = C.c_void_p
+    rxr = __import__("rusterix_amd").rxr_abi()
     info = (C.c_uint32 * 4)()
     assert rxr.rxr_debug_content(C.c_void_p(lib.rxh_context()), info) == 0
     assert info[0] == 1, "the frame's content rows are not known: the test tests nothing"
@@ -425,9 +420,6 @@ def test_rows_without_content_are_filled_not_rastered(oracle, product, kind, mon
     assert rxr.rxr_debug_content(C.c_void_p(lib.rxh_context()), info) == 0 and info[0] == 0 and info[3] == 0
     monkeypatch.delenv("RXR_CONTENT_ROWS")
     assert_exact(got, unclamped, f"sparse frame ({kind}): clamp on vs off")
-    lib.rxh_rasterizer_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    rxr.rxr_render_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
-    rxr.rxr_download_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]
     r = cfg.setup()
     assert lib.rxh_rasterizer_upload(r._h, cfg.scene._h, cfg.width, cfg.height, cfg.tile_size, cfg.assets._h) == 0
     ctx = lib.rxh_context()
@@ -454,7 +446,6 @@ def test_sparse_frame_into_caller_buffers_and_stripes(product, monkeypatch):
     whole = scenes.render(cfg).copy()
     lib = product.lib
     rxr = __import__("rusterix_amd").rxr_abi()
-    lib.rxh_context.restype = C.c_void_p
     r = cfg.setup()
     assert lib.rxh_rasterizer_upload(r._h, cfg.scene._h, cfg.width, cfg.height, cfg.tile_size, cfg.assets._h) == 0
     ctx = C.c_void_p(lib.rxh_context())
@@ -496,11 +487,7 @@ def test_stripes_equal_full_frame(product, world):
     cfg = scenes.map_scene(product, width=400, height=250, logo_size=64, n_lights=3)   # 250 rows: ragged last stripe
     full = scenes.render(cfg).copy()
     lib = product.lib
-    rxr = C.CDLL(__import__("rusterix_amd").lib_paths()["rxr"])
-    lib.rxh_context.restype = C.c_void_p
-    lib.rxh_rasterizer_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    rxr.rxr_render_stripes_to.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    rxr.rxr_synchronize.argtypes = [C.c_void_p]
+    rxr = __import__("rusterix_amd").rxr_abi()
     r = cfg.setup()
     assert lib.rxh_rasterizer_upload(r._h, cfg.scene._h, cfg.width, cfg.height, cfg.tile_size, cfg.assets._h) == 0
     ctx = lib.rxh_context()
@@ -633,11 +620,7 @@ def test_pipelined_download_equals_single_launch(product, kind, monkeypatch):
     piped = np.full((cfg.height, cfg.width, 4), 7, np.uint8)
     piped[...] = scenes.render(cfg)            # Rasterizer::rasterize -> rxr_render_download
     lib = product.lib
-    rxr = C.CDLL(__import__("rusterix_amd").lib_paths()["rxr"])
-    lib.rxh_context.restype = C.c_void_p
-    lib.rxh_rasterizer_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    rxr.rxr_render_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
-    rxr.rxr_download_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]
+    rxr = __import__("rusterix_amd").rxr_abi()
     r = cfg.setup()
     assert lib.rxh_rasterizer_upload(r._h, cfg.scene._h, cfg.width, cfg.height, cfg.tile_size, cfg.assets._h) == 0
     ctx = lib.rxh_context()
@@ -661,8 +644,7 @@ def test_pipelined_download_repairs_a_list_overflow(product, monkeypatch):
     general pipeline and renders the whole frame again, and the caller's buffer is downloaded once more -- never the incomplete bands"""
     import ctypes as C
 
-    rxr = C.CDLL(__import__("rusterix_amd").lib_paths()["rxr"])
-    product.lib.rxh_context.restype = C.c_void_p
+    rxr = __import__("rusterix_amd").rxr_abi()
     cfg = scenes.box_grid_scene(product, n=40, width=2304, height=1832)
     good = scenes.render(cfg).copy()
     before = rxr.rxr_debug_rerenders(C.c_void_p(product.lib.rxh_context()))

@@ -23,7 +23,7 @@ import pytest
 import rusterix_amd
 from rusterix_amd import binding as B
 from rusterix_amd import scenes
-from tests.test_gpu_device_projection import RxrEdges, devproj  # noqa: F401  (devproj: the fixture)
+from tests.test_gpu_device_projection import devproj  # noqa: F401  (devproj: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -211,17 +211,13 @@ def read_mesh(product, index, cap_v, cap_t):
     """rxr_read_projected_mesh into numpy buffers (the Edges records as [n, 10] float32 with `visible` converted, like the host mirror's copy)"""
     global _rxr
     if _rxr is None:
-        _rxr = C.CDLL(rusterix_amd.lib_paths()["rxr"])
-        _rxr.rxr_read_projected_mesh.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float),
-                                                 C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(RxrEdges), C.POINTER(C.c_float), C.c_uint32, C.c_uint32]
-    product.lib.rxh_context.restype = C.c_void_p
+        _rxr = rusterix_amd.rxr_abi()
     counts = (C.c_uint32 * 2)()
     pv, uv, nr = np.zeros((cap_v, 4), np.float32), np.zeros((cap_v, 2), np.float32), np.zeros((cap_v, 3), np.float32)
     idx, ed, bb = np.zeros((cap_t, 3), np.uint32), np.zeros((cap_t, 10), np.uint32), np.zeros(5, np.float32)
-    assert C.sizeof(RxrEdges) == 40
     fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
     rc = _rxr.rxr_read_projected_mesh(product.lib.rxh_context(), index, counts, fp(pv), fp(uv), fp(nr), idx.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                      ed.ctypes.data_as(C.POINTER(RxrEdges)), fp(bb), cap_v, cap_t)
+                                      ed.ctypes.data, fp(bb), cap_v, cap_t)
     assert rc == 0, (index, rc)
     nv, nt = counts[0], counts[1]
     edges = ed[:nt].view(np.float32).copy()

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import rusterix_amd
+from rusterix_amd.abi import RXR_ERR_UNSUPPORTED, RXR_OK
 from tests import bake_ref
 from tests import intersect_ref
 from tests import pick_fuzz
@@ -27,7 +28,6 @@ from tests import terrain_ref
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-RXR_OK, RXR_ERR_UNSUPPORTED = 0, -4
 
 
 def device(a):
@@ -78,7 +78,6 @@ class Intersect(Query):
 
     def set(self, ctx, k):
         arr, keep = pick_fuzz.mesh_array(self.data(k))
-        self.rxr.rxr_set_meshes.restype, self.rxr.rxr_set_meshes.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]
         assert self.rxr.rxr_set_meshes(ctx, C.cast(arr, C.c_void_p), 2) == RXR_OK, self.error(ctx)
 
     def inputs(self, which):
@@ -127,7 +126,6 @@ class ShaderBake(Query):
     def __init__(self, oracle):
         super().__init__()
         self.oracle = oracle
-        self.rxr.rxr_set_shaders.restype, self.rxr.rxr_set_shaders.argtypes = C.c_int, [C.c_void_p, C.c_void_p]
 
     def data(self, k):   # two programs of exactly rounded operations, without patterns or palette
         progs = bake_ref.exact_programs()

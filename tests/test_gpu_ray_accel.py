@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from rusterix_amd import trace as T
+from rusterix_amd.abi import RXR_ERR_INVALID, RXR_OK
 from tests import intersect_ref as R
 from tests import mesh_update_ref as M
 from tests import pick_fuzz as P
@@ -17,7 +18,6 @@ from tests import trace_scenes as S
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-RXR_OK, RXR_ERR_INVALID = 0, -1
 OFF, ON, COUNT = T.RAY_ACCEL_OFF, T.RAY_ACCEL_ON, T.RAY_ACCEL_COUNT
 L, W = A.LEAF, A.WIDTH
 COUNTS = (1, L - 1, L, L + 1, L * W - 1, L * W, L * W + 1, L * W * W + 1)

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from rusterix_amd import trace as T
+from rusterix_amd.abi import RXR_ERR_INVALID, RXR_OK
 from tests import intersect_ref as R
 from tests import mesh_update_ref as M
 from tests import pick_fuzz as P
@@ -25,7 +26,6 @@ from tests import trace_scenes as S
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-RXR_OK, RXR_ERR_INVALID = 0, -1
 OFF, ON = T.RAY_ACCEL_OFF, T.RAY_ACCEL_ON
 FULL, RANGED = T.RAY_REFRESH_FULL, T.RAY_REFRESH_RANGED
 L = A.LEAF

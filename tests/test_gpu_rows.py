@@ -99,7 +99,6 @@ def test_a_nan_texture_coordinate_under_bilinear_sampling_is_not_written(oracle,
     included, `NaN as u8` = 0 -- so the reference does not write the fragment (rasterizer.rs:1408) although every texel of the
     texture is opaque.  The device used to take 'all texels opaque' for 'alpha is 255' and wrote [0, 0, 0, 0] there; such triangles
     now carry the per-fragment alpha test (make_setup, rxr_kernels.hip)."""
-    product.lib.rxh_set_device_projection.argtypes = [C.c_int]
     product.lib.rxh_set_device_projection(1 if device_projection else 0)
     try:
         got = scenes.render(build(product, 48135, 203, 131, "mixed"))
@@ -145,11 +144,7 @@ def test_stripes_of_a_mesh_equal_the_full_frame(product, world):
     cfg = build(product, 1, 333, 250, "mixed")
     full = scenes.render(cfg).copy()
     lib = product.lib
-    rxr = C.CDLL(__import__("rusterix_amd").lib_paths()["rxr"])
-    lib.rxh_context.restype = C.c_void_p
-    lib.rxh_rasterizer_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    rxr.rxr_render_stripes_to.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
-    rxr.rxr_synchronize.argtypes = [C.c_void_p]
+    rxr = __import__("rusterix_amd").rxr_abi()
     r = cfg.setup()
     assert lib.rxh_rasterizer_upload(r._h, cfg.scene._h, cfg.width, cfg.height, cfg.tile_size, cfg.assets._h) == 0
     ctx = lib.rxh_context()

@@ -19,10 +19,7 @@ W, H = 192, 128
 
 
 def jit_info(product):
-    rxr = C.CDLL(rusterix_amd.lib_paths()["rxr"])
-    rxr.rxr_debug_jit_info.restype = C.c_char_p
-    rxr.rxr_debug_jit_info.argtypes = [C.c_void_p]
-    product.lib.rxh_context.restype = C.c_void_p
+    rxr = rusterix_amd.rxr_abi()
     return rxr.rxr_debug_jit_info(product.lib.rxh_context()).decode()
 
 

@@ -28,17 +28,11 @@ SCRATCH_BUFFERS = ("bin_count / blk_cnt", "3D counter set", "2D counter set", "b
 # ---- helpers shared with the other sparse-frame tests ---------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _rxr():
-    rxr = C.CDLL(rusterix_amd.lib_paths()["rxr"])   # (a handle of its own: the argtypes set here stay here)
-    rxr.rxr_debug_scratch.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    rxr.rxr_debug_content.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    rxr.rxr_render_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
-    rxr.rxr_download_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]
-    rxr.rxr_get_stats.argtypes = [C.c_void_p, C.c_void_p]
+    rxr = rusterix_amd.rxr_abi()
     return rxr
 
 
 def context_of(product):
-    product.lib.rxh_context.restype = C.c_void_p
     return C.c_void_p(product.lib.rxh_context())
 
 
@@ -71,7 +65,6 @@ def bin_entries(product):
 def render_bands(product, cfg, bands):
     """one upload, then rxr_render_rows + rxr_download_rows per band; the scratch state is checked behind every band launch"""
     lib = product.lib
-    lib.rxh_rasterizer_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     r = cfg.setup()
     assert lib.rxh_rasterizer_upload(r._h, cfg.scene._h, cfg.width, cfg.height, cfg.tile_size, cfg.assets._h) == 0
     ctx = context_of(product)
@@ -84,7 +77,6 @@ def render_bands(product, cfg, bands):
 
 
 def set_device_projection(product, on):
-    product.lib.rxh_set_device_projection.argtypes = [C.c_int]
     product.lib.rxh_set_device_projection(1 if on else 0)
 
 

@@ -59,7 +59,6 @@ MATRICES = [None, B.Mat3.from_rows([[1.1, 0.2, 3.0], [-0.1, 0.9, 2.0], [0.0, 0.0
 @pytest.mark.parametrize("sample_mode", [B.SAMPLE_NEAREST, B.SAMPLE_LINEAR])
 def test_poisoned_2d_batches(oracle, product, sample_mode, matrix, device_projection):
     lines = LINE_SPECIALS if matrix in (0, 1, 4) else []      # (a NaN / inf matrix entry makes every end point NaN: refused, below)
-    product.lib.rxh_set_device_projection.argtypes = [C.c_int]
     product.lib.rxh_set_device_projection(1 if device_projection else 0)
     try:
         got = scenes.render(build(product, sample_mode, MATRICES[matrix], lines))
@@ -79,7 +78,6 @@ def test_segments_the_reference_cannot_draw_the_same_way_twice_are_refused(produ
     `0` as isize, a point outside the batch's bounding box (min / max drop NaN), and the reference skips the batch for every tile its
     box does not meet -- which pixels it draws depends on ITS tile size.  Both are refused (RXR_ERR_UNSUPPORTED: the caller's CPU path
     draws them), host- and device-projected; the context renders the next frame as usual."""
-    product.lib.rxh_set_device_projection.argtypes = [C.c_int]
     product.lib.rxh_set_device_projection(1 if device_projection else 0)
     try:
         with pytest.raises(B.RasterizeError) as e:
@@ -95,7 +93,6 @@ def test_segments_the_reference_cannot_draw_the_same_way_twice_are_refused(produ
 def test_a_batch_with_an_infinite_box_is_not_drawn_at_all(oracle, product, device_projection):
     """-inf in a vertex: the batch's box is (x = -inf, width = inf), `x + width` is NaN and the reference's box test (:594-600) is false
     for every tile -- nothing of the batch is drawn, its unrepresentable end point included (no refusal)"""
-    product.lib.rxh_set_device_projection.argtypes = [C.c_int]
     product.lib.rxh_set_device_projection(1 if device_projection else 0)
     try:
         got = scenes.render(build(product, B.SAMPLE_NEAREST, None, [-INF]))
@@ -129,7 +126,6 @@ def test_batches_with_huge_coordinates_are_drawn_in_the_reference_s_tiles_only(o
 
         return scenes._result(api, scene, api.Assets.default(), setup, W, H, tile_size, "huge-2d")
 
-    product.lib.rxh_set_device_projection.argtypes = [C.c_int]
     product.lib.rxh_set_device_projection(1 if device_projection else 0)
     try:
         got = scenes.render(build(product))

@@ -56,7 +56,6 @@ def build(api, what, index, value, grid):
 @pytest.mark.parametrize("device_projection", [False, True])
 @pytest.mark.parametrize("grid", [False, True])
 def test_poisoned_frame_parameters(oracle, product, grid, device_projection):
-    product.lib.rxh_set_device_projection.argtypes = [C.c_int]
     clean = scenes.render(scenes.box_grid_scene(oracle, n=10, width=320, height=180) if grid else scenes.map_scene(oracle, width=320, height=180, n_lights=4, logo_size=16))
     changed = 0
     for exact in (0, 1):

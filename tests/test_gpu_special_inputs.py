@@ -73,7 +73,6 @@ def build(api, sample_mode, repeat_mode, cutout, seed=7, shape=(9, 7), mode="pla
 @pytest.mark.parametrize("repeat_mode", [B.REPEAT_CLAMP_XY, B.REPEAT_REPEAT_XY, B.REPEAT_REPEAT_X, B.REPEAT_REPEAT_Y])
 @pytest.mark.parametrize("sample_mode", [B.SAMPLE_NEAREST, B.SAMPLE_LINEAR])
 def test_poisoned_triangles(oracle, product, sample_mode, repeat_mode, cutout, device_projection):
-    product.lib.rxh_set_device_projection.argtypes = [C.c_int]
     product.lib.rxh_set_device_projection(1 if device_projection else 0)
     try:
         got = scenes.render(build(product, sample_mode, repeat_mode, cutout))
@@ -159,7 +158,6 @@ def build_random(api, seed):
 
 @pytest.mark.parametrize("seed", range(40))
 def test_random_combinations_of_poisoned_numbers(oracle, product, seed):
-    product.lib.rxh_set_device_projection.argtypes = [C.c_int]
     for dp in (0, 1):
         product.lib.rxh_set_device_projection(dp)
         try:
@@ -200,7 +198,6 @@ def test_3d_batches_with_huge_projected_coordinates_follow_the_reference_s_tiles
 
         return scenes._result(api, scene, api.Assets.default(), setup, W, H, tile_size, "huge-3d")
 
-    product.lib.rxh_set_device_projection.argtypes = [C.c_int]
     product.lib.rxh_set_device_projection(1 if device_projection else 0)
     try:
         got = scenes.render(build(product))

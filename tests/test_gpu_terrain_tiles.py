@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import rusterix_amd
+from rusterix_amd.abi import RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED, RXR_OK
 from tests import terrain_exclusion_ref as X
 from tests import terrain_gen_ref as G
 from tests import terrain_tiles_ref as T
@@ -17,7 +18,6 @@ from tests.terrain_gen_ref import F, Generator
 from tests.terrain_tiles_ref import Tiles
 
 pytestmark = pytest.mark.gpu
-RXR_OK, RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED = 0, -1, -4
 SENTINEL = F(-12345.75)
 ISENT = 0xABCDABCD
 GUARD = 8   # words behind every output
@@ -570,7 +570,6 @@ def test_a_moved_control_point_through_the_mirrors_scene(product):
     tiles = Tiles(T.stripes(0, 8, 0, 4, 2, width=2))
     before = Generator([(3.0, 2.0, 2.5, 1.5), (6.5, 1.0, 1.0, 1.0)], map_box=(-20, -20, 28, 24))
     after = Generator([(4.5, 2.5, 3.0, 1.5), (6.5, 1.0, 1.0, 1.0)], map_box=(-20, -20, 28, 24))
-    api.lib.rxh_set_device_projection.argtypes = [C.c_int]
     api.lib.rxh_set_device_projection(1)
     try:
         _, _, want_render = generated_scene(api, after, tiles)

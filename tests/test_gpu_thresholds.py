@@ -68,7 +68,6 @@ def mesh_scene(api, counts, two_d=0):
 @pytest.mark.parametrize("device_projection", [False, True])
 @pytest.mark.parametrize("counts", [[], [0], [0, 0, 5, 0], [127], [128], [129], [64, 64], [64, 65], [1023], [1024], [1025], [600, 424], [600, 425], [16384], [16385], [9000, 7384], [9000, 7385]])
 def test_triangle_counts_around_the_internal_thresholds(oracle, product, counts, device_projection):
-    product.lib.rxh_set_device_projection.argtypes = [C.c_int]
     product.lib.rxh_set_device_projection(1 if device_projection else 0)
     try:
         got = scenes.render(mesh_scene(product, counts))
@@ -81,7 +80,6 @@ def test_triangle_counts_around_the_internal_thresholds(oracle, product, counts,
 @pytest.mark.parametrize("device_projection", [False, True])
 @pytest.mark.parametrize("two_d", [1, 63, 64, 65, 511, 512, 513, 600])   # rectangles: two primitives each (128 = 64 rectangles; the sort capacity is 1024)
 def test_2d_primitive_counts_around_the_binning_threshold(oracle, product, two_d, device_projection):
-    product.lib.rxh_set_device_projection.argtypes = [C.c_int]
     product.lib.rxh_set_device_projection(1 if device_projection else 0)
     try:
         got = scenes.render(mesh_scene(product, [40], two_d))

@@ -20,13 +20,13 @@ import rusterix_amd
 from rusterix_amd import binding as B
 from rusterix_amd import scenes
 from rusterix_amd import trace as T
+from rusterix_amd.abi import RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED, RXR_OK
 from tests import intersect_ref as R
 from tests import trace_ref as TR
 from tests import trace_scenes as S
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-RXR_OK, RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED = 0, -1, -4
 GLOSSY_1 = (T.GLOSSY, T.MOD_NONE, 1.0)
 
 

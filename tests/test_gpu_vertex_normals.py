@@ -12,13 +12,13 @@ import numpy as np
 import pytest
 
 from rusterix_amd import binding as B
+from rusterix_amd.abi import RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED, RXR_OK
 from tests import vertex_normals_ref as R
 from tests.test_gpu_mesh_update import Ctx, camera
 from tests.vertex_normals_ref import F, SENTINEL
 
 pytestmark = pytest.mark.gpu
 
-RXR_OK, RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED = 0, -1, -4
 SMALL, GENERAL = 1, 2                    # RXR_VERTEX_NORMALS_ROUTE_*
 ROUTES = ["small", "general"]
 ORDER_SEEDS = (11, 12, 13, 14)           # tests/test_vertex_normals_cpu.py checks the conditions for the same seeds

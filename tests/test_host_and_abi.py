@@ -54,15 +54,11 @@ def test_struct_sizes_match_the_header():
 
 @pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="only meaningful on a box without a GPU")
 def test_no_gpu_means_loud_failure_not_fallback():
-    lib = rusterix_amd.load_rxr()
-    lib.rxr_device_count.restype = C.c_int
+    lib = rusterix_amd.rxr_abi()
     assert lib.rxr_device_count() == 0
     ctx = C.c_void_p()
-    lib.rxr_create.argtypes = [C.POINTER(C.c_void_p), C.c_int]
     rc = lib.rxr_create(C.byref(ctx), 0)
     assert rc == B.RXR_ERR_NO_DEVICE and not ctx.value
-    lib.rxr_last_error.restype = C.c_char_p
-    lib.rxr_last_error.argtypes = [C.c_void_p]
     assert b"no HIP device" in lib.rxr_last_error(None)
     # the reference-shaped call fails with the same status instead of producing pixels some other way
     prod = rusterix_amd.load()
@@ -75,9 +71,7 @@ def test_no_gpu_means_loud_failure_not_fallback():
 
 
 def test_argument_validation_without_a_context():
-    lib = rusterix_amd.load_rxr()
-    for fn in ("rxr_upload_frame", "rxr_render_rows", "rxr_synchronize"):
-        getattr(lib, fn).restype = C.c_int
+    lib = rusterix_amd.rxr_abi()
     assert lib.rxr_upload_frame(None, None) == B.RXR_ERR_INVALID
     assert lib.rxr_render_rows(None, 0, 0) == B.RXR_ERR_INVALID
     assert lib.rxr_synchronize(None) == B.RXR_ERR_INVALID
@@ -193,9 +187,7 @@ def test_tile_span_without_the_searches_equals_the_searched_one():
     """rxr_device.h: rxr_ref_tile_span_quick (k_spans_from_meshes: the row spans of device-projected frames) guesses the two bounds of the
     reference's per-tile batch box test (rasterizer.rs:978-983) and walks to where the predicate flips; rxr_ref_tile_span searches for them.
     Same interval for every box: random ones, boxes on tile and pixel boundaries, off-screen, huge, infinite and NaN ones (host code only)."""
-    lib = rusterix_amd.load_rxr()
-    lib.rxr_debug_tile_spans.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int, C.c_void_p]
-    lib.rxr_debug_tile_spans.restype = None
+    lib = rusterix_amd.rxr_abi()
     rng = np.random.default_rng(77)
     f32 = np.float32
     for size, ts in [(7680, 40), (4320, 40), (1920, 60), (1080, 64), (333, 40), (211, 7), (16, 100), (1, 1), (32768, 1), (640, 0)]:

@@ -10,12 +10,12 @@ import numpy as np
 import pytest
 
 import rusterix_amd
+from rusterix_amd.abi import RXR_ERR_INVALID
 from tests import intersect_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 NEW = ("rxr_intersect", "rxr_intersect_to", "rxr_screen_rays_to")
-RXR_ERR_INVALID = -1
 
 
 def test_entry_points_are_declared_and_exported():

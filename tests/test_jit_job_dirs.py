@@ -12,10 +12,7 @@ import rusterix_amd
 
 
 def _lib():
-    lib = C.CDLL(rusterix_amd.lib_paths()["rxr"])
-    lib.rxr_debug_jit_sweep.argtypes = [C.c_char_p]
-    lib.rxr_debug_jit_sweep.restype = None
-    lib.rxr_debug_jit_job_parent.argtypes = [C.c_char_p, C.c_uint32]
+    lib = rusterix_amd.rxr_abi()
     return lib
 
 

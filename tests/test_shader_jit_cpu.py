@@ -14,8 +14,7 @@ from tests import test_shader_validation as V
 
 
 def generate(programs, compile_):
-    lib = rusterix_amd.load_rxr()
-    lib.rxr_debug_jit_generate.argtypes = [C.POINTER(V.RxrShaderSet), C.c_int, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32]
+    lib = rusterix_amd.rxr_abi()
     keep = []
     progs = (V.RxrProgram * len(programs))()
     for i, p in enumerate(programs):
@@ -23,7 +22,7 @@ def generate(programs, compile_):
         for k, f in enumerate(p.functions):
             arr = np.asarray(f if len(f) else [0], np.uint32)
             keep.append(arr)
-            fns[k] = V.RxrFunction(arr.ctypes.data_as(C.POINTER(C.c_uint32)), len(f))
+            fns[k] = V.RxrFunction(arr.ctypes.data, len(f))
         keep.append(fns)
         progs[i] = V.RxrProgram(p.globals, p.shade_index, p.shade_locals, fns, len(p.functions))
     s = V.RxrShaderSet(progs, len(programs), None, 0, None, 0, None, None, 0)
@@ -187,8 +186,7 @@ def test_the_background_compiler_starts_without_a_gpu_and_without_the_parents_to
     monkeypatch.setenv("ROCR_VISIBLE_DEVICES", "0,1")
     monkeypatch.setenv("TMPDIR", "/somewhere/else")
     monkeypatch.setenv("RXR_KEEP_ME", "yes")
-    lib = rusterix_amd.load_rxr()
-    lib.rxr_debug_jit_child_env.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32]
+    lib = rusterix_amd.rxr_abi()
     buf = C.create_string_buffer(1 << 20)
     assert 0 < lib.rxr_debug_jit_child_env(str(tmp_path).encode(), buf, len(buf)) <= len(buf)
     env = dict(line.split("=", 1) for line in buf.value.decode().splitlines() if "=" in line)

@@ -7,27 +7,12 @@ import pytest
 
 import rusterix_amd
 from rusterix_amd import binding as B
+from rusterix_amd.abi import rxr_function as RxrFunction, rxr_program as RxrProgram, rxr_shader_set as RxrShaderSet
 from rusterix_amd.binding import Program, assemble
 
 
-class RxrFunction(C.Structure):
-    _fields_ = [("words", C.POINTER(C.c_uint32)), ("n_words", C.c_uint32)]
-
-
-class RxrProgram(C.Structure):
-    _fields_ = [("n_globals", C.c_uint32), ("shade_index", C.c_int32), ("shade_locals", C.c_uint32),
-                ("functions", C.POINTER(RxrFunction)), ("n_functions", C.c_uint32)]
-
-
-class RxrShaderSet(C.Structure):
-    _fields_ = [("programs", C.POINTER(RxrProgram)), ("n_programs", C.c_uint32), ("patterns", C.c_void_p), ("n_patterns", C.c_uint32),
-                ("normal_patterns", C.c_void_p), ("n_normal_patterns", C.c_uint32), ("palette_rgb", C.c_void_p),
-                ("palette_present", C.c_void_p), ("n_palette", C.c_uint32)]
-
-
 def check(*programs):
-    lib = rusterix_amd.load_rxr()
-    lib.rxr_check_shaders.argtypes = [C.POINTER(RxrShaderSet), C.POINTER(C.c_uint32), C.c_char_p, C.c_uint32]
+    lib = rusterix_amd.rxr_abi()
     keep = []
     progs = (RxrProgram * len(programs))()
     for i, p in enumerate(programs):
@@ -35,7 +20,7 @@ def check(*programs):
         for k, f in enumerate(p.functions):
             arr = np.asarray(f if len(f) else [0], np.uint32)
             keep.append(arr)
-            fns[k] = RxrFunction(arr.ctypes.data_as(C.POINTER(C.c_uint32)), len(f))
+            fns[k] = RxrFunction(arr.ctypes.data, len(f))
         keep.append(fns)
         progs[i] = RxrProgram(p.globals, p.shade_index, p.shade_locals, fns, len(p.functions))
     s = RxrShaderSet(progs, len(programs), None, 0, None, 0, None, None, 0)

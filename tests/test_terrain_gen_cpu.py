@@ -11,11 +11,11 @@ import numpy as np
 import pytest
 
 import rusterix_amd
+from rusterix_amd.abi import RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED, RXR_OK
 from tests import terrain_gen_ref as G
 from tests.terrain_gen_ref import F, Generator
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RXR_OK, RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED = 0, -1, -4
 NAN, INF = float("nan"), float("inf")
 
 

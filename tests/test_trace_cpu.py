@@ -14,12 +14,12 @@ import pytest
 import rusterix_amd
 from rusterix_amd import binding as B
 from rusterix_amd import trace as T
+from rusterix_amd.abi import RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED, RXR_OK
 from tests import trace_ref as TR
 from tests import trace_scenes as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-RXR_OK, RXR_ERR_INVALID, RXR_ERR_UNSUPPORTED = 0, -1, -4
 NAMES = ["rxr_check_trace_scene", "rxr_set_trace_scene", "rxr_trace_srgb_table", "rxr_trace_rand", "rxr_trace", "rxr_trace_to", "rxr_accum_to_rgba", "rxr_accum_to_rgba_to"]
 
 

@@ -8,10 +8,10 @@ import pytest
 
 import rusterix_amd
 from rusterix_amd import binding as B
+from rusterix_amd.abi import RXR_ERR_INVALID, RXR_OK
 from tests import vertex_normals_ref as R
 from tests.vertex_normals_ref import F
 
-RXR_OK, RXR_ERR_INVALID = 0, -1
 ORDER_SEEDS = (11, 12, 13, 14)          # tests/test_gpu_vertex_normals.py uses the same
 
 

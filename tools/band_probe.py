@@ -15,12 +15,7 @@ ap.add_argument("--config", default="C5")
 a = ap.parse_args()
 os.environ.setdefault("RXR_SHADER_JIT", "0")
 prod = rusterix_amd.load(); host = prod.lib
-rxr = C.CDLL(rusterix_amd.lib_paths()["rxr"])
-host.rxh_context.restype = C.c_void_p
-host.rxh_rasterizer_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-rxr.rxr_render_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
-rxr.rxr_synchronize.argtypes = [C.c_void_p]
-rxr.rxr_download_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]
+rxr = rusterix_amd.rxr_abi()
 cfg = config(prod, a.config)
 W, H = cfg.width, cfg.height
 r = cfg.setup()

@@ -168,8 +168,7 @@ def main():
     host.rxh_set_device_projection(0)
 
     # ---- commit/<k> ----
-    class Tex(C.Structure):
-        _fields_ = [("rgba", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
+    from rusterix_amd.abi import rxr_texture as Tex
 
     for k, side in ((1, 256), (8, 256), (64, 256), (1, 1024)):
         row = f"commit/{k}x{side}x{side}"

@@ -14,7 +14,6 @@ from tests.oracle_api import load_oracle  # noqa: E402
 from tests import test_gpu_special_inputs as SI  # noqa: E402
 
 prod, orc = rusterix_amd.load(), load_oracle()
-prod.lib.rxh_set_device_projection.argtypes = [C.c_int]
 first = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 200
 bad = []

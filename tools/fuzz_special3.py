@@ -78,7 +78,6 @@ def build(api, seed):
 
 if __name__ == "__main__":
     prod, orc = rusterix_amd.load(), load_oracle()
-    prod.lib.rxh_set_device_projection.argtypes = [C.c_int]
     first = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
     n = int(sys.argv[2]) if len(sys.argv) > 2 else 200
     bad, refused = [], 0

@@ -28,7 +28,6 @@ n = int(argv[2]) if len(argv) > 2 else 100
 if DEVPROJ:
     import ctypes as C
 
-    prod.lib.rxh_set_device_projection.argtypes = [C.c_int]
     prod.lib.rxh_set_device_projection(1)
 bad = []
 refused = []

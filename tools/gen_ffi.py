@@ -5,9 +5,13 @@
                                       compile-time asserts of every size and field offset (core::mem::offset_of!)
   tests/abi_layout_asserts.h          the same sizes / offsets as C11 _Static_asserts, compiled by tests/abi_host.c
                                       (a CPU test): the C compiler thereby confirms the layout model used for the Rust side
+  rusterix_amd/abi.py                 the Python mirror: constants, one ctypes.Structure per struct, the signature of every
+                                      prototype of rxr.h and -- the test entry points, which the other two leave out -- of
+                                      rusterix_amd/csrc/rxr_debug.h, and declare(lib), which types a loaded library with them
 
-    python tools/gen_ffi.py            rewrite both files
-    python tools/gen_ffi.py --check    exit 1 if either file is not what the header implies (tests/test_abi_c.py)
+    python tools/gen_ffi.py            rewrite the three files
+    python tools/gen_ffi.py --check    exit 1 if one of them is not what the headers imply (tests/test_abi_c.py,
+                                       tests/test_abi_python_cpu.py)
 
 The parser handles exactly the C subset the header uses: `#define NAME <integer expr>`, anonymous and named enums,
 `typedef struct NAME {...} NAME;` with scalar / pointer / fixed-array / nested-struct fields, and plain prototypes.
@@ -19,12 +23,18 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "rxr.h")
+DEBUG_HEADER = os.path.join(ROOT, "rusterix_amd", "csrc", "rxr_debug.h")
+ABI_PY = os.path.join(ROOT, "rusterix_amd", "abi.py")
 FFI_RS = os.path.join(ROOT, "shim", "rusterix-hip-shim", "src", "ffi.rs")
 ASSERTS_H = os.path.join(ROOT, "tests", "abi_layout_asserts.h")
 
 SCALARS = {  # C type -> (Rust type, size, alignment)
     "uint8_t": ("u8", 1, 1), "uint32_t": ("u32", 4, 4), "int32_t": ("i32", 4, 4), "uint64_t": ("u64", 8, 8), "float": ("f32", 4, 4),
     "int": ("c_int", 4, 4), "size_t": ("usize", 8, 8), "char": ("c_char", 1, 1), "void": ("c_void", 0, 1),
+}
+PY_SCALARS = {  # C type -> ctypes name (`unsigned long long`: rxr_debug.h only)
+    "uint8_t": "c_uint8", "uint32_t": "c_uint32", "int32_t": "c_int32", "uint64_t": "c_uint64", "float": "c_float", "int": "c_int",
+    "size_t": "c_size_t", "unsigned long long": "c_ulonglong", "void": "None",
 }
 
 
@@ -71,14 +81,19 @@ def parse(text):
                 am = re.match(r"^(\w+)\s*\[\s*(\w+)\s*\]$", item)
                 fields.append(dict(name=am.group(1) if am else item, ctype=ctype, ptr=ptr, const=bool(const), array=int(am.group(2)) if am else None))
         structs.append((m.group(1), fields))
-    body = text[text.index("typedef struct rxr_ctx rxr_ctx;"):]
-    for m in re.finditer(r"^([\w\s\*]+?)\b(rxr_\w+)\s*\(([^;{}]*?)\)\s*;", body, flags=re.M | re.S):
+    return defines, enums, structs, prototypes(text[text.index("typedef struct rxr_ctx rxr_ctx;"):])
+
+
+def prototypes(text):
+    """(return type, name, parameter list) of every plain prototype of comment-free text"""
+    funcs = []
+    for m in re.finditer(r"^([\w\s\*]+?)\b(rxr_\w+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.M | re.S):
         ret = " ".join(m.group(1).split())
         if ret.startswith("typedef"):
             continue
         args = " ".join(m.group(3).split())
         funcs.append((ret, m.group(2), args))
-    return defines, enums, structs, funcs
+    return funcs
 
 
 class Layout:
@@ -211,10 +226,80 @@ def gen_asserts(structs, layout):
     return "\n".join(o)
 
 
+def py_type(decl):
+    """THE type rule of rusterix_amd/abi.py's two tables, for a parameter (`const float *lo`, `uint32_t out[3]`) or a return type:
+    a scalar is its ctypes scalar; `char *` / `const char *` is c_char_p; every other pointer, `T x[N]` parameter or `T **` is c_void_p
+    -- which as an argument type takes byref(...), ctypes arrays and pointers, c_void_p, ints and None alike; `void` is None."""
+    decl = " ".join(decl.replace("*", " * ").split())
+    if "*" in decl or "[" in decl:
+        return "c_char_p" if re.match(r"^(const )?char \*( \w+)?$", decl) else "c_void_p"
+    words = [w for w in decl.split() if w != "const"]
+    if " ".join(words) not in PY_SCALARS:  # (a parameter carries its name behind the type)
+        words = words[:-1]
+    return PY_SCALARS[" ".join(words)]
+
+
+def py_field(f, struct_names):
+    if f["ptr"]:  # a pointer to a struct of the header keeps its type; every other pointer is an address
+        base = f"POINTER({f['ctype']})" if f["ctype"] in struct_names else "c_void_p"
+    else:
+        base = f["ctype"] if f["ctype"] in struct_names else PY_SCALARS[f["ctype"]]
+    return base if f["array"] is None else f"{base} * {f['array']}"
+
+
+def split_args(args):
+    return [] if args in ("", "void") else args.split(",")
+
+
+def gen_python(defines, enums, structs, funcs, debug_funcs):
+    o = ["# GENERATED by tools/gen_ffi.py from include/rxr.h and rusterix_amd/csrc/rxr_debug.h; do not edit.",
+         '"""The ctypes mirror of the C ABI: the constants and structs of include/rxr.h, the signature of every entry point of rxr.h',
+         "(SIGNATURES) and of every test entry point of rxr_debug.h (DEBUG_SIGNATURES), and declare(), which types a loaded library",
+         'with them.  The type rule of the tables is tools/gen_ffi.py::py_type; tests/test_abi_python_cpu.py checks the layouts."""',
+         "from ctypes import (POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_size_t, c_uint8, c_uint32, c_uint64, c_ulonglong,",
+         "                    c_void_p)",
+         ""]
+    for name, val in defines:
+        v = define_value(val)
+        if v is not None:
+            o.append(f"{name} = {v}")
+    o.append("")
+    for tname, items in enums:
+        if tname:
+            o.append(f"# enum {tname}")
+        o.extend(f"{k} = {v}" for k, v in items)
+        o.append("")
+    names = {name for name, _ in structs}
+    for name, fields in structs:
+        o.append("")
+        o.append(f"class {name}(Structure):")
+        o.append("    _fields_ = [" + ",\n                ".join(f'("{f["name"]}", {py_field(f, names)})' for f in fields) + "]")
+        o.append("")
+    for table, fs in (("SIGNATURES", funcs), ("DEBUG_SIGNATURES", debug_funcs)):
+        o.append("")
+        o.append(table + " = {")
+        for ret, name, args in fs:
+            o.append(f'    "{name}": ({py_type(ret)}, [{", ".join(py_type(a) for a in split_args(args))}]),')
+        o.append("}")
+    o.extend(["", "",
+              "def declare(lib, partial=False):",
+              '    """Sets restype and argtypes of every entry point on a loaded librxr_hip.so and returns the handle.  A missing function of',
+              '    SIGNATURES is an error, unless `partial` says that the build links only some of the library\'s files; one of',
+              '    DEBUG_SIGNATURES is skipped (rxr_debug_phase_read exists only in a RXR_PHASE_TIMING build)."""',
+              "    for name, (restype, argtypes) in {**SIGNATURES, **DEBUG_SIGNATURES}.items():",
+              "        f = getattr(lib, name, None) if partial or name in DEBUG_SIGNATURES else getattr(lib, name)",
+              "        if f is not None:",
+              "            f.restype, f.argtypes = restype, argtypes",
+              "    return lib"])
+    return "\n".join(o) + "\n"
+
+
 def main():
     defines, enums, structs, funcs = parse(open(HEADER).read())
+    debug_funcs = prototypes(strip_comments(open(DEBUG_HEADER).read()))
     layout = Layout(structs)
-    outputs = {FFI_RS: gen_rust(defines, enums, structs, funcs, layout), ASSERTS_H: gen_asserts(structs, layout)}
+    outputs = {FFI_RS: gen_rust(defines, enums, structs, funcs, layout), ASSERTS_H: gen_asserts(structs, layout),
+               ABI_PY: gen_python(defines, enums, structs, funcs, debug_funcs)}
     if "--check" in sys.argv:
         stale = [p for p, text in outputs.items() if not os.path.exists(p) or open(p).read() != text]
         for p in stale:

@@ -47,7 +47,6 @@ def main():
     from tests.pick_fuzz import IDENTITY, Mesh3D
 
     rxr = rusterix_amd.rxr_abi()
-    rxr.rxr_set_meshes.restype, rxr.rxr_set_meshes.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]
     ctx = C.c_void_p()
     assert rxr.rxr_create(C.byref(ctx), 0) == 0
     err = lambda: (rxr.rxr_last_error(ctx) or b"").decode()

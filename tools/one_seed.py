@@ -14,7 +14,6 @@ from tests import test_gpu_rows as R  # noqa: E402
 
 prod, orc = rusterix_amd.load(), load_oracle()
 dp, variant, seeds = int(sys.argv[1]), sys.argv[2], [int(x) for x in sys.argv[3:]]
-prod.lib.rxh_set_device_projection.argtypes = [C.c_int]
 prod.lib.rxh_set_device_projection(dp)
 tag = " ".join(f"{k}={v}" for k, v in os.environ.items() if k.startswith("RXR_"))
 for s in seeds:

@@ -21,7 +21,7 @@ ap.add_argument("--frames", type=int, default=5)
 ap.add_argument("--scene", default="map", help="map | boxes | boxes_shader (the reduced C5 grid, 1920x1080) | c5 | c5_shader (the full 1 M-triangle grid)")
 a = ap.parse_args()
 prod = rusterix_amd.load()
-rxr = C.CDLL(rusterix_amd.lib_paths()["rxr"])
+rxr = rusterix_amd.rxr_abi()
 if a.scene == "map":
     cfg = scenes.map_scene(prod, width=a.width, height=a.height, n_lights=a.lights)
 elif a.scene.startswith("c5"):

@@ -138,22 +138,9 @@ def main():
 
     prod = rusterix_amd.load()
     host = prod.lib
-    rxr = C.CDLL(rusterix_amd.lib_paths()["rxr"])
-    host.rxh_context.restype = C.c_void_p
-    host.rxh_last_error.restype = C.c_char_p
-    host.rxh_rasterizer_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    rxr.rxr_render_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
-    rxr.rxr_synchronize.argtypes = [C.c_void_p]
-    rxr.rxr_download_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]
-    rxr.rxr_profile_begin.argtypes = [C.c_void_p, C.c_uint32]
-    rxr.rxr_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32)]
+    rxr = rusterix_amd.rxr_abi()
 
-    class Stats(C.Structure):
-        _fields_ = [("setup_us", C.c_float), ("raster_us", C.c_float), ("total_us", C.c_float), ("n_triangles3d", C.c_uint32),
-                    ("n_triangles2d", C.c_uint32), ("n_bin_entries", C.c_uint32), ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32)]
-
-    rxr.rxr_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
-    host.rxh_set_device_projection.argtypes = [C.c_int]
+    Stats = rusterix_amd.RxrStats
     host.rxh_set_device_projection(1 if args.device_projection else 0)
 
     for name in args.configs.split(","):

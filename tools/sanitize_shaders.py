@@ -34,17 +34,17 @@ def jit_generate(p):
     import ctypes as C
 
     import rusterix_amd
+    from rusterix_amd.abi import rxr_function, rxr_program, rxr_shader_set
 
-    lib = rusterix_amd.load_rxr()
-    lib.rxr_debug_jit_generate.argtypes = [C.POINTER(V.RxrShaderSet), C.c_int, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32]
+    lib = rusterix_amd.rxr_abi()
     keep = []
-    fns = (V.RxrFunction * max(len(p.functions), 1))()
+    fns = (rxr_function * max(len(p.functions), 1))()
     for k, f in enumerate(p.functions):
         arr = np.asarray(f if len(f) else [0], np.uint32)
         keep.append(arr)
-        fns[k] = V.RxrFunction(arr.ctypes.data_as(C.POINTER(C.c_uint32)), len(f))
-    progs = (V.RxrProgram * 1)(V.RxrProgram(p.globals, p.shade_index, p.shade_locals, fns, len(p.functions)))
-    s = V.RxrShaderSet(progs, 1, None, 0, None, 0, None, None, 0)
+        fns[k] = rxr_function(arr.ctypes.data, len(f))
+    progs = (rxr_program * 1)(rxr_program(p.globals, p.shade_index, p.shade_locals, fns, len(p.functions)))
+    s = rxr_shader_set(progs, 1, None, 0, None, 0, None, None, 0)
     src, msg = C.create_string_buffer(1 << 18), C.create_string_buffer(512)
     rc = lib.rxr_debug_jit_generate(C.byref(s), 0, src, len(src), msg, len(msg))
     assert rc in (0, B.RXR_ERR_UNSUPPORTED), (rc, msg.value)

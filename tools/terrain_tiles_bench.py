@@ -69,7 +69,6 @@ def main():
 
     api = rusterix_amd.load()
     rxr = rusterix_amd.rxr_abi()
-    rxr.rxr_set_meshes.restype, rxr.rxr_set_meshes.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]
     ctx = C.c_void_p(api.lib.rxh_context())
     stream = torch.cuda.Stream()
     sp = C.c_void_p(stream.cuda_stream)

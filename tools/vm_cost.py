@@ -7,13 +7,7 @@ import rusterix_amd
 from rusterix_amd import scenes, binding as B
 prod = rusterix_amd.load()
 host = prod.lib
-rxr = C.CDLL(rusterix_amd.lib_paths()["rxr"])
-host.rxh_context.restype = C.c_void_p
-host.rxh_rasterizer_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-rxr.rxr_render_rows.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
-rxr.rxr_synchronize.argtypes = [C.c_void_p]
-rxr.rxr_profile_begin.argtypes = [C.c_void_p, C.c_uint32]
-rxr.rxr_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32)]
+rxr = rusterix_amd.rxr_abi()
 def run(name, prog):
     orig = scenes.box_grid_shader
     scenes.box_grid_shader = lambda: prog
