@@ -477,6 +477,39 @@ int rxr_update_meshes(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t n, co
 int rxr_update_meshes_to(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t n, const uint32_t *dev_counts, const float *dev_vertices,
                          const uint32_t *dev_indices, const float *dev_normals, uint32_t vertex_stride, uint32_t triangle_stride,
                          void *hip_stream);
+/* Replaces the geometry of n ALREADY REGISTERED meshes when their COUNTS CHANGE (an excluded sector added or removed, a tile override
+ * painted, a terrain cell added or removed): what rxr_update_meshes refuses.  The layout is that of rxr_update_meshes with one more
+ * array: counts [n][2] = the NEW vertices, triangles of mesh_indices[i] (they may grow, shrink, become 0 or stop being 0); vertices
+ * [n][vertex_stride][4]; uvs [n][vertex_stride][2], or NULL: every uv of the named meshes is [0, 0] (TerrainChunk::build_mesh;
+ * rxr_terrain_meshes[_to] writes no uv array); indices [n][triangle_stride][3], mesh-local; normals [n][vertex_stride][3].  Slots past a
+ * mesh's own counts are never read, so rxr_generated_tile_meshes[_to]'s output feeds the call with no repacking.  Transform, cull mode,
+ * repeat mode, source, ambient, shader, profile id, list and chunk stay as registered, and so do the number and the order of the meshes.
+ * After success the context is in the state rxr_set_meshes of the whole scene with the new geometry would have left: the object-space
+ * pools, the prefix arrays and the mesh table with every later mesh's bases moved, output pools and scratch of the new sizes with the
+ * static originals written (k_proj_static), every box (the named ones as rxr_update_meshes computes them: equal to the host loop's
+ * under ==), and -- exactly as after rxr_set_meshes -- NO RESIDENT FRAME, no pick records, no box tree, no pending ranged refresh and
+ * no trace scene: upload the frame again, call rxr_set_trace_scene again before tracing; the next query rebuilds its records.
+ * RXR_ERR_INVALID, with the message naming the first offending mesh and why, and NOTHING CHANGED (pools, boxes, the resident frame, the
+ * pick records and a pending refresh all stay): no valid registration, a mesh index out of range or named twice, a NULL pointer other
+ * than uvs with n > 0 (an array of 0 bytes -- a stride of 0 -- is not looked at), byte sizes that overflow, a count above its stride,
+ * an index that is not below the new vertex count, new totals that reach rxr_set_meshes' limit of 2^31 output slots.  n == 0 does nothing.
+ * Once the checks have passed, a failure to allocate the new object pools leaves the old registration in use; any later failure (the
+ * output pools, a HIP error) leaves the context WITHOUT a valid registration, as a failed rxr_set_meshes does: register again.
+ * Blocking like rxr_update_meshes: it waits for everything the context has queued, reads one 40-byte check record per named mesh back
+ * (k_mesh_resize_check: counts against strides, indices, box; the host reads the counts nowhere else) and returns behind the writes.
+ * The object pools are double-buffered: k_mesh_repack copies unnamed meshes from the old pools and named ones from the caller's arrays
+ * into a second blob, which replaces the first at the end.  Multi-device handles: every member.
+ * Replaces, for the whole registration: rxr_set_meshes (its host loop over batch3d.rs:494-507 and its copy of the scene over PCIe). */
+int rxr_resize_meshes(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t n, const uint32_t *counts, const float *vertices, const float *uvs,
+                      const uint32_t *indices, const float *normals, uint32_t vertex_stride, uint32_t triangle_stride);
+/* the same from DEVICE arrays (dev_counts too: each one's first and last byte are checked to be memory of the context's device, 4-byte
+ * aligned, else RXR_ERR_INVALID; dev_uvs may be NULL); mesh_indices is host memory and is read before the call returns.  Everything is
+ * queued on hip_stream (NULL = the context's stream), so the call is ordered behind the work on that stream that produced its inputs
+ * (rxr_generated_tile_meshes_to -> rxr_vertex_normals_to -> rxr_resize_meshes_to), and no geometry crosses PCIe.  BLOCKING like the
+ * host form.  Multi-device handles: RXR_ERR_UNSUPPORTED (use rxr_member). */
+int rxr_resize_meshes_to(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t n, const uint32_t *dev_counts, const float *dev_vertices,
+                         const float *dev_uvs, const uint32_t *dev_indices, const float *dev_normals, uint32_t vertex_stride,
+                         uint32_t triangle_stride, void *hip_stream);
 /* debugging / tests: the object-space box the context currently holds for mesh `mesh_index` (batch3d.rs:494-507), whether it came from
  * rxr_set_meshes or from an update; (+inf, -inf) for a mesh without vertices.  Multi-device handles: member 0. */
 int rxr_mesh_bounds(rxr_ctx *ctx, uint32_t mesh_index, float lo[3], float hi[3]);

@@ -492,6 +492,8 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
     has_terrain_hit = hasattr(lib, prefix + "terrain_ray_hits")
     if has_terrain_hit:
         L.terrain_set_height = fn("terrain_set_height", None, vp, i32, i32, f32)
+        if hasattr(lib, prefix + "terrain_remove_height"):
+            L.terrain_remove_height = fn("terrain_remove_height", None, vp, i32, i32)
         L.terrain_get_height = fn("terrain_get_height", f32, vp, i32, i32)
         L.terrain_sample_height = fn("terrain_sample_height", f32, vp, f32, f32)
         L.terrain_sample_height_bilinear = fn("terrain_sample_height_bilinear", f32, vp, f32, f32)
@@ -532,6 +534,11 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
     has_tile_mesh_update = hasattr(lib, prefix + "scene_rebuild_generated_tile_meshes")
     if has_tile_mesh_update:
         L.scene_rebuild_generated_tile_meshes = fn("scene_rebuild_generated_tile_meshes", i32, vp, vp, C.POINTER(C.c_float), u32, pu, u32)
+
+    has_resize_meshes = hasattr(lib, prefix + "scene_set_resize_meshes")
+    if has_resize_meshes:
+        L.scene_set_resize_meshes = fn("scene_set_resize_meshes", None, vp, i32)
+        L.scene_resize_meshes = fn("scene_resize_meshes", i32, vp)
 
     # vertex normals of whole batch lists, on the CPU or the device (product host library only)
     has_vertex_normals = hasattr(lib, prefix + "scene_compute_normals")
@@ -1057,6 +1064,20 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
             return out
 
         @property
+        def resize_meshes(self):
+            """Scene::resize_meshes (opt-in, off by default): when rebuild_terrain_meshes / rebuild_generated_tile_meshes find counts
+            that changed, the same device arrays go through rxr_resize_meshes_to (include/rxr.h) and the call returns 2 ("resized on the
+            device": the batches' host arrays take the new counts, their contents are stale) instead of rebuilding on the host and
+            returning 1.  A chunk whose number of groups changed still raises."""
+            return bool(L.scene_resize_meshes(self._h)) if has_resize_meshes else False
+
+        @resize_meshes.setter
+        def resize_meshes(self, on):
+            if not has_resize_meshes:
+                raise NotImplementedError(f"{name}: no device-side mesh resize in this library")
+            L.scene_set_resize_meshes(self._h, 1 if on else 0)
+
+        @property
         def resident_chunk_textures(self):
             """Scene::resident_chunk_textures (opt-in, off by default): the chunks' terrain and shader textures are registered once
             (rxr_set_chunk_textures, include/rxr.h) and frames go without them; registered again when a chunk's textures_generation
@@ -1217,6 +1238,12 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
             """Terrain::set_height (:92-95)"""
             self._need_hit()
             L.terrain_set_height(self._h, x, y, height)
+            return self
+
+        def remove_height(self, x, y):
+            """Terrain::remove_height (:98-104): the cell leaves its chunk's mesh"""
+            self._need_hit()
+            L.terrain_remove_height(self._h, x, y)
             return self
 
         def get_height(self, x, y):
@@ -1767,6 +1794,47 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         if rc != 0:
             raise RasterizeError(rc, (rxr.rxr_last_error(ctx) or b"").decode())
 
+    def resize_meshes(mesh_indices, counts, vertices, uvs, indices, normals):
+        """rxr_resize_meshes (include/rxr.h) on the process-wide context: update_meshes' arrays plus uvs [n][VS][2] (None: every uv of
+        the named meshes is [0, 0]); the counts may differ from the registered ones.  The resident frame, the pick records and the
+        trace scene are gone afterwards, as after a registration.  Raises RasterizeError with the library's message when the call is
+        refused."""
+        if not has_resize_meshes:
+            raise NotImplementedError(f"{name}: no device-side mesh resize in this library")
+        from .libs import rxr_abi
+
+        m = np.ascontiguousarray(np.asarray(mesh_indices, np.uint32).reshape(-1))
+        n = len(m)
+        c = _u32(counts, (n, 2))
+        v, i = np.ascontiguousarray(vertices, np.float32), np.ascontiguousarray(indices, np.uint32)
+        if v.ndim != 3 or i.ndim != 3 or v.shape[0] != n or i.shape[0] != n or v.shape[2] != 4 or i.shape[2] != 3:
+            raise ValueError("vertices must be [n][VS][4] and indices [n][TS][3]")
+        nr = _f32(normals, (n, v.shape[1], 3))
+        uv = None if uvs is None else _f32(uvs, (n, v.shape[1], 2))
+        rxr = rxr_abi()
+        ctx = lib.rxh_context()
+        rc = rxr.rxr_resize_meshes(ctx, m.ctypes.data, n, c.ctypes.data, v.ctypes.data, None if uv is None else uv.ctypes.data, i.ctypes.data, nr.ctypes.data,
+                                   v.shape[1], i.shape[1])
+        if rc != 0:
+            raise RasterizeError(rc, (rxr.rxr_last_error(ctx) or b"").decode())
+
+    def resize_meshes_to(mesh_indices, counts, vertices, uvs, indices, normals, vertex_stride, triangle_stride, stream=None):
+        """rxr_resize_meshes_to (include/rxr.h) on the process-wide context: the arrays are device memory, given as objects with a
+        data_ptr() (torch tensors) or as addresses (uvs may be None); mesh_indices is a host sequence; `stream` is a torch stream, a
+        hipStream_t address or None (the context's stream).  Blocking.  Raises RasterizeError when the call is refused."""
+        if not has_resize_meshes:
+            raise NotImplementedError(f"{name}: no device-side mesh resize in this library")
+        from .libs import rxr_abi
+
+        ptr = lambda a: None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else int(a)) or None
+        m = np.ascontiguousarray(np.asarray(mesh_indices, np.uint32).reshape(-1))
+        rxr = rxr_abi()
+        ctx = lib.rxh_context()
+        s = getattr(stream, "cuda_stream", stream)
+        rc = rxr.rxr_resize_meshes_to(ctx, m.ctypes.data, len(m), ptr(counts), ptr(vertices), ptr(uvs), ptr(indices), ptr(normals), vertex_stride, triangle_stride, s)
+        if rc != 0:
+            raise RasterizeError(rc, (rxr.rxr_last_error(ctx) or b"").decode())
+
     def vertex_normals(counts, vertices, indices, normals=None):
         """rxr_vertex_normals (include/rxr.h) on the process-wide context, over host arrays in the layout of rxr_terrain_meshes: counts
         [n][2], vertices [n][VS][4], indices [n][TS][3]; the strides are the arrays' second extents.  Returns normals [n][VS][3]: the
@@ -1828,7 +1896,7 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
     return types.SimpleNamespace(
         name=name, lib=lib, prefix=prefix, raw=L, update_meshes=update_meshes, chunk_texture_registrations=chunk_texture_registrations,
         d3_rows=d3_rows,
-        vertex_normals=vertex_normals, vertex_normals_to=vertex_normals_to,
+        vertex_normals=vertex_normals, vertex_normals_to=vertex_normals_to, resize_meshes=resize_meshes, resize_meshes_to=resize_meshes_to,
         Scene=Scene, Batch3D=Batch3D, Batch2D=Batch2D, Chunk=Chunk, Assets=Assets, Rasterizer=Rasterizer, Terrain=Terrain, TerrainGenerator=TerrainGenerator,
         D3OrbitCamera=D3OrbitCamera, D3FirstPCamera=D3FirstPCamera, AccumBuffer=AccumBuffer,
         # shared value types

@@ -153,6 +153,10 @@ int rxh_scene_resident_chunk_textures(void *s) { return ((Scene *)s)->resident_c
 void rxh_scene_set_ray_accel(void *s, uint32_t mode) { ((Scene *)s)->ray_accel = mode; }
 uint32_t rxh_scene_ray_accel(void *s) { return ((Scene *)s)->ray_accel; }
 int rxh_scene_ray_accel_info(void *s, uint64_t *out) { return ((Scene *)s)->ray_accel_info(out); }
+// ---- counts that change are resized on the device (Scene::resize_meshes) ---------------------------------
+void rxh_scene_set_resize_meshes(void *s, int on) { ((Scene *)s)->resize_meshes = on != 0; }
+int rxh_scene_resize_meshes(void *s) { return ((Scene *)s)->resize_meshes ? 1 : 0; }
+
 // ---- the ranged refresh after mesh updates (Scene::ray_refresh): RXR_RAY_REFRESH_* ----------------------
 void rxh_scene_set_ray_refresh(void *s, uint32_t mode) { ((Scene *)s)->ray_refresh = mode; }
 uint32_t rxh_scene_ray_refresh(void *s) { return ((Scene *)s)->ray_refresh; }
@@ -227,6 +231,7 @@ void rxh_terrain_set_blend_mode(void *t, int32_t x, int32_t y, uint32_t kind, ui
 }
 // Terrain::set_height / get_height
 void rxh_terrain_set_height(void *t, int32_t x, int32_t y, float height) { ((Terrain *)t)->set_height(x, y, height); }
+void rxh_terrain_remove_height(void *t, int32_t x, int32_t y) { ((Terrain *)t)->remove_height(x, y); }
 float rxh_terrain_get_height(void *t, int32_t x, int32_t y) { return ((Terrain *)t)->get_height(x, y); }
 float rxh_terrain_sample_height(void *t, float x, float y) { return ((Terrain *)t)->sample_height(x, y); }
 float rxh_terrain_sample_height_bilinear(void *t, float x, float y) { return ((Terrain *)t)->sample_height_bilinear(x, y); }

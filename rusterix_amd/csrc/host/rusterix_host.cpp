@@ -504,6 +504,7 @@ thread_local bool t_frame_edgeless = true;
 int g_light_math = RXR_LIGHT_MATH_RELAXED;  // the library's default
 uint64_t g_mesh_fingerprint = 0;
 uint64_t g_mesh_geometry_fingerprint = 0;  // what rxr_intersect reads of the registered meshes (Scene::intersect)
+std::vector<rxr_source> g_mesh_sources;    // the resolved sources the registration was made with (register_meshes), mesh by mesh
 uint64_t g_mesh2d_fingerprint = 0;
 // resident chunk textures: the Chunk::textures_generation of every chunk the context's registration was made from (g_ctex_held: there is one)
 bool g_ctex_held = false;
@@ -695,8 +696,10 @@ namespace {
 // everything rxr_set_meshes copies (transforms travel per frame), `geometry` over what rxr_intersect reads of it.  slots == nullptr
 // (an intersect without a frame): sources are left unresolved; they are not read by rxr_intersect.  false: a batch with triangles but
 // without normals (clip_and_project panics at batch3d.rs:605, and rxr_set_meshes refuses it).
+// sources (with slots == nullptr): the resolved sources of an earlier registration, mesh by mesh, in place of the unresolved ones -- `full` is
+// then what an upload with unchanged assets computes (Scene::rebuild_* after rxr_resize_meshes_to).
 bool scene_meshes(const Scene &scene, const SequenceSlots *slots, std::vector<rxr_mesh3d> &meshes, std::vector<float> *transforms,
-                  uint64_t &full, uint64_t &geometry) {
+                  uint64_t &full, uint64_t &geometry, const std::vector<rxr_source> *sources = nullptr) {
     full = geometry = 1469598103934665603ull;
     auto mix = [](uint64_t &fp, const void *p, size_t n) {
         const uint8_t *q = (const uint8_t *)p;
@@ -715,6 +718,7 @@ bool scene_meshes(const Scene &scene, const SequenceSlots *slots, std::vector<rx
         m.cull_mode = (uint32_t)b.cull_mode_;
         m.repeat_mode = b.repeat_mode_;
         if (slots) m.source = slots->resolve(b.source_);
+        else if (sources && meshes.size() < sources->size()) m.source = (*sources)[meshes.size()];
         m.ambient_color[0] = b.ambient_color_.x; m.ambient_color[1] = b.ambient_color_.y; m.ambient_color[2] = b.ambient_color_.z;
         m.shader = b.shader_;
         m.has_profile_id = b.has_profile_id ? 1u : 0u;
@@ -758,7 +762,30 @@ int register_meshes(rxr_ctx *ctx, const std::vector<rxr_mesh3d> &meshes, uint64_
     }
     g_mesh_fingerprint = full;
     g_mesh_geometry_fingerprint = geometry;
+    g_mesh_sources.clear();
+    for (const rxr_mesh3d &m : meshes) g_mesh_sources.push_back(m.source);
     return RXR_OK;
+}
+
+// Scene::resize_meshes: the context's registration was resized on the device (rxr_resize_meshes_to).  The host batches take the new
+// COUNTS -- their arrays keep whatever they held, cut or zero-filled, with every index 0: stale like after an in-place update, but
+// still a mesh rxr_set_meshes accepts -- and the fingerprints become what the next upload of this scene computes, so that it sends
+// matrices only.  The stamps stay.
+void adopt_counts(Batch3D &b, size_t nv, size_t nt) {
+    b.vertices.resize(nv * 4, 0.0f);
+    b.uvs.resize(nv * 2, 0.0f);
+    b.normals.resize(nv * 3, 0.0f);
+    b.indices.assign(nt * 3, 0u);
+}
+void refingerprint_meshes(const Scene &scene) {
+    std::vector<rxr_mesh3d> meshes;
+    uint64_t full = 0, geometry = 0;
+    if (scene_meshes(scene, nullptr, meshes, nullptr, full, geometry, &g_mesh_sources) && meshes.size() == g_mesh_sources.size()) {
+        g_mesh_fingerprint = full;
+        g_mesh_geometry_fingerprint = geometry;
+    } else {
+        g_mesh_fingerprint = g_mesh_geometry_fingerprint = 0;   // (the next upload registers again)
+    }
 }
 
 }  // namespace
@@ -1625,6 +1652,11 @@ void Terrain::set_height(int32_t x, int32_t y, float height) {
     heights_generation = next_generation();
 }
 
+void Terrain::remove_height(int32_t x, int32_t y) {
+    // (the cell leaves the chunk's mesh; the chunk itself stays listed even when this was its last height)
+    if (heights.erase({x, y})) heights_generation = next_generation();
+}
+
 void Terrain::flatten_heights(std::vector<int32_t> &xy, std::vector<float> &height) const {
     for (const auto &kv : heights) {
         xy.push_back(kv.first.first);
@@ -1898,6 +1930,19 @@ int Scene::rebuild_terrain_meshes(const Terrain &terrain, const int32_t *coords,
             return rc;
         }
         // refused (counts changed): nothing was changed on the device
+        if (resize_meshes) {
+            // the same arrays on the same stream, uvs absent (TerrainChunk::build_mesh's are [0, 0]); the counts come back for the batches
+            std::vector<uint32_t> got(2 * (size_t)n);
+            rc = rxr_resize_meshes_to(ctx, mesh_index.data(), n, dc, dv, nullptr, di, dn, (uint32_t)VS, (uint32_t)TS, nullptr);
+            if (rc == RXR_OK) rc = rxr_mirror_read(ctx, got.data(), dc, got.size() * sizeof(uint32_t));
+            if (rc != RXR_OK) {
+                g_error = rxr_last_error(ctx);
+                return rc;
+            }
+            for (uint32_t i = 0; i < n; ++i) adopt_counts(chunks[chunks_[i]].terrain_batch3d[0], got[2 * (size_t)i], got[2 * (size_t)i + 1]);
+            refingerprint_meshes(*this);
+            return 2;
+        }
     }
     std::vector<Batch3D> built;
     const int rc = terrain.build_meshes(coords, n, built);
@@ -1994,12 +2039,13 @@ int Scene::rebuild_generated_tile_meshes(const TerrainGenerator &gen, const floa
                 same_counts = same_counts && mc[0] == c.batches3d[g].vertex_count() && mc[1] == c.batches3d[g].triangle_count();
             }
         }
-        if (same_counts) rc = rxr_vertex_normals_to(ctx, (uint32_t)M, dc, dv, di, dn, nullptr, (uint32_t)VS, (uint32_t)TS, nullptr);
+        const bool resize = !same_counts && resize_meshes;   // (Scene::resize_meshes: counts that changed are resized on the device)
+        if (same_counts || resize) rc = rxr_vertex_normals_to(ctx, (uint32_t)M, dc, dv, di, dn, nullptr, (uint32_t)VS, (uint32_t)TS, nullptr);
         if (rc != RXR_OK) {
             g_error = rxr_last_error(ctx);
             return rc;
         }
-        if (!same_counts) rc = RXR_ERR_INVALID;   // (the host path below)
+        if (!same_counts && !resize) rc = RXR_ERR_INVALID;   // (the host path below)
         // a chunk's registered meshes are its groups; a chunk with fewer than max_groups of them leaves mesh slots no mesh answers to,
         // so the update is one call when every chunk is full and one call per chunk otherwise
         std::vector<uint32_t> mesh_index;
@@ -2009,8 +2055,27 @@ int Scene::rebuild_generated_tile_meshes(const TerrainGenerator &gen, const floa
             if (all_full && i + 1 < n) continue;
             const size_t m0 = all_full ? 0 : (size_t)i * max_groups;
             if (!mesh_index.empty())
-                rc = rxr_update_meshes_to(ctx, mesh_index.data(), (uint32_t)mesh_index.size(), dc + 2 * m0, dv + m0 * VS * 4, di + m0 * TS * 3, dn + m0 * VS * 3, (uint32_t)VS, (uint32_t)TS, nullptr);
+                rc = resize ? rxr_resize_meshes_to(ctx, mesh_index.data(), (uint32_t)mesh_index.size(), dc + 2 * m0, dv + m0 * VS * 4, du + m0 * VS * 2, di + m0 * TS * 3,
+                                                   dn + m0 * VS * 3, (uint32_t)VS, (uint32_t)TS, nullptr)
+                            : rxr_update_meshes_to(ctx, mesh_index.data(), (uint32_t)mesh_index.size(), dc + 2 * m0, dv + m0 * VS * 4, di + m0 * TS * 3, dn + m0 * VS * 3,
+                                                   (uint32_t)VS, (uint32_t)TS, nullptr);
             mesh_index.clear();
+        }
+        if (resize) {
+            if (rc != RXR_OK) {   // (a call of several may have gone through: the next upload registers again)
+                g_error = rxr_last_error(ctx);
+                g_mesh_fingerprint = g_mesh_geometry_fingerprint = 0;
+                return rc;
+            }
+            for (uint32_t i = 0; i < n; ++i) {
+                Chunk &c = chunks[chunks_[i]];
+                for (size_t g = 0; g < c.batches3d.size(); ++g) {
+                    const uint32_t *mc = got.data() + o_c / 4 + 2 * ((size_t)i * max_groups + g);
+                    adopt_counts(c.batches3d[g], mc[0], mc[1]);
+                }
+            }
+            refingerprint_meshes(*this);
+            return 2;
         }
         if (rc == RXR_OK) return 0;
         if (rc != RXR_ERR_INVALID) {

@@ -318,6 +318,13 @@ public:
     // when a chunk's textures_generation differs from the one registered, when chunks were added or removed, or when another scene's
     // registration is held; a scene with the option off removes a registration it finds.
     bool resident_chunk_textures = false;
+    // Opt-in, off by default: when rxr_update_meshes_to refuses rebuild_terrain_meshes / rebuild_generated_tile_meshes because counts
+    // changed, the same device arrays go through rxr_resize_meshes_to on the same stream (include/rxr.h) and the call returns
+    //   2  resized on the device: the context's registration is the new one, the named batches' host arrays take the new COUNTS
+    //      (their contents are stale, as after a return of 0; every index is 0) and the registration's fingerprints follow, so the
+    //      next upload sends matrices only.  The resident frame, the pick records and the trace scene are gone, as after a registration.
+    // instead of 1.  A chunk whose number of groups changed is still RXR_ERR_INVALID.  Off: every call behaves as described above.
+    bool resize_meshes = false;
     // Opt-in, off by default (RXR_RAY_ACCEL_OFF): intersect() and Tracer::trace hand the mode to the context (rxr_set_ray_accel,
     // include/rxr.h), which then culls its many-ray queries with a box tree built on the device over the registered triangles.  The
     // results are the same words; RXR_RAY_ACCEL_COUNT also counts the ray-triangle tests (ray_accel_info).
@@ -421,6 +428,7 @@ public:
     std::map<std::pair<int32_t, int32_t>, float> heights;         // what get_height returns per cell, keyed (x, y)
     uint64_t heights_generation = next_generation();              // re-stamped by set_height alone: a height edit does not re-register the bake's terrain
     void set_height(int32_t x, int32_t y, float height);          // :92-95
+    void remove_height(int32_t x, int32_t y);                     // :98-104 (an emptied chunk stays listed)
     float get_height(int32_t x, int32_t y) const;                 // :82-89: 0.0 for a cell that does not exist
     float sample_height(float x, float y) const;                  // :148-152
     float sample_height_bilinear(float x, float y) const;         // :155-173

@@ -20,12 +20,15 @@
 #include <vector>
 
 #include "rxr_debug.h"
+#include "rxr_mesh_resize.h"
 #include "rxr_query.h"
 
 thread_local LaunchTimes *rxr_launch_times = nullptr;  // rxr_launch.h: the profiling slot of the render this thread is queueing
 extern "C" void rxr_launch_proj_static(const ProjectParams *P, hipStream_t s);
 extern "C" void rxr_launch_mesh_check(const MeshUpdateArgs *A, uint32_t n, hipStream_t s);
 extern "C" void rxr_launch_mesh_commit(const MeshUpdateArgs *A, uint32_t n, hipStream_t s);
+extern "C" void rxr_launch_mesh_resize_check(const MeshResizeCheckArgs *A, uint32_t n, hipStream_t s);
+extern "C" void rxr_launch_mesh_repack(const MeshRepackArgs *A, hipStream_t s);
 extern "C" void rxr_launch_project(const ProjectParams *P, hipStream_t s);
 extern "C" void rxr_launch_proj_edges(const ProjectParams *P, hipStream_t s);
 extern "C" void rxr_launch_setup(const RasterParams *P, hipStream_t s);
@@ -178,7 +181,7 @@ void rxr_destroy(rxr_ctx *ctx) {
     }
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)rxr_quiesce(ctx);
-    DevBuf *bufs[] = {&ctx->d_stripes, &ctx->d_obj, &ctx->d_mesh_check, &ctx->d_mirror_scratch, &ctx->d_proj_out, &ctx->d_proj_misc, &ctx->d_tex, &ctx->d_texels, &ctx->d_frame, &ctx->d_tri_setup, &ctx->d_tri_shade, &ctx->d_tri_box, &ctx->d_bin_count, &ctx->d_bins, &ctx->d_bin2d_count, &ctx->d_bins2d,
+    DevBuf *bufs[] = {&ctx->d_stripes, &ctx->d_obj, &ctx->d_obj_alt, &ctx->d_mesh_check, &ctx->d_mirror_scratch, &ctx->d_proj_out, &ctx->d_proj_misc, &ctx->d_tex, &ctx->d_texels, &ctx->d_frame, &ctx->d_tri_setup, &ctx->d_tri_shade, &ctx->d_tri_box, &ctx->d_bin_count, &ctx->d_bins, &ctx->d_bin2d_count, &ctx->d_bins2d,
                       &ctx->d_list2d, &ctx->d_large2d,
                       &ctx->d_list, &ctx->d_large, &ctx->d_counters, &ctx->d_fb,
                       &ctx->d_vm_code, &ctx->d_programs, &ctx->d_patterns, &ctx->d_pattern_data, &ctx->d_palette,
@@ -202,6 +205,8 @@ void rxr_destroy(rxr_ctx *ctx) {
     if (ctx->ev2) (void)hipEventDestroy(ctx->ev2);
     if (ctx->ev_upload) (void)hipEventDestroy(ctx->ev_upload);
     if (ctx->ev_render) (void)hipEventDestroy(ctx->ev_render);
+    for (hipEvent_t e : ctx->ev_repack)
+        if (e) (void)hipEventDestroy(e);
     if (ctx->h_bake_fault) (void)hipHostFree(ctx->h_bake_fault);
     if (ctx->h_bake_jobs) (void)hipHostFree(ctx->h_bake_jobs);
     for (hipEvent_t ev : ctx->ev_band)
@@ -291,6 +296,76 @@ int rxr_set_textures(rxr_ctx *ctx, const rxr_tile *static_tiles, uint32_t n_stat
     return RXR_OK;
 }
 
+// the layout of the object blob (d_obj): the packed pools, the three prefix arrays and the registration's static DevMesh table
+struct ObjLayout {
+    size_t off_v, off_i, off_uv, off_n, off_pv, off_pt, off_po, off_dm, total;
+};
+static ObjLayout obj_layout(size_t n_meshes, size_t vin, size_t tin) {
+    BlobCursor take;
+    ObjLayout L;
+    L.off_v = take(vin * 16), L.off_i = take(tin * 12), L.off_uv = take(vin * 8), L.off_n = take(vin * 12);
+    L.off_pv = take((n_meshes + 1) * 4), L.off_pt = take((n_meshes + 1) * 4), L.off_po = take((n_meshes + 1) * 4);
+    L.off_dm = take(n_meshes * sizeof(DevMesh));
+    L.total = take.o;
+    return L;
+}
+
+// what a registration needs behind its object blob `d_obj` (laid out by L, its copy or kernel queued on `s`): the output pools and the
+// projection's scratch for these totals, zeroed; ctx->PP; the static originals (k_proj_static).  Shared by rxr_set_meshes and
+// rxr_resize_meshes, so that the two leave the same state.
+static int proj_pools(rxr_ctx *ctx, uint32_t n_meshes, size_t vin, size_t tin, size_t vout, size_t tout, const ObjLayout &L, void *d_obj, hipStream_t s) {
+    int rc;
+    // ---- output pools (the arrays k_setup3d reads) + scratch ----
+    BlobCursor take;
+    const size_t q_vs = take(vout * 16), q_pv = take(vout * 16), q_uv = take(vout * 8), q_nrm = take(vout * 12);
+    const size_t q_idx = take(tout * 12), q_edges = take(tout * sizeof(rxr_edges));
+    const size_t out_total = take.o;
+    if ((rc = rxr_ensure(ctx, ctx->d_proj_out, out_total)) != RXR_OK) return rc;
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_proj_out.p, 0, out_total, s));  // indices 0 / edges invisible until written
+    take.o = 0;
+    const size_t n_chunks = (tin + 1 + RXR_PROJ_SCAN_CHUNK - 1) / RXR_PROJ_SCAN_CHUNK + 1;
+    const size_t m_evis = take(tin + 1), m_app = take((tin + 1) * 8), m_ct = take(n_chunks * 8), m_cb = take(n_chunks * 8);
+    const size_t m_ticket = take(16), m_bbox = take((size_t)n_meshes * sizeof(DevBBox));
+    const size_t m_dm = take((size_t)n_meshes * sizeof(DevMesh));
+    const size_t m_live = take((size_t)n_meshes * sizeof(uint32_t));
+    if ((rc = rxr_ensure(ctx, ctx->d_proj_misc, take.o)) != RXR_OK) return rc;
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_proj_misc.p, 0, take.o, s));
+    ctx->pp_off_meshes = m_dm;
+    ctx->obj_off_meshes = L.off_dm;
+
+    ProjectParams &PP = ctx->PP;
+    memset(&PP, 0, sizeof(PP));
+    PP.n_meshes = n_meshes;
+    PP.n_verts_in = (uint32_t)vin;
+    PP.n_tris_in = (uint32_t)tin;
+    PP.n_tris_out = (uint32_t)tout;
+    uint8_t *d = (uint8_t *)d_obj, *q = (uint8_t *)ctx->d_proj_out.p, *mm = (uint8_t *)ctx->d_proj_misc.p;
+    PP.meshes = (const DevMesh *)(d + L.off_dm);  // static copy; replaced by the per-frame array at render time
+    PP.vin_prefix = (const uint32_t *)(d + L.off_pv);
+    PP.tin_prefix = (const uint32_t *)(d + L.off_pt);
+    PP.tout_prefix = (const uint32_t *)(d + L.off_po);
+    PP.obj_verts = (const float4 *)(d + L.off_v);
+    PP.obj_idx = (const uint32_t *)(d + L.off_i);
+    PP.obj_uvs = (const float2 *)(d + L.off_uv);
+    PP.obj_normals = (const float *)(d + L.off_n);
+    PP.view_verts = (float4 *)(q + q_vs);
+    PP.pv = (float4 *)(q + q_pv);
+    PP.uv = (float2 *)(q + q_uv);
+    PP.nrm = (float *)(q + q_nrm);
+    PP.idx = (uint32_t *)(q + q_idx);
+    PP.edges = (rxr_edges *)(q + q_edges);
+    PP.edge_vis = (uint8_t *)(mm + m_evis);
+    PP.append = (AppendCount *)(mm + m_app);
+    PP.chunk_tot = (AppendCount *)(mm + m_ct);
+    PP.chunk_base = (AppendCount *)(mm + m_cb);
+    PP.ticket = (uint32_t *)(mm + m_ticket);
+    PP.bbox = (DevBBox *)(mm + m_bbox);
+    PP.mesh_live = (uint32_t *)(mm + m_live);
+    rxr_launch_proj_static(&PP, s);
+    HIPCHK(ctx, hipGetLastError());
+    return RXR_OK;
+}
+
 int rxr_set_meshes(rxr_ctx *ctx, const rxr_mesh3d *meshes, uint32_t n_meshes) {
     if (!ctx) return RXR_ERR_INVALID;
     if (n_meshes && !meshes) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_set_meshes: NULL mesh array");
@@ -356,11 +431,9 @@ int rxr_set_meshes(rxr_ctx *ctx, const rxr_mesh3d *meshes, uint32_t n_meshes) {
     ctx->mesh_tris_out = tout;
 
     // ---- object-space pools + static prefix arrays: one staging blob, one copy ----
-    BlobCursor take;
-    const size_t off_v = take(vin * 16), off_i = take(tin * 12), off_uv = take(vin * 8), off_n = take(vin * 12);
-    const size_t off_pv = take((n_meshes + 1) * 4), off_pt = take((n_meshes + 1) * 4), off_po = take((n_meshes + 1) * 4);
-    const size_t off_dm = take((size_t)n_meshes * sizeof(DevMesh));
-    const size_t obj_total = take.o;
+    const ObjLayout L = obj_layout(n_meshes, vin, tin);
+    const size_t off_v = L.off_v, off_i = L.off_i, off_uv = L.off_uv, off_n = L.off_n, off_pv = L.off_pv, off_pt = L.off_pt, off_po = L.off_po, off_dm = L.off_dm;
+    const size_t obj_total = L.total;
     int rc;
     if ((rc = rxr_ensure_stage(ctx, obj_total)) != RXR_OK) return rc;
     if ((rc = rxr_ensure(ctx, ctx->d_obj, obj_total)) != RXR_OK) return rc;
@@ -387,54 +460,7 @@ int rxr_set_meshes(rxr_ctx *ctx, const rxr_mesh3d *meshes, uint32_t n_meshes) {
     po[n_meshes] = (uint32_t)tout;
     HIPCHK(ctx, hipMemcpyAsync(ctx->d_obj.p, st, obj_total, hipMemcpyHostToDevice, ctx->stream));
 
-    // ---- output pools (the arrays k_setup3d reads) + scratch ----
-    take.o = 0;
-    const size_t q_vs = take(vout * 16), q_pv = take(vout * 16), q_uv = take(vout * 8), q_nrm = take(vout * 12);
-    const size_t q_idx = take(tout * 12), q_edges = take(tout * sizeof(rxr_edges));
-    const size_t out_total = take.o;
-    if ((rc = rxr_ensure(ctx, ctx->d_proj_out, out_total)) != RXR_OK) return rc;
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_proj_out.p, 0, out_total, ctx->stream));  // indices 0 / edges invisible until written
-    take.o = 0;
-    const size_t n_chunks = (tin + 1 + RXR_PROJ_SCAN_CHUNK - 1) / RXR_PROJ_SCAN_CHUNK + 1;
-    const size_t m_evis = take(tin + 1), m_app = take((tin + 1) * 8), m_ct = take(n_chunks * 8), m_cb = take(n_chunks * 8);
-    const size_t m_ticket = take(16), m_bbox = take((size_t)n_meshes * sizeof(DevBBox));
-    const size_t m_dm = take((size_t)n_meshes * sizeof(DevMesh));
-    const size_t m_live = take((size_t)n_meshes * sizeof(uint32_t));
-    if ((rc = rxr_ensure(ctx, ctx->d_proj_misc, take.o)) != RXR_OK) return rc;
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_proj_misc.p, 0, take.o, ctx->stream));
-    ctx->pp_off_meshes = m_dm;
-    ctx->obj_off_meshes = off_dm;
-
-    ProjectParams &PP = ctx->PP;
-    memset(&PP, 0, sizeof(PP));
-    PP.n_meshes = n_meshes;
-    PP.n_verts_in = (uint32_t)vin;
-    PP.n_tris_in = (uint32_t)tin;
-    PP.n_tris_out = (uint32_t)tout;
-    uint8_t *d = (uint8_t *)ctx->d_obj.p, *q = (uint8_t *)ctx->d_proj_out.p, *mm = (uint8_t *)ctx->d_proj_misc.p;
-    PP.meshes = (const DevMesh *)(d + off_dm);  // static copy; replaced by the per-frame array at render time
-    PP.vin_prefix = (const uint32_t *)(d + off_pv);
-    PP.tin_prefix = (const uint32_t *)(d + off_pt);
-    PP.tout_prefix = (const uint32_t *)(d + off_po);
-    PP.obj_verts = (const float4 *)(d + off_v);
-    PP.obj_idx = (const uint32_t *)(d + off_i);
-    PP.obj_uvs = (const float2 *)(d + off_uv);
-    PP.obj_normals = (const float *)(d + off_n);
-    PP.view_verts = (float4 *)(q + q_vs);
-    PP.pv = (float4 *)(q + q_pv);
-    PP.uv = (float2 *)(q + q_uv);
-    PP.nrm = (float *)(q + q_nrm);
-    PP.idx = (uint32_t *)(q + q_idx);
-    PP.edges = (rxr_edges *)(q + q_edges);
-    PP.edge_vis = (uint8_t *)(mm + m_evis);
-    PP.append = (AppendCount *)(mm + m_app);
-    PP.chunk_tot = (AppendCount *)(mm + m_ct);
-    PP.chunk_base = (AppendCount *)(mm + m_cb);
-    PP.ticket = (uint32_t *)(mm + m_ticket);
-    PP.bbox = (DevBBox *)(mm + m_bbox);
-    PP.mesh_live = (uint32_t *)(mm + m_live);
-    rxr_launch_proj_static(&PP, ctx->stream);
-    HIPCHK(ctx, hipGetLastError());
+    if ((rc = proj_pools(ctx, n_meshes, vin, tin, vout, tout, L, ctx->d_obj.p, ctx->stream)) != RXR_OK) return rc;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     ctx->meshes_valid = true;
     return RXR_OK;
@@ -442,7 +468,9 @@ int rxr_set_meshes(rxr_ctx *ctx, const rxr_mesh3d *meshes, uint32_t n_meshes) {
 
 // ---- rxr_update_meshes: registered meshes' geometry replaced in place (kernels: rxr_project.hip) ------------------------------
 // what both forms refuse before anything is queued, but for their pointers; bytes[4]: the arrays' sizes
-static int update_check(rxr_ctx *ctx, const char *who, const uint32_t *mesh_indices, uint32_t n, uint32_t vstride, uint32_t tstride, size_t bytes[4]) {
+// (against_registration false: rxr_resize_meshes, whose strides bound the NEW counts -- the check kernel compares those)
+static int update_check(rxr_ctx *ctx, const char *who, const uint32_t *mesh_indices, uint32_t n, uint32_t vstride, uint32_t tstride, size_t bytes[4],
+                        bool against_registration = true) {
     const std::string w = who;
     if (!ctx->meshes_valid) return rxr_fail(ctx, RXR_ERR_INVALID, w + ": no valid registration (the last rxr_set_meshes failed)");
     if (!mesh_indices) return rxr_fail(ctx, RXR_ERR_INVALID, w + ": NULL mesh_indices");
@@ -459,6 +487,7 @@ static int update_check(rxr_ctx *ctx, const char *who, const uint32_t *mesh_indi
         if (m >= ctx->meshes.size()) return rxr_fail(ctx, RXR_ERR_INVALID, at + ": no such mesh (" + std::to_string(ctx->meshes.size()) + " are registered)");
         if (named[m]) return rxr_fail(ctx, RXR_ERR_INVALID, at + ": named twice");
         named[m] = 1;
+        if (!against_registration) continue;
         const DevMesh &M = ctx->meshes[m].dev;
         if (M.n_verts > vstride) return rxr_fail(ctx, RXR_ERR_INVALID, at + ": vertex_stride " + std::to_string(vstride) + " is below its " + std::to_string(M.n_verts) + " vertices");
         if (M.n_tris > tstride) return rxr_fail(ctx, RXR_ERR_INVALID, at + ": triangle_stride " + std::to_string(tstride) + " is below its " + std::to_string(M.n_tris) + " triangles");
@@ -581,6 +610,240 @@ int rxr_update_meshes_to(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t n,
     if ((rc = rxr_quiesce(ctx)) != RXR_OK) return rc;   // renders and picks read the pools
     return update_run(ctx, "rxr_update_meshes_to", mesh_indices, n, dev_counts, dev_vertices, dev_indices, dev_normals, vertex_stride, triangle_stride,
                       hip_stream ? (hipStream_t)hip_stream : ctx->stream);
+}
+
+// ---- rxr_resize_meshes: registered meshes whose counts change (kernels: rxr_project.hip; the layout arithmetic: rxr_mesh_resize.h) --------
+// Over DEVICE arrays on `s`; the streams are idle (rxr_quiesce) and stay so until this returns.  Three steps: the check kernel and its
+// records (a refusal changes nothing); the new layout, on the host in O(registered meshes); the new object blob built in d_obj_alt from
+// d_obj and the caller's arrays, the output pools as rxr_set_meshes makes them, and only then the swap.
+static int resize_run(rxr_ctx *ctx, const char *who, const uint32_t *mesh_indices, uint32_t n, const uint32_t *counts, const float *vertices, const float *uvs,
+                      const uint32_t *indices, const float *normals, uint32_t vstride, uint32_t tstride, hipStream_t s) {
+    int rc = rxr_ensure(ctx, ctx->d_mesh_check, (size_t)n * sizeof(MeshResizeRec));
+    if (rc != RXR_OK) return rc;
+    MeshResizeCheckArgs C{};
+    C.counts = counts;
+    C.vertices = vertices;
+    C.indices = indices;
+    C.vstride = vstride;
+    C.tstride = tstride;
+    C.rec = (MeshResizeRec *)ctx->d_mesh_check.p;
+    rxr_launch_mesh_resize_check(&C, n, s);
+    HIPCHK(ctx, hipGetLastError());
+    std::vector<MeshResizeRec> rec(n);
+    HIPCHK(ctx, hipMemcpyAsync(rec.data(), ctx->d_mesh_check.p, (size_t)n * sizeof(MeshResizeRec), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    const std::string w = who;
+    auto at = [&](uint32_t i) { return w + ": mesh_indices[" + std::to_string(i) + "] = " + std::to_string(mesh_indices[i]) + ": "; };
+    const char *unchanged = " (nothing was changed)";
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!rec[i].status) continue;
+        std::string why;
+        if (rec[i].status & MESH_RSZ_BAD_VSTRIDE) why = "its " + std::to_string(rec[i].n_verts) + " vertices exceed vertex_stride " + std::to_string(vstride);
+        else if (rec[i].status & MESH_RSZ_BAD_TSTRIDE) why = "its " + std::to_string(rec[i].n_tris) + " triangles exceed triangle_stride " + std::to_string(tstride);
+        else why = "triangle " + std::to_string(rec[i].bad_triangle) + " has a vertex index that is not below its " + std::to_string(rec[i].n_verts) + " vertices";
+        return rxr_fail(ctx, RXR_ERR_INVALID, at(i) + why + unchanged);
+    }
+    // the new layout
+    const uint32_t n_meshes = (uint32_t)ctx->meshes.size();
+    std::vector<uint32_t> all_counts(2 * (size_t)n_meshes), slot(n_meshes, 0xFFFFFFFFu), bases(4 * (size_t)n_meshes);
+    for (uint32_t m = 0; m < n_meshes; ++m) {
+        all_counts[2 * (size_t)m] = ctx->meshes[m].dev.n_verts;
+        all_counts[2 * (size_t)m + 1] = ctx->meshes[m].dev.n_tris;
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+        slot[mesh_indices[i]] = i;
+        all_counts[2 * (size_t)mesh_indices[i]] = rec[i].n_verts;
+        all_counts[2 * (size_t)mesh_indices[i] + 1] = rec[i].n_tris;
+    }
+    uint64_t totals[4];
+    const size_t reached = rxr_resize_bases(all_counts.data(), n_meshes, bases.data(), totals);
+    if (reached != n_meshes) {
+        // the old registration fitted, so a named mesh at or before `reached` grew: the last of them is the one the message names
+        uint32_t i = 0xFFFFFFFFu;
+        for (uint32_t k = 0; k < n; ++k)
+            if (mesh_indices[k] <= reached && (i == 0xFFFFFFFFu || mesh_indices[k] > mesh_indices[i])) i = k;
+        if (i == 0xFFFFFFFFu) i = 0;
+        return rxr_fail(ctx, RXR_ERR_INVALID, at(i) + "with its " + std::to_string(rec[i].n_verts) + " vertices and " + std::to_string(rec[i].n_tris) +
+                                                  " triangles the meshes are too large (>= 2^31 output slots at mesh " + std::to_string(reached) + ")" + unchanged);
+    }
+    const size_t vin = totals[0], tin = totals[1], vout = totals[2], tout = totals[3];
+
+    // ---- accepted.  The small tables go through the staging blob; the new pools are built next to the old ones ----
+    const HostMesh &last = ctx->meshes[n_meshes - 1];   // (n >= 1 named meshes passed update_check: there is one)
+    const ObjLayout L = obj_layout(n_meshes, vin, tin), L0 = obj_layout(n_meshes, (size_t)last.dev.vin_base + last.dev.n_verts, (size_t)last.dev.tin_base + last.dev.n_tris);
+    BlobCursor take;
+    take.o = L.total;
+    const size_t off_src = take((size_t)n_meshes * 8);
+    const size_t blob_total = take.o, tables = blob_total - L.off_pv;
+    if ((rc = rxr_ensure_stage(ctx, tables)) != RXR_OK) return rc;
+    if ((rc = rxr_ensure(ctx, ctx->d_obj_alt, blob_total)) != RXR_OK) return rc;   // (a failure here: the old registration stays in use)
+    uint8_t *st = (uint8_t *)ctx->h_stage;   // (the staged range is [off_pv, blob_total) of the blob)
+    uint32_t *pv = (uint32_t *)st, *pt = (uint32_t *)(st + (L.off_pt - L.off_pv)), *po = (uint32_t *)(st + (L.off_po - L.off_pv)), *src = (uint32_t *)(st + (off_src - L.off_pv));
+    DevMesh *dm = (DevMesh *)(st + (L.off_dm - L.off_pv));
+    for (uint32_t m = 0; m < n_meshes; ++m) {
+        DevMesh d = ctx->meshes[m].dev;
+        src[2 * (size_t)m] = slot[m] != 0xFFFFFFFFu ? (RXR_MESH_RESIZE_NAMED | slot[m]) : d.vin_base;   // (the OLD bases)
+        src[2 * (size_t)m + 1] = slot[m] != 0xFFFFFFFFu ? 0u : d.tin_base;
+        d.vin_base = bases[4 * (size_t)m], d.tin_base = bases[4 * (size_t)m + 1], d.vout_base = bases[4 * (size_t)m + 2], d.tout_base = bases[4 * (size_t)m + 3];
+        d.n_verts = all_counts[2 * (size_t)m], d.n_tris = all_counts[2 * (size_t)m + 1];
+        pv[m] = d.vin_base, pt[m] = d.tin_base, po[m] = d.tout_base;
+        dm[m] = d;
+    }
+    pv[n_meshes] = (uint32_t)vin, pt[n_meshes] = (uint32_t)tin, po[n_meshes] = (uint32_t)tout;
+    uint8_t *d0 = (uint8_t *)ctx->d_obj.p, *d1 = (uint8_t *)ctx->d_obj_alt.p;
+    HIPCHK(ctx, hipMemcpyAsync(d1 + L.off_pv, ctx->h_stage, tables, hipMemcpyHostToDevice, s));
+    MeshRepackArgs R{};
+    R.n_meshes = n_meshes, R.n_verts = (uint32_t)vin, R.n_tris = (uint32_t)tin;
+    R.meshes = (const DevMesh *)(d1 + L.off_dm);
+    R.vin_prefix = (const uint32_t *)(d1 + L.off_pv), R.tin_prefix = (const uint32_t *)(d1 + L.off_pt);
+    R.source = (const uint32_t *)(d1 + off_src);
+    R.old_verts = (const uint4 *)(d0 + L0.off_v), R.old_idx = (const uint32_t *)(d0 + L0.off_i);
+    R.old_uvs = (const uint2 *)(d0 + L0.off_uv), R.old_normals = (const uint32_t *)(d0 + L0.off_n);
+    R.vertices = (const uint32_t *)vertices, R.uvs = (const uint32_t *)uvs, R.indices = indices, R.normals = (const uint32_t *)normals;
+    R.vstride = vstride, R.tstride = tstride;
+    R.new_verts = (uint4 *)(d1 + L.off_v), R.new_idx = (uint32_t *)(d1 + L.off_i);
+    R.new_uvs = (uint2 *)(d1 + L.off_uv), R.new_normals = (uint32_t *)(d1 + L.off_n);
+    for (hipEvent_t &e : ctx->ev_repack)
+        if (!e) HIPCHK(ctx, hipEventCreate(&e));
+    HIPCHK(ctx, hipEventRecord(ctx->ev_repack[0], s));
+    rxr_launch_mesh_repack(&R, s);
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipEventRecord(ctx->ev_repack[1], s));
+    ctx->repack_bytes = (uint64_t)vin * 36 + (uint64_t)tin * 12;
+
+    // from here on as rxr_set_meshes: no valid registration until the call completes
+    ctx->has_frame = false;
+    ctx->meshes_valid = false;
+    ctx->isect_ready = false;
+    ctx->refresh_named.clear();
+    ctx->refresh_pending = 0;
+    ctx->trace_set = false;
+    if ((rc = proj_pools(ctx, n_meshes, vin, tin, vout, tout, L, d1, s)) != RXR_OK) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    std::swap(ctx->d_obj, ctx->d_obj_alt);
+    ctx->mesh_verts_out = vout;
+    ctx->mesh_tris_out = tout;
+    for (uint32_t m = 0; m < n_meshes; ++m) {
+        HostMesh &h = ctx->meshes[m];
+        h.dev.vin_base = bases[4 * (size_t)m], h.dev.tin_base = bases[4 * (size_t)m + 1], h.dev.vout_base = bases[4 * (size_t)m + 2], h.dev.tout_base = bases[4 * (size_t)m + 3];
+        h.dev.n_verts = all_counts[2 * (size_t)m], h.dev.n_tris = all_counts[2 * (size_t)m + 1];
+        if (slot[m] != 0xFFFFFFFFu) {
+            memcpy(h.aabb_lo, rec[slot[m]].lo, 12);
+            memcpy(h.aabb_hi, rec[slot[m]].hi, 12);
+            h.has_vertices = h.dev.n_verts > 0;
+        }
+    }
+    ctx->meshes_valid = true;
+    return RXR_OK;
+}
+
+int rxr_resize_meshes(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t n, const uint32_t *counts, const float *vertices, const float *uvs,
+                      const uint32_t *indices, const float *normals, uint32_t vertex_stride, uint32_t triangle_stride) {
+    if (!ctx) return RXR_ERR_INVALID;
+    if (ctx->group) return rxr_group_resize_meshes(ctx, mesh_indices, n, counts, vertices, uvs, indices, normals, vertex_stride, triangle_stride);
+    if (!n) return RXR_OK;
+    size_t bytes[4];
+    int rc = update_check(ctx, "rxr_resize_meshes", mesh_indices, n, vertex_stride, triangle_stride, bytes, false);
+    if (rc != RXR_OK) return rc;
+    const void *arrays[4] = {counts, vertices, indices, normals};
+    for (int i = 0; i < 4; ++i)
+        if (bytes[i] && !arrays[i]) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_resize_meshes: NULL array");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if ((rc = rxr_quiesce(ctx)) != RXR_OK) return rc;   // renders and picks read the pools
+    QueryLane &lane = ctx->lane[Q_MESH_UPDATE];
+    QueryIO io{ctx, lane};
+    const size_t uv_bytes = uvs ? bytes[1] / 2 : 0;
+    const unsigned i_c = io.in(counts, bytes[0]), i_v = io.in(bytes[1] ? vertices : nullptr, bytes[1]), i_u = io.in(uv_bytes ? uvs : nullptr, uv_bytes),
+                   i_i = io.in(bytes[2] ? indices : nullptr, bytes[2]), i_n = io.in(bytes[3] ? normals : nullptr, bytes[3]);
+    if ((rc = io.upload()) != RXR_OK) return rc;
+    rc = resize_run(ctx, "rxr_resize_meshes", mesh_indices, n, io.dev<uint32_t>(i_c), io.dev<float>(i_v), io.dev<float>(i_u), io.dev<uint32_t>(i_i), io.dev<float>(i_n),
+                    vertex_stride, triangle_stride, ctx->stream);
+    if (rc != RXR_OK) (void)hipStreamSynchronize(ctx->stream);   // (the caller's arrays have been read before the call returns)
+    return rc;
+}
+
+int rxr_resize_meshes_to(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t n, const uint32_t *dev_counts, const float *dev_vertices, const float *dev_uvs,
+                         const uint32_t *dev_indices, const float *dev_normals, uint32_t vertex_stride, uint32_t triangle_stride, void *hip_stream) {
+    if (!ctx) return RXR_ERR_INVALID;
+    if (ctx->group) return rxr_fail(ctx, RXR_ERR_UNSUPPORTED, "rxr_resize_meshes_to on a multi-device context: device pointers and streams belong to ONE device (use rxr_member)");
+    if (!n) return RXR_OK;
+    size_t bytes[4];
+    int rc = update_check(ctx, "rxr_resize_meshes_to", mesh_indices, n, vertex_stride, triangle_stride, bytes, false);
+    if (rc != RXR_OK) return rc;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const struct {
+        const void *p;
+        const char *name;
+        size_t bytes;
+        bool optional;
+    } arrays[5] = {{dev_counts, "dev_counts", bytes[0], false}, {dev_vertices, "dev_vertices", bytes[1], false}, {dev_uvs, "dev_uvs", bytes[1] / 2, true},
+                   {dev_indices, "dev_indices", bytes[2], false}, {dev_normals, "dev_normals", bytes[3], false}};
+    for (int i = 0; i < 5; ++i) {
+        if (!arrays[i].bytes || (arrays[i].optional && !arrays[i].p)) continue;   // (strides of 0: the array is not looked at; no uvs: [0, 0])
+        if (!arrays[i].p || ((uintptr_t)arrays[i].p & 3u))
+            return rxr_fail(ctx, RXR_ERR_INVALID, std::string("rxr_resize_meshes_to: ") + arrays[i].name + " must be 4-byte aligned device memory");
+        if (!rxr_on_device(ctx, arrays[i].p, arrays[i].bytes))
+            return rxr_fail(ctx, RXR_ERR_INVALID, std::string("rxr_resize_meshes_to: ") + arrays[i].name + " is not device memory of the context's device (or is too small)");
+    }
+    if ((rc = rxr_quiesce(ctx)) != RXR_OK) return rc;   // renders and picks read the pools
+    return resize_run(ctx, "rxr_resize_meshes_to", mesh_indices, n, dev_counts, dev_vertices, bytes[1] ? dev_uvs : nullptr, dev_indices, dev_normals, vertex_stride,
+                      triangle_stride, hip_stream ? (hipStream_t)hip_stream : ctx->stream);
+}
+
+// tools/mesh_resize_bench.py: the stream time of the last accepted resize's k_mesh_repack, the time of one device-to-device copy of
+// the bytes it wrote (old blob -> spare blob, after a warm-up copy: the yardstick of a memory-bound kernel) and that byte count
+int rxr_debug_resize_repack(rxr_ctx *ctx, float *us2, uint64_t *bytes) {
+    if (!ctx || ctx->group || !us2 || !bytes) return RXR_ERR_INVALID;
+    if (!ctx->ev_repack[1] || !ctx->meshes_valid) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_debug_resize_repack: no accepted resize yet");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = rxr_quiesce(ctx);
+    if (rc != RXR_OK) return rc;
+    float ms = 0.0f;
+    HIPCHK(ctx, hipEventElapsedTime(&ms, ctx->ev_repack[0], ctx->ev_repack[1]));
+    us2[0] = ms * 1000.0f;
+    const size_t n = std::min<size_t>({(size_t)ctx->repack_bytes, ctx->d_obj.cap, ctx->d_obj_alt.cap});
+    *bytes = n;
+    us2[1] = 0.0f;
+    if (!n) return RXR_OK;
+    hipEvent_t e0, e1;   // (the repack's own pair keeps its times)
+    HIPCHK(ctx, hipEventCreate(&e0));
+    HIPCHK(ctx, hipEventCreate(&e1));
+    hipError_t e = hipMemcpyAsync(ctx->d_obj_alt.p, ctx->d_obj.p, n, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(e0, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_obj_alt.p, ctx->d_obj.p, n, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    HIPCHK(ctx, e);
+    us2[1] = ms * 1000.0f;
+    return RXR_OK;
+}
+
+// tests / tools: the object-space pools as the context holds them, whole: totals[2] = vertices, triangles; the arrays (each may be
+// NULL) take min(total, capacity) items of vertices [4], uvs [2], indices [3], normals [3]
+int rxr_debug_object_pools(rxr_ctx *ctx, uint64_t *totals, float *vertices, float *uvs, uint32_t *indices, float *normals, uint64_t capacity_vertices,
+                           uint64_t capacity_triangles) {
+    if (!ctx || ctx->group || !totals) return RXR_ERR_INVALID;
+    if (!ctx->meshes_valid) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_debug_object_pools: no valid registration");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = rxr_quiesce(ctx);
+    if (rc != RXR_OK) return rc;
+    const ProjectParams &PP = ctx->PP;
+    totals[0] = ctx->meshes.empty() ? 0 : PP.n_verts_in;
+    totals[1] = ctx->meshes.empty() ? 0 : PP.n_tris_in;
+    const size_t nv = (size_t)std::min<uint64_t>(totals[0], capacity_vertices), nt = (size_t)std::min<uint64_t>(totals[1], capacity_triangles);
+    if (vertices && nv) HIPCHK(ctx, hipMemcpy(vertices, PP.obj_verts, nv * 16, hipMemcpyDeviceToHost));
+    if (uvs && nv) HIPCHK(ctx, hipMemcpy(uvs, PP.obj_uvs, nv * 8, hipMemcpyDeviceToHost));
+    if (normals && nv) HIPCHK(ctx, hipMemcpy(normals, PP.obj_normals, nv * 12, hipMemcpyDeviceToHost));
+    if (indices && nt) HIPCHK(ctx, hipMemcpy(indices, PP.obj_idx, nt * 12, hipMemcpyDeviceToHost));
+    return RXR_OK;
+}
+
+// tests: the layout arithmetic of rxr_resize_meshes (rxr_mesh_resize.h) as the library compiled it
+uint32_t rxr_debug_resize_bases(const uint32_t *counts, uint32_t n, uint32_t *bases, uint64_t *totals) {
+    return (uint32_t)rxr_resize_bases(counts, n, bases, totals);
 }
 
 int rxr_mesh_bounds(rxr_ctx *ctx, uint32_t mesh_index, float lo[3], float hi[3]) {

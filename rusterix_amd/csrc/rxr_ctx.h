@@ -240,7 +240,10 @@ struct rxr_ctx {
     size_t mesh_verts_out = 0, mesh_tris_out = 0;
     size_t pp_off_meshes = 0;  // byte offset of the per-frame DevMesh array inside d_proj_misc
     size_t obj_off_meshes = 0; // byte offset of the registration's static DevMesh array inside d_obj (PP.meshes moves to the per-frame one)
-    DevBuf d_mesh_check;       // rxr_update_meshes: one MeshCheckRec per named mesh
+    DevBuf d_mesh_check;       // rxr_update_meshes: one MeshCheckRec per named mesh (rxr_resize_meshes: one MeshResizeRec)
+    hipEvent_t ev_repack[2] = {nullptr, nullptr};   // rxr_resize_meshes: around the last k_mesh_repack launch (rxr_debug_resize_repack; made by the first resize)
+    uint64_t repack_bytes = 0;                      // ... and the bytes it wrote (it reads as many)
+    DevBuf d_obj_alt;          // rxr_resize_meshes: the object blob that is not in use; the new pools are built in it from d_obj, then the two swap
     DevBuf d_mirror_scratch;   // rxr_mirror_scratch (rxr_api.hip): a host layer's device scratch
     bool frame_uses_meshes = false;
     // ... and its 2D half (rxr_set_meshes2d / rxr_set_projection2d)
@@ -493,6 +496,8 @@ int rxr_group_set_textures(rxr_ctx *ctx, const rxr_tile *static_tiles, uint32_t 
 int rxr_group_set_meshes(rxr_ctx *ctx, const rxr_mesh3d *meshes, uint32_t n_meshes);
 int rxr_group_update_meshes(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t n, const uint32_t *counts, const float *vertices, const uint32_t *indices,
                             const float *normals, uint32_t vertex_stride, uint32_t triangle_stride);
+int rxr_group_resize_meshes(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t n, const uint32_t *counts, const float *vertices, const float *uvs,
+                            const uint32_t *indices, const float *normals, uint32_t vertex_stride, uint32_t triangle_stride);
 int rxr_group_each(rxr_ctx *ctx, const std::function<int(rxr_ctx *)> &fn);   // fn(member) for every member, on the members' worker threads
 int rxr_group_set_meshes2d(rxr_ctx *ctx, const rxr_mesh2d *meshes, uint32_t n_meshes);
 int rxr_group_set_projection2d(rxr_ctx *ctx, const float *mat3);

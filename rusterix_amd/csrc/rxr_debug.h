@@ -42,6 +42,20 @@ int rxr_debug_download_bytes(rxr_ctx *ctx, uint64_t *out2);
  * frame appends" (proj_init_item clears it, clip_count_item raises it: 0 lets k_proj_scan and k_clip_emit leave at once) */
 int rxr_debug_projection_ticket(rxr_ctx *ctx, uint32_t *out2);
 
+/* tests (host only, no device): the layout arithmetic of rxr_resize_meshes (rxr_mesh_resize.h, rxr_resize_bases) as the library
+ * compiled it, over counts [n][2]: bases [n][4] = vin, tin, vout, tout base of every mesh, totals [4]; returns n, or the index of the
+ * first mesh with which a total reaches 2^31 output slots */
+uint32_t rxr_debug_resize_bases(const uint32_t *counts, uint32_t n, uint32_t *bases, uint64_t *totals);
+
+/* tools/mesh_resize_bench.py: us2[0] = the stream time of the last accepted resize's k_mesh_repack, us2[1] = the time of one
+ * device-to-device copy of *bytes (what that kernel wrote) between the two object blobs, after a warm-up copy */
+int rxr_debug_resize_repack(rxr_ctx *ctx, float *us2, uint64_t *bytes);
+
+/* tests / tools: the object-space pools the context holds, whole: totals[2] = vertices, triangles; each array (may be NULL) takes
+ * min(total, capacity) items of vertices [4], uvs [2], indices [3], normals [3] */
+int rxr_debug_object_pools(rxr_ctx *ctx, uint64_t *totals, float *vertices, float *uvs, uint32_t *indices, float *normals, uint64_t capacity_vertices,
+                           uint64_t capacity_triangles);
+
 /* tests: how the resident frame's 3D arrays arrived -- 0 plain rxr_upload_frame, 1 streamed and copied, 2 streamed out of page-locked
  * memory */
 int rxr_debug_stream_info(rxr_ctx *ctx);

@@ -365,6 +365,14 @@ int rxr_group_update_meshes(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t
     });
 }
 
+int rxr_group_resize_meshes(rxr_ctx *ctx, const uint32_t *mesh_indices, uint32_t n, const uint32_t *counts, const float *vertices, const float *uvs,
+                            const uint32_t *indices, const float *normals, uint32_t vertex_stride, uint32_t triangle_stride) {
+    // (every member holds the same registration, so all accept or all refuse)
+    return run_all(ctx, [&](uint32_t i) {
+        return rxr_resize_meshes(ctx->group->members[i], mesh_indices, n, counts, vertices, uvs, indices, normals, vertex_stride, triangle_stride);
+    });
+}
+
 // fn(member) for every member, each on its own worker thread: for entry points that live in other files (rxr_chunk_tex.hip)
 int rxr_group_each(rxr_ctx *ctx, const std::function<int(rxr_ctx *)> &fn) {
     return run_all(ctx, [&](uint32_t i) { return fn(ctx->group->members[i]); });

@@ -129,3 +129,43 @@ struct MeshUpdateArgs {
     uint32_t *idx;
     uint32_t mesh[RXR_MESH_UPDATE_LAUNCH];   // the named meshes, rxr_set_meshes order
 };
+
+// ---- rxr_resize_meshes (include/rxr.h): some registered meshes' geometry replaced when their counts change ------------------------------
+// what k_mesh_resize_check finds out about one named mesh: MeshCheckRec plus the two counts (the host reads the caller's counts nowhere else)
+enum : uint32_t { MESH_RSZ_BAD_VSTRIDE = 8u, MESH_RSZ_BAD_TSTRIDE = 16u };   // next to MESH_UPD_BAD_INDEX
+struct MeshResizeRec {
+    uint32_t status;         // MESH_RSZ_* | MESH_UPD_BAD_INDEX (0: accepted)
+    uint32_t bad_triangle;   // MESH_UPD_BAD_INDEX: the first triangle with a vertex index >= the new vertex count
+    float lo[3], hi[3];      // the object-space box of the new vertices: +-inf without a non-NaN coordinate
+    uint32_t n_verts, n_tris;
+};  // 40 B
+struct MeshResizeCheckArgs {
+    const uint32_t *counts;      // [n][2]
+    const float *vertices;       // [n][vstride][4]
+    const uint32_t *indices;     // [n][tstride][3], mesh-local
+    uint32_t vstride, tstride;
+    MeshResizeRec *rec;          // [n]
+};
+// k_mesh_repack: the NEW object pools from the old ones and the caller's arrays.  source [n_meshes][2]: for a named mesh
+// (RXR_MESH_RESIZE_NAMED | its slot k in the caller's arrays, unused), for any other (its OLD vin_base, its OLD tin_base) -- bases are
+// below 2^31 (rxr_set_meshes' limit), so the top bit is free.  The table lives in device memory: no cut at a number of named meshes.
+#define RXR_MESH_RESIZE_NAMED 0x80000000u
+struct MeshRepackArgs {
+    uint32_t n_meshes, n_verts, n_tris;      // of the NEW registration
+    const DevMesh *meshes;                   // the new static table (bases and counts)
+    const uint32_t *vin_prefix, *tin_prefix; // the new prefix arrays, n_meshes + 1
+    const uint32_t *source;
+    // the old pools
+    const uint4 *old_verts;
+    const uint32_t *old_idx;
+    const uint2 *old_uvs;
+    const uint32_t *old_normals;
+    // the caller's arrays (words: a NaN keeps its payload), 4-byte aligned; uvs may be null: [0, 0]
+    const uint32_t *vertices, *uvs, *indices, *normals;
+    uint32_t vstride, tstride;
+    // the new pools
+    uint4 *new_verts;
+    uint32_t *new_idx;
+    uint2 *new_uvs;
+    uint32_t *new_normals;
+};

@@ -902,3 +902,147 @@ extern "C" void rxr_launch_project2d(const Project2DParams *P, hipStream_t s) {
     if (P->n_verts) RXR_LAUNCH(k_proj2d_bbox, dim3((P->n_verts + 255u) / 256u), dim3(256), s, *P);
     if (P->n_prims) RXR_LAUNCH(k_proj2d_prims, dim3((P->n_prims + 255u) / 256u), dim3(256), s, *P);
 }
+
+// =================================================================================================
+// rxr_resize_meshes (include/rxr.h): registered meshes whose counts change.  (At the end of the file: the kernels above keep their
+// places in the listing.)  k_mesh_resize_check is k_mesh_check without a registration to compare with; the host lays the new
+// registration out from its records (rxr_mesh_resize.h) and k_mesh_repack builds the new object pools next to the old ones.
+// =================================================================================================
+namespace {
+struct alignas(4) Words3 {
+    uint32_t x, y, z;
+};
+struct alignas(4) Words2 {
+    uint32_t x, y;
+};
+}  // namespace
+
+// One workgroup per named mesh: counts against strides, every index against the NEW vertex count, the object-space box
+// (batch3d.rs:494-507).  Reads no slot past the mesh's counts, nothing at all of a mesh whose counts exceed the strides, and writes
+// nothing but its record.
+extern "C" __global__ void __launch_bounds__(256) k_mesh_resize_check(MeshResizeCheckArgs A) {
+    __shared__ uint32_t s_part[4][8];   // per wave: first bad triangle, lo[3], hi[3]
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, b = blockIdx.x;
+    const uint32_t nv = A.counts[2 * (size_t)b], nt = A.counts[2 * (size_t)b + 1];
+    const uint32_t status = (nv > A.vstride ? MESH_RSZ_BAD_VSTRIDE : 0u) | (nt > A.tstride ? MESH_RSZ_BAD_TSTRIDE : 0u);
+    // (workgroup-uniform.  3 * nt in 64 bits: the count is the caller's, bounded by the stride alone)
+    const size_t n_words = status ? 0u : 3u * (size_t)nt;
+    const uint32_t n_box = status ? 0u : nv;
+
+    const uint32_t *ix = A.indices + (size_t)b * A.tstride * 3;
+    uint32_t bad = 0xFFFFFFFFu;
+    for (size_t w = tid; w < n_words; w += 256u)   // (consecutive lanes, consecutive words)
+        if (ix[w] >= nv) bad = min(bad, (uint32_t)(w / 3u));
+
+    const float *vx = A.vertices + (size_t)b * A.vstride * 4;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (uint32_t v = tid; v < n_box; v += 256u) {
+        Words4 p;
+        __builtin_memcpy(&p, vx + 4 * (size_t)v, sizeof(p));
+        const float c[3] = {__uint_as_float(p.x), __uint_as_float(p.y), __uint_as_float(p.z)};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {   // f32::min / f32::max: a NaN operand is ignored
+            lo[k] = fminf(lo[k], c[k]);
+            hi[k] = fmaxf(hi[k], c[k]);
+        }
+    }
+    // (every lane is back here: the loops above are the only divergence)
+    const uint32_t wbad = wave_min_u32(bad);
+    float wlo[3], whi[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        wlo[k] = wave_min_f32(lo[k]);
+        whi[k] = wave_max_f32(hi[k]);
+    }
+    if (lane == 0u) {
+        s_part[wave][0] = wbad;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            s_part[wave][1 + k] = __float_as_uint(wlo[k]);
+            s_part[wave][4 + k] = __float_as_uint(whi[k]);
+        }
+    }
+    __syncthreads();
+    if (tid == 0u) {
+        MeshResizeRec r;
+        uint32_t first = 0xFFFFFFFFu;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            r.lo[k] = INFINITY;
+            r.hi[k] = -INFINITY;
+        }
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            first = min(first, s_part[w][0]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                r.lo[k] = fminf(r.lo[k], __uint_as_float(s_part[w][1 + k]));
+                r.hi[k] = fmaxf(r.hi[k], __uint_as_float(s_part[w][4 + k]));
+            }
+        }
+        r.status = status | (first != 0xFFFFFFFFu ? MESH_UPD_BAD_INDEX : 0u);
+        r.bad_triangle = first != 0xFFFFFFFFu ? first : 0u;
+        r.n_verts = nv;
+        r.n_tris = nt;
+        A.rec[b] = r;
+    }
+}
+
+// The new object pools.  Item i is vertex i of the new pools (position, uv, normal) AND triangle i (three index words); consecutive
+// lanes take consecutive items, so a wave's accesses to every pool are one contiguous run (16-byte accesses for the positions on the
+// pool side, words at the caller's 4-byte alignment), and its 64 items nearly always belong to one mesh (find_mesh_wave).  A
+// memory-bound copy: whole waves stride over the items with a capped grid; no LDS, no atomics.
+extern "C" __global__ void __launch_bounds__(256) k_mesh_repack(MeshRepackArgs A) {
+    const uint32_t n_items = max(A.n_verts, A.n_tris);
+    const uint32_t stride = gridDim.x * 256u;
+    // (whole waves: i0 is a multiple of 64, and the lanes without an item are the LAST ones of the pools' last wave)
+    for (uint32_t i0 = blockIdx.x * 256u + (threadIdx.x & ~63u); i0 < n_items; i0 += stride) {   // (no wrap: stride <= 2^19, n_items < 2^31)
+        const uint32_t i = i0 + (threadIdx.x & 63u);
+        if (i0 < A.n_verts && i < A.n_verts) {
+            const uint32_t m = find_mesh_wave(A.vin_prefix, A.n_meshes, i);
+            const uint32_t local = i - A.meshes[m].vin_base;
+            const uint32_t s0 = A.source[2 * (size_t)m];
+            uint4 p;
+            uint2 uv;
+            Words3 nr;
+            if (s0 & RXR_MESH_RESIZE_NAMED) {
+                const size_t at = (size_t)(s0 & ~RXR_MESH_RESIZE_NAMED) * A.vstride + local;
+                Words4 pw;
+                __builtin_memcpy(&pw, A.vertices + 4 * at, sizeof(pw));
+                p = make_uint4(pw.x, pw.y, pw.z, pw.w);
+                Words2 uw = {0u, 0u};
+                if (A.uvs) __builtin_memcpy(&uw, A.uvs + 2 * at, sizeof(uw));
+                uv = make_uint2(uw.x, uw.y);
+                __builtin_memcpy(&nr, A.normals + 3 * at, sizeof(nr));
+            } else {
+                const size_t at = (size_t)s0 + local;
+                p = A.old_verts[at];
+                uv = A.old_uvs[at];
+                __builtin_memcpy(&nr, A.old_normals + 3 * at, sizeof(nr));
+            }
+            A.new_verts[i] = p;
+            A.new_uvs[i] = uv;
+            __builtin_memcpy(A.new_normals + 3 * (size_t)i, &nr, sizeof(nr));
+        }
+        if (i0 < A.n_tris && i < A.n_tris) {
+            const uint32_t m = find_mesh_wave(A.tin_prefix, A.n_meshes, i);
+            const uint32_t local = i - A.meshes[m].tin_base;
+            const uint32_t s0 = A.source[2 * (size_t)m];
+            const uint32_t *src = (s0 & RXR_MESH_RESIZE_NAMED) ? A.indices + 3 * ((size_t)(s0 & ~RXR_MESH_RESIZE_NAMED) * A.tstride + local)
+                                                               : A.old_idx + 3 * ((size_t)A.source[2 * (size_t)m + 1] + local);
+            Words3 t;
+            __builtin_memcpy(&t, src, sizeof(t));
+            __builtin_memcpy(A.new_idx + 3 * (size_t)i, &t, sizeof(t));
+        }
+    }
+}
+
+extern "C" void rxr_launch_mesh_resize_check(const MeshResizeCheckArgs *A, uint32_t n, hipStream_t s) {
+    if (n) RXR_LAUNCH(k_mesh_resize_check, dim3(n), dim3(256), s, *A);
+}
+extern "C" void rxr_launch_mesh_repack(const MeshRepackArgs *A, hipStream_t s) {
+    const uint32_t n = A->n_verts > A->n_tris ? A->n_verts : A->n_tris;
+    if (!n) return;
+    const uint32_t blocks = (n + 255u) / 256u;
+    RXR_LAUNCH(k_mesh_repack, dim3(blocks < 2048u ? blocks : 2048u), dim3(256), s, *A);
+}

@@ -224,6 +224,28 @@ pub fn update_meshes(mesh_indices: &[u32], counts: &[u32], vertices: &[f32], ind
     }
 }
 
+// ---- registered meshes whose counts change (include/rxr.h rxr_resize_meshes) ------------------------------------
+/// Replaces the geometry of already registered meshes when their COUNTS CHANGE -- a terrain cell added or removed, an excluded sector
+/// moved -- instead of registering the whole scene again: `update_meshes`' slices plus `uvs` [n][vertex_stride][2] (`None`: every uv
+/// of the named meshes is [0, 0]).  True: the device is in the state a registration of the whole scene with the new geometry would
+/// have left (upload the next frame as usual; the pick records and the trace scene are built again by their next calls; the shim's
+/// mesh fingerprint is left alone, as with `update_meshes`).  False: no device context, slices too short, or the library refused (a
+/// count above its stride, an index out of range, the 2^31 output-slot limit): nothing was changed on the device.
+#[allow(clippy::too_many_arguments)]
+pub fn resize_meshes(mesh_indices: &[u32], counts: &[u32], vertices: &[f32], uvs: Option<&[f32]>, indices: &[u32], normals: &[f32], vertex_stride: u32,
+                     triangle_stride: u32) -> bool {
+    let guard = STATE.lock().unwrap();
+    let Some(ctx) = guard.as_ref().and_then(|st| st.ctx.as_ref()) else { return false };
+    let (n, vs, ts) = (mesh_indices.len(), vertex_stride as usize, triangle_stride as usize);
+    if counts.len() < 2 * n || vertices.len() < n * vs * 4 || indices.len() < n * ts * 3 || normals.len() < n * vs * 3 || uvs.map_or(false, |u| u.len() < n * vs * 2) {
+        return false;
+    }
+    unsafe {
+        rxr_resize_meshes(ctx.0, mesh_indices.as_ptr(), n as u32, counts.as_ptr(), vertices.as_ptr(), uvs.map_or(std::ptr::null(), |u| u.as_ptr()), indices.as_ptr(),
+                          normals.as_ptr(), vertex_stride, triangle_stride) == RXR_OK
+    }
+}
+
 // ---- vertex normals (include/rxr.h rxr_vertex_normals) ------------------------------------------------------------
 /// `Batch3D::compute_vertex_normals` for n meshes in one device call, bit for bit the reference's sums (ascending triangle index, from
 /// +0.0).  The slices are in the layout `rxr_terrain_meshes` writes and `update_meshes` reads: `counts` [n][2] (vertices, triangles),
