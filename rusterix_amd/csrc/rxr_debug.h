@@ -87,6 +87,30 @@ const char *rxr_debug_jit_info(rxr_ctx *ctx);
  * Returns RXR_OK, the validation status, or RXR_ERR_UNSUPPORTED with the reason in `message` when the set is not covered. */
 int rxr_debug_jit_generate(const rxr_shader_set *set, int compile, char *source, uint32_t source_capacity, char *message, uint32_t message_capacity);
 
+/* ---- rxr_selftest.hip ---- */
+
+/* tests: ONE public helper of rxr_exact_math.h on n operand tuples of the caller's choosing (host, n x 4 floats), every result handed
+ * back as raw bits (host, n x 4 floats; unused operand and result slots are zero).  Tuple i is evaluated by lane i % 64 of wave i / 64
+ * in workgroups of 256: the helpers vote per wave, so the caller decides which operands share a vote; the last wave may be partial.
+ * Kinds, operands -> results:
+ *    0 div1_known          (n, d)           -> q, with ok = in_window(n) && in_window(d)
+ *    1 div1_static         (n, d)           -> q, with ok = true: only operands a call site claims statically
+ *    2 div2                (n0, n1, d)      -> q0, q1
+ *    3 div2_pre            (n0, n1, d)      -> q0, q1, with r = denominator_part(d) as the row-mode kernels compute it
+ *    4 div3                (n0, n1, n2, d)  -> q0, q1, q2
+ *    5 div3_self           (n0, n1, n2, d)  -> q0, q1, q2, qd
+ *    6 normalize3          (x, y, z)        -> ox, oy, oz, magnitude
+ *    7 normalize3_z        (x, y, z)        -> ox, oy, oz
+ *    8 normalize3_relaxed  (x, y, z)        -> ox, oy, oz, magnitude
+ *    9 sqrt_exact          (x)              -> root
+ *   10 pow_exp2_log2       (x, k)           -> power
+ *   11 sat_u32             (x)              -> the integer, as bits
+ *   12 wave_max_nonneg     (v)              -> the wave's maximum, in every lane
+ *   13 wave_inclusive_add  (integer bits)   -> the prefix sum, as bits
+ * Stages through device memory on the context's stream and blocks.  RXR_ERR_INVALID (results untouched): a NULL pointer, n == 0, an
+ * unknown kind, n % 64 != 0 for kinds 12 and 13 (every lane must be active).  A multi-device handle answers as member 0. */
+int rxr_debug_exact_math(rxr_ctx *ctx, uint32_t kind, const float *operands, uint32_t n, float *results);
+
 /* ---- rxr_kernels.hip ---- */
 
 /* ONLY in a library built with -DRXR_PHASE_TIMING=1 (no ordinary build defines it, so the symbol is normally absent): the sums of

@@ -21,7 +21,10 @@
 // compiler's own expansion otherwise (wave-uniform branch).  In the window the short sequence IS the
 // compiler's sequence with the no-op instructions removed, so the result is the same float; outside
 // the window it is the compiler's code.  tests/test_gpu_exact_math.py checks bit equality over
-// billions of operand pairs, including the window edges and every special value.
+// billions of operand pairs, including the window edges and every special value -- against the compiler's own `/`, sqrtf, exp2f and
+// log2f in the same translation unit.  tests/test_gpu_exact_math_ref.py holds every helper to IEEE-754 as the HOST computes it
+// (rxr_debug_exact_math: operands placed by the host, results float by float, numpy's float32 operators as the reference), which
+// also notices when a build flag moves both the sequence and the compiler's expansion (flushed denormals, for one).
 #pragma once
 #ifndef RXR_JIT
 #include <hip/hip_runtime.h>
@@ -176,9 +179,13 @@ __device__ __forceinline__ void normalize3(float x, float y, float z, float &ox,
 }
 
 // RELAXED form for the light loop of lit 3D fragments (north_star: "within 1 per channel for float-interpolated 3D/lit paths"):
-// v * rsq(|v|^2) and |v|^2 * rsq(|v|^2) -- every component and the magnitude within 2 ulp of the correctly rounded values, six
-// instructions instead of twenty-five.  The same window vote as the exact form: zero, denormal, infinite and NaN magnitudes take
-// the exact path, so the special cases of both forms are the same values.
+// v * rsq(|v|^2) and |v|^2 * rsq(|v|^2), six instructions instead of twenty-five.  Against the exact form (normalize3) on the
+// operand sets of tests/exact_math_ref.py an MI355X returns every component and the magnitude within 2 ulp (measured maxima: 2.0 and
+// 2.0; profiles/exact_math/README.md).  ASSERTED are 4 ulp per component and 3 for the magnitude (tests/test_gpu_exact_math_ref.py):
+// what x * inv, m2 * inv give when inv is within 1 ulp of the correctly rounded 1 / sqrt(m2), the ISA manual's figure for v_rsq_f32.
+// A correctly rounded inv would give 2 and 1; the magnitude's measured 2 shows that v_rsq_f32 is not that.  The same window vote as
+// the exact form, on the squared magnitude alone: zero, denormal, infinite and NaN magnitudes take the exact path, so the special
+// cases of both forms are the same values.
 __device__ __forceinline__ void normalize3_relaxed(float x, float y, float z, float &ox, float &oy, float &oz, float &mag) {
     float m2 = (x * x + y * y) + z * z;
     if (wave_all(sq_in_window(m2))) {

@@ -152,7 +152,8 @@ __device__ __forceinline__ f3 norm3_fast(f3 a) {
     float m;
     return norm3_fast(a, m);
 }
-// relaxed-light mode (RXR_LIGHT_MATH, shade3d_lights): within 2 ulp per component
+// relaxed-light mode (RXR_LIGHT_MATH, shade3d_lights): measured 2 ulp per component and for the magnitude against the exact form,
+// asserted within 4 and 3 (tests/test_gpu_exact_math_ref.py, profiles/exact_math/README.md)
 __device__ __forceinline__ f3 norm3_relaxed(f3 a, float &mag) {
     f3 o;
     rxm::normalize3_relaxed(a.x, a.y, a.z, o.x, o.y, o.z, mag);

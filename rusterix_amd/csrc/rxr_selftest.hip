@@ -1,9 +1,15 @@
 // rxr_selftest.hip -- on-device self-test of rxr_exact_math.h: every short sequence against the
 // compiler's expansion of the plain operator, bit for bit, over seeded operand tuples.
 // Diagnostics only (rxr_selftest_math in include/rxr.h); not on the frame path.
+// Second half: rxr_debug_exact_math (rxr_debug.h) runs ONE helper on operand tuples the host chose and hands every result back as
+// raw bits, so that a test can hold the header to a reference that owes nothing to this compiler (tests/exact_math_ref.py).
 #include <hip/hip_runtime.h>
 
+#include <string>
+
 #include "../../include/rxr.h"
+#include "rxr_ctx.h"
+#include "rxr_debug.h"
 #include "rxr_exact_math.h"
 
 namespace {
@@ -192,8 +198,128 @@ __global__ void __launch_bounds__(256) k_selftest_math(uint64_t seed, uint32_t i
 
 }  // namespace
 
-// runs `blocks` x 256 threads x `iters` tuples per operation kind; mismatch must point at 8 zeroed
-// device words
+// runs `blocks` x 256 threads x `iters` tuples per operation kind; mismatch must point at RXR_MATH_KINDS
+// zeroed device words
 extern "C" void rxr_launch_selftest_math(uint64_t seed, uint32_t blocks, uint32_t iters, unsigned long long *mismatch, hipStream_t s) {
     hipLaunchKernelGGL(k_selftest_math, dim3(blocks), dim3(256), 0, s, seed, iters, mismatch);
+}
+
+// ---- the probe: one public helper of rxr_exact_math.h per kind, on the host's operands --------------------------------------------
+
+namespace {
+
+// (the order of rxr_debug.h's table)
+enum ProbeKind : uint32_t {
+    PK_DIV1_KNOWN,
+    PK_DIV1_STATIC,
+    PK_DIV2,
+    PK_DIV2_PRE,
+    PK_DIV3,
+    PK_DIV3_SELF,
+    PK_NORMALIZE3,
+    PK_NORMALIZE3_Z,
+    PK_NORMALIZE3_RELAXED,
+    PK_SQRT_EXACT,
+    PK_POW_EXP2_LOG2,
+    PK_SAT_U32,
+    PK_WAVE_MAX_NONNEG,
+    PK_WAVE_INCLUSIVE_ADD,
+    PK_COUNT
+};
+
+// Tuple i is lane i % 64 of wave i / 64 (256 threads: four waves of consecutive tuples), so the host decides which operands share a
+// helper's vote.  The lanes behind the last tuple leave before the helper: a partial last wave votes among its tuples only.  Operands
+// and results cross as bits: no conversion, no canonicalisation of a NaN on the way.
+template <uint32_t KIND>
+__global__ void __launch_bounds__(256) k_exact_math_probe(const uint4 *__restrict__ operands, uint32_t n, uint4 *__restrict__ results) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint4 in = operands[i];
+    const float a = __uint_as_float(in.x), b = __uint_as_float(in.y), c = __uint_as_float(in.z), d = __uint_as_float(in.w);
+    float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f, r3 = 0.0f;
+    uint4 out = make_uint4(0u, 0u, 0u, 0u);
+    bool as_float = true;
+    if constexpr (KIND == PK_DIV1_KNOWN) {
+        r0 = rxm::div1_known(a, b, rxm::in_window(a) && rxm::in_window(b));
+    } else if constexpr (KIND == PK_DIV1_STATIC) {
+        r0 = rxm::div1_known(a, b, true);
+    } else if constexpr (KIND == PK_DIV2) {
+        rxm::div2(a, b, c, r0, r1);
+    } else if constexpr (KIND == PK_DIV2_PRE) {
+        rxm::div2_pre(a, b, c, rxm::denominator_part(c), r0, r1);
+    } else if constexpr (KIND == PK_DIV3) {
+        rxm::div3(a, b, c, d, r0, r1, r2);
+    } else if constexpr (KIND == PK_DIV3_SELF) {
+        rxm::div3_self(a, b, c, d, r0, r1, r2, r3);
+    } else if constexpr (KIND == PK_NORMALIZE3) {
+        rxm::normalize3(a, b, c, r0, r1, r2, r3);
+    } else if constexpr (KIND == PK_NORMALIZE3_Z) {
+        rxm::normalize3_z(a, b, c, r0, r1, r2);
+    } else if constexpr (KIND == PK_NORMALIZE3_RELAXED) {
+        rxm::normalize3_relaxed(a, b, c, r0, r1, r2, r3);
+    } else if constexpr (KIND == PK_SQRT_EXACT) {
+        r0 = rxm::sqrt_exact(a);
+    } else if constexpr (KIND == PK_POW_EXP2_LOG2) {
+        r0 = rxm::pow_exp2_log2(a, b);
+    } else if constexpr (KIND == PK_SAT_U32) {
+        out.x = rxm::sat_u32(a);
+        as_float = false;
+    } else if constexpr (KIND == PK_WAVE_MAX_NONNEG) {
+        r0 = rxm::wave_max_nonneg(a);   // (n is a multiple of 64: every lane of the wave is here)
+    } else {
+        out.x = rxm::wave_inclusive_add(in.x);
+        as_float = false;
+    }
+    if (as_float) out = make_uint4(__float_as_uint(r0), __float_as_uint(r1), __float_as_uint(r2), __float_as_uint(r3));
+    results[i] = out;
+}
+
+template <uint32_t KIND>
+void launch_probe(const uint4 *operands, uint32_t n, uint4 *results, hipStream_t s) {
+    hipLaunchKernelGGL(k_exact_math_probe<KIND>, dim3((n + 255u) / 256u), dim3(256), 0, s, operands, n, results);
+}
+
+}  // namespace
+
+extern "C" int rxr_debug_exact_math(rxr_ctx *ctx, uint32_t kind, const float *operands, uint32_t n, float *results) {
+    if (!ctx || !operands || !results) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_debug_exact_math: NULL argument");
+    if (ctx->group) return rxr_debug_exact_math(rxr_member(ctx, 0), kind, operands, n, results);
+    if (n == 0) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_debug_exact_math: no tuples");
+    if (kind >= PK_COUNT) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_debug_exact_math: unknown kind " + std::to_string(kind));
+    if ((kind == PK_WAVE_MAX_NONNEG || kind == PK_WAVE_INCLUSIVE_ADD) && n % 64u != 0u)
+        return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_debug_exact_math: the wave reductions need every lane active (n must be a multiple of 64)");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)n * sizeof(uint4);
+    uint4 *d = nullptr;   // operands, then results
+    HIPCHK(ctx, hipMalloc(&d, 2 * bytes));
+    hipError_t e = hipMemcpyAsync(d, operands, bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        uint4 *out = d + n;
+        switch (kind) {
+#define RXR_PROBE_CASE(K) case K: launch_probe<K>(d, n, out, ctx->stream); break
+            RXR_PROBE_CASE(PK_DIV1_KNOWN);
+            RXR_PROBE_CASE(PK_DIV1_STATIC);
+            RXR_PROBE_CASE(PK_DIV2);
+            RXR_PROBE_CASE(PK_DIV2_PRE);
+            RXR_PROBE_CASE(PK_DIV3);
+            RXR_PROBE_CASE(PK_DIV3_SELF);
+            RXR_PROBE_CASE(PK_NORMALIZE3);
+            RXR_PROBE_CASE(PK_NORMALIZE3_Z);
+            RXR_PROBE_CASE(PK_NORMALIZE3_RELAXED);
+            RXR_PROBE_CASE(PK_SQRT_EXACT);
+            RXR_PROBE_CASE(PK_POW_EXP2_LOG2);
+            RXR_PROBE_CASE(PK_SAT_U32);
+            RXR_PROBE_CASE(PK_WAVE_MAX_NONNEG);
+            default: launch_probe<PK_WAVE_INCLUSIVE_ADD>(d, n, out, ctx->stream); break;
+#undef RXR_PROBE_CASE
+        }
+        e = hipGetLastError();
+        // (into the caller's array only once the launch stands: a refusal or a failure leaves `results` as it was)
+        if (e == hipSuccess) e = hipMemcpyAsync(results, out, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = es;
+    (void)hipFree(d);
+    if (e != hipSuccess) return rxr_fail(ctx, RXR_ERR_HIP, std::string("rxr_debug_exact_math: ") + hipGetErrorString(e));
+    return RXR_OK;
 }
