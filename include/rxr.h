@@ -755,6 +755,26 @@ int rxr_set_ray_accel(rxr_ctx *ctx, uint32_t mode);
 #define RXR_RAY_ACCEL_INFO_TESTS 8u       /* ray-triangle tests of the last call under RXR_RAY_ACCEL_COUNT                */
 #define RXR_RAY_ACCEL_INFO_WORDS 9u
 int rxr_ray_accel_info(rxr_ctx *ctx, uint64_t out[RXR_RAY_ACCEL_INFO_WORDS]);
+/* Opt-in, on top of rxr_set_ray_accel: batches of rays too small to fill the device with a thread per ray walk the same tree a WAVE
+ * per ray, 64 boxes or 64 triangles at a step (k_accel_by_wave, rusterix_amd/csrc/rxr_ray_accel.hip).  It applies
+ * only when the tree takes -- the accel mode is _ON or _COUNT and a tree stands; with the accel mode off the switch does nothing -- and
+ * then ahead of both existing routes, in rxr_intersect / _to and every round of rxr_trace / _to.  Every output word stays what the
+ * brute-force kernels write, under the margin of section 19 and no new one; _COUNT's tests cover this route too.  RXR_RAY_WAVE_OFF is
+ * the default: batches route exactly as without the call (64 rays or fewer never open a tree batch).  Any other mode: RXR_ERR_INVALID,
+ * nothing changed.  Multi-device handles: member 0. */
+#define RXR_RAY_WAVE_OFF 0u    /* default: routes exactly as today                                                     */
+#define RXR_RAY_WAVE_ON 1u     /* batches that rxr_ray_wave_takes() names go a wave per ray, when the tree takes       */
+#define RXR_RAY_WAVE_FORCE 2u  /* every batch of >= 1 ray goes that way when the tree takes (tests, sweeps)            */
+int rxr_set_ray_wave(rxr_ctx *ctx, uint32_t mode);
+/* the rule of RXR_RAY_WAVE_ON for a batch of n_rays against a scene of n_triangles: 1 or 0.  No context, no device: a closed form over
+ * the constants of rusterix_amd/csrc/rxr_isect.h, which profiles/ray_wave/README.md derives from its table. */
+int rxr_ray_wave_takes(uint32_t n_rays, uint32_t n_triangles);
+/* not blocking; out[..]: */
+#define RXR_RAY_WAVE_INFO_MODE 0u     /* RXR_RAY_WAVE_*                                                                */
+#define RXR_RAY_WAVE_INFO_BATCHES 1u  /* batches of rays that went a wave per ray since rxr_create                     */
+#define RXR_RAY_WAVE_INFO_RAYS 2u     /* ... and their rays (RXR_RAY_ACCEL_INFO_BATCHES counts neither)                */
+#define RXR_RAY_WAVE_INFO_WORDS 3u
+int rxr_ray_wave_info(rxr_ctx *ctx, uint64_t out[RXR_RAY_WAVE_INFO_WORDS]);
 /* Opt-in: what rxr_update_meshes / _to leaves for the next rxr_intersect / rxr_trace.  RXR_RAY_REFRESH_FULL, the
  * default: the pick records and the tree are invalid, the next query builds all of them again.  RXR_RAY_REFRESH_RANGED: a successful
  * update adds the meshes it named to a set on the context (a union; a refused update adds nothing, rxr_set_meshes empties it), and the

@@ -21,6 +21,8 @@ from .abi import RXR_ERR_HIP, RXR_ERR_INVALID, RXR_ERR_NO_DEVICE, RXR_ERR_OOM, R
 SAMPLE_NEAREST, SAMPLE_LINEAR = 0, 1
 RAY_ACCEL_OFF, RAY_ACCEL_ON, RAY_ACCEL_COUNT = 0, 1, 2   # rxr_set_ray_accel's modes (include/rxr.h)
 RAY_ACCEL_INFO = ("mode", "valid", "triangles", "nodes", "levels", "wild", "builds", "batches", "tests")   # rxr_ray_accel_info's words
+RAY_WAVE_OFF, RAY_WAVE_ON, RAY_WAVE_FORCE = 0, 1, 2   # rxr_set_ray_wave's modes (include/rxr.h)
+RAY_WAVE_INFO = ("mode", "batches", "rays")   # rxr_ray_wave_info's words
 RAY_REFRESH_FULL, RAY_REFRESH_RANGED = 0, 1   # rxr_set_ray_refresh's modes (include/rxr.h)
 RAY_REFRESH_INFO = ("mode", "pending", "refreshes", "refits", "triangles", "leaves", "nodes", "route")   # rxr_ray_refresh_info's words
 REPEAT_CLAMP_XY, REPEAT_REPEAT_XY, REPEAT_REPEAT_X, REPEAT_REPEAT_Y = 0, 1, 2, 3
@@ -451,6 +453,11 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         L.scene_set_ray_accel = fn("scene_set_ray_accel", None, vp, u32)
         L.scene_ray_accel = fn("scene_ray_accel", u32, vp)
         L.scene_ray_accel_info = fn("scene_ray_accel_info", i32, vp, C.POINTER(C.c_uint64))
+    has_ray_wave = hasattr(lib, prefix + "scene_set_ray_wave")
+    if has_ray_wave:
+        L.scene_set_ray_wave = fn("scene_set_ray_wave", None, vp, u32)
+        L.scene_ray_wave = fn("scene_ray_wave", u32, vp)
+        L.scene_ray_wave_info = fn("scene_ray_wave_info", i32, vp, C.POINTER(C.c_uint64))
     has_ray_refresh = hasattr(lib, prefix + "scene_set_ray_refresh")
     if has_ray_refresh:
         L.scene_set_ray_refresh = fn("scene_set_ray_refresh", None, vp, u32)
@@ -1112,6 +1119,29 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
             if rc != 0:
                 raise RasterizeError(rc, last_error())
             return dict(zip(RAY_ACCEL_INFO, (int(x) for x in out)))
+
+        @property
+        def ray_wave(self):
+            """Scene::ray_wave (opt-in, on top of ray_accel; 0 off, the default; 1 the batches rxr_ray_wave_takes() names; 2 every
+            batch): with the tree on, such batches walk it a wave per ray (rxr_set_ray_wave, include/rxr.h).  The results are the
+            same words."""
+            return int(L.scene_ray_wave(self._h)) if has_ray_wave else 0
+
+        @ray_wave.setter
+        def ray_wave(self, mode):
+            if not has_ray_wave:
+                raise NotImplementedError(f"{name}: no wave-per-ray route in this library")
+            L.scene_set_ray_wave(self._h, int(mode))
+
+        def ray_wave_info(self):
+            """rxr_ray_wave_info of the context as a dict: mode, batches, rays"""
+            if not has_ray_wave:
+                raise NotImplementedError(f"{name}: no wave-per-ray route in this library")
+            out = (C.c_uint64 * len(RAY_WAVE_INFO))()
+            rc = L.scene_ray_wave_info(self._h, out)
+            if rc != 0:
+                raise RasterizeError(rc, last_error())
+            return dict(zip(RAY_WAVE_INFO, (int(x) for x in out)))
 
         @property
         def ray_refresh(self):

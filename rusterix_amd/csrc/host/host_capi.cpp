@@ -153,6 +153,10 @@ int rxh_scene_resident_chunk_textures(void *s) { return ((Scene *)s)->resident_c
 void rxh_scene_set_ray_accel(void *s, uint32_t mode) { ((Scene *)s)->ray_accel = mode; }
 uint32_t rxh_scene_ray_accel(void *s) { return ((Scene *)s)->ray_accel; }
 int rxh_scene_ray_accel_info(void *s, uint64_t *out) { return ((Scene *)s)->ray_accel_info(out); }
+// ---- a wave per ray through that tree (Scene::ray_wave): RXR_RAY_WAVE_* --------------------------------
+void rxh_scene_set_ray_wave(void *s, uint32_t mode) { ((Scene *)s)->ray_wave = mode; }
+uint32_t rxh_scene_ray_wave(void *s) { return ((Scene *)s)->ray_wave; }
+int rxh_scene_ray_wave_info(void *s, uint64_t *out) { return ((Scene *)s)->ray_wave_info(out); }
 // ---- counts that change are resized on the device (Scene::resize_meshes) ---------------------------------
 void rxh_scene_set_resize_meshes(void *s, int on) { ((Scene *)s)->resize_meshes = on != 0; }
 int rxh_scene_resize_meshes(void *s) { return ((Scene *)s)->resize_meshes ? 1 : 0; }

@@ -900,8 +900,19 @@ int Scene::intersect(const float *origins, const float *dirs, uint32_t n, uint32
         if (rc != RXR_OK) return rc;
     }
     int rc = rxr_set_ray_accel(ctx, ray_accel);
+    if (rc == RXR_OK) rc = rxr_set_ray_wave(ctx, ray_wave);
     if (rc == RXR_OK) rc = rxr_set_ray_refresh(ctx, ray_refresh);
     if (rc == RXR_OK) rc = rxr_intersect(ctx, origins, dirs, n, flags, t, mesh, triangle, hitpoint, uv, normal);
+    if (rc != RXR_OK) g_error = rxr_last_error(ctx);
+    return rc;
+}
+
+int Scene::ray_wave_info(uint64_t *out) const {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::string err;
+    rxr_ctx *ctx = context(&err);
+    if (!ctx) return RXR_ERR_NO_DEVICE;
+    const int rc = rxr_ray_wave_info(ctx, out);
     if (rc != RXR_OK) g_error = rxr_last_error(ctx);
     return rc;
 }
@@ -1333,6 +1344,7 @@ int Tracer::trace(uint32_t camera_kind, const float *camera, const Scene &scene,
     int rc = rxr_set_trace_scene(ctx, kinds.data(), values.data(), (uint32_t)meshes.size(), lights.data(), (uint32_t)lights.size(), sample_mode,
                                  (uint64_t)scene.animation_frame, chunk_rec.data(), (uint32_t)scene.chunks.size());
     if (rc == RXR_OK) rc = rxr_set_ray_accel(ctx, scene.ray_accel);
+    if (rc == RXR_OK) rc = rxr_set_ray_wave(ctx, scene.ray_wave);
     if (rc == RXR_OK) rc = rxr_set_ray_refresh(ctx, scene.ray_refresh);
     if (rc == RXR_OK) rc = rxr_trace(ctx, camera_kind, camera, (uint32_t)accum.width, (uint32_t)accum.height, (uint32_t)accum.frame, n_frames, seed, bounces, accum.pixels.data());
     if (rc != RXR_OK) {

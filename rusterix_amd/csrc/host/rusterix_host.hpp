@@ -331,6 +331,12 @@ public:
     uint32_t ray_accel = RXR_RAY_ACCEL_OFF;
     // rxr_ray_accel_info of the context: RXR_RAY_ACCEL_INFO_WORDS words.  RXR_OK or a negative rxr_status.
     int ray_accel_info(uint64_t *out) const;
+    // Opt-in, RXR_RAY_WAVE_OFF by default, on top of ray_accel and handed over next to it (rxr_set_ray_wave, include/rxr.h): with the
+    // tree on, RXR_RAY_WAVE_ON sends the batches rxr_ray_wave_takes() names through it a wave per ray, RXR_RAY_WAVE_FORCE every batch.
+    // The results are the same words.
+    uint32_t ray_wave = RXR_RAY_WAVE_OFF;
+    // rxr_ray_wave_info of the context: RXR_RAY_WAVE_INFO_WORDS words.  RXR_OK or a negative rxr_status.
+    int ray_wave_info(uint64_t *out) const;
     // Opt-in, RXR_RAY_REFRESH_FULL by default: what an rxr_update_meshes on the shared context leaves for the next intersect() or
     // Tracer::trace -- handed over next to ray_accel (rxr_set_ray_refresh, include/rxr.h).  RXR_RAY_REFRESH_RANGED rewrites only the
     // updated meshes' records and refits the tree; the results are the same words.

@@ -291,6 +291,9 @@ struct rxr_ctx {
     bool accel_stats_zeroed = false;
     uint32_t accel_ntri = 0, accel_nodes = 0, accel_levels = 0;
     uint64_t accel_builds = 0, accel_batches = 0;
+    // a wave per ray through that tree (rxr_set_ray_wave; k_accel_by_wave): the mode, and the batches and rays that went that way
+    uint32_t wave_mode = 0;          // RXR_RAY_WAVE_*
+    uint64_t wave_batches = 0, wave_rays = 0;
 
     // ranged refresh after rxr_update_meshes (rxr_set_ray_refresh).  refresh_named: one byte per registered mesh,
     // 1 while an update named it and no query has run since (refresh_pending of them; only ever set while isect_ready);

@@ -178,6 +178,13 @@ uint32_t rxr_debug_vertex_normals(rxr_ctx *ctx, uint32_t *launches);
 /* test-only: the small route's bound as compiled (the environment's override is not applied) and what an override is cut to */
 void rxr_debug_vertex_normals_constants(uint32_t out[3]);
 
+/* ---- rxr_ray_accel.hip ---- */
+
+/* tests: the box tree as it stands after the context's streams have drained (no build, no refresh is started): *n_nodes = its nodes,
+ * leaves first, and, where `nodes` is not NULL, min(*n_nodes, capacity) of them as eight floats each: lo[3], kappa, hi[3], maxabs.
+ * *n_nodes = 0 when no tree stands. */
+int rxr_debug_ray_accel_nodes(rxr_ctx *ctx, float *nodes, uint64_t capacity, uint64_t *n_nodes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -464,6 +464,8 @@ int isect_closest(rxr_ctx *ctx, const IsectArgs &A, uint32_t r0, uint32_t nr, hi
     const uint32_t ntri = A.ntri;
     if (!ntri || !A.nseg || !nr) return RXR_OK;
     HIPCHK(ctx, hipMemsetAsync(A.keys, 0xFF, (size_t)nr * A.nseg * 8, s));
+    if (rxr_ray_wave_route(ctx, nr))   // opt-in: the same keys through the box tree, a wave per ray (rxr_set_ray_wave)
+        return rxr_ray_wave_closest(ctx, A.segs, A.nseg, A.origins, A.dirs, r0, nr, A.keys, s);
     if (nr > ISECT_FEW_RAYS && rxr_ray_accel_takes(ctx))   // opt-in: the same keys through the box tree
         return rxr_ray_accel_closest(ctx, A.segs, A.nseg, A.origins, A.dirs, r0, nr, A.keys, s);
     if (nr <= ISECT_FEW_RAYS) {

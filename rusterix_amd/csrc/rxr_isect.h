@@ -82,6 +82,20 @@ int rxr_ray_accel_build(rxr_ctx *ctx, hipStream_t s);
 bool rxr_ray_accel_takes(const rxr_ctx *ctx);
 // the start of a picking or tracing call: the count of RXR_RAY_ACCEL_COUNT starts again
 int rxr_ray_accel_begin_call(rxr_ctx *ctx, hipStream_t s);
+// ---- a wave per ray through the same tree (rxr_set_ray_wave) -------------------------------------------------
+// The rule of RXR_RAY_WAVE_ON, rxr_ray_wave_takes(n_rays, n_triangles): RXR_RAY_WAVE_MIN_RAYS <= n_rays <= RXR_RAY_WAVE_MAX_RAYS and
+// n_triangles >= RXR_RAY_WAVE_MIN_TRIANGLES.  The ray bounds are the measured ray counts between which the wave walk's median was ahead
+// of the better of brute force and the thread walk by more than twice the larger spread on every scene of profiles/ray_wave/README.md
+// (at 64 rays and at 1920 x 1080 it is not); the triangle bound is the smallest measured scene above the teapot's 2 256 triangles,
+// which stays with the existing routes whatever the ray count.
+#define RXR_RAY_WAVE_MIN_RAYS 256u
+#define RXR_RAY_WAVE_MAX_RAYS 65536u
+#define RXR_RAY_WAVE_MIN_TRIANGLES 12288u
+// does this batch of nr rays go a wave per ray?  (rxr_isect_closest asks ahead of its own two routes)
+bool rxr_ray_wave_route(const rxr_ctx *ctx, uint32_t nr);
+// rxr_isect_closest's keys, a wave per ray through the tree (k_accel_by_wave)
+int rxr_ray_wave_closest(rxr_ctx *ctx, const void *dev_segs, uint32_t nseg, const float *dev_origins, const float *dev_dirs, uint32_t r0,
+                         uint32_t nr, unsigned long long *dev_keys, hipStream_t s);
 // ---- the ranged refresh after rxr_update_meshes (rxr_set_ray_refresh) -----------------------------------------
 // The dirty triangles of a refresh, as the kernels of both files read them: per dirty mesh (in mesh order, none empty) its first global
 // triangle = its first sorted position, its first vertex in the pools, and the prefix of the dirty meshes' triangle counts

@@ -26,6 +26,8 @@
 // descends to index * W; otherwise index + 1, and while that index is a multiple of W or the end of its level, up to
 // (index - 1) / W + 1.  The position only moves forward, so the walk ends after at most `nodes` steps whatever the boxes hold.
 // Leaves come in increasing position, hence in segment order: the segment's minimum is flushed when the position crosses its end.
+// Walk (k_accel_by_wave, a wave per ray, opt-in on top: rxr_set_ray_wave): for batches too small to fill the
+// device with a thread per ray -- the comment above that kernel has its visit rule and why the duty above still holds.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -34,6 +36,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "rxr_debug.h"
 #include "rxr_isect.h"
 #include "rxr_query.h"
 #include "rxr_ray_refresh.h"
@@ -361,6 +364,145 @@ __global__ __launch_bounds__(ACCEL_WG) void k_accel_by_ray(AccelArgs A, uint32_t
         for (int off = 32; off >= 1; off >>= 1) tests += __shfl_xor(tests, off);
         if (__lane_id() == 0 && tests) atomicAdd(A.stats, tests);
     }
+}
+
+// ---- a wave per ray (rxr_set_ray_wave) -----------------------------------------------------------------------
+// k_accel_by_wave: the 64 lanes of a wave walk ONE ray together over the same nodes, records, perm and segment table, for batches too
+// small to fill the device with a thread per ray.  ACCEL_WG threads are four rays; the four waves never meet (no barrier: each wave
+// writes the level table itself -- the same words -- and reads what it wrote).
+//
+// Walk: depth-first over the implicit levels, two levels a step.  Entering node (l, i):
+//   l odd, >= 3   lane j runs box_pass on node i * 64 + j of level l - 2 (clipped to that level's count); the ballot of the passing
+//                 ones is pushed as a frame, its set bits are entered lowest first
+//   l even, >= 2  (only the root of a tree with an even top level can be: every frame below it is on an odd level) one level: lanes
+//                 0 .. 7 test the children i * 8 + j of level l - 1, so that every later step ends on level 1 with 64 lanes at work
+//   l == 1        the lanes take the node's sorted positions [i * 64, min(i * 64 + 64, ntri)), one each, through mt_test
+//   l == 0        (a tree of one leaf) the lanes take its up to 8 positions
+// The root's own box is not tested.  LEAF BOXES: at l == 1 the eight leaf boxes below the node are NOT tested (RXR_RAY_WAVE_LEAF_BOXES
+// 0, the shipped choice; 1 tests them with lanes 0 .. 7 first and masks each leaf's eight lanes by its box: the A-B of
+// profiles/ray_wave/README.md).  tests/ray_wave_ref.py: wave_walk restates this rule.
+// The frames' masks live in LDS, ACCEL_WAVE_STACK per wave, the top one in scalar registers; a frame's level and its parent's index
+// follow from the depth (a frame is two levels below the one under it; the parent's index is the child's >> 6), so nothing else is
+// stacked.  ACCEL_MAX_LEVELS = 24 bounds the depth: the root's frame and one per odd level below the top, at most 12.
+//
+// THE ONE DUTY IS UNCHANGED.  A position is left out only because box_pass -- the same function on the same node and the same o, inv,
+// omax that k_accel_by_ray computes -- failed on one of its ancestors.  The ancestors tested here are a subset of those the thread walk
+// tests (every other level, never the root, by default not the leaf), so this walk enters a superset of the thread walk's leaves, and
+// mt_test on the same records gives the same t bits and the same keys; whole keys go through atomicMin, whose result does not depend
+// on order.  Its keys equal the brute-force keys under the measured margin of section 19 and no new one.
+// TERMINATION.  Every turn of the loop either clears one bit of the top mask, or drops an empty top mask, or (entering a node) pushes
+// a mask for a strictly lower level; a node is entered once per bit, bits are only ever cleared, and the level table bounds the nodes.
+// The loop ends when the stack is empty whatever the boxes hold: a build or refit bug cannot hang the device.
+#ifndef RXR_RAY_WAVE_LEAF_BOXES
+#define RXR_RAY_WAVE_LEAF_BOXES 0
+#endif
+constexpr uint32_t ACCEL_WAVE_STACK = 12;
+static_assert(ACCEL_W == 8 && ACCEL_L == 8, "k_accel_by_wave: 64 grandchildren a node, 64 positions a level-1 node");
+static_assert(ACCEL_MAX_LEVELS / 2 <= ACCEL_WAVE_STACK, "k_accel_by_wave: a frame per odd level and the root's");
+
+__device__ __forceinline__ uint32_t uniform32(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+__device__ __forceinline__ unsigned long long uniform64(unsigned long long x) {
+    return ((unsigned long long)uniform32((uint32_t)(x >> 32)) << 32) | uniform32((uint32_t)x);
+}
+
+template <bool COUNT>
+__global__ __launch_bounds__(ACCEL_WG) void k_accel_by_wave(AccelArgs A, uint32_t r0, uint32_t nr) {
+    __shared__ uint2 lev[ACCEL_MAX_LEVELS];   // (first node, nodes) per level
+    __shared__ unsigned long long stack[ACCEL_WG / 64][ACCEL_WAVE_STACK];   // a wave's masks: written by lane 0, read back by all
+    const uint32_t lane = threadIdx.x & 63u, wave = uniform32(threadIdx.x >> 6);
+    if (lane < ACCEL_MAX_LEVELS) lev[lane] = make_uint2(A.lev.off[lane], A.lev.cnt[lane]);
+    const uint32_t r = blockIdx.x * (ACCEL_WG / 64) + wave;
+    if (r >= nr) return;
+    const F3 o = load3(A.origins, (uint64_t)r0 + r);
+    const F3 d = normalized3(load3(A.dirs, (uint64_t)r0 + r));
+    if (!(finite3(o) && finite3(d))) return;   // as k_accel_by_ray: every mt_test rejects such a ray
+    const F3 inv = {1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
+    const float omax = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
+    const size_t st = A.stride;
+    unsigned long long *slot = A.keys + (uint64_t)r * A.nseg;
+
+    // flush: the wave's minimum of `best` into the segment's slot, one atomic
+    unsigned long long best = RXR_ISECT_NO_HIT;
+    uint32_t s = 0, send = 0;   // the segment of the last positions taken: [.., send)
+    auto flush = [&]() {
+        if (__ballot(best != RXR_ISECT_NO_HIT)) {
+            unsigned long long m = best;
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                const unsigned long long x = __shfl_xor(m, off);
+                m = x < m ? x : m;
+            }
+            if (lane == 0) atomicMin(slot + s, m);
+        }
+        best = RXR_ISECT_NO_HIT;
+    };
+
+    unsigned long long tests = 0;
+    // the frames: `cur` = the top mask, over nodes pidx * 64 + bit of level `flevel`; the root is a frame of one bit
+    unsigned long long cur = 1;
+    uint32_t sp = 1, pidx = 0, flevel = A.lev.n - 1;
+    while (sp) {
+        if (!cur) {   // the frame is done: back to the one below
+            --sp;
+            __builtin_amdgcn_wave_barrier();   // (no instruction: LDS operations of one wave complete in order)
+            if (sp) cur = uniform64(stack[wave][sp - 1]);
+            pidx >>= 6;
+            flevel += 2;
+            continue;
+        }
+        const uint32_t bit = (uint32_t)__builtin_ctzll(cur);
+        cur &= cur - 1;
+        const uint32_t level = flevel, idx = (pidx << 6) + bit;
+        if (level >= 2) {
+            const uint32_t down = (level & 1u) ? 2u : 1u, fan = (level & 1u) ? 64u : 8u;
+            const uint32_t off = uniform32(lev[level - down].x), cnt = uniform32(lev[level - down].y);
+            const uint32_t c = idx * fan + lane;
+            bool pass = false;
+            if (lane < fan && c < cnt) pass = box_pass(A.nodes[off + c], o, inv, omax);
+            const unsigned long long m = __ballot(pass);
+            if (m && sp < ACCEL_WAVE_STACK) {   // (sp cannot reach the bound: the static_assert above)
+                if (lane == 0) stack[wave][sp - 1] = cur;
+                __builtin_amdgcn_wave_barrier();
+                cur = m;
+                ++sp;
+                pidx = idx;
+                flevel = level - down;
+            }
+            continue;
+        }
+        // level 1: the 64 positions below the node; level 0 (a tree of one leaf): its 8
+        const uint32_t p0 = idx * (level ? ACCEL_L * ACCEL_W : ACCEL_L), p1 = min(p0 + (level ? ACCEL_L * ACCEL_W : ACCEL_L), A.ntri);
+        if (p0 >= p1) continue;
+        const uint32_t pos = p0 + lane;
+        bool take = pos < p1;
+#if RXR_RAY_WAVE_LEAF_BOXES
+        {
+            const uint32_t leaf = p0 / ACCEL_L + lane, cnt0 = uniform32(lev[0].y);
+            bool pass = false;
+            if (lane < ACCEL_W && leaf < cnt0) pass = box_pass(A.nodes[uniform32(lev[0].x) + leaf], o, inv, omax);
+            take = take && ((__ballot(pass) >> (lane / ACCEL_L)) & 1ull);
+        }
+#endif
+        if (p0 >= send) {   // the first positions, or positions were skipped
+            flush();
+            s = uniform32(accel_seg_of(A, p0));
+            send = uniform32(A.segs[s].end);
+        }
+        const bool one_segment = p1 <= send;
+        if (!one_segment) flush();
+        if (COUNT) tests += (unsigned long long)__popcll(__ballot(take));
+        if (take) {
+            const float *p = A.tris + pos;
+            float t, u, v;
+            if (mt_test(o, d, {p[0], p[st], p[2 * st]}, {p[3 * st], p[4 * st], p[5 * st]}, {p[6 * st], p[7 * st], p[8 * st]}, t, u, v)) {
+                const unsigned long long key = ((unsigned long long)__float_as_uint(t) << 32) | A.perm[pos];
+                if (one_segment) best = key < best ? key : best;
+                else atomicMin(slot + accel_seg_of(A, pos), key);   // the positions straddle segments: each lane finds its own
+            }
+        }
+    }
+    flush();
+    if (COUNT && lane == 0 && tests) atomicAdd(A.stats, tests);
 }
 
 // ---- the ranged refit after rxr_update_meshes (rxr_set_ray_refresh) ------------------------------------------
@@ -702,7 +844,59 @@ int rxr_ray_accel_closest(rxr_ctx *ctx, const void *dev_segs, uint32_t nseg, con
     return RXR_OK;
 }
 
+bool rxr_ray_wave_route(const rxr_ctx *ctx, uint32_t nr) {
+    if (ctx->wave_mode == RXR_RAY_WAVE_OFF || !nr || !rxr_ray_accel_takes(ctx)) return false;
+    return ctx->wave_mode == RXR_RAY_WAVE_FORCE || rxr_ray_wave_takes(nr, ctx->accel_ntri) != 0;
+}
+
+int rxr_ray_wave_closest(rxr_ctx *ctx, const void *dev_segs, uint32_t nseg, const float *dev_origins, const float *dev_dirs, uint32_t r0, uint32_t nr,
+                         unsigned long long *dev_keys, hipStream_t s) {
+    AccelArgs A{};
+    A.ntri = ctx->accel_ntri;
+    A.nseg = nseg;
+    A.stride = ctx->isect_stride;
+    A.tris = (const float *)ctx->d_accel_tris.p;
+    A.perm = (const uint32_t *)ctx->d_accel_perm.p;
+    A.nodes = (const AccelNode *)ctx->d_accel_nodes.p;
+    A.segs = (const AccelSeg *)dev_segs;
+    A.origins = dev_origins;
+    A.dirs = dev_dirs;
+    A.keys = dev_keys;
+    A.stats = (unsigned long long *)ctx->d_accel_stats.p;
+    A.lev = accel_levels(A.ntri);
+    const uint32_t per_group = ACCEL_WG / 64;   // a wave per ray
+    const dim3 grid((nr + per_group - 1) / per_group), wg(ACCEL_WG);
+    if (ctx->accel_mode == RXR_RAY_ACCEL_COUNT) hipLaunchKernelGGL(k_accel_by_wave<true>, grid, wg, 0, s, A, r0, nr);
+    else hipLaunchKernelGGL(k_accel_by_wave<false>, grid, wg, 0, s, A, r0, nr);
+    HIPCHK(ctx, hipGetLastError());
+    ++ctx->wave_batches;
+    ctx->wave_rays += nr;
+    return RXR_OK;
+}
+
 extern "C" {
+
+int rxr_set_ray_wave(rxr_ctx *ctx, uint32_t mode) {
+    if (!ctx) return RXR_ERR_INVALID;
+    if (mode > RXR_RAY_WAVE_FORCE) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_set_ray_wave: mode must be RXR_RAY_WAVE_OFF, _ON or _FORCE");
+    if (ctx->group) return rxr_as_member0(ctx, [&](rxr_ctx *m) { return rxr_set_ray_wave(m, mode); });
+    ctx->wave_mode = mode;
+    return RXR_OK;
+}
+
+int rxr_ray_wave_takes(uint32_t n_rays, uint32_t n_triangles) {
+    return n_rays >= RXR_RAY_WAVE_MIN_RAYS && n_rays <= RXR_RAY_WAVE_MAX_RAYS && n_triangles >= RXR_RAY_WAVE_MIN_TRIANGLES;
+}
+
+int rxr_ray_wave_info(rxr_ctx *ctx, uint64_t out[RXR_RAY_WAVE_INFO_WORDS]) {
+    if (!ctx) return RXR_ERR_INVALID;
+    if (!out) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_ray_wave_info: out is NULL");
+    if (ctx->group) return rxr_as_member0(ctx, [&](rxr_ctx *m) { return rxr_ray_wave_info(m, out); });
+    out[RXR_RAY_WAVE_INFO_MODE] = ctx->wave_mode;
+    out[RXR_RAY_WAVE_INFO_BATCHES] = ctx->wave_batches;
+    out[RXR_RAY_WAVE_INFO_RAYS] = ctx->wave_rays;
+    return RXR_OK;
+}
 
 int rxr_set_ray_accel(rxr_ctx *ctx, uint32_t mode) {
     if (!ctx) return RXR_ERR_INVALID;
@@ -733,6 +927,20 @@ int rxr_ray_accel_info(rxr_ctx *ctx, uint64_t out[RXR_RAY_ACCEL_INFO_WORDS]) {
     out[RXR_RAY_ACCEL_INFO_BUILDS] = ctx->accel_builds;
     out[RXR_RAY_ACCEL_INFO_BATCHES] = ctx->accel_batches;
     out[RXR_RAY_ACCEL_INFO_TESTS] = stats[0];
+    return RXR_OK;
+}
+
+int rxr_debug_ray_accel_nodes(rxr_ctx *ctx, float *nodes, uint64_t capacity, uint64_t *n_nodes) {
+    if (!ctx) return RXR_ERR_INVALID;
+    if (!n_nodes) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_debug_ray_accel_nodes: n_nodes is NULL");
+    if (ctx->group) return rxr_as_member0(ctx, [&](rxr_ctx *m) { return rxr_debug_ray_accel_nodes(m, nodes, capacity, n_nodes); });
+    static_assert(sizeof(AccelNode) == 32, "eight floats a node");
+    *n_nodes = ctx->accel_ready ? ctx->accel_nodes : 0u;
+    if (!*n_nodes || !nodes || !capacity) return RXR_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = rxr_quiesce(ctx);
+    if (rc != RXR_OK) return rc;
+    HIPCHK(ctx, hipMemcpy(nodes, ctx->d_accel_nodes.p, (size_t)std::min<uint64_t>(*n_nodes, capacity) * sizeof(AccelNode), hipMemcpyDeviceToHost));
     return RXR_OK;
 }
 

@@ -25,6 +25,8 @@ F = np.float32
 MAX_BOUNCES = 8
 RAY_ACCEL_OFF, RAY_ACCEL_ON, RAY_ACCEL_COUNT = 0, 1, 2   # rxr_set_ray_accel's modes (include/rxr.h)
 RAY_ACCEL_INFO = ("mode", "valid", "triangles", "nodes", "levels", "wild", "builds", "batches", "tests")   # rxr_ray_accel_info's words
+RAY_WAVE_OFF, RAY_WAVE_ON, RAY_WAVE_FORCE = 0, 1, 2   # rxr_set_ray_wave's modes (include/rxr.h)
+RAY_WAVE_INFO = ("mode", "batches", "rays")   # rxr_ray_wave_info's words
 RAY_REFRESH_FULL, RAY_REFRESH_RANGED = 0, 1   # rxr_set_ray_refresh's modes (include/rxr.h)
 RAY_REFRESH_INFO = ("mode", "pending", "refreshes", "refits", "triangles", "leaves", "nodes", "route")   # rxr_ray_refresh_info's words
 RAY_REFRESH_VERIFY = ("pick_words", "sorted_words", "nodes", "wild", "checked")   # rxr_ray_refresh_verify's words
@@ -233,6 +235,22 @@ class Tracer:
         out = (C.c_uint64 * len(RAY_ACCEL_INFO))()
         self._check(self.rxr.rxr_ray_accel_info(self.ctx, out))
         return dict(zip(RAY_ACCEL_INFO, (int(x) for x in out)))
+
+    @property
+    def ray_wave(self):
+        """rxr_set_ray_wave's mode (0 off, the default; 1: the batches rxr_ray_wave_takes() names walk the tree a wave per ray;
+        2: every batch does) -- only with ray_accel on; the results are the same words"""
+        return self.ray_wave_info()["mode"]
+
+    @ray_wave.setter
+    def ray_wave(self, mode):
+        self._check(self.rxr.rxr_set_ray_wave(self.ctx, int(mode)))
+
+    def ray_wave_info(self):
+        """rxr_ray_wave_info as a dict: mode, batches, rays"""
+        out = (C.c_uint64 * len(RAY_WAVE_INFO))()
+        self._check(self.rxr.rxr_ray_wave_info(self.ctx, out))
+        return dict(zip(RAY_WAVE_INFO, (int(x) for x in out)))
 
     @property
     def ray_refresh(self):

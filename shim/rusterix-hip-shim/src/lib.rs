@@ -100,6 +100,22 @@ pub fn set_ray_accel(on: bool) -> bool {
     }
 }
 
+/// Opt-in, on top of `set_ray_accel`: batches of rays that `rxr_ray_wave_takes` names walk the box tree a wave per ray
+/// (include/rxr.h `rxr_set_ray_wave`): `on = false` is the library's default.  The queries' results are the same words either way.
+/// Returns false when there is no device context.
+pub fn set_ray_wave(on: bool) -> bool {
+    let mut guard = STATE.lock().unwrap();
+    let st = guard.get_or_insert_with(Caches::default);
+    if st.ctx.is_none() && !st.tried {
+        st.tried = true;
+        st.ctx = create_context();
+    }
+    match &st.ctx {
+        Some(ctx) => unsafe { rxr_set_ray_wave(ctx.0, if on { RXR_RAY_WAVE_ON } else { RXR_RAY_WAVE_OFF }) == RXR_OK },
+        None => false,
+    }
+}
+
 /// Opt-in: after `rxr_update_meshes` the next device ray query rewrites only the updated meshes' pick records and refits the box tree
 /// instead of building both again (include/rxr.h `rxr_set_ray_refresh`): `ranged = false` is the library's default.  The queries'
 /// results are the same words either way.  Returns false when there is no device context.
