@@ -614,6 +614,10 @@ RXR_HD inline void rxr_union_tile_rows(const TriSetup &S, uint32_t width, uint32
     }
 }
 
+// RasterParams.flags carries the frame's RXR_FLAG_* bits (rxr.h, bits 0..6) and, from the top down, bits that rxr_upload_frame sets itself:
+constexpr uint32_t RPF_LIGHT_PREFIX = 1u << 31;  // relaxed light loop: the leading run of fast lights goes through its own loop (shade3d_lights<LV, true>);
+                                                 // set unless RXR_LIGHT_PREFIX=0 (read per upload: tests and A-B runs)
+
 // kernel parameter block (passed by value; lives in the kernarg segment -> scalar loads)
 #if defined(__HIPCC__) || defined(RXR_JIT)  // (HIP's vector types: a plain C++ compiler gets everything above)
 struct RasterParams {

@@ -756,8 +756,11 @@ __device__ __forceinline__ void shade3d_begin(const RasterParams &P, const TriSh
 // Three A-B variants of the relaxed point-light term were tried against what stands below and are retired: the light's
 // constants read from its rxr_light record in the loop (now its LightFast record), the light direction formed and normalised
 // first (now folded into the dot products), and exp2(6 log2 x) at levels without programs (now three multiplies).
-template <Level LV, bool RL = false>
+// PREFIX: relaxed kernels walk the leading fast lights in a loop of their own (below; not k_raster_pair_rl and the *_cut_rl kernels,
+// which sit at their 64 registers with scratch already and answered with 16 and 8 more bytes of it).
+template <Level LV, bool RL = false, bool PREFIX = RL>
 __device__ __forceinline__ void shade3d_lights(const RasterParams &P, bool hit, Frag &F) {
+    static_assert(RL || !PREFIX, "the prefix loop is the relaxed term");
     const unsigned long long hitmask = __ballot(hit);
     if (hitmask == 0ull) return;
     const int lane = (int)(threadIdx.x & 63u);
@@ -852,6 +855,57 @@ __device__ __forceinline__ void shade3d_lights(const RasterParams &P, bool hit, 
             }
         }
         unsigned long long todo = __ballot(cand);
+        if constexpr (PREFIX) {
+            // The leading run of lights with a LightFast record in a loop of its own, whose body is the fast term of the loop below and
+            // nothing else (the same operations in the same order, so the same floats).  What the loop below pays around that term per
+            // light and wave is paid here once per step: the table's base stays in SGPRs instead of being re-read from the kernarg
+            // segment in front of every record (one scalar round trip per light, not two dependent ones); exec is never narrowed to
+            // `hit`; and with no second path to join, F.lit is updated in place (no copies at the latch): 44 VALU instructions
+            // per light and wave against 47, no s_and_saveexec.  Every lane takes part: a wave-uniform `todo` cannot come out of a
+            // region entered under `hit` as a scalar, so a lane without a fragment computes a term nobody reads (its F is zeros,
+            // its colour the miss colour) and only the window test is masked with `hitmask`.
+            // The run ends at the first light without a record or whose squared distance leaves the window for a fragment: that
+            // light is still in `todo`, and it and everything behind it go through the loop below, unchanged.
+            // RXR_LIGHT_PREFIX=0 (RPF_LIGHT_PREFIX clear) leaves every light to the loop below: the parent's frame by the parent's code.
+            // Tried on top and dropped (profiles/light_prefix/): the next light's record fetched under this light's arithmetic --
+            // the bench frame 1.4 us SLOWER than without (eight more live SGPRs, five s_mov and a select per light).
+            const unsigned long long slow = todo & ~fast_mask;
+            unsigned long long pre = slow ? (todo & ((slow & (0ull - slow)) - 1ull)) : todo;
+            if (!(P.flags & RPF_LIGHT_PREFIX)) pre = 0ull;
+            if (pre) {
+                const LightFast *tbl = P.lights_fast + base_i;
+                LightFast LF = uniform_record_x8(tbl, (uint32_t)(__ffsll((long long)pre) - 1));
+                for (;;) {
+                    // (the record stays in the scalar registers it was loaded into: the arithmetic reads it from there, as the loop below does)
+                    asm volatile("" : "+s"(LF.pos[0]), "+s"(LF.pos[1]), "+s"(LF.pos[2]), "+s"(LF.ss_r), "+s"(LF.cfi[0]), "+s"(LF.cfi[1]), "+s"(LF.cfi[2]), "+s"(LF.c0));
+                    pre &= pre - 1ull;
+                    const f3 d = sub3(mk3(LF.pos[0], LF.pos[1], LF.pos[2]), F.world);
+                    const float m2 = fmaf(d.z, d.z, fmaf(d.y, d.y, d.x * d.x));
+                    if (__ballot(!rxm::sq_in_window(m2)) & hitmask) break;  // (wave_all over the lanes that own a fragment)
+                    const float inv = __builtin_amdgcn_rsqf(m2);
+                    const float t = __builtin_amdgcn_fmed3f(fmaf(m2 * inv, LF.ss_r, LF.c0), 0.0f, 1.0f);
+                    const float ss = t * t * fmaf(-2.0f, t, 3.0f);
+                    const float ndl = __builtin_amdgcn_fmed3f(fmaf(F.normal.z, d.z, fmaf(F.normal.y, d.y, F.normal.x * d.x)) * inv, 0.0f, 1.0f);
+                    const f3 hu = mk3(fmaf(d.x, inv, F.view_dir.x), fmaf(d.y, inv, F.view_dir.y), fmaf(d.z, inv, F.view_dir.z));
+                    const float hh = fmaf(hu.z, hu.z, fmaf(hu.y, hu.y, hu.x * hu.x));
+                    const float ndh = __builtin_amdgcn_fmed3f(fmaf(F.normal.z, hu.z, fmaf(F.normal.y, hu.y, F.normal.x * hu.x)) * __builtin_amdgcn_rsqf(hh), 0.0f, 1.0f);
+                    float spec;
+                    if constexpr (!feat<LV>.programs) {
+                        const float ndh2 = ndh * ndh;
+                        spec = ndh2 * ndh2 * ndh2;
+                    } else {
+                        spec = __builtin_amdgcn_exp2f(rl_shininess * __builtin_amdgcn_logf(ndh));
+                    }
+                    const float s = ss * ndl * ndl;
+                    F.lit.x = fmaf(fmaf(rl_f.x, spec, rl_kd.x), LF.cfi[0] * s, F.lit.x);
+                    F.lit.y = fmaf(fmaf(rl_f.y, spec, rl_kd.y), LF.cfi[1] * s, F.lit.y);
+                    F.lit.z = fmaf(fmaf(rl_f.z, spec, rl_kd.z), LF.cfi[2] * s, F.lit.z);
+                    todo &= todo - 1ull;  // (this light was the lowest of `todo`)
+                    if (!pre) break;
+                    LF = uniform_record_x8(tbl, (uint32_t)(__ffsll((long long)pre) - 1));
+                }
+            }
+        }
         while (todo) {
             const int li_lane = __ffsll((long long)todo) - 1;
             const uint32_t li = base_i + (uint32_t)li_lane;
@@ -3263,7 +3317,8 @@ __device__ __forceinline__ void raster_tile(const RasterParams &P) {
             shade3d_begin<LV, RL>(P, HS, vis.batch, vis.alpha, vis.beta, vis.zmin, fx, fy, F, have_flags, win_flags);
         }
         PHASE_MARK(2);
-        if (P.n_lights) shade3d_lights<LV, RL>(P, hit, F);  // wave-uniform call
+        // (the kernels with split rounds keep the general loop alone, like the pair kernel: k_raster_rows_cut_rl answered with 8 more bytes of scratch)
+        if (P.n_lights) shade3d_lights<LV, RL, RL && !SPLITR>(P, hit, F);  // wave-uniform call
         PHASE_MARK(3);
         color = hit ? shade3d_end<LV, RL>(F) : pack4(0u, 0u, 0u, 255u);
         if constexpr (feat<LV>.chunk) {
@@ -3456,7 +3511,7 @@ __device__ __forceinline__ void raster_tile_pair(const RasterParams &P) {
         F.rough = 0.5f;
         F.metal = 0.0f;
         if (hit) shade3d_begin<LV, RL>(P, HS, vis.batch, vis.alpha, vis.beta, vis.zmin, fx, fy, F);
-        if (P.n_lights) shade3d_lights<LV, RL>(P, hit, F);  // wave-uniform call
+        if (P.n_lights) shade3d_lights<LV, RL, false>(P, hit, F);  // wave-uniform call (no prefix loop: see shade3d_lights)
         uint32_t color = hit ? shade3d_end<LV, RL>(F) : pack4(0u, 0u, 0u, 255u);
         const uint32_t tile_yh = tile_y0px + h * RXR_TILE_H;
         const bool d2_here = (P.flags & RXR_FLAG_D2_ACTIVE) && P.n_prims2d && d2_box_meets(P, tile_x0, tile_yh);

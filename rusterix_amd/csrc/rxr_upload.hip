@@ -1424,6 +1424,9 @@ struct FrameBuild {
                 for (float x : v)
                     if (!(std::fabs(x) <= 1.0e9f)) P.relaxed_lights = 0u;
             }
+            // RXR_LIGHT_PREFIX=0 (read per upload: tests, A-B runs): the relaxed kernels send every light through their general loop
+            const char *lp = getenv("RXR_LIGHT_PREFIX");
+            P.flags = (P.flags & ~RPF_LIGHT_PREFIX) | ((lp && atoi(lp) == 0) ? 0u : RPF_LIGHT_PREFIX);
             P.rl_flip_guard = 1e-4f;
             if (const char *fg = getenv("RXR_RL_FLIP_GUARD")) {  // tests: a large guard sends every wave down the exact normal sequences
                 const float v = (float)atof(fg);
