@@ -3,16 +3,14 @@
 // One rxr_ctx == one HIP device == one process (multi-GPU hosts run one process per GPU and gather
 // the rendered row bands with RCCL, see rusterix_amd/distributed.py).
 //
-// This file: the context's life cycle, the resident textures / meshes / programs (with the shader flattener), rendering, download,
-// profiling and the debug hooks.  The frame hand-over (rxr_upload_frame, rxr_stream_*) lives in rxr_upload.hip, multi-device handles
-// in rxr_multi.hip, ray picking in rxr_intersect.hip.  There is no CPU fallback anywhere in this file.
+// This file: the context's life cycle, the resident textures / meshes / programs (with the shader flattener) and the debug hooks.
+// The frame hand-over (rxr_upload_frame, rxr_stream_*) lives in rxr_upload.hip, rendering, synchronize, download and profiling in
+// rxr_render.hip, multi-device handles in rxr_multi.hip, ray picking in rxr_intersect.hip.  There is no CPU fallback anywhere in this file.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <memory>
-#include <thread>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -29,21 +27,8 @@ extern "C" void rxr_launch_mesh_check(const MeshUpdateArgs *A, uint32_t n, hipSt
 extern "C" void rxr_launch_mesh_commit(const MeshUpdateArgs *A, uint32_t n, hipStream_t s);
 extern "C" void rxr_launch_mesh_resize_check(const MeshResizeCheckArgs *A, uint32_t n, hipStream_t s);
 extern "C" void rxr_launch_mesh_repack(const MeshRepackArgs *A, hipStream_t s);
-extern "C" void rxr_launch_project(const ProjectParams *P, hipStream_t s);
 extern "C" void rxr_launch_proj_edges(const ProjectParams *P, hipStream_t s);
 extern "C" void rxr_launch_setup(const RasterParams *P, hipStream_t s);
-extern "C" void rxr_launch_scan(const ScanArgs *A, hipStream_t s);
-extern "C" void rxr_launch_bin2d_count(const RasterParams *P, hipStream_t s);
-extern "C" void rxr_launch_bin2d_fill(const RasterParams *P, hipStream_t s);
-extern "C" void rxr_launch_fill(const RasterParams *P, hipStream_t s);
-extern "C" void rxr_launch_blockscan(const RasterParams *P, hipStream_t s);
-extern "C" void rxr_launch_blockscan2d(const RasterParams *P, hipStream_t s);
-extern "C" const char *rxr_launch_raster(const RasterParams *P, hipStream_t s);
-extern "C" void rxr_launch_fill_words(uint32_t *dst, uint64_t n_words, uint32_t value, hipStream_t s);
-extern "C" void rxr_launch_fill_outside_spans(const RasterParams *P, hipStream_t s);
-extern "C" void rxr_launch_spans_from_meshes(const RasterParams *P, uint32_t n_tile_rows, const uint32_t *d2_box, uint2 *host_copy, hipStream_t s);
-extern "C" const char *rxr_launch_raster_grid(const RasterParams *P, uint32_t grid_x, hipStream_t s);
-extern "C" int rxr_raster_takes_spans(const RasterParams *P);
 extern "C" void rxr_launch_selftest_math(uint64_t seed, uint32_t blocks, uint32_t iters, unsigned long long *mismatch, hipStream_t s);
 
 namespace {
@@ -877,8 +862,6 @@ int rxr_mirror_read(rxr_ctx *ctx, void *host, const void *dev, size_t bytes) {
 }
 
 // ---- the 2D half of the device-side projection (row N1): Batch2D::project's inputs, registered once ---------------------------
-extern "C" void rxr_launch_project2d(const Project2DParams *P, hipStream_t s);
-
 int rxr_set_meshes2d(rxr_ctx *ctx, const rxr_mesh2d *meshes, uint32_t n_meshes) {
     if (!ctx) return RXR_ERR_INVALID;
     if (n_meshes && !meshes) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_set_meshes2d: NULL mesh array");
@@ -1068,744 +1051,6 @@ int rxr_read_projected_mesh(rxr_ctx *ctx, uint32_t index, uint32_t counts[2], fl
     }
     return RXR_OK;
 }
-
-// the rows [c0, c1) of a contiguous band spec that the resident frame can draw in, rounded out to tile rows (false: not known -- all of them)
-static bool content_band(const rxr_ctx *ctx, const RenderSpec &spec, uint32_t &c0, uint32_t &c1) {
-    c0 = spec.row0;
-    c1 = spec.row1;
-    if (!(ctx->content_known && spec.tile_stride == 1u && !spec.compact && spec.row0 < spec.row1)) return false;
-    c0 = std::min(std::max(ctx->content_row0 / RXR_TILE_H * RXR_TILE_H, spec.row0), spec.row1);
-    c1 = std::max(std::min((ctx->content_row1 + RXR_TILE_H - 1u) / RXR_TILE_H * RXR_TILE_H, spec.row1), c0);
-    // (an empty tile costs the raster launch about half a nanosecond of the chip's time, a fill launch two to three microseconds: the teapot
-    // at 1080p lost 5 us of set-up to save 3 of raster.  Fewer than content_min_tiles() empty tiles: the whole band is rastered)
-    const size_t saved_tiles = (size_t)((c0 - spec.row0) + (spec.row1 - c1)) / RXR_TILE_H * ctx->P.tiles_x;
-    if (saved_tiles < content_min_tiles()) {
-        c0 = spec.row0;
-        c1 = spec.row1;
-        return false;
-    }
-    return true;
-}
-
-// n_raster_bands > 1 (contiguous band specs only): ONE pre-pass over the spec's rows, then the raster kernel in that many launches over
-// consecutive groups of tile rows, an event of band_events recorded behind each -- the caller ships finished rows while the next ones
-// render (rxr_render_download).  The bins are those of the one pre-pass (RasterParams.bin_row0); every bin is still handed back zeroed
-// by its own tile's workgroup; the frame is byte-identical to one launch (tests/test_gpu_parity.py).
-// spans_event (device-projected sparse frames): recorded behind k_spans_from_meshes, which then also writes the completed row-span
-// table to the second half of ctx->h_row_spans; *spans_recorded says whether that happened in this call.
-static int render_impl(rxr_ctx *ctx, const RenderSpec &spec, void *dev_pixels, hipStream_t s, bool retry = false, uint32_t n_raster_bands = 1,
-                       hipEvent_t *band_events = nullptr, uint32_t *band_row_of = nullptr, hipEvent_t spans_event = nullptr,
-                       bool *spans_recorded = nullptr) {
-    if (!ctx) return RXR_ERR_INVALID;
-    if (!ctx->has_frame) return rxr_fail(ctx, RXR_ERR_INVALID, "render: no frame uploaded");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    // every launch sequence uses the context's one set of scratch buffers (records, bins, counters): a render on another
-    // stream than the previous one is ordered behind it
-    // (the event is recorded here, at the switch, on the PREVIOUS stream -- it then covers that stream's renders and whatever the
-    // caller queued behind them, a superset -- and not behind every launch sequence: an event record is a barrier packet that idles
-    // the GPU for microseconds, and a caller that stays on one stream never needs it)
-    if (ctx->rendered && ctx->last_stream != s) {
-        HIPCHK(ctx, hipEventRecord(ctx->ev_render, ctx->last_stream));
-        HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_render, 0));
-    }
-    if (retry) ctx->rerenders++;
-    if (!ctx->upload_ordered_on || ctx->upload_ordered_on != s) {
-        if (s != ctx->stream) {
-            // the upload ran on the context stream: order the external stream behind it (once per upload)
-            HIPCHK(ctx, hipEventRecord(ctx->ev_upload, ctx->stream));
-            HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_upload, 0));
-        }
-        ctx->upload_ordered_on = s;
-    }
-    RasterParams P = ctx->P;
-    P.row0 = spec.row0;
-    P.row1 = spec.row1;
-    P.tile_y0 = spec.tile_y0;
-    P.tile_stride = spec.tile_stride;
-    P.tiles_y = spec.tiles_y;
-    P.compact = spec.compact ? 1u : 0u;
-    P.out = (uint32_t *)dev_pixels;
-    P.out_row_stride = P.width;
-    P.out_base_row = (spec.external && !spec.compact) ? (int64_t)spec.row0 : 0;
-    // Rows that nothing of the frame can reach (ctx->content_row0 / 1) take the miss colour from a fill at memory speed; the pre-pass and
-    // the raster kernel are launched over the tile rows in between only.  A sparse frame pays for its empty tiles otherwise: a workgroup
-    // each that fetches its bin's length to learn that there is nothing to do -- on the 1 M-triangle grid (the 84 tile rows above the grid
-    // are empty) 0.575 -> 0.531 ms for the band alone (tools/band_probe.py, profiles/r04).  Contiguous bands only (not the stripe
-    // launches of a multi-GPU share).
-    uint32_t fill_a0 = 0, fill_a1 = 0, fill_b0 = 0, fill_b1 = 0;  // rows [a0, a1) above and [b0, b1) below the content
-    uint32_t c0 = 0, c1 = 0;
-    if (content_band(ctx, spec, c0, c1)) {
-        fill_a0 = spec.row0; fill_a1 = c0; fill_b0 = c1; fill_b1 = spec.row1;
-        P.row0 = c0;
-        P.row1 = c1;
-        P.tile_y0 = c0 / RXR_TILE_H;
-        P.tiles_y = c1 > c0 ? (c1 + RXR_TILE_H - 1u) / RXR_TILE_H - P.tile_y0 : 0u;
-    }
-    P.row_spans = nullptr;
-    bool use_spans = ctx->spans_active && fill_a0 < fill_b1 /* (the clamp above applied) */ && P.tiles_y;
-    auto widest_span = [&](uint32_t first_row, uint32_t n_rows) {
-        uint32_t w = 1u;
-        for (uint32_t r = first_row; r < first_row + n_rows && r < RXR_MAX_TILE_ROWS; ++r) w = std::max(w, ctx->h_row_spans[r].y - ctx->h_row_spans[r].x);
-        return w;
-    };
-    const size_t n_bins = (size_t)P.tiles_x * P.tiles_y;
-
-    // Kernel timing is opt-in (rxr_profile_begin): per-dispatch start / stop events (rxr_launch.h), no event record on the stream.
-    // Without it rxr_stats' *_us fields stay zero.
-    const bool timed = !retry && !ctx->prof.empty() && (ctx->prof_calls++ % ctx->prof_stride) == 0u;  // (a re-render after a list overflow takes no profiling slot)
-    ProfSlot *slot = nullptr;
-    if (timed) {
-        slot = &ctx->prof[ctx->prof_next % ctx->prof.size()];
-        slot->n = 0;
-        slot->raster_first = RXR_PROF_MAX_KERNELS;
-        ctx->prof_next++;
-    }
-    ctx->last_prof = slot;
-    // (every kernel this thread launches until the guard goes takes a start / stop pair of the slot: rxr_launch.h)
-    struct TimesGuard {
-        explicit TimesGuard(ProfSlot *p) { rxr_launch_times = p; }
-        ~TimesGuard() { rxr_launch_times = nullptr; }
-    } times_guard(slot);
-    // small scenes: one staging round of k_raster holds every triangle -> no set-up / binning launches at all
-    const bool d3 = P.tiles_y && (P.flags & RXR_FLAG_D3_ACTIVE);
-    P.fused_small = (d3 && P.n_tris3d <= RXR_STAGE_TRIS) ? ctx->small_mode : 0u;
-    if (P.kernel_level != KL_COMMON && P.fused_small == 1u) P.fused_small = 2u;  // k_raster_vm reads the records k_setup3d writes
-    ctx->last_setup_route = 0u;
-    if (d3 && P.fused_small) {
-        if (ctx->frame_uses_meshes) rxr_launch_project(&ctx->PP, s);
-        // The frame's own records, made by rxr_upload_frame for the band [0, height), serve every render whose band starts on a tile row
-        // and ends on one or at the frame's height: the only words of a record that depend on the band are its pixel box's min_y / max_y,
-        // and whatever reads them (visit, the tile reject and covers_plainly of scan_implicit) compares them with rows of launched tiles or
-        // of pixels inside the band -- with the same answer under the whole-frame clamp.  Under any other band a tile's set of active lanes,
-        // and with it the wave votes of the relaxed paths, would differ: such a render keeps the launch with its own clamp.
-        const bool band_on_tiles = P.row0 % RXR_TILE_H == 0u && (P.row1 % RXR_TILE_H == 0u || P.row1 == P.height);
-        if (P.fused_small == 2u && ctx->host_records && band_on_tiles) {
-            P.tri_setup = (TriSetup *)((uint8_t *)ctx->d_frame.p + ctx->off_host_setup);  // (read only: no launch of this render writes records)
-            P.tri_shade = (TriShade *)((uint8_t *)ctx->d_frame.p + ctx->off_host_shade);
-            ctx->last_setup_route = 1u;
-        } else if (P.fused_small == 2u) {
-            rxr_launch_setup(&P, s);  // records only; no counters, bins or lists are touched
-            ctx->last_setup_route = 2u;
-        }
-    }
-    use_spans = use_spans && rxr_raster_takes_spans(&P) != 0;  // (the kernel this launch gets must be one that looks the table up)
-    if (use_spans) {
-        // the pixels to the left and right of each tile row's span, and -- in the same launch: their spans are empty -- the rows above
-        // and below the content (one launch of 13 us where two fills of whole rows and one of row ends took 16 and two more gaps)
-        P.row_spans = (const uint2 *)ctx->d_row_spans.p;
-        RasterParams Pf = P;
-        Pf.row0 = spec.row0;
-        Pf.row1 = spec.row1;
-        Pf.tile_y0 = spec.tile_y0;
-        Pf.tiles_y = spec.tiles_y;
-        rxr_launch_fill_outside_spans(&Pf, s);
-    } else {
-        for (int part = 0; part < 2; ++part) {  // the rows outside the content: the 3D miss colour [0, 0, 0, 255] (:420-461)
-            const uint32_t a = part ? fill_b0 : fill_a0, b = part ? fill_b1 : fill_a1;
-            if (a < b) rxr_launch_fill_words(P.out + (size_t)((int64_t)a - P.out_base_row) * P.out_row_stride, (uint64_t)(b - a) * P.out_row_stride, 0xFF000000u, s);
-        }
-    }
-    const bool prepass = d3 && !P.fused_small;
-    // (device-projected frames: the spans are completed on the device, behind the projection -- see rxr_upload_frame)
-    const bool dev_spans = prepass && ctx->dev_spans && ctx->frame_uses_meshes && spec.tile_stride == 1u && !spec.compact && rxr_raster_takes_spans(&P) != 0;
-    // device-projected 2D batches: Batch2D::project + the Prim2D records, before anything reads them
-    // (a frame without 2D primitives never reads what they would write: no launch)
-    const bool project2d = ctx->frame_uses_meshes2d && P.tiles_y && (P.flags & RXR_FLAG_D2_ACTIVE) && ctx->PP2.n_prims;
-    bool projected2d = false;
-    auto project_meshes = [&]() {
-        rxr_launch_project(&ctx->PP, s);  // clip_and_project + Edges + boxes on the device
-        if (dev_spans) {
-            if (project2d) {  // (its union box belongs to the table)
-                rxr_launch_project2d(&ctx->PP2, s);
-                projected2d = true;
-            }
-            P.row_spans = (const uint2 *)ctx->d_row_spans.p;
-            rxr_launch_spans_from_meshes(&P, (P.height + RXR_TILE_H - 1u) / RXR_TILE_H, project2d ? ctx->PP2.d2_box : nullptr,
-                                         spans_event ? ctx->h_row_spans + RXR_MAX_TILE_ROWS : nullptr, s);
-            if (spans_event && hipEventRecord(spans_event, s) == hipSuccess && spans_recorded) *spans_recorded = true;
-            rxr_launch_fill_outside_spans(&P, s);
-        }
-    };
-    if (prepass && ctx->scratch_dirty) {
-        // a previous launch sequence was cut short: restore the all-zero invariants explicitly
-        HIPCHK(ctx, hipMemsetAsync(ctx->d_bin_count.p, 0, ctx->d_bin_count.cap, s));
-        HIPCHK(ctx, hipMemsetAsync(ctx->d_counters.p, 0, ctx->d_counters.cap, s));
-    }
-    // mid-sized scenes: k_setup3d (records and boxes only) + k_blockscan; the counters are not touched (the clean set stays clean, the
-    // large list stays empty: every block of bins looks at every triangle)
-    const bool blockscan = prepass && !ctx->blockscan_off && (size_t)n_bins * ctx->blockscan_cap <= (size_t)P.list_capacity;
-    ctx->last_used_blockscan = blockscan;
-    if (blockscan) {
-        ctx->scratch_dirty = true;
-        P.blockscan_cap = ctx->blockscan_cap;
-        // (the scatter form counts its wide groups in the clean counter set and clears the other one, as k_scan does)
-        P.counters = (uint32_t *)ctx->d_counters.p + (size_t)ctx->parity * CNT_WORDS;
-        P.counters_next = (uint32_t *)ctx->d_counters.p + (size_t)(ctx->parity ^ 1u) * CNT_WORDS;
-        if (P.blockscan_scatter) ctx->parity ^= 1u;
-        if (ctx->frame_uses_meshes) project_meshes();
-        rxr_launch_setup(&P, s);
-        ctx->last_setup_route = 2u;
-        rxr_launch_blockscan(&P, s);
-    } else if (prepass) {
-        ctx->scratch_dirty = true;
-        // counter set `parity` is clean (cleared by the previous launch's k_scan); this launch's k_scan
-        // clears the other set.  bin_count is clean because k_raster hands every bin back zeroed -- under row spans every bin that a
-        // triangle is counted into lies inside its row's span (make_setup clips the pixel boxes to the batch's reference tiles, from which
-        // the spans are made), so its workgroup runs and hands it back too.
-        P.counters = (uint32_t *)ctx->d_counters.p + (size_t)ctx->parity * CNT_WORDS;
-        P.counters_next = (uint32_t *)ctx->d_counters.p + (size_t)(ctx->parity ^ 1u) * CNT_WORDS;
-        ctx->parity ^= 1u;
-        if (ctx->frame_uses_meshes) project_meshes();
-        rxr_launch_setup(&P, s);
-        ctx->last_setup_route = 2u;
-        ScanArgs A{};
-        A.n = P.tiles_x * P.tiles_y;
-        A.list_capacity = P.list_capacity;
-        A.count = P.bin_count;
-        A.offset = P.bin_offset;
-        A.cursor = P.bin_cursor;
-        A.chunk_tot = P.chunk_tot;
-        A.chunk_base = P.chunk_base;
-        A.counters = P.counters;
-        A.counters_next = P.counters_next;
-        A.host_status = P.host_status;
-        rxr_launch_scan(&A, s);
-        rxr_launch_fill(&P, s);
-    }
-    // (the pinned status words are never written by the host while launches may be in flight: earlier queued k_scan
-    // launches write them; rxr_synchronize clears them once the streams have drained)
-    (void)n_bins;
-    if (project2d && !projected2d) rxr_launch_project2d(&ctx->PP2, s);
-    // 2D binning pre-pass (many 2D primitives): count -> scan -> fill; k_raster sorts each tile's list
-    const bool prepass2d = P.tiles_y && (P.flags & RXR_FLAG_D2_ACTIVE) && P.binned2d;
-    if (prepass2d) {
-        if (ctx->scratch2d_dirty) {
-            HIPCHK(ctx, hipMemsetAsync(ctx->d_bin2d_count.p, 0, ctx->d_bin2d_count.cap, s));
-            HIPCHK(ctx, hipMemsetAsync((uint32_t *)ctx->d_counters.p + 2 * CNT_WORDS, 0, 2 * CNT_WORDS * sizeof(uint32_t), s));
-        }
-        ctx->scratch2d_dirty = true;
-        const bool blockscan2d = !ctx->blockscan2d_off && (size_t)n_bins * RXR_BLOCKSCAN_CAP <= (size_t)P.list2d_capacity;
-        ctx->last_used_blockscan2d = blockscan2d;
-        if (blockscan2d) {  // the counters stay clean (no large list, no ticket); the raster kernel skips its per-tile sort
-            P.blockscan2d_cap = RXR_BLOCKSCAN_CAP;
-            P.counters2d = (uint32_t *)ctx->d_counters.p + (size_t)(2u + ctx->parity2d) * CNT_WORDS;
-            rxr_launch_blockscan2d(&P, s);
-        } else {
-        P.counters2d = (uint32_t *)ctx->d_counters.p + (size_t)(2u + ctx->parity2d) * CNT_WORDS;
-        P.counters2d_next = (uint32_t *)ctx->d_counters.p + (size_t)(2u + (ctx->parity2d ^ 1u)) * CNT_WORDS;
-        ctx->parity2d ^= 1u;
-        rxr_launch_bin2d_count(&P, s);
-        ScanArgs A{};
-        A.n = P.tiles_x * P.tiles_y;
-        A.list_capacity = P.list2d_capacity;
-        A.count = P.bin2d_count;
-        A.offset = P.bin2d_offset;
-        A.cursor = P.bin2d_cursor;
-        A.chunk_tot = P.chunk2d_tot;
-        A.chunk_base = P.chunk2d_base;
-        A.counters = P.counters2d;
-        A.counters_next = P.counters2d_next;
-        A.host_status = P.host_status2d;
-        rxr_launch_scan(&A, s);
-        rxr_launch_bin2d_fill(&P, s);
-        }
-    }
-    if (slot) slot->raster_first = slot->n;
-    ctx->last_raster_kernel = "";  // (a frame that launches none: empty, or only filled)
-    if (n_raster_bands > 1u && spec.tile_stride == 1u && !spec.compact) {
-        if (band_row_of)
-            for (uint32_t k = 0; k <= n_raster_bands; ++k) band_row_of[k] = k ? spec.row1 : spec.row0;  // (a frame without content: one band of filled rows)
-        const uint32_t rows_all = P.tiles_y, first_row = P.tile_y0, r0_all = P.row0, r1_all = P.row1;
-        for (uint32_t k = 0; k < n_raster_bands; ++k) {
-            const uint32_t a = (uint32_t)((uint64_t)rows_all * k / n_raster_bands), b = (uint32_t)((uint64_t)rows_all * (k + 1u) / n_raster_bands);
-            P.bin_row0 = a;
-            P.tile_y0 = first_row + a;
-            P.tiles_y = b - a;
-            P.row0 = std::max(r0_all, (first_row + a) * (uint32_t)RXR_TILE_H);
-            P.row1 = std::min(r1_all, (first_row + b) * (uint32_t)RXR_TILE_H);
-            if (band_row_of) {  // (the first and the last band take the filled rows above / below the content with them)
-                band_row_of[k] = k ? P.row0 : spec.row0;
-                band_row_of[k + 1u] = k + 1u < n_raster_bands ? P.row1 : spec.row1;
-            }
-            if (P.tiles_y && !rxr_jit_launch(ctx, &P, s)) ctx->last_raster_kernel = rxr_launch_raster_grid(&P, use_spans ? widest_span(P.tile_y0, P.tiles_y) : 0u, s);
-            if (band_events) HIPCHK(ctx, hipEventRecord(band_events[k], s));
-        }
-    } else if (!rxr_jit_launch(ctx, &P, s)) ctx->last_raster_kernel = rxr_launch_raster_grid(&P, use_spans ? widest_span(P.tile_y0, P.tiles_y) : 0u, s);
-    HIPCHK(ctx, hipGetLastError());
-    ctx->scratch_dirty = false;  // the raster launch that hands the bins back is queued
-    ctx->scratch2d_dirty = false;
-    ctx->rendered = true;
-    ctx->last_had_prepass = prepass;
-    ctx->last_had_prepass2d = prepass2d;
-    ctx->launches_since_sync++;
-    ctx->last_spec = spec;
-    ctx->last_out = dev_pixels;
-    ctx->last_stream = s;
-    ctx->stats.tiles_x = P.tiles_x;
-    ctx->stats.tiles_y = P.tiles_y;
-    ctx->stats.n_triangles3d = P.n_tris3d;
-    ctx->stats.n_triangles2d = ctx->n_tris2d;
-    return RXR_OK;
-}
-
-static int band_spec(rxr_ctx *ctx, uint32_t row0, uint32_t row1, bool external, RenderSpec &spec) {
-    if (!ctx->has_frame) return rxr_fail(ctx, RXR_ERR_INVALID, "render: no frame uploaded");
-    if (row0 > row1 || row1 > ctx->P.height) return rxr_fail(ctx, RXR_ERR_INVALID, "render: bad row range");
-    spec.row0 = row0;
-    spec.row1 = row1;
-    spec.tile_y0 = row0 / RXR_TILE_H;
-    spec.tile_stride = 1;
-    spec.tiles_y = row1 > row0 ? (row1 + RXR_TILE_H - 1) / RXR_TILE_H - spec.tile_y0 : 0;
-    spec.compact = false;
-    spec.external = external;
-    return RXR_OK;
-}
-
-int rxr_render_rows(rxr_ctx *ctx, uint32_t row0, uint32_t row1) {
-    if (!ctx) return RXR_ERR_INVALID;
-    if (ctx->group) {
-        (void)row0;
-        (void)row1;
-        return rxr_fail(ctx, RXR_ERR_UNSUPPORTED, "rxr_render_rows on a multi-device context: use rxr_rasterize / rxr_render_download / rxr_render_gather, or drive the members (rxr_member) yourself");
-    }
-    RenderSpec spec{};
-    int rc = band_spec(ctx, row0, row1, false, spec);
-    if (rc != RXR_OK) return rc;
-    return render_impl(ctx, spec, ctx->d_fb.p, ctx->stream);
-}
-
-int rxr_render_rows_to(rxr_ctx *ctx, uint32_t row0, uint32_t row1, void *dev_pixels, void *hip_stream) {
-    if (!ctx) return RXR_ERR_INVALID;
-    if (!dev_pixels) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_render_rows_to: dev_pixels is NULL");
-    if (ctx->group) return rxr_fail(ctx, RXR_ERR_UNSUPPORTED, "rxr_render_rows_to on a multi-device context: device pointers and streams belong to ONE device (use rxr_member)");
-    RenderSpec spec{};
-    int rc = band_spec(ctx, row0, row1, true, spec);
-    if (rc != RXR_OK) return rc;
-    return render_impl(ctx, spec, dev_pixels, hip_stream ? (hipStream_t)hip_stream : ctx->stream);
-}
-
-int rxr_render_stripes_to(rxr_ctx *ctx, uint32_t first, uint32_t stride, void *dev_pixels, void *hip_stream) {
-    if (!ctx) return RXR_ERR_INVALID;
-    if (!dev_pixels) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_render_stripes_to: dev_pixels is NULL");
-    if (ctx->group) return rxr_fail(ctx, RXR_ERR_UNSUPPORTED, "rxr_render_stripes_to on a multi-device context: device pointers and streams belong to ONE device (use rxr_member)");
-    if (!ctx->has_frame) return rxr_fail(ctx, RXR_ERR_INVALID, "render: no frame uploaded");
-    if (stride == 0) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_render_stripes_to: stride 0");
-    const uint32_t n_stripes = (ctx->P.height + RXR_TILE_H - 1) / RXR_TILE_H;
-    RenderSpec spec{};
-    spec.row0 = 0;
-    spec.row1 = ctx->P.height;
-    spec.tile_y0 = first;
-    spec.tile_stride = stride;
-    spec.tiles_y = first < n_stripes ? (n_stripes - first + stride - 1) / stride : 0;
-    spec.compact = true;
-    spec.external = true;
-    return render_impl(ctx, spec, dev_pixels, hip_stream ? (hipStream_t)hip_stream : ctx->stream);
-}
-
-static int stripes_spec(rxr_ctx *ctx, uint32_t first, uint32_t stride, RenderSpec &spec) {
-    if (!ctx->has_frame) return rxr_fail(ctx, RXR_ERR_INVALID, "render: no frame uploaded");
-    if (stride == 0) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_render_stripes: stride 0");
-    const uint32_t n_stripes = (ctx->P.height + RXR_TILE_H - 1) / RXR_TILE_H;
-    spec.row0 = 0;
-    spec.row1 = ctx->P.height;
-    spec.tile_y0 = first;
-    spec.tile_stride = stride;
-    spec.tiles_y = first < n_stripes ? (n_stripes - first + stride - 1) / stride : 0;
-    spec.compact = true;
-    spec.external = true;
-    return RXR_OK;
-}
-
-int rxr_render_stripes_batch(rxr_ctx *ctx, uint32_t first, uint32_t stride, uint32_t n_frames, void *dev_pixels, size_t frame_stride_bytes,
-                             void *hip_stream) {
-    if (!ctx) return RXR_ERR_INVALID;
-    if (!dev_pixels) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_render_stripes_batch: dev_pixels is NULL");
-    if (ctx->group) return rxr_group_render_stripes_batch(ctx, first, stride, n_frames, dev_pixels, frame_stride_bytes, hip_stream);
-    RenderSpec spec{};
-    int rc = stripes_spec(ctx, first, stride, spec);
-    if (rc != RXR_OK) return rc;
-    if (n_frames > 1u && frame_stride_bytes < (size_t)spec.tiles_y * RXR_TILE_H * ctx->P.width * 4u)
-        return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_render_stripes_batch: frame_stride_bytes is smaller than one compact stripe buffer");
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-    for (uint32_t k = 0; k < n_frames; ++k)
-        if ((rc = render_impl(ctx, spec, (uint8_t *)dev_pixels + (size_t)k * frame_stride_bytes, s)) != RXR_OK) return rc;
-    return RXR_OK;
-}
-
-int rxr_profile_begin(rxr_ctx *ctx, uint32_t max_frames) {
-    if (!ctx) return RXR_ERR_INVALID;
-    if (ctx->group) return rxr_profile_begin(rxr_member(ctx, 0), max_frames);  // kernel timing of a multi-device context: member 0's
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc = rxr_synchronize(ctx);
-    if (rc != RXR_OK) return rc;
-    for (ProfSlot &p : ctx->prof)
-        for (hipEvent_t e : p.ev)
-            if (e) (void)hipEventDestroy(e);
-    ctx->prof.clear();
-    ctx->last_prof = nullptr;
-    ctx->prof_next = 0;
-    ctx->prof_calls = 0;
-    if (max_frames > 65536) max_frames = 65536;
-    ctx->prof.assign(max_frames, ProfSlot{});  // (the events of a slot are created when a render first needs them: rxr_launch.h)
-    return RXR_OK;
-}
-
-int rxr_profile_stride(rxr_ctx *ctx, uint32_t stride) {
-    if (!ctx || stride == 0) return RXR_ERR_INVALID;
-    if (ctx->group) return rxr_profile_stride(rxr_member(ctx, 0), stride);
-    ctx->prof_stride = stride;
-    ctx->prof_calls = 0;
-    return RXR_OK;
-}
-
-int rxr_profile_read(rxr_ctx *ctx, float *setup_us, float *raster_us, uint32_t capacity, uint32_t *n_out) {
-    if (!ctx || !n_out) return RXR_ERR_INVALID;
-    if (ctx->group) return rxr_profile_read(rxr_member(ctx, 0), setup_us, raster_us, capacity, n_out);
-    int rc = rxr_synchronize(ctx);
-    if (rc != RXR_OK) return rc;
-    uint32_t n = (uint32_t)std::min<size_t>(std::min<size_t>(ctx->prof_next, ctx->prof.size()), capacity);
-    for (uint32_t i = 0; i < n; ++i) {
-        float a = 0, b = 0;
-        if (!rxr_prof_slot_us(ctx->prof[i], &a, &b)) return rxr_fail(ctx, RXR_ERR_HIP, "rxr_profile_read: a kernel's start / stop events could not be read");
-        if (setup_us) setup_us[i] = a;
-        if (raster_us) raster_us[i] = b;
-    }
-    *n_out = n;
-    ctx->prof_next = 0;
-    return RXR_OK;
-}
-
-int rxr_render_spec(rxr_ctx *ctx, const RenderSpec &spec, void *dev_pixels, hipStream_t s) { return render_impl(ctx, spec, dev_pixels, s); }
-
-// Waits for everything this context has queued and reports what the launches since the previous call left in the pinned
-// status words.  Those words are sticky (the device only sets / raises them), so an overflow or a program fault of ANY
-// launch since the last call is seen, not only the last one's:
-//   - a bin list overflowed: the lists are grown; the LAST launch is rendered again (its output is then complete); if
-//     earlier launches were queued in between (an asynchronous caller that does not synchronize per frame) their frames
-//     were shipped incomplete and the call returns RXR_ERR_OVERFLOW to say so;
-//   - a fragment's program faulted, or an opacity staircase dropped an entry: an error, see the messages.
-int rxr_synchronize(rxr_ctx *ctx) {
-    if (!ctx) return RXR_ERR_INVALID;
-    if (ctx->group) return rxr_group_synchronize(ctx);
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    bool earlier_incomplete = false;
-    for (int attempt = 0; attempt < 4; ++attempt) {
-        int qrc = rxr_quiesce(ctx);
-        if (qrc != RXR_OK) return qrc;
-        const uint32_t launches = ctx->launches_since_sync;
-        ctx->launches_since_sync = 0;
-        if (ctx->h_bake_fault && ctx->h_bake_fault[0]) return rxr_bake_report_fault(ctx);  // a queued bake's program faulted (rxr_bake.hip)
-        if (!ctx->rendered) return RXR_OK;
-        uint32_t *hc = ctx->h_counters;
-        if (hc[HS_VM_FAULT] == VMF_JIT_PALETTE_MISS) {
-            // not a fault of the program: a compiled set met a palette slot without a colour, where the reference pushes nothing -- only
-            // the interpreter's dynamic stack follows that.  The set runs interpreted from now on; the last launch is rendered again, an
-            // earlier one of this batch of launches was incomplete (reported like an overflow).
-            hc[HS_VM_FAULT] = 0;
-            ctx->jit_palette_miss = true;
-            ctx->jit_info = "not compiled: a PaletteIndex met a missing or empty palette slot (the interpreter follows the reference's shorter stack)";
-            if (launches > 1u) earlier_incomplete = true;
-            int rc = render_impl(ctx, ctx->last_spec, ctx->last_out, ctx->last_stream, true);
-            if (rc != RXR_OK) return rc;
-            continue;
-        }
-        if (hc[HS_VM_FAULT]) {
-            // a fragment's program did what makes the reference panic (rxr_vm.h, VMF_*)
-            static const char *const what[] = {"", "stack underflow", "stack overflow", "local index out of range", "global index out of range",
-                                               "call depth", "loop depth", "instruction limit (runaway loop)", "clamp with min > max",
-                                               "call of a missing function", "bad opcode", "too many locals"};
-            uint32_t code = hc[HS_VM_FAULT];
-            hc[HS_VM_FAULT] = 0;
-            return rxr_fail(ctx, RXR_ERR_INVALID, std::string("shader program fault: ") + (code < sizeof(what) / sizeof(what[0]) ? what[code] : "?"));
-        }
-        if (hc[HS_BAD_LINE2D]) {
-            hc[HS_BAD_LINE2D] = 0;
-            return rxr_fail(ctx, RXR_ERR_UNSUPPORTED, "batch2d: line end point NaN or beyond +-2^30");
-        }
-        if (hc[HS_STAIRCASE]) {
-            hc[HS_STAIRCASE] = 0;
-            return rxr_fail(ctx, RXR_ERR_UNSUPPORTED,
-                        "four or more groups of opacity batches nest as prefix minima in one pixel: the device keeps three per pixel (surface_id, "
-                        "rasterizer.rs:314-357, :1044-1048) and had to drop one; the frame may differ from the reference");
-        }
-        ctx->stats.n_bin_entries = (ctx->last_had_prepass && !ctx->last_used_blockscan) ? hc[CNT_ENTRIES] : 0u;  // (k_blockscan does not count its entries)
-        const bool over3d = hc[CNT_OVERFLOW] != 0, over2d = hc[CNT_WORDS + CNT_OVERFLOW] != 0;
-        if (!over3d && !over2d) {
-            float a = 0, b = 0;
-            if (ctx->last_prof && rxr_prof_slot_us(*ctx->last_prof, &a, &b)) {
-                ctx->stats.setup_us = a;
-                ctx->stats.raster_us = b;
-                ctx->stats.total_us = a + b;
-            }
-            if (earlier_incomplete)
-                return rxr_fail(ctx, RXR_ERR_OVERFLOW,
-                            "a bin list overflowed in a launch that was not the last one before this rxr_synchronize: that frame was "
-                            "incomplete (the lists have been grown and the last launch rendered again)");
-            return RXR_OK;
-        }
-        if (launches > 1u) earlier_incomplete = true;
-        int rc;
-        if (over2d && ctx->last_used_blockscan2d) {
-            // a block of bins or a bin had more 2D primitives than k_blockscan2d keeps: count / scan / fill (and the per-tile sort) for this frame
-            ctx->blockscan2d_off = true;
-            ctx->blockscan2d_bad.add(ctx->P.n_prims2d, (size_t)ctx->P.tiles_x * ((ctx->P.height + RXR_TILE_H - 1) / RXR_TILE_H));
-            hc[CNT_WORDS + CNT_OVERFLOW] = hc[CNT_WORDS + HS_MAX_ENTRIES] = 0;
-        } else if (over2d) {
-            const size_t seen = std::max(hc[CNT_WORDS + HS_MAX_ENTRIES], hc[CNT_WORDS + CNT_ENTRIES]);
-            if ((rc = rxr_ensure(ctx, ctx->d_list2d, (seen + seen / 2 + 1024) * sizeof(uint32_t))) != RXR_OK) return rc;
-            ctx->list2d_capacity = (uint32_t)std::min<size_t>(ctx->d_list2d.cap / sizeof(uint32_t), 0xFFFFFFF0u);
-            ctx->P.bin2d_list = (uint32_t *)ctx->d_list2d.p;
-            ctx->P.list2d_capacity = ctx->list2d_capacity;
-            hc[CNT_WORDS + CNT_OVERFLOW] = hc[CNT_WORDS + HS_MAX_ENTRIES] = 0;
-        }
-        if (over3d && ctx->last_used_blockscan) {
-            // a block of bins or a bin had more candidates than k_blockscan keeps: this frame takes the general pipeline
-            ctx->blockscan_off = true;
-            ctx->blockscan_bad.add(ctx->P.n_tris3d, (size_t)ctx->P.tiles_x * ((ctx->P.height + RXR_TILE_H - 1) / RXR_TILE_H));
-            hc[CNT_OVERFLOW] = hc[HS_MAX_ENTRIES] = 0;
-        } else if (over3d) {
-            const size_t seen = std::max(hc[HS_MAX_ENTRIES], hc[CNT_ENTRIES]);
-            if ((rc = rxr_ensure(ctx, ctx->d_list, (seen + seen / 2 + 1024) * sizeof(uint32_t))) != RXR_OK) return rc;
-            ctx->list_capacity = (uint32_t)std::min<size_t>(ctx->d_list.cap / sizeof(uint32_t), 0xFFFFFFF0u);
-            ctx->P.bin_list = (uint32_t *)ctx->d_list.p;
-            ctx->P.list_capacity = ctx->list_capacity;
-            hc[CNT_OVERFLOW] = hc[HS_MAX_ENTRIES] = 0;
-        }
-        // the same launch again, now with room (the streams are idle: see rxr_quiesce above)
-        if ((rc = render_impl(ctx, ctx->last_spec, ctx->last_out, ctx->last_stream, true)) != RXR_OK) return rc;
-    }
-    return rxr_fail(ctx, RXR_ERR_OOM, "bin list kept overflowing");
-}
-
-int rxr_download_rows(rxr_ctx *ctx, uint8_t *pixels, uint32_t row0, uint32_t row1) {
-    if (!ctx || !pixels) return RXR_ERR_INVALID;
-    if (ctx->group) return rxr_fail(ctx, RXR_ERR_UNSUPPORTED, "rxr_download_rows on a multi-device context: use rxr_rasterize / rxr_render_download");
-    if (!ctx->has_frame || row0 > row1 || row1 > ctx->P.height) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_download_rows: bad row range or no frame");
-    int rc = rxr_synchronize(ctx);
-    if (rc != RXR_OK) return rc;
-    size_t off = (size_t)row0 * ctx->P.width * 4, bytes = (size_t)(row1 - row0) * ctx->P.width * 4;
-    if (bytes) {
-        HIPCHK(ctx, hipMemcpyAsync(pixels + off, (uint8_t *)ctx->d_fb.p + off, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return RXR_OK;
-}
-
-int rxr_rasterize(rxr_ctx *ctx, const rxr_frame *frame, uint8_t *pixels) {
-    if (!ctx || !pixels) return RXR_ERR_INVALID;
-    int rc = rxr_upload_frame(ctx, frame);
-    if (rc != RXR_OK) return rc;
-    return rxr_render_download(ctx, pixels);
-}
-
-int rxr_render_download(rxr_ctx *ctx, uint8_t *pixels) {
-    if (!ctx || !pixels) return RXR_ERR_INVALID;
-    if (ctx->group) return rxr_group_render_download(ctx, pixels);
-    if (!ctx->has_frame) return rxr_fail(ctx, RXR_ERR_INVALID, "rxr_render_download: no frame uploaded");
-    int rc = RXR_OK;
-    // The download of a 4K frame over PCIe takes longer than rendering it, so frames of 4 Mpixel and more are rastered in bands of tile
-    // rows and every finished band travels to the caller's buffer while the next ones render; rendering in bands is byte-identical to
-    // one launch (tested).  Measured: 3840x2160 0.90 -> 0.76 ms per call; at 1920x1080 the extra launches cost more than the overlap
-    // gains (0.26 -> 0.31 ms), hence the threshold.  Rounds 1-3 made four whole launch sequences of it and therefore served frames
-    // without a pre-pass only; since round 4 ONE pre-pass (projection, set-up, bins) is followed by four raster launches over its bins
-    // (render_impl, RasterParams.bin_row0), which serves binned and device-projected frames as well: the 8K frame of 1 M triangles
-    // downloads 133 MB in 2.4 ms behind 0.6 ms of kernels that used to come first.  A list overflow is repaired by rxr_synchronize as
-    // ever (lists grown, the whole frame rendered again); the frame is then downloaded once more.
-    const RasterParams &P = ctx->P;
-    const uint32_t H = P.height;
-    static const bool no_pipeline = getenv("RXR_NO_DOWNLOAD_PIPELINE") != nullptr;  // A-B runs
-    if (no_pipeline || (size_t)P.width * H < (1u << 22)) {
-        static const bool timing = getenv("RXR_E2E_TIMING") != nullptr;  // diagnostics (tools/e2e_probe.py): where a large frame's call goes
-        if (timing) {
-            using clk = std::chrono::steady_clock;
-            HIPCHK(ctx, hipSetDevice(ctx->device));
-            const auto t0 = clk::now();
-            HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // the tail of the upload's host->device copies
-            const auto t1 = clk::now();
-            rc = rxr_render_rows(ctx, 0, H);
-            if (rc != RXR_OK) return rc;
-            rc = rxr_synchronize(ctx);
-            if (rc != RXR_OK) return rc;
-            const auto t2 = clk::now();
-            rc = rxr_download_rows(ctx, pixels, 0, H);
-            const auto t3 = clk::now();
-            auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-            fprintf(stderr, "rxr_e2e_timing h2d_tail_ms=%.3f kernels_ms=%.3f download_ms=%.3f\n", ms(t0, t1), ms(t1, t2), ms(t2, t3));
-            return rc;
-        }
-        rc = rxr_render_rows(ctx, 0, H);
-        if (rc != RXR_OK) return rc;
-        return rxr_download_rows(ctx, pixels, 0, H);
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    constexpr uint32_t n_bands = 4;
-    uint32_t row_of[n_bands + 1] = {};
-    RenderSpec spec{};
-    rc = band_spec(ctx, 0, H, false, spec);
-    if (rc != RXR_OK) return rc;
-    const uint32_t rerenders_before = ctx->rerenders;
-    bool spans_back = false;
-    rc = render_impl(ctx, spec, ctx->d_fb.p, ctx->stream, false, n_bands, ctx->ev_band, row_of, ctx->ev_band[7], &spans_back);
-    if (rc != RXR_OK) return rc;
-    // Rows outside the frame's content are the miss colour on the device AND need not cross PCIe: the caller's rows are written here,
-    // by the host, while the device renders and the content rows travel (the 8K frame of the box grid: 40 of 133 MB that are not
-    // downloaded; the link is what bounds this call).
-    uint32_t c0 = 0, c1 = H;
-    bool clipped = content_band(ctx, spec, c0, c1);
-    if (spans_back) {
-        // device-projected meshes: the content is known once the projection has run -- the device hands its row-span table back a
-        // fraction of a millisecond into the frame (k_spans_from_meshes writes a copy into page-locked memory, an event behind it),
-        // long before the first band is rastered; this thread would only wait for the bands otherwise
-        HIPCHK(ctx, hipEventSynchronize(ctx->ev_band[7]));
-        const uint2 *back = ctx->h_row_spans + RXR_MAX_TILE_ROWS;
-        const uint32_t n_rows = (H + RXR_TILE_H - 1u) / RXR_TILE_H;
-        uint32_t r0 = n_rows, r1 = 0;
-        for (uint32_t r = 0; r < n_rows; ++r)
-            if (back[r].x < back[r].y) {
-                r0 = std::min(r0, r);
-                r1 = r + 1u;
-            }
-        const uint32_t d0 = r0 < r1 ? r0 * RXR_TILE_H : 0u, d1 = r0 < r1 ? std::min(r1 * (uint32_t)RXR_TILE_H, H) : 0u;
-        if ((size_t)(d0 + (H - d1)) / RXR_TILE_H * P.tiles_x >= content_min_tiles()) {  // (as content_band: a few rows are not worth the fills)
-            c0 = d0;
-            c1 = d1;
-            clipped = true;
-        }
-    }
-    // ... and inside the content rows the columns outside the tile rows' spans (host-projected frames: the table of rxr_upload_frame;
-    // device-projected ones: the table the device has just handed back) are the miss colour as well: each band travels as two strips of
-    // hipMemcpy2DAsync over the union of its tile rows' spans, the host writes what lies to the left and right.  Strips, not tile rows:
-    // a 2D copy costs about 13 us of its own (tools/microbench/copy2d.hip: 91 MB of whole rows 1.64 ms; the same trapezoid in 4 / 24 /
-    // 93 strips 1.18 / 1.33 / 2.05 ms).
-    struct Rect {
-        uint32_t r0, r1, x0, x1;  // pixel rows [r0, r1), pixel columns [x0, x1)
-    };
-    std::vector<Rect> fills, copies;
-    const uint32_t W = P.width;
-    if (clipped) {
-        fills.push_back({0u, c0, 0u, W});
-        fills.push_back({c1, H, 0u, W});
-    }
-    // (the table says where anything CAN be drawn whether or not the launches above used it: a frame whose content reaches from the
-    // first row to the last is not clamped in rows, but its row ends are still the miss colour)
-    const uint2 *table = spans_back ? ctx->h_row_spans + RXR_MAX_TILE_ROWS : (ctx->spans_active && ctx->content_known ? ctx->h_row_spans : nullptr);
-    if (getenv("RXR_NO_COLUMN_TRIM")) table = nullptr;  // A-B runs, tests (read per call)
-    constexpr uint32_t n_sub = 2;
-    size_t trimmed_px = 0;
-    for (uint32_t k = 0; k < n_bands; ++k) {
-        const uint32_t a = std::max(row_of[k], c0), b = std::min(row_of[k + 1], c1);
-        if (b <= a) continue;
-        const uint32_t ta = a / RXR_TILE_H, tb = (b + RXR_TILE_H - 1u) / RXR_TILE_H;   // tile rows of the band
-        for (uint32_t j = 0; j < (table ? n_sub : 1u); ++j) {
-            const uint32_t t0 = table ? ta + (tb - ta) * j / n_sub : ta, t1 = table ? ta + (tb - ta) * (j + 1u) / n_sub : tb;
-            const uint32_t r0 = std::max(a, t0 * (uint32_t)RXR_TILE_H), r1 = std::min(b, t1 * (uint32_t)RXR_TILE_H);
-            if (r1 <= r0) continue;
-            uint32_t x0 = 0u, x1 = W;
-            if (table) {
-                uint32_t lo = 0xFFFFFFFFu, hi = 0u;
-                for (uint32_t t = t0; t < t1 && t < RXR_MAX_TILE_ROWS; ++t)
-                    if (table[t].x < table[t].y) {
-                        lo = std::min(lo, table[t].x);
-                        hi = std::max(hi, table[t].y);
-                    }
-                if (lo >= hi) {  // nothing in these rows at all
-                    fills.push_back({r0, r1, 0u, W});
-                    trimmed_px += (size_t)(r1 - r0) * W;
-                    continue;
-                }
-                x0 = std::min(lo * (uint32_t)RXR_TILE_W, W);
-                x1 = std::min(hi * (uint32_t)RXR_TILE_W, W);
-                if ((size_t)(x1 - x0) * 10u >= (size_t)W * 9u) {  // (nearly the whole width: one contiguous copy is cheaper than a strided one)
-                    x0 = 0u;
-                    x1 = W;
-                }
-                trimmed_px += (size_t)(r1 - r0) * (W - (x1 - x0));
-            }
-            copies.push_back({r0, r1, x0, x1});
-        }
-    }
-    if (table && trimmed_px < content_min_tiles() * (size_t)(RXR_TILE_W * RXR_TILE_H)) {  // (8 MB by default) not worth the strided copies and the fills: whole rows, as without a table
-        copies.clear();
-        fills.resize(clipped ? 2u : 0u);
-        for (uint32_t k = 0; k < n_bands; ++k) {
-            const uint32_t a = std::max(row_of[k], c0), b = std::min(row_of[k + 1], c1);
-            if (b > a) copies.push_back({a, b, 0u, W});
-        }
-    }
-    for (const Rect &c : copies)
-        if (!(c.x0 == 0u && c.x1 == W)) {
-            fills.push_back({c.r0, c.r1, 0u, c.x0});
-            fills.push_back({c.r0, c.r1, c.x1, W});
-        }
-    // [0, 0, 0, 255] per pixel (:420-461), written by helper threads while the device renders and the link is busy (they start BEFORE the
-    // copies are queued: a copy into pageable memory keeps the calling thread until it has landed); the caller's buffer may be unaligned:
-    // bytes then.  Rows are dealt round robin.
-    size_t n_px = 0;
-    for (const Rect &f : fills) n_px += f.r1 > f.r0 && f.x1 > f.x0 ? (size_t)(f.r1 - f.r0) * (f.x1 - f.x0) : 0u;
-    const uint32_t n_threads = n_px >= (12u << 20) ? 8u : (n_px >= (4u << 20) ? 4u : (n_px ? 1u : 0u));
-    auto part = [&fills, pixels, W](uint32_t me, uint32_t of) {
-        const bool aligned = ((uintptr_t)pixels & 3u) == 0u;
-        uint32_t turn = 0;
-        for (const Rect &f : fills) {
-            if (f.r1 <= f.r0 || f.x1 <= f.x0) continue;
-            for (uint32_t r = f.r0; r < f.r1; ++r, ++turn) {
-                if (turn % of != me) continue;
-                uint8_t *p = pixels + ((size_t)r * W + f.x0) * 4;
-                const size_t n = f.x1 - f.x0;
-                if (aligned) std::fill((uint32_t *)p, (uint32_t *)p + n, 0xFF000000u);
-                else
-                    for (size_t i = 0; i < n; ++i) { p[4 * i] = 0; p[4 * i + 1] = 0; p[4 * i + 2] = 0; p[4 * i + 3] = 255; }
-            }
-        }
-    };
-    ctx->last_download_bytes = 0;
-    for (const Rect &c : copies) ctx->last_download_bytes += (uint64_t)(c.r1 - c.r0) * (c.x1 - c.x0) * 4u;
-    ctx->last_host_fill_bytes = (uint64_t)n_px * 4u;
-    std::vector<std::thread> helpers;
-    helpers.reserve(n_threads);
-    for (uint32_t t = 0; t < n_threads; ++t) {
-        try {
-            helpers.emplace_back(part, t, n_threads);
-        } catch (...) {  // (no thread to be had: this share is written here and now -- nothing may leave through the C ABI)
-            part(t, n_threads);
-        }
-    }
-    struct JoinAll {  // (every return path below, errors included, waits for the helpers: they write the caller's buffer)
-        std::vector<std::thread> &h;
-        ~JoinAll() { for (std::thread &th : h) if (th.joinable()) th.join(); }
-    } join_all{helpers};
-    {
-        size_t ci = 0;
-        for (uint32_t k = 0; k < n_bands; ++k) {
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->ev_band[k], 0));
-            for (; ci < copies.size() && copies[ci].r0 < row_of[k + 1]; ++ci) {  // (ascending rows; every strip lies inside one band)
-                const Rect &c = copies[ci];
-                const size_t off = ((size_t)c.r0 * W + c.x0) * 4;
-                if (c.x0 == 0u && c.x1 == W) {
-                    HIPCHK(ctx, hipMemcpyAsync(pixels + off, (uint8_t *)ctx->d_fb.p + off, (size_t)(c.r1 - c.r0) * W * 4, hipMemcpyDeviceToHost, ctx->copy_stream));
-                } else {
-                    HIPCHK(ctx, hipMemcpy2DAsync(pixels + off, (size_t)W * 4, (uint8_t *)ctx->d_fb.p + off, (size_t)W * 4, (size_t)(c.x1 - c.x0) * 4, c.r1 - c.r0,
-                                                 hipMemcpyDeviceToHost, ctx->copy_stream));
-                }
-            }
-        }
-    }
-    for (std::thread &th : helpers) th.join();  // (before anything below can write the same bytes again: the repaired frame's download)
-    HIPCHK(ctx, hipStreamSynchronize(ctx->copy_stream));
-    rc = rxr_synchronize(ctx);  // (program faults and list overflows are reported / repaired here)
-    if (rc != RXR_OK) return rc;
-    if (ctx->rerenders != rerenders_before) return rxr_download_rows(ctx, pixels, 0, H);  // the bands that travelled were incomplete
-    return RXR_OK;
-}
-
-int rxr_get_stats(rxr_ctx *ctx, rxr_stats *out) {
-    if (!ctx || !out) return RXR_ERR_INVALID;
-    if (ctx->group) return rxr_group_get_stats(ctx, out);
-    *out = ctx->stats;
-    return RXR_OK;
-}
-
-void *rxr_device_framebuffer(rxr_ctx *ctx) { return (ctx && !ctx->group) ? ctx->d_fb.p : nullptr; }
 
 // ---- Rusteria programs: NodeOp tree (include/rxr.h) -> jump code (rxr_device.h) ------------------
 namespace {
@@ -2645,3 +1890,8 @@ extern "C" int rxr_debug_jit_generate(const rxr_shader_set *set, int compile, ch
     }
     return RXR_OK;
 }
+
+// ---- rendering, rxr_synchronize, download, profiling ---------------------------------------------
+// A file of its own, but ONE translation unit with this one: tools/sanitize_cpu.sh builds the host side of the library from a fixed list
+// of sources, this file among them, and its library has to load -- every other file calls rxr_synchronize.
+#include "rxr_render.hip"

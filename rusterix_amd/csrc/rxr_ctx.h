@@ -435,10 +435,10 @@ int rxr_ensure_stage(rxr_ctx *ctx, size_t bytes);  // the same for the pinned st
 // waits until nothing queued by this context -- on its own streams or on the caller's stream of the last render -- is
 // still running: the precondition for rewriting the staging blob, the frame blob or any scratch buffer
 int rxr_quiesce(rxr_ctx *ctx);
-// one render launch sequence of a plain context (rxr_api.hip)
+// one render launch sequence of a plain context (rxr_render.hip)
 extern "C" int rxr_render_spec(rxr_ctx *ctx, const RenderSpec &spec, void *dev_pixels, hipStream_t s);
 
-// ---- defined here: what rxr_api.hip and rxr_upload.hip both need ----------------------------------
+// ---- defined here: what several host files need (rxr_render.hip, rxr_upload.hip, ...) ----------------------------------
 // sparse frames (rxr_ctx::content_row0 / 1, row spans): the empty tiles a clamp must save before its fill launches pay (RXR_CONTENT_MIN_TILES
 // overrides it -- the tests use small frames)
 static inline size_t content_min_tiles() {
