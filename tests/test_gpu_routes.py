@@ -186,12 +186,22 @@ SPARSE_W, SPARSE_H = 250, 150            # 16 x 10 tiles, the last column and ro
 SPAN_END_A, SPAN_END_B = 16 * 9, 16 * 13
 
 
-def sparse_scene(api, lights=0, overlay=True):
+def sparse_span_ends(width=SPARSE_W):
+    """the tile boundaries the two sheets of sparse_scene end next to, for a frame `width` pixels wide: (144, 208) at the default 250"""
+    return 16 * int(9 * width / SPARSE_W), 16 * int(13 * width / SPARSE_W)
+
+
+def sparse_scene(api, lights=0, overlay=True, width=SPARSE_W, height=SPARSE_H):
     """Identity view and projection (a vertex (x, y, z) lands at ((x + 1) W / 2, (1 - y) H / 2)): two sheets of small triangles.  Sheet A
     fills pixel rows 4..60 and ends one pixel LEFT of the tile boundary x = 144, sheet B fills rows 84..148 and ends one pixel RIGHT of
     x = 208; tile row 4 (pixels 64..79) is reached by nothing.  Under row spans the raster grid of rows 0..3 ends at column 9 and that of
-    rows 5..9 at column 14.  Every sheet is two layers of different depths, layer 0 of sheet A submitted twice (exact ties)."""
-    W, H = SPARSE_W, SPARSE_H
+    rows 5..9 at column 14.  Every sheet is two layers of different depths, layer 0 of sheet A submitted twice (exact ties).
+    `width`, `height`: every pixel position above scaled by width / 250 and height / 150 (the same number of triangles, each as much
+    larger), but for the two sheet ends, which stay one pixel left and right of a tile boundary (sparse_span_ends); the defaults give the
+    250 x 150 scene float for float (every factor is then 1.0)."""
+    W, H = width, height
+    kx, ky = W / SPARSE_W, H / SPARSE_H
+    end_a, end_b = sparse_span_ends(W)
     rng = np.random.default_rng([0x52585231, 3333])
     scene = api.Scene.empty()
     assets = api.Assets.default().textures([B.Tile([_texture(rng, 16, 16, False)])])
@@ -199,12 +209,12 @@ def sparse_scene(api, lights=0, overlay=True):
 
     def sheet(x0, y0, x1, y1, step, shift, z_lo):
         verts = []
-        xs, ys = np.arange(x0, x1, step), np.arange(y0, y1, step)
+        xs, ys = np.arange(x0, x1, step * kx), np.arange(y0, y1, step * ky)
         for sy in ys:
             for sx in xs:
                 z = float(rng.uniform(z_lo, z_lo + 0.2))
-                ax, ay = min(sx + shift, x1), min(sy + shift, y1)
-                bx, by = min(sx + shift + step, x1), min(sy + shift + step, y1)
+                ax, ay = min(sx + shift * kx, x1), min(sy + shift * ky, y1)
+                bx, by = min(sx + (shift + step) * kx, x1), min(sy + (shift + step) * ky, y1)
                 for px, py in ((ax, ay), (bx, ay), (ax, by), (bx, ay), (bx, by), (ax, by)):
                     verts.append((px / (W / 2) - 1.0, 1.0 - py / (H / 2), z))
         v = np.asarray(verts, np.float32)
@@ -212,10 +222,10 @@ def sparse_scene(api, lights=0, overlay=True):
         uv = (rng.random((len(v), 2)) * 2.0).astype(np.float32)
         return lambda: api.Batch3D.new(v4.copy(), np.arange(len(v), dtype=np.uint32).reshape(-1, 3), uv.copy()).with_computed_normals().cull_mode(B.CULL_OFF), len(v) // 3
 
-    for (x0, y0, x1, y1) in ((10.0, 4.0, SPAN_END_A - 1.0, 60.0), (100.0, 84.0, SPAN_END_B + 1.0, 148.0)):
+    for first, (x0, y0, x1, y1) in ((True, (10.0 * kx, 4.0 * ky, end_a - 1.0, 60.0 * ky)), (False, (100.0 * kx, 84.0 * ky, end_b + 1.0, 148.0 * ky))):
         for layer, (shift, z_lo) in enumerate(((0.0, -0.6), (3.0, -0.9))):
             make, nt = sheet(x0, y0, x1, y1, 7.0, shift, z_lo)
-            copies = 2 if (layer == 0 and y0 < 50.0) else 1
+            copies = 2 if (layer == 0 and first) else 1
             for c in range(copies):
                 src = B.PixelSource.StaticTileIndex(0) if c == 0 else B.PixelSource.Pixel((220, 50, 60, 255))
                 scene.add_d3_static(make().source(src).repeat_mode(B.REPEAT_REPEAT_XY).ambient_color((0.8, 0.9, 0.7)))
@@ -223,8 +233,8 @@ def sparse_scene(api, lights=0, overlay=True):
     if lights:
         scene.lights(point_lights(np.random.default_rng([9, lights]), lights, centre=(-0.1, 0.0, -0.2), spread=0.9, end=2.5))
     if overlay:
-        scene.add_d2_static(api.Batch2D.from_rectangle(20.0, 10.0, 41.0, 27.0).source(B.PixelSource.Pixel((250, 240, 30, 140))))
-        scene.add_d2_static(api.Batch2D.from_rectangle(120.0, 100.0, 33.0, 21.0).source(B.PixelSource.StaticTileIndex(0)))
+        scene.add_d2_static(api.Batch2D.from_rectangle(20.0 * kx, 10.0 * ky, 41.0 * kx, 27.0 * ky).source(B.PixelSource.Pixel((250, 240, 30, 140))))
+        scene.add_d2_static(api.Batch2D.from_rectangle(120.0 * kx, 100.0 * ky, 33.0 * kx, 21.0 * ky).source(B.PixelSource.StaticTileIndex(0)))
 
     def setup():
         return api.Rasterizer.setup(None, B.Mat4.identity(), B.Mat4.identity()).ambient((0.6, 0.6, 0.6, 1.0))
