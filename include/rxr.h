@@ -1007,7 +1007,8 @@ int rxr_terrain_hits_to(rxr_ctx *ctx, const float *dev_origins, const float *dev
  *   to its three vertices; each sum is divided by its count and normalised again.
  * Kept as it is: the last row and column of corners read the neighbouring chunks' heights, or 0.0 where no cell is listed; uvs are
  * all [0, 0] and do not cross this boundary; a NaN height gives NaN normals (a NaN is a NaN: sign and payload are the device's); a
- * sum of length zero divides by zero.  build_mesh_d2 and process_batch_modifiers are host work and not part of this. */
+ * sum of length zero divides by zero.  build_mesh_d2 and process_batch_modifiers' Colorize pass are host work and not part of
+ * this (its Height pass: rxr_flatten_terrain below). */
 #define RXR_TERRAIN_MESH_MAX_CHUNK_SIZE 64
 /* n chunks in one call, with the fixed strides VS = (chunk_size + 1)^2 vertices and TS = 2 * chunk_size^2 triangles a chunk:
  * counts [n][2] = vertices, triangles of chunk i; vertices [n][VS][4]; indices [n][TS][3], chunk-local (they index chunk i's own
@@ -1025,6 +1026,94 @@ int rxr_terrain_meshes(rxr_ctx *ctx, const int32_t *chunk_coords /* [n][2] */, u
  * Asynchronous.  Multi-device handles: RXR_ERR_UNSUPPORTED (use rxr_member). */
 int rxr_terrain_meshes_to(rxr_ctx *ctx, const int32_t *chunk_coords, uint32_t n, int32_t chunk_size, uint32_t *dev_counts,
                           float *dev_vertices, uint32_t *dev_indices, float *dev_normals, void *hip_stream);
+
+/* ---- flattened terrain heights: the Height pass of TerrainChunk::process_batch_modifiers (rusterix_amd/csrc/rxr_terrain_flatten.hip) --
+ * processed_heights, the map get_height reads and build_mesh walks (src/terrain/chunk.rs:144-208), from the resident heights and a
+ * resident list of FLATTEN OPS, exact to the bit.  An op is one Flatten node applied to one sector (ShapeFX::sector_modify_heightmap,
+ * src/shapestack/shapefx.rs:414-478) or to one group of linedefs (linedef_modify_heightmap, :682-820).  THE ORDER IS THE CALLER'S: for
+ * the reference, the sectors in sorted_sectors_by_area() order, each with the Flatten nodes its graph chain reaches in chain order,
+ * then the linedef groups (the reference walks a hash map of groups: the list's order is this library's definition), each with its
+ * chain's Flatten nodes.  A sector whose signed_distance is None (a linedef with a missing vertex) makes no op, a linedef with a
+ * missing vertex no segment.  INTEGRATION.md says how the shim builds the list.
+ * Per chunk: processed = heights.clone(), then every op in order inserts into it.  Every op reads the UNPROCESSED height, never an
+ * earlier op's result: per cell the last op that writes wins; a cell no op writes keeps its height and its presence; a cell an op
+ * writes becomes PRESENT even where the terrain had no height.  All f32, one operation per reference operation, nothing fused; the
+ * casts are Rust's saturating `as i32` (NaN gives 0).  With the chunk's bounds B = origin as f32 .. origin as f32 + (size as f32 -
+ * 1.0), BBox::intersects / contains / expand as src/map/bbox.rs writes them (expand(a) moves each side by a * 0.5):
+ *   sector op    applies to the chunk iff B intersects box.expanded(2.0), the sector's bounding_box moved by 1 -- NOT by the bevel.  Cell
+ *                (x, y) is written iff x lies in floor(R.min.x) as i32 ..= ceil(R.max.x) as i32, R = box after expand(bevel), likewise
+ *                y; B after expand(bevel) contains p = (x as f32, y as f32); sd < bevel * 4.0; and B contains p.  sd is
+ *                Sector::signed_distance (src/map/sector.rs:308-333): min_dist from f32::MAX over the edges, t = dot(p - v0, edge) /
+ *                dot(edge, edge) clamped as f32::clamp (a NaN stays), dist = |p - (v0 + edge * t)|, f32::min (which drops a NaN), negated
+ *                when is_inside (:272-305, over the edges' START points; fewer than three: outside).  Value: original * (1 - s) +
+ *                floor_height * s, s = smoothstep(0, bevel, bevel - sd) (:2258-2261), original = the unprocessed height, or floor_height
+ *                where the cell is absent.
+ *   linedef op   its segments for the chunk are those whose box.expanded(2.0) intersects B, in list order -- a filter PER CHUNK, so two
+ *                neighbouring chunks may see different closest segments.  Cell (tx, ty) is written iff it lies in tile_min .. tile_max,
+ *                EXCLUSIVE at the top, tile_min = floor((B.min - bevel * scale) / scale) as i32, tile_max = ceil((B.max + bevel * scale)
+ *                / scale) as i32 (with bevel == 0 the chunk's last row and column are never written); the chunk has a segment; NOT
+ *                dist > bevel for the closest segment to ((tx as f32 + 0.5) * scale.x, (ty as f32 + 0.5) * scale.y) (a NaN distance
+ *                writes); and B contains (tx as f32, ty as f32).  closest_segment takes the first segment unconditionally and a later one
+ *                only under dist < best: a degenerate FIRST segment (NaN) is never displaced.  Value: original * (1 - blend) + height *
+ *                blend, height = height_start * (1 - t) + height_end * t, blend = smoothstep(0, bevel, bevel - dist), original = the
+ *                unprocessed height, or `height` where the cell is absent.
+ * Any f32 bit pattern is legal in heights, parameters and geometry; a NaN result is a NaN, its sign and payload are the device's.
+ * Not kept: beyond +-2^24, where `x as f32` rounds, B can contain cells of a NEIGHBOURING chunk, which the reference inserts under keys
+ * outside 0 .. size - 1 that nothing reads back through get_height; only the chunk's own size x size cells are computed here.
+ * The Colorize pass (ShapeFX node graphs per texel of the baked texture) stays on the host. */
+#define RXR_TERRAIN_FLATTEN_SECTOR 0u
+#define RXR_TERRAIN_FLATTEN_LINEDEFS 1u
+#define RXR_TERRAIN_FLATTEN_OP_FLOATS 6u       /* bevel, floor_height, then the sector's bounding_box: min x, min y, max x, max y
+                                                  (a linedef op reads the bevel alone)                                              */
+#define RXR_TERRAIN_FLATTEN_RECORD_FLOATS 10u  /* x0, y0, x1, y1 -- a sector's edge in linedef order, or a segment --, then for a
+                                                  segment height_start, height_end and its linedef's bounding_box: min x, min y,
+                                                  max x, max y (a sector op reads the first four alone)                            */
+#define RXR_TERRAIN_FLATTEN_MAX_OPS 1024u
+#define RXR_TERRAIN_FLATTEN_MAX_RECORDS (1u << 16)   /* records of the pool, and the sum of the ops' range lengths (ranges may overlap) */
+#define RXR_TERRAIN_FLATTEN_MAX_SEGMENTS (1u << 14)  /* the sum of the LINEDEF ops' range lengths: a chunk's segment list lies in LDS  */
+#define RXR_TERRAIN_HEIGHTS_REGISTERED 0u
+#define RXR_TERRAIN_HEIGHTS_PROCESSED 1u
+/* validation only, no context: the status rxr_set_terrain_flatten would return and, in `message`, the reason.  RXR_ERR_UNSUPPORTED:
+ * n_ops above RXR_TERRAIN_FLATTEN_MAX_OPS, n_records or the sum of the range lengths above RXR_TERRAIN_FLATTEN_MAX_RECORDS, the sum of
+ * the linedef ops' range lengths above RXR_TERRAIN_FLATTEN_MAX_SEGMENTS.
+ * RXR_ERR_INVALID: a NULL array with a non-zero count, a kind that is neither RXR_TERRAIN_FLATTEN_SECTOR nor _LINEDEFS, a range
+ * (first, count) that does not lie inside the pool.  An empty range is legal (a sector without edges has distance f32::MAX). */
+int rxr_check_terrain_flatten(const uint32_t *op_kinds, const float *op_params, const uint32_t *op_ranges, uint32_t n_ops,
+                              const float *records, uint32_t n_records, char *message, uint32_t message_capacity);
+/* makes the op list resident (it stays until the next call; n_ops == 0 clears it: a flatten then copies the registered cells).
+ * What does not depend on the cell is computed here, once, in the reference's f32 operations: an edge's v1 - v0 and dot(edge, edge),
+ * the differences of is_inside, bevel * 4.0, the boxes moved by 1 and the sector's integer ranges.  Re-registration waits for queued
+ * flattens.  Independent of rxr_set_terrain_heights.  Arrays are read before the call returns.  A refused call leaves the resident
+ * list as it was.  Multi-device handles: member 0.
+ * Replaces: the map walk of process_batch_modifiers per chunk, src/terrain/chunk.rs:153-208. */
+int rxr_set_terrain_flatten(rxr_ctx *ctx, const uint32_t *op_kinds /* [n_ops] */,
+                            const float *op_params /* [n_ops][RXR_TERRAIN_FLATTEN_OP_FLOATS] */,
+                            const uint32_t *op_ranges /* [n_ops][2] first record, records */, uint32_t n_ops,
+                            const float *records /* [n_records][RXR_TERRAIN_FLATTEN_RECORD_FLOATS] */, uint32_t n_records);
+/* The library keeps a second grid and mask next to the registered ones, over the same bounding rectangle: the PROCESSED heights, a copy
+ * of the registered grid after every rxr_set_terrain_heights (where the caller now registers chunk.heights, the unprocessed map).  For
+ * the n named chunks this computes every cell's processed height and presence from the registered grid and the resident ops, writes
+ * them into the processed grid (cells outside the rectangle are returned but not kept) and into heights [n][chunk_size * chunk_size]
+ * and present (the same shape, 1 / 0), row by row; an absent cell's height is 0.0, get_height's answer.  Either array may be NULL.
+ * No rxr_set_terrain_flatten yet is zero ops.  RXR_ERR_INVALID: no rxr_set_terrain_heights yet, chunk_size < 1, a chunk whose cells
+ * leave +-2^30, a chunk named twice, NULL chunk_coords; RXR_ERR_UNSUPPORTED: chunk_size above RXR_TERRAIN_MESH_MAX_CHUNK_SIZE.  A
+ * refused call queues nothing; n == 0 does nothing.  Host memory, blocking.  The call is split into launches of at most 256 chunks
+ * (RXR_TERRAIN_FLATTEN_LAUNCH_CHUNKS in the environment, read at each call, lowers the bound).  Changes no frame, scratch, bake or mesh
+ * state.  Multi-device handles: member 0.
+ * Replaces: the Height pass of TerrainChunk::process_batch_modifiers, src/terrain/chunk.rs:144-208. */
+int rxr_flatten_terrain(rxr_ctx *ctx, const int32_t *chunk_coords /* [n][2] */, uint32_t n, int32_t chunk_size, float *heights,
+                        uint8_t *present);
+/* the same into DEVICE arrays (each one's first and last byte are checked to be memory of the context's device; dev_heights 4-byte
+ * aligned; NULL = not wanted), queued on hip_stream (NULL = the context's stream); chunk_coords is host memory and is read before the
+ * call returns.  Asynchronous.  The processed grid is written in stream order: picks and mesh builds queued before it have read the
+ * grid when it is written, those queued after it under RXR_TERRAIN_HEIGHTS_PROCESSED read what it wrote, on whichever streams they
+ * run.  Multi-device handles: RXR_ERR_UNSUPPORTED (use rxr_member). */
+int rxr_flatten_terrain_to(rxr_ctx *ctx, const int32_t *chunk_coords, uint32_t n, int32_t chunk_size, float *dev_heights,
+                           uint8_t *dev_present, void *hip_stream);
+/* which grid and mask rxr_terrain_hits[_to] and rxr_terrain_meshes[_to] read from now on: RXR_TERRAIN_HEIGHTS_REGISTERED (the default:
+ * what rxr_set_terrain_heights listed) or RXR_TERRAIN_HEIGHTS_PROCESSED.  A choice of pointer on the host; calls already queued are
+ * not affected.  It stays across rxr_set_terrain_heights.  Anything else is RXR_ERR_INVALID.  Multi-device handles: member 0. */
+int rxr_set_terrain_height_source(rxr_ctx *ctx, uint32_t source);
 
 /* ---- vertex normals: Batch3D::compute_vertex_normals (rusterix_amd/csrc/rxr_normals.hip) ------------------------------------------
  * The smooth normals of n meshes of ANY topology (src/batch/batch3d.rs:771-809), exact to the bit, in the strided layout

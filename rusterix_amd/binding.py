@@ -514,6 +514,13 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         L.terrain_build_mesh = fn("terrain_build_mesh", vp, vp, i32, i32)
         L.terrain_build_meshes = fn("terrain_build_meshes", i32, vp, C.POINTER(C.c_int32), u32, i32, C.POINTER(vp))
 
+    # processed_heights: the Height pass of process_batch_modifiers (product host library only)
+    has_terrain_flatten = hasattr(lib, prefix + "terrain_process_heights")
+    if has_terrain_flatten:
+        L.terrain_set_flatten_ops = fn("terrain_set_flatten_ops", i32, vp, pu, pf, pu, u32, pf, u32)
+        L.terrain_process_heights = fn("terrain_process_heights", i32, vp, C.POINTER(C.c_int32), u32, i32, pf, C.POINTER(C.c_uint8))
+        L.terrain_set_device_modifiers = fn("terrain_set_device_modifiers", None, vp, i32)
+        L.terrain_registrations = fn("terrain_registrations", None, C.POINTER(C.c_uint64))
     # the generated terrain's height field (product host library only)
     has_terrain_gen = hasattr(lib, prefix + "terrain_generator_new")
     if has_terrain_gen:
@@ -1352,6 +1359,60 @@ def make_api(lib: C.CDLL, prefix: str, name: str):
         def build_meshes_cpu(self, coords):
             """the same list from the CPU build_mesh over the host's worker pool"""
             return self._meshes(coords, False)
+
+        # ---- processed_heights (reference src/terrain/chunk.rs:144-208, the Height pass) ----
+        def set_flatten_ops(self, kinds, params, ranges, records):
+            """Terrain::flatten_ops from the arrays of rxr_set_terrain_flatten (include/rxr.h): kinds [n], params [n][6] (bevel,
+            floor_height, the sector's box), ranges [n][2] into records [m][10]; the order is the caller's"""
+            if not has_terrain_flatten:
+                raise NotImplementedError(f"{name}: no terrain flatten in this library")
+            k = np.ascontiguousarray(np.asarray(kinds, np.uint32).reshape(-1))
+            pr = np.ascontiguousarray(np.asarray(params, np.float32).reshape(-1, 6))
+            rg = np.ascontiguousarray(np.asarray(ranges, np.uint32).reshape(-1, 2))
+            rec = np.ascontiguousarray(np.asarray(records, np.float32).reshape(-1, 10))
+            if not (len(k) == len(pr) == len(rg)):
+                raise ValueError("kinds, params and ranges must name the same number of ops")
+            rc = L.terrain_set_flatten_ops(self._h, _up(k) if len(k) else None, _fp(pr) if len(k) else None, _up(rg) if len(k) else None, len(k),
+                                           _fp(rec) if len(rec) else None, len(rec))
+            if rc != 0:
+                raise RasterizeError(rc, last_error())
+            return self
+
+        def _process(self, coords, device):
+            if not has_terrain_flatten:
+                raise NotImplementedError(f"{name}: no terrain flatten in this library")
+            cc = np.ascontiguousarray(np.asarray(coords, np.int32).reshape(-1, 2))
+            n, per = cc.shape[0], self.chunk_size * self.chunk_size
+            heights, present = np.zeros((n, per), np.float32), np.zeros((n, per), np.uint8)
+            rc = L.terrain_process_heights(self._h, cc.ctypes.data_as(C.POINTER(C.c_int32)), n, 1 if device else 0, _fp(heights),
+                                           present.ctypes.data_as(C.POINTER(C.c_uint8)))
+            if rc != 0:
+                raise RasterizeError(rc, last_error())
+            return heights, present
+
+        def process_heights(self, coords):
+            """processed_heights of every chunk of `coords` in one device call (rxr_flatten_terrain, include/rxr.h): heights
+            [n][chunk_size^2] (0.0 for an absent cell) and present, the chunks' own cells row by row"""
+            return self._process(coords, True)
+
+        def process_heights_cpu(self, coords):
+            """the same arrays from the dictionary transcription over the host's worker pool"""
+            return self._process(coords, False)
+
+        def set_device_modifiers(self, on):
+            """Terrain::device_modifiers (opt-in, off by default): Scene.rebuild_terrain_meshes and build_meshes flatten on the device
+            first and build from the processed grid"""
+            if not has_terrain_flatten:
+                raise NotImplementedError(f"{name}: no terrain flatten in this library")
+            L.terrain_set_device_modifiers(self._h, 1 if on else 0)
+            return self
+
+        @staticmethod
+        def registrations():
+            """(rxr_set_terrain_heights calls, rxr_set_terrain_flatten calls) the mirror has made so far"""
+            out = (C.c_uint64 * 2)()
+            L.terrain_registrations(out)
+            return int(out[0]), int(out[1])
 
     class TerrainGenerator:
         """reference src/chunkbuilder/terrain_generator.rs: the height field of the generated 3D terrain over the lists

@@ -273,6 +273,23 @@ int rxh_terrain_build_meshes(void *t, const int32_t *coords, uint32_t n, int dev
     for (uint32_t i = 0; i < n; ++i) out[i] = new Batch3D(std::move(meshes[i]));
     return RXR_OK;
 }
+// Terrain::flatten_ops from the arrays of rxr_set_terrain_flatten (include/rxr.h); 0, or what rxr_check_terrain_flatten refuses (nothing changes then)
+int rxh_terrain_set_flatten_ops(void *t, const uint32_t *kinds, const float *params, const uint32_t *ranges, uint32_t n_ops, const float *records, uint32_t n_records) {
+    return ((Terrain *)t)->set_flatten_ops(kinds, params, ranges, n_ops, records, n_records);
+}
+// processed_heights of n chunks in the layout of rxr_flatten_terrain: on the device, or, device == 0, the dictionary transcription over
+// the host's worker pool; RXR_OK or a negative rxr_status
+int rxh_terrain_process_heights(void *t, const int32_t *coords, uint32_t n, int device, float *heights, uint8_t *present) {
+    if (device) return ((Terrain *)t)->process_heights(coords, n, heights, present);
+    ((Terrain *)t)->process_heights_cpu(coords, n, heights, present);
+    return RXR_OK;
+}
+void rxh_terrain_set_device_modifiers(void *t, int on) { ((Terrain *)t)->device_modifiers = on != 0; }
+// out[0], out[1]: how often a Terrain has called rxr_set_terrain_heights / rxr_set_terrain_flatten
+void rxh_terrain_registrations(uint64_t *out) {
+    out[0] = terrain_height_registrations();
+    out[1] = terrain_flatten_registrations();
+}
 // ---- the generated terrain's height field (rusterix::TerrainGenerator) ----------------------------
 void *rxh_terrain_generator_new(uint32_t subdivisions) {
     TerrainGenerator *g = new TerrainGenerator();

@@ -492,6 +492,9 @@ uint64_t g_tex_static_gen = 0, g_tex_dynamic_gen = 0;
 uint64_t g_shaders_gen = 0, g_shader_env_gen = 0;
 uint64_t g_terrain_gen = 0;   // the Terrain::generation the context's resident terrain was registered from (0: none)
 uint64_t g_heights_gen = 0;   // the Terrain::heights_generation the context's resident heights were registered from (0: none)
+uint64_t g_flatten_gen = 0;   // the Terrain::flatten_generation the context's resident flatten ops were registered from (0: none)
+uint64_t g_processed_heights_gen = 0, g_processed_flatten_gen = 0;   // the pair every chunk of the processed grid was last flattened under (0: none)
+uint64_t g_heights_registrations = 0, g_flatten_registrations = 0;
 uint64_t g_generator_gen = 0; // the TerrainGenerator::generation the context's resident generator records were registered from (0: none)
 uint64_t g_exclusion_gen = 0; // ... and the one its resident excluded sectors were registered from (0: none)
 uint64_t g_tiles_gen = 0;     // ... and the one its resident tile overrides were registered from (0: none)
@@ -513,6 +516,8 @@ uint64_t g_ctex_registrations = 0;
 }  // namespace
 
 uint64_t chunk_texture_registrations() { return g_ctex_registrations; }
+uint64_t terrain_height_registrations() { return g_heights_registrations; }
+uint64_t terrain_flatten_registrations() { return g_flatten_registrations; }
 
 void set_device_projection(bool on) { g_device_projection = on; }
 bool device_projection() { return g_device_projection; }
@@ -537,6 +542,7 @@ void drop_context_locked() {
     g_shaders_gen = g_shader_env_gen = 0;
     g_terrain_gen = 0;
     g_heights_gen = 0;
+    g_flatten_gen = g_processed_heights_gen = g_processed_flatten_gen = 0;
     g_generator_gen = 0;
     g_exclusion_gen = 0;
     g_tiles_gen = 0;
@@ -1807,6 +1813,8 @@ int Terrain::register_heights(rxr_ctx *ctx) const {
         return rc;
     }
     g_heights_gen = heights_generation;
+    g_processed_heights_gen = 0;   // (the registration reset the processed grid)
+    ++g_heights_registrations;
     return RXR_OK;
 }
 
@@ -1851,6 +1859,20 @@ void Terrain::build_meshes_cpu(const int32_t *coords, uint32_t n, std::vector<Ba
     rxr_parallel::run(n, (size_t)n * chunk_size * chunk_size * 64, [&](size_t i) { out[i] = build_mesh(coords[2 * i], coords[2 * i + 1]); });
 }
 
+namespace {
+// Terrain::device_modifiers: RXR_TERRAIN_HEIGHTS_PROCESSED for the length of a call (the choice is made when a launch is queued)
+struct ProcessedSource {
+    rxr_ctx *ctx;
+    bool on;
+    ProcessedSource(rxr_ctx *c, bool o) : ctx(c), on(o) {
+        if (on) (void)rxr_set_terrain_height_source(ctx, RXR_TERRAIN_HEIGHTS_PROCESSED);
+    }
+    ~ProcessedSource() {
+        if (on) (void)rxr_set_terrain_height_source(ctx, RXR_TERRAIN_HEIGHTS_REGISTERED);
+    }
+};
+}  // namespace
+
 int Terrain::build_meshes(const int32_t *coords, uint32_t n, std::vector<Batch3D> &out) const {
     std::lock_guard<std::recursive_mutex> lk(g_mu);
     std::string err;
@@ -1859,6 +1881,8 @@ int Terrain::build_meshes(const int32_t *coords, uint32_t n, std::vector<Batch3D
     int rc = register_heights(ctx);
     if (rc != RXR_OK) return rc;
     out.clear();
+    ProcessedSource processed(ctx, device_modifiers);   // (device_modifiers: the mesh kernels read the processed grid until this returns)
+    if (device_modifiers && (rc = flatten_resident(ctx, coords, n)) != RXR_OK) return rc;
     if (chunk_size < 1 || chunk_size > RXR_TERRAIN_MESH_MAX_CHUNK_SIZE) {   // (the strides below need a size the library takes: its own answer)
         rc = rxr_terrain_meshes(ctx, coords, n, chunk_size, nullptr, nullptr, nullptr, nullptr);
         if (rc != RXR_OK) g_error = rxr_last_error(ctx);
@@ -1881,6 +1905,250 @@ int Terrain::build_meshes(const int32_t *coords, uint32_t n, std::vector<Batch3D
         b.normals.assign(normals.begin() + i * VS * 3, normals.begin() + i * VS * 3 + nv * 3);
         out.push_back(std::move(b));
     }
+    return RXR_OK;
+}
+
+// ---- processed_heights: the Height pass of process_batch_modifiers ----
+namespace {
+// src/map/bbox.rs
+struct BBox {
+    float min_x, min_y, max_x, max_y;
+    bool contains(float x, float y) const { return x >= min_x && x <= max_x && y >= min_y && y <= max_y; }
+    bool intersects(const BBox &o) const { return min_x <= o.max_x && max_x >= o.min_x && min_y <= o.max_y && max_y >= o.min_y; }
+    BBox expanded(float amount) const { return BBox{min_x - amount * 0.5f, min_y - amount * 0.5f, max_x + amount * 0.5f, max_y + amount * 0.5f}; }
+};
+// f32::clamp(0.0, 1.0): a NaN stays
+float flat_clamp01(float t) {
+    if (t < 0.0f) t = 0.0f;
+    if (t > 1.0f) t = 1.0f;
+    return t;
+}
+// ShapeFX::smoothstep (src/shapestack/shapefx.rs:2258-2261)
+float flat_smoothstep(float edge0, float edge1, float x) {
+    const float t = flat_clamp01((x - edge0) / (edge1 - edge0));
+    return t * t * (3.0f - 2.0f * t);
+}
+float flat_magnitude(float x, float y) { return std::sqrt(x * x + y * y); }
+
+// Sector::signed_distance (src/map/sector.rs:308-333) with is_inside (:272-305) over the op's edges
+float flat_signed_distance(const Terrain::FlattenOp &op, float px, float py) {
+    const size_t n = op.records.size() / RXR_TERRAIN_FLATTEN_RECORD_FLOATS;
+    float min_dist = std::numeric_limits<float>::max();
+    for (size_t i = 0; i < n; ++i) {
+        const float *r = op.records.data() + RXR_TERRAIN_FLATTEN_RECORD_FLOATS * i;
+        const float ex = r[2] - r[0], ey = r[3] - r[1];
+        const float tx = px - r[0], ty = py - r[1];
+        const float t = (tx * ex + ty * ey) / (ex * ex + ey * ey);
+        const float t_clamped = flat_clamp01(t);
+        const float cx = r[0] + ex * t_clamped, cy = r[1] + ey * t_clamped;
+        const float dist = flat_magnitude(px - cx, py - cy);
+        min_dist = std::fmin(min_dist, dist);   // f32::min drops a NaN operand
+    }
+    bool inside = false;
+    if (n >= 3) {
+        size_t j = n - 1;
+        for (size_t i = 0; i < n; ++i) {
+            const float *pi = op.records.data() + RXR_TERRAIN_FLATTEN_RECORD_FLOATS * i, *pj = op.records.data() + RXR_TERRAIN_FLATTEN_RECORD_FLOATS * j;
+            if ((pi[1] > py) != (pj[1] > py) && px < (pj[0] - pi[0]) * (py - pi[1]) / (pj[1] - pi[1]) + pi[0]) inside = !inside;
+            j = i;
+        }
+    }
+    return inside ? -min_dist : min_dist;
+}
+}  // namespace
+
+int Terrain::set_flatten_ops(const uint32_t *kinds, const float *params, const uint32_t *ranges, uint32_t n_ops, const float *records, uint32_t n_records) {
+    char message[256] = "";
+    const int rc = rxr_check_terrain_flatten(kinds, params, ranges, n_ops, records, n_records, message, sizeof message);
+    if (rc != RXR_OK) {
+        std::lock_guard<std::recursive_mutex> lk(g_mu);
+        g_error = std::string("Terrain::set_flatten_ops: ") + message;
+        return rc;
+    }
+    flatten_ops.assign(n_ops, FlattenOp());
+    for (uint32_t i = 0; i < n_ops; ++i) {
+        FlattenOp &op = flatten_ops[i];
+        const float *p = params + RXR_TERRAIN_FLATTEN_OP_FLOATS * (size_t)i;
+        op.kind = kinds[i];
+        op.bevel = p[0], op.floor_height = p[1];
+        for (int k = 0; k < 4; ++k) op.box[k] = p[2 + k];
+        const float *r = records + RXR_TERRAIN_FLATTEN_RECORD_FLOATS * (size_t)ranges[2 * (size_t)i];
+        op.records.assign(r, r + RXR_TERRAIN_FLATTEN_RECORD_FLOATS * (size_t)ranges[2 * (size_t)i + 1]);
+    }
+    touch_flatten();
+    return RXR_OK;
+}
+
+void Terrain::flatten_op_arrays(std::vector<uint32_t> &kinds, std::vector<float> &params, std::vector<uint32_t> &ranges, std::vector<float> &records) const {
+    for (const FlattenOp &op : flatten_ops) {
+        kinds.push_back(op.kind);
+        const float p[RXR_TERRAIN_FLATTEN_OP_FLOATS] = {op.bevel, op.floor_height, op.box[0], op.box[1], op.box[2], op.box[3]};
+        params.insert(params.end(), p, p + RXR_TERRAIN_FLATTEN_OP_FLOATS);
+        ranges.push_back((uint32_t)(records.size() / RXR_TERRAIN_FLATTEN_RECORD_FLOATS));
+        ranges.push_back((uint32_t)(op.records.size() / RXR_TERRAIN_FLATTEN_RECORD_FLOATS));
+        records.insert(records.end(), op.records.begin(), op.records.end());
+    }
+}
+
+void Terrain::process_chunk_cpu(int32_t cx, int32_t cy, std::map<std::pair<int32_t, int32_t>, float> &processed) const {
+    const int64_t ox = (int64_t)cx * chunk_size, oy = (int64_t)cy * chunk_size;
+    // let mut processed_heights = self.heights.clone() -- keyed by local cell
+    for (auto it = heights.lower_bound({(int32_t)std::max<int64_t>(ox, INT32_MIN), INT32_MIN}); it != heights.end() && it->first.first < ox + chunk_size; ++it)
+        if (it->first.second >= oy && it->first.second < oy + chunk_size) processed[{(int32_t)(it->first.first - ox), (int32_t)(it->first.second - oy)}] = it->second;
+    auto unprocessed = [&](int64_t x, int64_t y, float &h) {   // terrain.get_height_unprocessed
+        if (x < INT32_MIN || x > INT32_MAX || y < INT32_MIN || y > INT32_MAX) return false;
+        auto it = heights.find({(int32_t)x, (int32_t)y});
+        if (it == heights.end()) return false;
+        h = it->second;
+        return true;
+    };
+    // TerrainChunk::bounds (:130-134)
+    const float size_f = (float)chunk_size - 1.0f;
+    const BBox bbox{(float)ox, (float)oy, (float)ox + size_f, (float)oy + size_f};
+    for (const FlattenOp &op : flatten_ops) {
+        const float bevel = op.bevel;
+        const size_t n_records = op.records.size() / RXR_TERRAIN_FLATTEN_RECORD_FLOATS;
+        if (op.kind == RXR_TERRAIN_FLATTEN_SECTOR) {
+            const BBox sector_box{op.box[0], op.box[1], op.box[2], op.box[3]};
+            if (!bbox.intersects(sector_box.expanded(2.0f))) continue;
+            // ShapeFX::sector_modify_heightmap (src/shapestack/shapefx.rs:414-478), the Height pass
+            const float floor_height = op.floor_height;
+            const BBox expanded_bbox = bbox.expanded(bevel);
+            const BBox chunk_bbox = bbox;
+            const BBox bounds = sector_box.expanded(bevel);
+            int64_t min_x = as_i32(std::floor(bounds.min_x)), max_x = as_i32(std::ceil(bounds.max_x));
+            int64_t min_y = as_i32(std::floor(bounds.min_y)), max_y = as_i32(std::ceil(bounds.max_y));
+            // (the clip the header states: no cell farther than this from the chunk passes chunk_bbox.contains)
+            min_x = std::max(min_x, ox - 130), max_x = std::min(max_x, ox + chunk_size + 130);
+            min_y = std::max(min_y, oy - 130), max_y = std::min(max_y, oy + chunk_size + 130);
+            for (int64_t y = min_y; y <= max_y; ++y)
+                for (int64_t x = min_x; x <= max_x; ++x) {
+                    const float px = (float)x, py = (float)y;
+                    if (!expanded_bbox.contains(px, py)) continue;
+                    const float sd = flat_signed_distance(op, px, py);
+                    if (sd < bevel * 4.0f) {
+                        const float s = flat_smoothstep(0.0f, bevel, bevel - sd);
+                        float original;
+                        if (!unprocessed(x, y, original)) original = floor_height;
+                        const float new_height = original * (1.0f - s) + floor_height * s;
+                        if (chunk_bbox.contains((float)x, (float)y)) processed[{(int32_t)(x - ox), (int32_t)(y - oy)}] = new_height;
+                    }
+                }
+        } else {
+            // the group's linedefs whose bounding_box.expanded(2.0) intersects the chunk (:181-191), then linedef_modify_heightmap (:682-820)
+            std::vector<const float *> segments;
+            for (size_t i = 0; i < n_records; ++i) {
+                const float *r = op.records.data() + RXR_TERRAIN_FLATTEN_RECORD_FLOATS * i;
+                if (bbox.intersects(BBox{r[6], r[7], r[8], r[9]}.expanded(2.0f))) segments.push_back(r);
+            }
+            if (segments.empty()) continue;
+            const BBox chunk_bbox = bbox;
+            const float min_fx = bbox.min_x - bevel * scale[0], min_fy = bbox.min_y - bevel * scale[1];
+            const float max_fx = bbox.max_x + bevel * scale[0], max_fy = bbox.max_y + bevel * scale[1];
+            const int64_t tile_min_x = as_i32(std::floor(min_fx / scale[0])), tile_min_y = as_i32(std::floor(min_fy / scale[1]));
+            const int64_t tile_max_x = as_i32(std::ceil(max_fx / scale[0])), tile_max_y = as_i32(std::ceil(max_fy / scale[1]));
+            for (int64_t ty = tile_min_y; ty < tile_max_y; ++ty)
+                for (int64_t tx = tile_min_x; tx < tile_max_x; ++tx) {
+                    const float center_x = ((float)tx + 0.5f) * scale[0], center_y = ((float)ty + 0.5f) * scale[1];
+                    // closest_segment (:721-738) over point_to_line_segment (:711-719)
+                    const float *seg = nullptr;
+                    float best_dist = 0.0f, best_t = 0.0f;
+                    for (const float *r : segments) {
+                        const float abx = r[2] - r[0], aby = r[3] - r[1];
+                        const float apx = center_x - r[0], apy = center_y - r[1];
+                        const float t = (apx * abx + apy * aby) / (abx * abx + aby * aby);
+                        const float t_clamped = flat_clamp01(t);
+                        const float qx = r[0] + abx * t_clamped, qy = r[1] + aby * t_clamped;
+                        const float dist = flat_magnitude(center_x - qx, center_y - qy);
+                        if (!seg || dist < best_dist) seg = r, best_dist = dist, best_t = t_clamped;
+                    }
+                    if (best_dist > bevel) continue;
+                    const float height = seg[4] * (1.0f - best_t) + seg[5] * best_t;
+                    const float blend = flat_smoothstep(0.0f, bevel, bevel - best_dist);
+                    if (chunk_bbox.contains((float)tx, (float)ty)) {
+                        float original;
+                        if (!unprocessed(tx, ty, original)) original = height;
+                        processed[{(int32_t)(tx - ox), (int32_t)(ty - oy)}] = original * (1.0f - blend) + height * blend;
+                    }
+                }
+        }
+    }
+}
+
+void Terrain::process_heights_cpu(const int32_t *coords, uint32_t n, float *out_heights, uint8_t *out_present) const {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);   // (the worker pool runs one job at a time)
+    if (chunk_size < 1) return;
+    const size_t per = (size_t)chunk_size * (size_t)chunk_size;
+    rxr_parallel::run(n, (size_t)n * per * 64 * std::max<size_t>(flatten_ops.size(), 1), [&](size_t i) {
+        std::map<std::pair<int32_t, int32_t>, float> processed;
+        process_chunk_cpu(coords[2 * i], coords[2 * i + 1], processed);
+        if (out_heights) std::fill(out_heights + i * per, out_heights + (i + 1) * per, 0.0f);
+        if (out_present) std::fill(out_present + i * per, out_present + (i + 1) * per, (uint8_t)0);
+        for (const auto &kv : processed) {
+            const int32_t lx = kv.first.first, ly = kv.first.second;
+            if (lx < 0 || ly < 0 || lx >= chunk_size || ly >= chunk_size) continue;   // (a neighbour's cell, beyond +-2^24: include/rxr.h)
+            if (out_heights) out_heights[i * per + (size_t)ly * chunk_size + lx] = kv.second;
+            if (out_present) out_present[i * per + (size_t)ly * chunk_size + lx] = 1;
+        }
+    });
+}
+
+int Terrain::register_flatten(rxr_ctx *ctx) const {
+    if (g_flatten_gen == flatten_generation) return RXR_OK;
+    std::vector<uint32_t> kinds, ranges;
+    std::vector<float> params, records;
+    flatten_op_arrays(kinds, params, ranges, records);
+    const int rc = rxr_set_terrain_flatten(ctx, kinds.data(), params.data(), ranges.data(), (uint32_t)kinds.size(), records.data(),
+                                           (uint32_t)(records.size() / RXR_TERRAIN_FLATTEN_RECORD_FLOATS));
+    if (rc != RXR_OK) {
+        g_error = rxr_last_error(ctx);
+        return rc;
+    }
+    g_flatten_gen = flatten_generation;
+    ++g_flatten_registrations;
+    return RXR_OK;
+}
+
+int Terrain::process_heights(const int32_t *coords, uint32_t n, float *out_heights, uint8_t *out_present) const {
+    std::lock_guard<std::recursive_mutex> lk(g_mu);
+    std::string err;
+    rxr_ctx *ctx = context(&err);
+    if (!ctx) return RXR_ERR_NO_DEVICE;
+    int rc = register_heights(ctx);
+    if (rc == RXR_OK) rc = register_flatten(ctx);
+    if (rc != RXR_OK) return rc;
+    rc = rxr_flatten_terrain(ctx, coords, n, chunk_size, out_heights, out_present);
+    if (rc != RXR_OK) g_error = rxr_last_error(ctx);
+    return rc;
+}
+
+int Terrain::flatten_resident(rxr_ctx *ctx, const int32_t *coords, uint32_t n) const {
+    int rc = register_heights(ctx);
+    if (rc == RXR_OK) rc = register_flatten(ctx);
+    if (rc != RXR_OK) return rc;
+    std::vector<int32_t> all;
+    if (g_processed_heights_gen != heights_generation || g_processed_flatten_gen != flatten_generation) {
+        // a registration reset the processed grid, or the ops changed: every chunk of the terrain, the named ones among them
+        std::set<std::pair<int32_t, int32_t>> every(chunks);
+        for (uint32_t i = 0; i < n; ++i) every.insert({coords[2 * (size_t)i], coords[2 * (size_t)i + 1]});
+        for (const auto &c : every) {
+            bool fits = true;
+            for (const int32_t v : {c.first, c.second}) {
+                const int64_t lo = (int64_t)v * chunk_size;
+                fits = fits && lo >= -(1ll << 30) && lo + chunk_size - 1 <= (1ll << 30);
+            }
+            if (fits) all.push_back(c.first), all.push_back(c.second);
+        }
+        coords = all.data();
+        n = (uint32_t)(all.size() / 2);
+    }
+    rc = rxr_flatten_terrain_to(ctx, coords, n, chunk_size, nullptr, nullptr, nullptr);   // (the context's stream)
+    if (rc != RXR_OK) {
+        g_error = rxr_last_error(ctx);
+        return rc;
+    }
+    g_processed_heights_gen = heights_generation;
+    g_processed_flatten_gen = flatten_generation;
     return RXR_OK;
 }
 
@@ -1924,6 +2192,9 @@ int Scene::rebuild_terrain_meshes(const Terrain &terrain, const int32_t *coords,
     if (held && rxr_member_count(ctx) == 1 && cs >= 1 && cs <= RXR_TERRAIN_MESH_MAX_CHUNK_SIZE) {
         int rc = terrain.register_heights(ctx);
         if (rc != RXR_OK) return rc;
+        // device_modifiers: flatten -> meshes (with their normals) -> update, one after the other on the context's stream
+        ProcessedSource processed(ctx, terrain.device_modifiers);
+        if (terrain.device_modifiers && (rc = terrain.flatten_resident(ctx, coords, n)) != RXR_OK) return rc;
         const size_t VS = (size_t)(cs + 1) * (cs + 1), TS = 2 * (size_t)cs * cs;
         auto up = [](size_t x) { return (x + 255) / 256 * 256; };
         const size_t o_v = up((size_t)n * 8), o_i = o_v + up((size_t)n * VS * 16), o_n = o_i + up((size_t)n * TS * 12), total = o_n + up((size_t)n * VS * 12);

@@ -378,6 +378,9 @@ public:
 
 // how many times Rasterizer::upload has called rxr_set_chunk_textures with textures (tests: an unchanged scene registers nothing)
 uint64_t chunk_texture_registrations();
+// how many times a Terrain has called rxr_set_terrain_heights / rxr_set_terrain_flatten (tests: unchanged heights and ops register nothing)
+uint64_t terrain_height_registrations();
+uint64_t terrain_flatten_registrations();
 
 // src/terrain/mod.rs, src/terrain/chunk.rs: what Terrain::bake_chunk reads -- `sources` and `blend_modes` per cell, behind the asset
 // lookup: a cell's source is the texture sample_source would sample (tile.textures.first()), or a source without one (a PixelSource
@@ -463,8 +466,42 @@ public:
     // build_mesh for n chunks over the host's worker pool (what tools/terrain_mesh_bench.py measures the device against)
     void build_meshes_cpu(const int32_t *coords, uint32_t n, std::vector<Batch3D> &out) const;
 
+    // ---- processed_heights: the Height pass of TerrainChunk::process_batch_modifiers (src/terrain/chunk.rs:144-208) ----
+    // One Flatten node applied to one sector or to one group of linedefs, as rxr_set_terrain_flatten takes it (include/rxr.h):
+    // `records` holds RXR_TERRAIN_FLATTEN_RECORD_FLOATS floats an edge or segment.  The list's order is the caller's.
+    struct FlattenOp {
+        uint32_t kind = RXR_TERRAIN_FLATTEN_SECTOR;
+        float bevel = 0.5f, floor_height = 0.0f;
+        float box[4] = {0.0f, 0.0f, 0.0f, 0.0f};      // the sector's bounding_box: min x, min y, max x, max y
+        std::vector<float> records;
+    };
+    std::vector<FlattenOp> flatten_ops;
+    uint64_t flatten_generation = next_generation();              // code that edits flatten_ops calls touch_flatten()
+    void touch_flatten() { flatten_generation = next_generation(); }
+    // the list from the arrays of rxr_set_terrain_flatten; RXR_OK, or what rxr_check_terrain_flatten refuses (nothing changes then)
+    int set_flatten_ops(const uint32_t *kinds, const float *params, const uint32_t *ranges, uint32_t n_ops, const float *records, uint32_t n_records);
+    // ... and back: every op's records one after the other
+    void flatten_op_arrays(std::vector<uint32_t> &kinds, std::vector<float> &params, std::vector<uint32_t> &ranges, std::vector<float> &records) const;
+    // The Height pass for n chunks on the CPU over the host's worker pool, a chunk a task: the plain dictionary transcription -- the
+    // reference's loops over each op's integer range, inserts into a map, nothing hoisted; a sector's range is clipped to the chunk's
+    // cells +- 130 before it is walked, which drops no insert (every insert sits behind chunk_bbox.contains, and `x as f32` is within
+    // 64 of x up to 2^30).  heights [n][chunk_size^2] (0.0 for an absent cell) and present, the chunk's own cells row by row, as
+    // rxr_flatten_terrain returns them; either may be null.
+    void process_heights_cpu(const int32_t *coords, uint32_t n, float *heights, uint8_t *present) const;
+    // the same on the device (rxr_set_terrain_heights / rxr_set_terrain_flatten when heights / ops changed since they were
+    // registered, then rxr_flatten_terrain).  RXR_OK or a negative rxr_status; there is no fall-back to the CPU.
+    int process_heights(const int32_t *coords, uint32_t n, float *heights, uint8_t *present) const;
+    // Opt-in, off by default: Scene::rebuild_terrain_meshes and build_meshes build from processed_heights -- the chunks are flattened
+    // on the device first (every chunk of the terrain after a registration, which resets the processed grid; else the named ones:
+    // rxr_flatten_terrain_to), and the mesh kernels read the processed grid (rxr_set_terrain_height_source for the length of the
+    // call), all on the context's stream.
+    bool device_modifiers = false;
+
 private:
     friend class Scene;   // (rebuild_terrain_meshes registers the heights)
+    int register_flatten(rxr_ctx *ctx) const;   // rxr_set_terrain_flatten unless the context holds this generation
+    int flatten_resident(rxr_ctx *ctx, const int32_t *coords, uint32_t n) const;   // device_modifiers: the processed grid made current for these chunks
+    void process_chunk_cpu(int32_t cx, int32_t cy, std::map<std::pair<int32_t, int32_t>, float> &processed) const;
     // get_height's answers as a dense grid over the cells' bounding rectangle, rebuilt when heights_generation moved (the CPU march
     // looks a cell up 1500 times a ray)
     struct HeightGrid {

@@ -173,7 +173,7 @@ void rxr_destroy(rxr_ctx *ctx) {
                       &ctx->d_isect_tris, &ctx->d_isect_misc, &ctx->d_isect_keys, &ctx->d_accel_tris, &ctx->d_accel_perm, &ctx->d_accel_nodes, &ctx->d_accel_stats, &ctx->d_accel_scratch, &ctx->d_refresh_table, &ctx->d_refresh_verify, &ctx->d_trace_scene, &ctx->d_trace_paths, &ctx->d_trace_keys,
                       &ctx->d_bake_jobs, &ctx->d_bake_fault,
                       &ctx->d_terrain_cells, &ctx->d_terrain_tex, &ctx->d_terrain_texels, &ctx->d_terrain_weights,
-                      &ctx->d_heights, &ctx->d_heights_tk, &ctx->d_heights_mask, &ctx->d_gen, &ctx->d_excl, &ctx->d_excl_scratch, &ctx->d_tiles, &ctx->d_nrm_scratch, &ctx->ctex.pool, &ctx->ctex.flags};
+                      &ctx->d_heights, &ctx->d_heights_tk, &ctx->d_heights_mask, &ctx->d_pheights, &ctx->d_pheights_mask, &ctx->d_flatten, &ctx->d_gen, &ctx->d_excl, &ctx->d_excl_scratch, &ctx->d_tiles, &ctx->d_nrm_scratch, &ctx->ctex.pool, &ctx->ctex.flags};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (QueryLane &q : ctx->lane) {

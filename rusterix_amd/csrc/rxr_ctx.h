@@ -42,6 +42,8 @@ enum : uint32_t {
     Q_EXCL,          // rxr_generated_meshes_to: the resident generator records, the resident excluded sectors and the call scratch
     Q_TRACE,         // rxr_trace_to: the trace scene, the path state and its keys (it takes Q_ISECT as well: the triangle records)
     Q_NORMALS,       // rxr_vertex_normals_to: the general route's scratch (face normals, corner keys, the sort's own)
+    Q_FLATTEN,       // rxr_flatten_terrain_to: the resident flatten ops; it WRITES the processed heights, so it waits for Q_HEIGHTS and
+                     // Q_MESH as well, and picks and mesh builds that read the processed grid wait for it
     Q_LANES
 };
 #define RXR_MAX_TILE_ROWS 2048u   // frames of at most 32768 rows
@@ -349,6 +351,16 @@ struct rxr_ctx {
     uint32_t heights_gw = 0, heights_gh = 0;
     uint32_t heights_launches = 0;    // march launches of the last hit call (rxr_debug_terrain_hit_kernel)
     const char *heights_kernel = "";  // ... and their kernel's symbol name; a static string
+    // flattened heights (rxr_terrain_flatten.hip): d_pheights / d_pheights_mask, the PROCESSED grid and mask over the rectangle of
+    // d_heights, a copy of it after every rxr_set_terrain_heights and rewritten chunk by chunk by rxr_flatten_terrain[_to];
+    // height_source: which pair the picks and the mesh builds read (rxr_set_terrain_height_source); d_flatten: the resident op and
+    // edge / segment records of rxr_set_terrain_flatten (flatten_off: their byte offsets)
+    DevBuf d_pheights, d_pheights_mask, d_flatten;
+    uint32_t height_source = 0;       // RXR_TERRAIN_HEIGHTS_REGISTERED
+    size_t flatten_off[2] = {};
+    uint32_t flatten_ops = 0;         // resident ops
+    uint32_t flatten_seg_slots = 0;   // the sum of the linedef ops' range lengths: a workgroup's segment list in LDS
+    uint32_t flatten_launches = 0;    // launches of the last flatten call (rxr_debug_terrain_flatten_launches)
     uint32_t mesh_launches = 0;       // k_terrain_mesh launches of the last mesh call (rxr_debug_terrain_mesh_launches)
 
     // generated terrain heights (rxr_terrain_gen.hip): the resident records of rxr_set_terrain_generator, independent of both terrains

@@ -149,6 +149,11 @@ uint32_t rxr_debug_terrain_hit_few_rays(void);
 /* test-only: the k_terrain_mesh launches of the last mesh call */
 uint32_t rxr_debug_terrain_mesh_launches(rxr_ctx *ctx);
 
+/* ---- rxr_terrain_flatten.hip ---- */
+
+/* test-only: the k_terrain_flatten launches of the last flatten call */
+uint32_t rxr_debug_terrain_flatten_launches(rxr_ctx *ctx);
+
 /* ---- rxr_terrain_gen.hip ---- */
 
 /* test-only: the launches of the last evaluation call */

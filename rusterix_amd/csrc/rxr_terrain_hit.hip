@@ -270,7 +270,9 @@ int hits_run(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n, 
         else if (e[0]) return rxr_fail(ctx, RXR_ERR_INVALID, std::string("RXR_TERRAIN_HIT_ROUTE must be lane or wave, not ") + e);
     }
     HitArgs A{};
-    A.heights = (const float *)ctx->d_heights.p;
+    // (rxr_set_terrain_height_source: the processed grid lies over the same rectangle; rxr_flatten_terrain_to writes it in stream order)
+    const bool processed = ctx->height_source == RXR_TERRAIN_HEIGHTS_PROCESSED;
+    A.heights = (const float *)(processed ? ctx->d_pheights.p : ctx->d_heights.p);
     A.tk = (const float *)ctx->d_heights_tk.p;
     A.x0 = ctx->heights_x0;
     A.y0 = ctx->heights_y0;
@@ -285,8 +287,8 @@ int hits_run(rxr_ctx *ctx, const float *origins, const float *dirs, uint32_t n, 
     A.t = t;
     A.world_pos = world_pos;
     A.grid_pos = grid_pos;
-    const int rc = rxr_query_begin(ctx, ctx->lane[Q_HEIGHTS], s);
-    if (rc != RXR_OK) return rc;
+    int rc = rxr_query_begin(ctx, ctx->lane[Q_HEIGHTS], s);
+    if (rc != RXR_OK || (processed && (rc = rxr_query_begin(ctx, ctx->lane[Q_FLATTEN], s)) != RXR_OK)) return rc;
     ctx->heights_launches = 0;
     ctx->heights_kernel = wave ? "k_terrain_hit_wave" : "k_terrain_hit_lane";
     for (uint32_t first = 0; first < n;) {
@@ -344,6 +346,11 @@ int rxr_set_terrain_heights(rxr_ctx *ctx, const float scale[2], const int32_t *c
     if (n_grid) HIPCHK(ctx, hipMemcpyAsync(ctx->d_heights.p, grid.data(), n_grid * sizeof(float), hipMemcpyHostToDevice, s));
     if (n_grid) HIPCHK(ctx, hipMemcpyAsync(ctx->d_heights_mask.p, mask.data(), n_grid, hipMemcpyHostToDevice, s));
     if (table_new) HIPCHK(ctx, hipMemcpyAsync(ctx->d_heights_tk.p, march_table(), RXR_TERRAIN_MARCH_STEPS * sizeof(float), hipMemcpyHostToDevice, s));
+    // the processed grid (rxr_terrain_flatten.hip) starts over as a copy of the registered one
+    if ((rc = rxr_ensure(ctx, ctx->d_pheights, std::max<size_t>(n_grid * sizeof(float), 256))) != RXR_OK) return rc;
+    if ((rc = rxr_ensure(ctx, ctx->d_pheights_mask, std::max<size_t>(n_grid, 256))) != RXR_OK) return rc;
+    if (n_grid) HIPCHK(ctx, hipMemcpyAsync(ctx->d_pheights.p, ctx->d_heights.p, n_grid * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (n_grid) HIPCHK(ctx, hipMemcpyAsync(ctx->d_pheights_mask.p, ctx->d_heights_mask.p, n_grid, hipMemcpyDeviceToDevice, s));
     HIPCHK(ctx, hipStreamSynchronize(s));   // (the host vectors above are read until here)
     ctx->heights_scale[0] = scale[0];
     ctx->heights_scale[1] = scale[1];

@@ -248,8 +248,10 @@ bool mesh_bytes(uint32_t n, int32_t cs, size_t bytes[4]) {
 // every chunk of a call into device arrays, queued on `s`
 int mesh_run(rxr_ctx *ctx, const int32_t *coords, uint32_t n, int32_t cs, uint32_t *counts, float *vertices, uint32_t *indices, float *normals, hipStream_t s) {
     MeshArgs A{};
-    A.heights = (const float *)ctx->d_heights.p;
-    A.mask = (const uint8_t *)ctx->d_heights_mask.p;
+    // (rxr_set_terrain_height_source: the processed grid and mask lie over the same rectangle; rxr_flatten_terrain_to writes them in stream order)
+    const bool processed = ctx->height_source == RXR_TERRAIN_HEIGHTS_PROCESSED;
+    A.heights = (const float *)(processed ? ctx->d_pheights.p : ctx->d_heights.p);
+    A.mask = (const uint8_t *)(processed ? ctx->d_pheights_mask.p : ctx->d_heights_mask.p);
     A.x0 = ctx->heights_x0;
     A.y0 = ctx->heights_y0;
     A.gw = ctx->heights_gw;
@@ -258,8 +260,8 @@ int mesh_run(rxr_ctx *ctx, const int32_t *coords, uint32_t n, int32_t cs, uint32
     A.sy = ctx->heights_scale[1];
     A.cs = (uint32_t)cs;
     const size_t VS = (size_t)(cs + 1) * (size_t)(cs + 1), TS = 2 * (size_t)cs * (size_t)cs;
-    const int rc = rxr_query_begin(ctx, ctx->lane[Q_MESH], s);
-    if (rc != RXR_OK) return rc;
+    int rc = rxr_query_begin(ctx, ctx->lane[Q_MESH], s);
+    if (rc != RXR_OK || (processed && (rc = rxr_query_begin(ctx, ctx->lane[Q_FLATTEN], s)) != RXR_OK)) return rc;
     ctx->mesh_launches = 0;
     for (uint32_t c0 = 0; c0 < n; c0 += MESH_LAUNCH_CHUNKS) {
         const uint32_t nc = std::min(n - c0, MESH_LAUNCH_CHUNKS);
